@@ -18,12 +18,20 @@ trace_screen_centred does with sbuf, main.c:107) is measured in the same run
 through the frames-in-flight API and reported as `d2h_inclusive`.
 
 Timing: the K timed steps are one block, bracketed by barrier + synchronize.
-A block of 20 frames lasts 9 ms, so blocks are repeated until a second has
-been timed and `value` is the MEDIAN block (every block is exactly K steps);
-the spread over blocks and over single launches is reported next to it.
+A plain run times exactly one block: `ms_per_step` = that block / K, `value` =
+pixels per second over it.  --min-time S repeats the block until S seconds were
+timed and `value` is then the MEDIAN block (every block is exactly K steps); the
+spread over blocks and over single launches is reported next to it.
 
-Prints ONE JSON line on rank 0.  After the timed region the last frame is
-hashed and compared with the golden hash of the compiled reference.
+A plain run does only what `value` needs: set-up, warm-up, the timed steps, the
+outputs (--dump-outputs DIR) and ONE JSON line on rank 0.  Everything else is
+--full (blocks repeated for 3 s by default): the CPU baseline, the roofline leg
+and figures, the work counters, the blocking call, the D2H-inclusive leg, the
+parity of the last frame with the compiled reference's golden hash, the
+non-finite scenes and, for N > 1, the first legs, the host-sink leg and the sweep.
+
+--dump-outputs DIR writes what the timed path handed its caller in its last step
+(dump_outputs()); the inputs are fixed, so two builds can be compared file by file.
 
 N > 1: the line carries what it takes to read a first multi-GPU run from the driver's output alone --
 `tiling.per_rank` (every rank's trace / blur kernel times, the durations of the two grouped exchanges,
@@ -232,6 +240,27 @@ def cpu_baseline(w, h, cam, spheres, level_file, target_s=10.0):
                       "with table-emulated rcpps/rsqrtps, OpenMP over rows" % (reps + 1, w, h, reps + 1)}
 
 
+DUMP_MAX_PIXELS = 1 << 20
+
+
+def dump_outputs(out_dir, r, f, w, h, with_depth=True):
+    """--dump-outputs: the frame the timed path delivered last, as float32 .npy files in out_dir --
+    colour.npy (pixels, 4): the four bytes of each pixel's colour word, lowest byte first; depth.npy (pixels,): its depth
+    (one GPU); pixel_index.npy (pixels,), float64: the row-major index of each pixel.  A frame of more than DUMP_MAX_PIXELS
+    pixels is sampled at a fixed, seeded set of them (the same set for every run of that size): 28 MB at most."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = w * h
+    if n > DUMP_MAX_PIXELS:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_PIXELS, replace=False))
+    else:
+        idx = np.arange(n)
+    colour = np.ascontiguousarray(r.read_plane(f["d_sbuf"]).reshape(-1)[idx])
+    np.save(os.path.join(out_dir, "colour.npy"), colour.view(np.uint8).reshape(-1, 4).astype(np.float32))
+    if with_depth and f.get("d_zbuf"):
+        np.save(os.path.join(out_dir, "depth.npy"), r.read_plane(f["d_zbuf"], np.float32).reshape(-1)[idx])
+    np.save(os.path.join(out_dir, "pixel_index.npy"), idx.astype(np.float64))
+
+
 def d2h_leg_one_gpu(r, args, w, h, cam, sec, spheres, blocking_best, same_as_resident):
     """The metric as SURVEY.md 8(d) words it, on one GPU: every frame handed over to the host.  Same step as the
     resident loop (re-bin + upload, trace, blur) plus the D2H into the library's pinned sbuf, `slots` frames in
@@ -257,7 +286,7 @@ def d2h_leg_one_gpu(r, args, w, h, cam, sec, spheres, blocking_best, same_as_res
         return time.perf_counter() - t1
     d2h_block(args.warmup)
     d2h_s = []
-    while sum(d2h_s) < args.min_time and len(d2h_s) < 500:
+    while not d2h_s or (sum(d2h_s) < args.min_time and len(d2h_s) < 500):
         d2h_s.append(d2h_block(args.steps))
     d2h_dt = float(np.median(d2h_s))
     d2h_ok = bool(same_as_resident(held["f"]["sbuf"])) if same_as_resident is not None else None
@@ -408,7 +437,7 @@ def single_process(args):
         run(warmup)
         launch_ms.clear()
         blocks = []
-        while sum(blocks) < min_time and len(blocks) < 500:
+        while not blocks or (sum(blocks) < min_time and len(blocks) < 500):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             run(args.steps)
@@ -417,24 +446,27 @@ def single_process(args):
         return float(np.median(blocks)), blocks
     r.frames_config(nsl, sbuf=False)
     dt, block_s = leg(args.warmup, args.min_time)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, r, last["f"], w, h, with_depth=n == 1)
     one = {"members": 1, "transport": None, "devices": devices, "cuts": [0, h], "halo_rows": 0, "host_sink": False, "frames": 0, "frames_redone": 0, "recuts": 0, "note": ""}
     gi = r.group_info() if n > 1 else one
     trace_ms = float(np.mean(launch_ms)) if launch_ms else 0.0
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     frame_hash, parity = None, None
-    try:
-        import oracle
-        frame_hash = oracle.fnv64(r.read_plane(last["f"]["d_sbuf"]))
-        with open(os.path.join(GOLD, "frames.json")) as f:
-            want = [c for c in json.load(f)["cases"] if c["level"] == args.level and (c["w"], c["h"]) == (w, h) and c["sec"] == 0.0
-                    and c["nspheres"] == len(spheres) and c["name"].startswith(("level_spawn", args.level + "_cam0"))]
-        if want and args.level == "pwnfps_level":
-            parity = bool(frame_hash == (want[0]["post"] if args.blur else want[0]["pre"]))
-    except Exception as e:                                           # noqa: BLE001
-        sys.stderr.write("parity check skipped: %s\n" % e)
+    if args.full:
+        try:
+            import oracle
+            frame_hash = oracle.fnv64(r.read_plane(last["f"]["d_sbuf"]))
+            with open(os.path.join(GOLD, "frames.json")) as f:
+                want = [c for c in json.load(f)["cases"] if c["level"] == args.level and (c["w"], c["h"]) == (w, h) and c["sec"] == 0.0
+                        and c["nspheres"] == len(spheres) and c["name"].startswith(("level_spawn", args.level + "_cam0"))]
+            if want and args.level == "pwnfps_level":
+                parity = bool(frame_hash == (want[0]["post"] if args.blur else want[0]["pre"]))
+        except Exception as e:                                       # noqa: BLE001
+            sys.stderr.write("parity check skipped: %s\n" % e)
     # ---- every frame delivered to the host
     pcie = None
-    if not args.no_d2h:
+    if args.full and not args.no_d2h:
         r.frames_config(nsl, sbuf=True)
         dth, bh = leg(max(2, args.warmup // 2), args.min_time)
         same = bool(oracle.fnv64(last["f"]["sbuf"]) == frame_hash) if frame_hash is not None else None
@@ -502,8 +534,13 @@ def main():
     ap.add_argument("--height", type=int, default=2160)
     ap.add_argument("--level", default="pwnfps_level")
     ap.add_argument("--blur", type=int, default=1)
-    ap.add_argument("--min-time", type=float, default=3.0, help="repeat the K-step block until this many seconds were timed (each of the "
-                    "resident and the d2h leg: the GPU is busy for >= 6 s of a default run)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: CPU baseline, roofline leg and figures, work counters, blocking call, D2H leg, "
+                         "parity with the reference's golden frame, non-finite scenes; N > 1: first legs, host-sink leg, sweep")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed frame (colour bytes, depth; a seeded sample above 2^20 pixels) to DIR/*.npy as float32")
+    ap.add_argument("--min-time", type=float, default=None, help="repeat the K-step block until this many seconds were timed (each of the "
+                    "resident and the d2h leg); default: one block, 3 s with --full")
     ap.add_argument("--sweep-time", type=float, default=0.3, help="N > 1: seconds timed per leg of tiling.sweep (0 = no sweep)")
     ap.add_argument("--sweep-budget", type=float, default=100.0,
                     help="N > 1: seconds the sweep legs that set the tiling up again may take together; the legs left over are marked skipped")
@@ -538,6 +575,8 @@ def main():
                     help="--gpus N in ONE process: one handle (pwn_init_multi), the library's member threads row-tile every frame over devices 0..N-1; "
                          "started plainly (python bench.py --gpus N --single-process), not under torch.distributed.run")
     args = ap.parse_args()
+    if args.min_time is None:
+        args.min_time = 3.0 if args.full else 0.0
     if args.single_process:
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -643,9 +682,9 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    # The CPU baseline runs FIRST (rank 0, N = 1): ~15 s of host work, then the GPU legs in one piece (>= 6 s busy).
+    # --full: the CPU baseline runs FIRST (rank 0, N = 1): ~15 s of host work, then the GPU legs in one piece (>= 6 s busy).
     cpu_line = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if world == 1 and rank == 0 and args.full and not args.no_cpu_baseline:
         cpu_line = cpu_baseline(w, h, cam, spheres, level_file)
 
     nres = max(1, min(args.resident_slots, 4))
@@ -913,9 +952,11 @@ def main():
     if world > 1:
         board.mark("headline_done")
         dog.disarm()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r, last["f"], w, h)
     room_state = r.trace_room_state()          # PWN_OPT_TRACE_ROOM as the headline leg left it
     roofline_leg = None
-    if world == 1 and overlap_on:
+    if world == 1 and overlap_on and args.full:
         # ---- the roofline's launch duration: the same loop on ONE compute stream, every time_every-th frame between HIP
         # events on the launch stream -- a launch by itself, as `roofline` is defined
         r.set_frame_overlap(False)
@@ -939,7 +980,7 @@ def main():
     parity = None
     frame_hash = None
     oracle = None
-    if rank == 0 and last["f"] is not None:
+    if rank == 0 and last["f"] is not None and args.full:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         try:
             import oracle  # checker only: FNV of the frame vs the compiled reference's golden
@@ -954,7 +995,7 @@ def main():
             sys.stderr.write("parity check skipped: %s\n" % e)
 
     nonfinite = None
-    if world == 1 and rank == 0:
+    if world == 1 and rank == 0 and args.full:
         try:
             nonfinite = nonfinite_scenes(pwnfps_amd)
         except Exception as e:  # noqa: BLE001
@@ -979,8 +1020,6 @@ def main():
             par = "rows/%d with moving cuts, two grouped %s send/recv launches per frame in order on the frame's own stream (%s in front of the blur; the gather of the finished strips behind it), 3 frames in flight on %s" % (
                 world, transport.upper(), ("%d halo rows per neighbour" % tinfo["halo_rows"]) if tinfo["halo_rows"] else "whole pre-blur strips to every rank",
                 "two compute streams" if tinfo["two_streams"] else "one compute stream")
-        achieved = TRACE_BYTES_PER_PIXEL * strip_pix / (trace_ms * 1e-3) / 1e9 if trace_ms > 0 else 0.0
-        vf = valu_fractions("pwn_trace_kernel", w, h, trace_ms) if world == 1 else None
         line = {
             "metric": ("Mpixels/s at %dx%d (level.txt scene, trace + blur), frames resident on the device; mean steps/ray alongside"
                        % (w, h)) + ("; d2h_inclusive = the rate with every frame delivered to the host (SURVEY 8d)" if not args.no_d2h else "")
@@ -1012,6 +1051,12 @@ def main():
                        "host_loop": ("set_objects(i) / wait for a free slot / submit(i)" if args.prepare == "early"
                                      else "wait for a free slot / set_objects(i) / submit(i)") + ", every frame re-bins and re-uploads the spheres",
                        "frames_repeated_with_whole_strips": int(redone) if world > 1 else 0},
+        }
+        if not args.full:
+            return line
+        achieved = TRACE_BYTES_PER_PIXEL * strip_pix / (trace_ms * 1e-3) / 1e9 if trace_ms > 0 else 0.0
+        vf = valu_fractions("pwn_trace_kernel", w, h, trace_ms) if world == 1 else None
+        line.update({
             "roofline": {"bound": "hbm", "kernel": "pwn_trace_kernel", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
                          "traffic": pmc_traffic("pwn_trace_kernel", w, h) if world == 1 else None,
@@ -1050,7 +1095,7 @@ def main():
                                    "there the frames equal the same sources built with -fno-finite-math-only everywhere, and the shipped-flags "
                                    "build wherever depth is finite (DESIGN.md 2)",
                        "nonfinite_scenes": nonfinite},
-        }
+        })
         if world > 1:
             line["tiling"] = {k: tinfo[k] for k in ("rows_per_rank", "halo_rows", "groups", "frames", "frames_redone", "bytes_sent", "bytes_received",
                                                     "max_rows", "balance_every", "grid_reserve", "two_streams", "recuts")}
@@ -1139,7 +1184,7 @@ def main():
             return None
         return round(max(k, x), 4)
     first_legs = None
-    if world > 1:
+    if world > 1 and args.full:
         first_legs = {"default": {"what": "fixed root (rank 0), in-stream choreography: the headline", "measured_ms": round(dt / args.steps * 1e3, 4),
                                   "value": round(w * h * args.steps / dt / 1e6, 3), "predicted_ms": link_model("fixed_root")}}
         leg_name[0] = "first.rotating_root"
@@ -1152,7 +1197,7 @@ def main():
         except LegFailed as e:
             first_legs["rotating_root"] = {"error": str(e)}
             sweep_dead[0] = "first.rotating_root: %s" % e
-    if world > 1 and not args.no_d2h and sweep_dead[0] is None:
+    if world > 1 and args.full and not args.no_d2h and sweep_dead[0] is None:
         leg_name[0] = "host_sink"
         pcie = host_sink_leg(r, args, w, h, cam, sec, spheres, rank, world, transport, barrier, max_over_ranks,
                              (lambda buf: oracle.fnv64(buf) == frame_hash) if (rank == 0 and oracle is not None and frame_hash is not None) else None,
@@ -1164,9 +1209,9 @@ def main():
         elif pcie:
             first_legs["host_sink"] = {"error": pcie.get("error")}
     # ---- N > 1: the same run, other settings, a fraction of a second each: what a first multi-GPU run should look at
-    if world > 1 and args.sweep_time > 0 and not tiling_up and sweep_dead[0] is None:
+    if world > 1 and args.full and args.sweep_time > 0 and not tiling_up and sweep_dead[0] is None:
         tiling_up, _ = bring_up(transport, tag="sweep:")
-    if world > 1 and args.sweep_time > 0 and tiling_up and sweep_dead[0] is None:
+    if world > 1 and args.full and args.sweep_time > 0 and tiling_up and sweep_dead[0] is None:
         sweep = {}
 
         def point(name, what):
@@ -1288,7 +1333,7 @@ def main():
                 point("rccl_nonblocking", "PWN_TILED_RCCL_MODE=nonblocking: ncclCommInitRankConfig(blocking = 0), every call polled with ncclCommGetAsyncError")
             del os.environ["PWN_TILED_RCCL_MODE"]
 
-    if world == 1:
+    if world == 1 and args.full:
         r.set_call_strips(0)               # counters, wave stamps and kernel_ms: one launch per pass
         r.set_counters(True)
         sb = np.empty((h, w), np.uint32)
@@ -1351,7 +1396,7 @@ def main():
                                      "the copy (PWN_OPT_CALL_STRIPS 0); in row strips (the default) into a malloc'ed sbuf; in row strips into the same "
                                      "sbuf registered with pwn_host_register"}
         r.set_call_strips(-1)
-    if world == 1 and not args.no_d2h:
+    if world == 1 and args.full and not args.no_d2h:
         pcie = d2h_leg_one_gpu(r, args, w, h, cam, sec, spheres, blocking_best,
                                (lambda buf: oracle.fnv64(buf) == frame_hash) if (oracle is not None and frame_hash is not None) else None)
         pcie["blocking_call"] = blocking_call

@@ -10,9 +10,10 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
-from conftest import ROOT
+from conftest import ROOT, level_path, load_spheres
 
 pytestmark = pytest.mark.gpu
 
@@ -32,7 +33,7 @@ def test_bench_single_process_over_one_device(members, size, golden):
     loop and the blocking call."""
     env = dict(os.environ)
     env.update(PWN_BENCH_ONE_DEVICE="1")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(members), "--single-process", "--steps", "6", "--warmup", "2", "--min-time", "0.2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(members), "--single-process", "--steps", "6", "--warmup", "2", "--min-time", "0.2",
            "--time-every", "2", "--width", str(size[0]), "--height", str(size[1])]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -54,7 +55,7 @@ def test_bench_single_process_over_one_device(members, size, golden):
     assert q["blocking_call_mpix_s"] > 0 and q["blocking_call_frame_equals_resident_frame"] is True
     # under torch.distributed.run it refuses: it IS the one process
     cmd2 = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
-            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--single-process"]
+            os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--single-process"]
     if members == 2:
         p2 = subprocess.run(cmd2, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
         assert p2.returncode != 0 and "one process" in (p2.stderr + p2.stdout)
@@ -68,7 +69,7 @@ def test_bench_with_ranks_on_one_device(world, size, golden):
         env.update(PWN_BENCH_ALL_LEGS="1")          # the sweep legs that only an RCCL run has, so that their lines have run somewhere
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "6", "--warmup", "2", "--min-time", "0.2", "--sweep-time", "0.05",
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(world), "--steps", "6", "--warmup", "2", "--min-time", "0.2", "--sweep-time", "0.05",
            "--time-every", "2", "--width", str(size[0]), "--height", str(size[1])]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -138,7 +139,7 @@ def test_bench_line_survives_a_leg_that_does_not_finish():
     env.update(PWN_BENCH_ONE_DEVICE="1", PWN_BENCH_TRANSPORT="shm", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--min-time", "0.1", "--sweep-time", "30",
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "4", "--warmup", "1", "--min-time", "0.1", "--sweep-time", "30",
            "--post-timeout", "0.2", "--time-every", "2", "--width", "1280", "--height", "720"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert p.returncode != 0
@@ -160,7 +161,7 @@ def test_a_sweep_leg_that_fails_is_recorded_and_the_line_is_complete():
     env.update(PWN_BENCH_ONE_DEVICE="1", PWN_BENCH_TRANSPORT="shm", MASTER_ADDR="127.0.0.1", PWN_BENCH_FAIL_LEG="sweep.five_in_flight:1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--min-time", "0.1", "--sweep-time", "0.05",
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "4", "--warmup", "1", "--min-time", "0.1", "--sweep-time", "0.05",
            "--headline-timeout", "16", "--time-every", "2", "--width", "1280", "--height", "720"]          # (the library's wait deadline: a quarter of it)
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -183,7 +184,7 @@ def test_sweep_legs_that_set_the_tiling_up_again_stay_inside_their_budget():
     env.update(PWN_BENCH_ONE_DEVICE="1", PWN_BENCH_TRANSPORT="shm", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--min-time", "0.1", "--sweep-time", "0.05",
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "4", "--warmup", "1", "--min-time", "0.1", "--sweep-time", "0.05",
            "--sweep-budget", "0", "--no-d2h", "--time-every", "2", "--width", "1280", "--height", "720"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -205,7 +206,7 @@ def test_a_rank_that_leaves_during_the_bring_up_costs_a_diagnostic_line_not_a_ha
     env.update(PWN_BENCH_ONE_DEVICE="1", PWN_BENCH_TRANSPORT="shm", MASTER_ADDR="127.0.0.1", PWN_BENCH_DIE_AT="%s:1" % stage)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "4", "--warmup", "1", "--min-time", "0.1", "--sweep-time", "0",
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "3", "--steps", "4", "--warmup", "1", "--min-time", "0.1", "--sweep-time", "0",
            "--bringup-timeout", "20", "--headline-timeout", "20", "--width", "1280", "--height", "720", "--no-d2h"]
     t0 = time.time()
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
@@ -232,7 +233,7 @@ def test_bench_falls_back_when_rccl_does_not_come_up():
     env.update(PWN_BENCH_ONE_DEVICE="1", PWN_BENCH_TRANSPORT="rccl", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--min-time", "0.1",
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "4", "--warmup", "1", "--min-time", "0.1",
            "--width", "1280", "--height", "720", "--no-cpu-baseline"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -246,7 +247,7 @@ def test_bench_falls_back_when_rccl_does_not_come_up():
 def test_bench_line_on_one_gpu():
     """The contract of the one-GPU line (the driver's BENCH run): one JSON line with the metric, the roofline object of
     the dominant kernel, the D2H-inclusive leg and the work counters; the last frame is the golden frame."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--min-time", "0.2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "10", "--warmup", "2", "--min-time", "0.2",
            "--width", "1280", "--height", "720", "--no-cpu-baseline"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -275,3 +276,33 @@ def test_bench_line_on_one_gpu():
     assert d["frame_fnv64"] == "078fb94a5cd068f5" and d["parity_vs_reference_golden"] is True
     assert d["d2h_inclusive"]["value"] > 0 and d["d2h_inclusive"]["last_frame_equals_resident_frame"] is True
     assert abs(d["work"]["steps_per_ray"] - 4.007) < 0.001 and d["work"]["rays_per_pixel"] == 3.0
+
+
+def test_plain_bench_line_times_k_steps_and_dumps_the_last_frame(tmp_path, oracle_lib):
+    """A plain run (no --full): exactly --steps timed steps in one block, the headline keys and none of the --full legs; --dump-outputs
+    writes the last timed frame, which is the oracle's frame of the bench scene (colour bytes and depth bits; 720p: every pixel)."""
+    out = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+           "--width", "1280", "--height", "720", "--dump-outputs", str(out)]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["timing"]["blocks_of_k_steps"] == 1
+    assert d["unit"] == "Mpixels/s" and d["dtype"] == "f32" and d["higher_is_better"] is True and "frames resident on the device" in d["metric"]
+    assert abs(d["value"] - 1280 * 720 / (d["ms_per_step"] * 1e-3) / 1e6) < 0.01 * d["value"]
+    for k in ("roofline", "cpu_baseline", "d2h_inclusive", "work", "parity", "kernel_ms"):
+        assert k not in d, k
+    colour, depth, idx = (np.load(str(out / (n + ".npy"))) for n in ("colour", "depth", "pixel_index"))
+    assert colour.dtype == np.float32 and depth.dtype == np.float32 and idx.dtype == np.float64
+    assert colour.shape == (1280 * 720, 4) and depth.shape == (1280 * 720,) and (idx == np.arange(1280 * 720)).all()
+    sb = colour.astype(np.uint8).view(np.uint32).reshape(720, 1280)
+    assert oracle_lib.fnv64(sb) == "078fb94a5cd068f5"
+    import pwnfps_amd
+    O = oracle_lib.Oracle()
+    O.load_level(level_path("pwnfps_level"))
+    O.set_spheres(load_spheres("t0"))
+    cam = pwnfps_amd.spawn_camera(O.get_level()[2])
+    ob, oz = O.render(1280, 720, cam, sec=0.0, blur=1)
+    assert (ob == sb).all() and (oz.view(np.uint32) == depth.reshape(720, 1280).view(np.uint32)).all()

@@ -8,7 +8,7 @@ import pytest
 import refharness
 from conftest import GOLD, host_is_intel, level_path, load_spheres
 
-pytestmark = pytest.mark.skipif(not refharness.available("tab"), reason="oracle/_ref not built")
+needs_ref = pytest.mark.skipif(not refharness.available("tab"), reason="oracle/_ref not built")
 
 
 def _pose(x, y, z, ay, ax):
@@ -22,6 +22,7 @@ def _pose(x, y, z, ay, ax):
     return m
 
 
+@needs_ref
 def test_random_scenes(oracle_lib):
     rng = np.random.default_rng(777)
     R = refharness.RefHarness("tab")
@@ -49,6 +50,7 @@ def test_random_scenes(oracle_lib):
                 assert (za.view(np.uint32) == zb.view(np.uint32)).all(), (lvl, it)
 
 
+@needs_ref
 def test_w_lane_generality(oracle_lib):
     """v_dot / v_normalise are 4-lane (util.h:18-46): a camera matrix with
     non-zero w entries must still agree."""
@@ -65,6 +67,7 @@ def test_w_lane_generality(oracle_lib):
     assert (a == b).all() and (za.view(np.uint32) == zb.view(np.uint32)).all()
 
 
+@needs_ref
 def test_native_and_table_builds_agree_on_intel():
     """The goldens come from the build whose rcpps / rsqrtps read captured tables; on an Intel host the untouched build
     (the host's own instructions) must render the same frames: one pose per level here, every golden case in
@@ -95,14 +98,22 @@ def test_every_golden_case_is_pinned_by_the_native_build(cases):
 
 
 def test_upscale_vs_reference(oracle_lib):
-    R = refharness.RefHarness("tab")
+    """tests/golden/upscale_ref.npz: the compiled reference's screen_upscale of the same source; the live reference as well
+    where oracle/_ref is built."""
+    k = np.load(os.path.join(GOLD, "upscale_ref.npz"))
+    R = refharness.RefHarness("tab") if refharness.available("tab") else None
     O = oracle_lib.Oracle()
     rng = np.random.default_rng(3)
     src = rng.integers(0, 2 ** 32, (9, 20), dtype=np.uint32)
+    assert (src == k["src"]).all()
     for scale, pitch in ((1, 80), (2, 176), (3, 240), (4, 336)):
-        assert (R.upscale(src, scale, pitch) == O.upscale(src, scale, pitch)).all()
+        mine = O.upscale(src, scale, pitch)
+        assert (k["ref_%d_%d" % (scale, pitch)] == mine).all(), (scale, pitch)
+        if R is not None:
+            assert (R.upscale(src, scale, pitch) == mine).all(), (scale, pitch)
 
 
+@needs_ref
 def test_edge_scenes(oracle_lib, tmp_path):
     """The oracle on the edge-of-domain scenes that the GPU parity test uses,
     against the reference's own code."""
@@ -129,6 +140,7 @@ def test_edge_scenes(oracle_lib, tmp_path):
         assert (za.view(np.uint32) == zb.view(np.uint32)).all(), sc.name
 
 
+@needs_ref
 def test_random_levels_loader_three_way(oracle_lib, tmp_path):
     """level.txt format (level.h:107-228) on random files: the reference's own
     level_load, the oracle's and the product's (pwnfps_amd/csrc/level_host.c) parse
@@ -173,6 +185,7 @@ def test_random_levels_loader_three_way(oracle_lib, tmp_path):
             assert (np.asarray(s) == np.asarray(s0)).all(), (it, name, "spawn")
 
 
+@needs_ref
 def test_fuzz_scenes_oracle_vs_reference():
     """The scenes of the GPU fuzz campaign (tools/fuzz_parity.py, same generator and seed as
     tests/test_gpu_fuzz.py) with the compiled reference in place of the GPU: the oracle is
@@ -187,6 +200,7 @@ def test_fuzz_scenes_oracle_vs_reference():
     assert "120 scenes, 0 mismatches" in p.stdout
 
 
+@needs_ref
 def test_axis_aligned_cameras_and_the_ramp_divide_by_zero(oracle_lib):
     """Axis-aligned cameras give rays with exactly rational slopes; where such a
     ray meets a ramp with ray.y == 0.5*ray.x the tilt divides by zero
@@ -216,6 +230,7 @@ def test_axis_aligned_cameras_and_the_ramp_divide_by_zero(oracle_lib):
     assert seen > 0    # the case is really exercised
 
 
+@needs_ref
 def test_far_start_scenes(oracle_lib):
     """tests/golden/far_starts.npz: lattice scenes of tools/fuzz_parity.py (seeds 9002, 9004) in which a bounced
     ray starts its next segment far outside the grid (its cell number beyond 16 bits).  The oracle against the

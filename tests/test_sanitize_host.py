@@ -11,20 +11,19 @@ import pytest
 
 from conftest import ROOT
 
-OUT = "/tmp/pwn_sanitize_pytest"
 
-
-def _build(target):
-    p = subprocess.run(["make", "-C", os.path.join(ROOT, "tools", "sanitize"), target, "OUT=" + OUT], capture_output=True, text=True, timeout=600)
+def _build(target, out):
+    p = subprocess.run(["make", "-C", os.path.join(ROOT, "tools", "sanitize"), target, "OUT=" + out], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
 
 
 @pytest.mark.parametrize("target,modes", [("tsan", ("group", "late", "shm")), ("asan", ("all",))])
-def test_host_logic_under_sanitizers(target, modes):
-    _build(target)
+def test_host_logic_under_sanitizers(target, modes, tmp_path):
+    out_dir = str(tmp_path)
+    _build(target, out_dir)
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1 second_deadlock_stack=1", ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1")
     for m in modes:
-        p = subprocess.run([os.path.join(OUT, "group_" + target), m], capture_output=True, text=True, timeout=600, env=env, cwd="/tmp")
+        p = subprocess.run([os.path.join(out_dir, "group_" + target), m], capture_output=True, text=True, timeout=600, env=env, cwd=out_dir)
         out = p.stdout + p.stderr
         assert p.returncode == 0 and out.strip().endswith("ok"), out[-4000:]
         assert "Sanitizer" not in out, out[-4000:]

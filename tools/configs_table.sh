@@ -2,7 +2,7 @@
 # one bench.py line per BASELINE configuration on one GPU (resident loop and, for the sizes that matter, the D2H leg)
 cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out/configs
-run() { python bench.py --steps 100 --warmup 10 --no-cpu-baseline "$@" 2>/dev/null | python -c "
+run() { python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 w=d['work']; k=d['kernel_ms']; p=d.get('d2h_inclusive') or {}

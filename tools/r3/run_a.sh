@@ -31,10 +31,10 @@ done
 } > $O/wavelogs.txt 2>&1
 for ov in 0 1; do
   for lr in 0 -1; do
-    PWN_FRAME_OVERLAP=$ov PWN_DBG_LATE_ROUNDS=$lr python bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-d2h > $O/bench_ov${ov}_lr${lr}.json 2> $O/bench_ov${ov}_lr${lr}.err
+    PWN_FRAME_OVERLAP=$ov PWN_DBG_LATE_ROUNDS=$lr python bench.py --full --steps 100 --warmup 20 --no-cpu-baseline --no-d2h > $O/bench_ov${ov}_lr${lr}.json 2> $O/bench_ov${ov}_lr${lr}.err
   done
 done
-PWN_FRAME_OVERLAP=1 python bench.py --steps 100 --warmup 20 --no-cpu-baseline > $O/bench_full.json 2> $O/bench_full.err
+PWN_FRAME_OVERLAP=1 python bench.py --full --steps 100 --warmup 20 --no-cpu-baseline > $O/bench_full.json 2> $O/bench_full.err
 PWN_FRAME_OVERLAP=0 PWN_DBG_LATE_ROUNDS=0 PWN_DBG_BLUR_TH=32 bash tools/configs_table.sh > $O/configs_old.txt 2>&1
 bash tools/configs_table.sh > $O/configs_new.txt 2>&1
 grep -h '"value"' $O/bench_*.json | python -c "

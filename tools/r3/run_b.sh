@@ -14,8 +14,8 @@ echo "== synth256 8K 8 strips"; STRIP_LEVEL=synth256 python tools/strip_time.py 
 PWN_FRAME_OVERLAP=0 bash tools/configs_table.sh > $O/configs_ov0.txt 2>&1
 bash tools/configs_table.sh > $O/configs_ov1.txt 2>&1
 for te in 8 32 1000000; do
-PWN_FRAME_OVERLAP=1 python bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-d2h --time-every $te > $O/bench_ov1_te$te.json 2> $O/bench_ov1_te$te.err
-PWN_FRAME_OVERLAP=0 python bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-d2h --time-every $te > $O/bench_ov0_te$te.json 2> $O/bench_ov0_te$te.err
+PWN_FRAME_OVERLAP=1 python bench.py --full --steps 100 --warmup 20 --no-cpu-baseline --no-d2h --time-every $te > $O/bench_ov1_te$te.json 2> $O/bench_ov1_te$te.err
+PWN_FRAME_OVERLAP=0 python bench.py --full --steps 100 --warmup 20 --no-cpu-baseline --no-d2h --time-every $te > $O/bench_ov0_te$te.json 2> $O/bench_ov0_te$te.err
 done
 grep -h '"value"' $O/bench_*.json | python -c "
 import sys, json

@@ -14,4 +14,4 @@ open("gpurun_out/r3_n/valu_rate.txt","w").write("\n".join(out)+"\n")
 print("\n".join(out))
 PY
 bash tools/variants.sh base 3840 2160 40 | grep -v amdgpu
-python bench.py --no-cpu-baseline --min-time 1 --no-d2h | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['kernel_ms'])"
+python bench.py --full --no-cpu-baseline --min-time 1 --no-d2h | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['kernel_ms'])"

@@ -8,7 +8,7 @@ for v in _prev ""; do
   export PWNHIP_LIB=$PWD/pwnfps_amd/libpwnhip$v.so
   echo "== lib '$v' rep $rep"
   for wh in "3840 2160 pwnfps_level" "1280 720 pwnfps_level" "7680 4320 synth256"; do set -- $wh
-    python bench.py --no-cpu-baseline --min-time 1.5 --no-d2h --width $1 --height $2 --level $3 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$1x$2 $3', d['value'], d['ms_per_step'], d['kernel_ms'], d['blur_roofline']['avg_launch_ms'])"
+    python bench.py --full --no-cpu-baseline --min-time 1.5 --no-d2h --width $1 --height $2 --level $3 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$1x$2 $3', d['value'], d['ms_per_step'], d['kernel_ms'], d['blur_roofline']['avg_launch_ms'])"
   done
   python3 tools/strip_time.py 8 2>&1 | grep -v amdgpu | tail -1
 done; done > $O/ab.txt 2>&1

@@ -8,7 +8,7 @@ for cfg in "32 32 1" "64 32 1" "128 16 1" "128 32 1" "128 32 0" "64 16 1" "32 64
   export PWN_DBG_BLUR_TW=$1 PWN_DBG_BLUR_TH=$2 PWN_DBG_BLUR_BATCH=$3
   line="tile $1x$2 batch $3:"
   for wh in "3840 2160 pwnfps_level" "1280 720 pwnfps_level" "1920 1080 synth64" "7680 4320 pwnfps_level"; do set -- $wh
-    r=$(python bench.py --no-cpu-baseline --min-time 1 --no-d2h --width $1 --height $2 --level $3 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.0f' % (d['value']))")
+    r=$(python bench.py --full --no-cpu-baseline --min-time 1 --no-d2h --width $1 --height $2 --level $3 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.0f' % (d['value']))")
     line="$line  $1x$2 $r"
   done
   s=$(python3 tools/strip_time.py 8 2>&1 | grep -v amdgpu | tail -1 | sed 's/.*sum over strips of the 2-stream figure //')

@@ -3,7 +3,7 @@ set -u
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r4_ab; mkdir -p $O
 export PWN_BENCH_ONE_DEVICE=1 PWN_BENCH_TRANSPORT=shm MASTER_ADDR=127.0.0.1
-python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 50 --warmup 10 --min-time 1 > $O/bench_2ranks_one_device_shm.json 2> $O/bench_2ranks.err
+python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 50 --warmup 10 --min-time 1 > $O/bench_2ranks_one_device_shm.json 2> $O/bench_2ranks.err
 tail -c 400 $O/bench_2ranks.err
 python3 - <<"PY"
 import json

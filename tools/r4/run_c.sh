@@ -14,4 +14,4 @@ for mode in blocking nonblocking blocking nonblocking; do
 	done
 done > $O/rccl_mode_host_cost.txt 2>&1
 cat $O/rccl_mode_host_cost.txt
-python bench.py > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; cat $O/bench.json
+python bench.py --full > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; cat $O/bench.json
