@@ -303,6 +303,32 @@ int pwn_host_unregister(pwn_ctx *ctx, void *base);
 int pwn_call_strips_state(pwn_ctx *ctx, unsigned long long out[6]);
 
 /*
+ * trace_screen_centred (screen.h:31-124) once per view, for n views of the one level and object table: split-screen,
+ * camera or portal previews, stereo pairs, many poses.  Blocking; one trace launch and one blur launch per pass for the
+ * whole batch.  cams = n x 16 floats (view i's mat4 rows x,y,z,w as for pwn_trace_screen_centred), secs = n sec_current;
+ * sbuf = n x h x w BGRA8 and zbuf (or NULL) = n x h x w depth, view-major.  View i is bit-identical, colour and depth, to
+ * pwn_trace_screen_centred(cams[i], secs[i]) on a context of the same size, level and objects whose earlier frames were
+ * view slot i's earlier cameras.
+ *   depth per view slot  view slot i has a device depth plane of its own, zero when first allocated; where the primary ray
+ *                        runs out of steps it keeps its previous value (trace.h:677).  Planes persist by index across calls;
+ *                        a larger n keeps the existing ones; pwn_destroy frees them.  Cost: 12 B x n x w x h on the device
+ *                        (pre-blur, colour, depth), allocated by the first call with that many views.
+ *   blur                 PWN_OPT_BLUR_PASSES as the blocking call; PWN_EINVAL for w % 4 != 0 with blur on.
+ *   counters             with PWN_OPT_COUNTERS on, pwn_get_stats returns the counters summed over the views; trace_ms,
+ *                        blur_ms and total_ms time the batch call.
+ *   ordering             behind the frames in flight, as the blocking call.
+ *   left alone           the blocking call's own planes (its depth persistence, and pwn_screen_upscale(NULL, ...), still
+ *                        refer to the last blocking frame), the unit-order state, the trace-room measurement.
+ *   not followed         always the units scheduler, whatever PWN_OPT_SCHEDULER says; never in row strips
+ *                        (PWN_OPT_CALL_STRIPS); PWN_OPT_UNIT_ORDER and PWN_OPT_WAVE_LOG are ignored.
+ *   errors               PWN_EINVAL for NULL ctx / cams / secs / sbuf, n < 1, n > PWN_VIEWS_MAX, n x w x h > 2^28;
+ *                        PWN_ENOLEVEL before a level; PWN_ENOTSUP on a pwn_init_multi handle; PWN_EBUSY while the context
+ *                        runs a row tiling (pwn_tiled_init).
+ */
+#define PWN_VIEWS_MAX 1024
+int pwn_trace_views(pwn_ctx *ctx, int n, const float *cams, const float *secs, uint32_t *sbuf, float *zbuf);
+
+/*
  * Frames in flight.  The reference presents every frame on the host
  * (trace_screen_centred fills sbuf, screen_upscale fills screen->pixels, SDL_Flip:
  * main.c:107-109).  Over PCIe that hand-over takes longer than the kernels of a

@@ -33,6 +33,9 @@ struct pwn_blur_params
 	// the frame, and clears the accumulator for the stream's next trace.  Both NULL otherwise.
 	uint32_t *cost_acc, *cost_out;
 	uint32_t cost_mul, cost_div;   // ... scaled on the way: the resident grid over the grid the trace ran with (PWN_OPT_TRACE_ROOM), so that ranks with and without room compare
+	// a batch of views (pwn_trace_views): 0 = one frame; else that many frames of w x h, view v's planes at pre / zbuf / out + v * plane
+	int views;
+	unsigned long long plane;
 };
 
 __device__ __forceinline__ uint32_t avg_u8x4(uint32_t a, uint32_t b)
@@ -127,6 +130,8 @@ pwn_blur_kernel(pwn_blur_params P)
 // pixel and the fastest launch BY ITSELF); judged by the frame rate with the next frame's trace grid on the chip
 // beside it, small workgroups win -- 32 x 32 (256 threads, 17 KB) on wide frames, 128 x 16 on narrow ones
 // (profiles/r3_blur_sweep.txt).
+// VIEWS: a batch of views in one launch (pwn_trace_views), blockIdx.y = the view.  Every view is blurred as a frame of its own --
+// its row seeds (cy*cy + 415135) and edge clamps are those of one frame -- so the batch is not one tall frame.
 #ifndef BLUR_HALO
 #define BLUR_HALO 16        // measured 8 / 16 / 24 / 32: 45.6 / 45.4 / 46.6 / 48.0 us at 4K (less staging beats fewer fall-backs)
 #endif
@@ -135,11 +140,16 @@ pwn_blur_kernel(pwn_blur_params P)
 #define BLUR_PITCH (BLUR_LW + (BATCH == 2 ? 0 : 4)) // words; +4 keeps rows 16-B aligned and off one bank (direct-to-LDS staging: rows back to back)
 #define BLUR_THREADS (BLUR_TW / 4 * BLUR_TH)       // one thread per 4-pixel group
 
-template<bool CHECK, int BLUR_TW, int BLUR_TH, int BATCH>
+template<bool CHECK, int BLUR_TW, int BLUR_TH, int BATCH, bool VIEWS>
 __global__ void __launch_bounds__(BLUR_THREADS)
 pwn_blur_tiled_kernel(pwn_blur_params P)
 {
 	extern __shared__ __attribute__((aligned(16))) uint32_t tile[];
+	if constexpr(VIEWS)
+	{
+		const size_t off = (size_t)blockIdx.y * (size_t)P.plane;
+		P.pre += off; P.zbuf += off; P.out += off;
+	}
 	// Workgroup w runs on XCD w % 8 (round-robin dispatch) and every XCD has its
 	// own L2.  Neighbouring tiles share their halos, so XCD k takes the k-th
 	// contiguous eighth of the tiles in row-major order: the halo re-reads then
@@ -393,7 +403,7 @@ pwn_blur_tiled_kernel(pwn_blur_params P)
 	if(CHECK) { if(missed) atomicAdd(P.miss, 1u); }
 }
 
-template<bool CHECK, int TW, int TH, int BATCH>
+template<bool CHECK, int TW, int TH, int BATCH, bool VIEWS = false>
 static hipError_t launch_blur_variant(const pwn_blur_params *P, hipStream_t stream)
 {
 	const int BLUR_TW = TW, BLUR_TH = TH;
@@ -408,14 +418,14 @@ static hipError_t launch_blur_variant(const pwn_blur_params *P, hipStream_t stre
 		bool &lds_set = lds_mark[dev & 63];
 		if(!lds_set)
 		{
-			hipError_t e = hipFuncSetAttribute((const void *)pwn_blur_tiled_kernel<CHECK, TW, TH, BATCH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+			hipError_t e = hipFuncSetAttribute((const void *)pwn_blur_tiled_kernel<CHECK, TW, TH, BATCH, VIEWS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 			if(e != hipSuccess) return e;
 			lds_set = true;
 		}
 	}
 	const int ntiles = ((P->w + BLUR_TW - 1) / BLUR_TW) * ((P->y1 - P->y0 + BLUR_TH - 1) / BLUR_TH);
-	dim3 grid(((ntiles + 7) / 8) * 8);
-	hipLaunchKernelGGL((pwn_blur_tiled_kernel<CHECK, TW, TH, BATCH>), grid, dim3(BLUR_THREADS), lds, stream, *P);
+	dim3 grid(((ntiles + 7) / 8) * 8, VIEWS ? P->views : 1);
+	hipLaunchKernelGGL((pwn_blur_tiled_kernel<CHECK, TW, TH, BATCH, VIEWS>), grid, dim3(BLUR_THREADS), lds, stream, *P);
 	return hipGetLastError();
 }
 
@@ -428,6 +438,15 @@ static hipError_t launch_blur_check(const pwn_blur_params *P, hipStream_t stream
 extern "C" hipError_t pwn_launch_blur(const pwn_blur_params *P, hipStream_t stream)
 {
 	if(P->groups <= 0 || P->y1 <= P->y0) return hipSuccess;
+	// a batch of views: the two shipped tile shapes, no row-tiling check
+	if(P->views > 0)
+	{
+		if(P->miss != NULL || P->cost_acc != NULL) return hipErrorInvalidValue;
+		const int key = P->tile_w * 1000 + P->tile_h * 10 + P->batch;
+		if(key == 128161) return launch_blur_variant<false, 128, 16, 1, true>(P, stream);
+		if(key == 32321) return launch_blur_variant<false, 32, 32, 1, true>(P, stream);
+		return hipErrorInvalidValue;
+	}
 #ifdef PWN_BLUR_PLAIN
 	dim3 grid((P->groups + 255) / 256, P->y1 - P->y0);
 	hipLaunchKernelGGL(pwn_blur_kernel, grid, dim3(256), 0, stream, *P);

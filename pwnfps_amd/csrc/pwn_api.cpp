@@ -90,6 +90,8 @@ extern "C" int pwn_init(pwn_ctx **out, int device, int width, int height)
 	for(int i = 0; i < PWN_NSTAGE; i++) { c->h_stage[i] = NULL; c->ev_stage[i] = NULL; c->stage_used[i] = false; }
 	c->d_pre = c->d_out = NULL; c->d_z = NULL; c->d_skip = NULL; c->d_counters = NULL; c->d_tickets = NULL; c->ticket_set = 0; c->launch_rot = 2; c->launch_waits = 0;
 	c->trace_clear_word = NULL; c->trace_cost_word = NULL; c->trace_tables_event = NULL; c->grid_reserve = 0;
+	c->trace_views = NULL; c->blur_views = 0;
+	c->d_vpre = c->d_vout = NULL; c->d_vz = NULL; c->views_cap = 0; c->h_vrec = c->d_vrec = NULL; c->vrec_cap = 0;
 	memset(&c->room, 0, sizeof(c->room)); c->room.mode = -1; c->launch_room = 0;
 	c->cost_mul = c->cost_div = 1u; c->blur_cost_mul = c->blur_cost_div = 0u;
 	if(const char *e = getenv("PWN_TRACE_ROOM")) if(*e) c->room.mode = atoi(e) < 0 ? -1 : atoi(e);      // (the option's default for every context of a process)
@@ -234,6 +236,8 @@ extern "C" void pwn_destroy(pwn_ctx *c)
 	if(c->up_stream) (void)hipStreamDestroy(c->up_stream);
 	(void)hipFree(c->d_pre); (void)hipFree(c->d_out); (void)hipFree(c->d_z); (void)hipFree(c->d_pre2);
 	(void)hipFree(c->d_wave_log);
+	(void)hipFree(c->d_vpre); (void)hipFree(c->d_vout); (void)hipFree(c->d_vz); (void)hipFree(c->d_vrec);
+	if(c->h_vrec) (void)hipHostFree(c->h_vrec);
 	for(int i = 0; i < 4; i++) { (void)hipFree(c->order[i].d_cost); (void)hipFree(c->order[i].d_perm); }
 	(void)hipFree(c->d_skip); (void)hipFree(c->d_counters); (void)hipFree(c->d_tickets); (void)hipFree(c->d_scratch);
 	delete c;
@@ -797,6 +801,8 @@ int pwn_i_launch_trace(pwn_ctx *c, const float cam[16], float sec, int y0, int y
 	c->trace_cost_word = NULL;
 	hipEvent_t caller_event = c->trace_tables_event;       // (pwn_internal.h)
 	c->trace_tables_event = NULL;
+	const pwn_views_launch *views = c->trace_views;       // (pwn_trace_views)
+	c->trace_views = NULL;
 	if(!c->have_level) return PWN_ENOLEVEL;
 	if(c->blob_dirty) { int rc = pack_blob(c); if(rc != PWN_OK) return rc; }
 	if(y1 == y0) return PWN_OK;
@@ -812,6 +818,13 @@ int pwn_i_launch_trace(pwn_ctx *c, const float cam[16], float sec, int y0, int y
 	unit_div_magic((uint32_t)P.tiles_x, &P.ux_magic, &P.ux_shift);
 	// (the kernel takes unit / tiles_x = unit where there is no shift: true for one unit per row only)
 	if(P.ux_shift < 0 && P.tiles_x != 1) { snprintf(c->err, sizeof(c->err), "no division constant for %d units per row", P.tiles_x); return PWN_EINVAL; }
+	// a batch of views: the frame's units once per view, every view's camera set-up in its record (the one above is not read)
+	if(views != NULL)
+	{
+		P.views = views->d_recs; P.nviews = views->n; P.plane = views->plane;
+		unit_div_magic((uint32_t)views->n, &P.views_magic, &P.views_shift);
+		P.tiles_total *= views->n;
+	}
 	P.blob_bytes = (uint32_t)c->blob.size();
 	P.off_sph = c->off_sph;
 	P.off_recsph = c->off_recsph;
@@ -840,11 +853,13 @@ int pwn_i_launch_trace(pwn_ctx *c, const float cam[16], float sec, int y0, int y
 	// main.c:61-64) never put anything but 0 / 1 into the w lanes; the kernel has a
 	// 3-lane specialisation for them that is arithmetically identical
 	P.has_w = !(cam[3] == 0.0f && cam[7] == 0.0f && cam[11] == 0.0f && cam[15] == 1.0f);
+	if(views != NULL) P.has_w = views->has_w;        // (the same rule over all the batch's cameras)
 	// test hook (tests/test_gpu_fuzz.py): send every camera through the general variant
 	if(c->dbg_force_hasw) P.has_w = 1;
 	if(c->counters_on) HIPCHK(c, hipMemsetAsync(c->d_counters, 0, PWN_NCOUNTERS * sizeof(unsigned long long), stream));
 	// persistent grid: as many workgroups as are resident at once, each striding over tiles
-	const bool refill = c->scheduler == PWN_SCHED_REFILL;
+	// (a batch of views always runs the units scheduler)
+	const bool refill = c->scheduler == PWN_SCHED_REFILL && views == NULL;
 	const size_t lds_bytes = ((P.blob_bytes + 15u) & ~15u) + (refill ? pwn_trace_refill_lds_extra(P.has_w != 0) : pwn_trace_lds_extra());
 	// resident workgroups per CU depend on (LDS bytes, kernel variant) only: ask once per combination
 	P.scheduler = c->scheduler;
@@ -889,7 +904,7 @@ int pwn_i_launch_trace(pwn_ctx *c, const float cam[16], float sec, int y0, int y
 	}
 	// PWN_OPT_WAVE_LOG: every wave of this launch writes its start and end time; entry 0 is unused, entry
 	// 1 + 4 * workgroup + SIMD is a wave's (the buffer follows the grid of the launch)
-	if(c->wave_log_on)
+	if(c->wave_log_on && views == NULL)
 	{
 		const size_t entries = (size_t)grid * 4 + 1;
 		if(entries > c->wave_log_cap)
@@ -906,8 +921,9 @@ int pwn_i_launch_trace(pwn_ctx *c, const float cam[16], float sec, int y0, int y
 	// and hands its units out in the order sorted from the last launch of the same rows on this stream
 	// (with the wave log only where the dump is asked for, PWN_DBG_UNIT_COST: the kernel variant that writes the costs is 2-3 % slower,
 	// and the wave log's span and residency are figures of the ordinary launch)
-	const bool want_cost = !refill && (c->unit_order || (c->wave_log_on && getenv("PWN_DBG_UNIT_COST") != NULL));
-	pwn_ctx::unit_order_state *uop = order_entry(c, stream, want_cost);
+	// (a batch of views neither writes nor reads nor invalidates any of this)
+	const bool want_cost = !refill && views == NULL && (c->unit_order || (c->wave_log_on && getenv("PWN_DBG_UNIT_COST") != NULL));
+	pwn_ctx::unit_order_state *uop = views != NULL ? NULL : order_entry(c, stream, want_cost);
 	if(uop != NULL && want_cost)
 	{
 		pwn_ctx::unit_order_state &uo = *uop;
@@ -1019,8 +1035,11 @@ extern "C" int pwn_unit_order_state(pwn_ctx *c, unsigned long long out[4])
 int pwn_i_launch_blur(pwn_ctx *c, int y0, int y1, const uint32_t *d_pre, const float *d_z, uint32_t *d_out, hipStream_t stream,
 	int avail_y0, int avail_y1, uint32_t *d_miss, uint32_t *d_cost_acc, uint32_t *d_cost_out)
 {
+	const int views = c->blur_views;        // for this launch only (pwn_trace_views)
+	c->blur_views = 0;
 	if((c->w & 3) != 0) return PWN_EINVAL; // screen.h:88,117: aligned 16-B store per group
 	pwn_blur_params B;
+	B.views = views; B.plane = (unsigned long long)c->w * (unsigned long long)c->h;
 	B.w = c->w; B.h = c->h; B.y0 = y0; B.y1 = y1;
 	B.groups = c->w / 4;
 	B.pre = d_pre; B.zbuf = d_z; B.out = d_out; B.skip = c->d_skip;
@@ -1347,6 +1366,16 @@ static int call_in_strips(pwn_ctx *c, const float cam[16], float sec, uint32_t *
 	return PWN_OK;
 }
 
+// The blocking calls (pwn_trace_screen_centred, pwn_trace_views) on compute stream s: behind the frames in flight, whichever
+// compute stream their kernels are on
+static int wait_frames_in_flight(pwn_ctx *c, hipStream_t s)
+{
+	if(c->last_frame_done != NULL && c->last_frame_stream != s) HIPCHK(c, hipStreamWaitEvent(s, c->last_frame_done, 0));
+	if(c->last_frame_done != NULL && c->stream2 != NULL && c->last_frame_stream != c->stream2) HIPCHK(c, hipStreamWaitEvent(c->stream2, c->last_frame_done, 0));      // (strips use both)
+	c->last_frame_done = NULL;       // (the call ends with the stream empty)
+	return PWN_OK;
+}
+
 extern "C" int pwn_trace_screen_centred(pwn_ctx *c, const float cam[16], float sec, uint32_t *sbuf, float *zbuf)
 {
 	if(GRP_HEAD(c)) return pwn_group_trace_screen_centred(c, cam, sec, sbuf, zbuf);
@@ -1355,10 +1384,7 @@ extern "C" int pwn_trace_screen_centred(pwn_ctx *c, const float cam[16], float s
 	(void)hipSetDevice(c->device);
 	size_t n = (size_t)c->w * (size_t)c->h;
 	hipStream_t s = c->stream;
-	// behind the frames in flight, whichever compute stream their kernels are on
-	if(c->last_frame_done != NULL && c->last_frame_stream != s) HIPCHK(c, hipStreamWaitEvent(s, c->last_frame_done, 0));
-	if(c->last_frame_done != NULL && c->stream2 != NULL && c->last_frame_stream != c->stream2) HIPCHK(c, hipStreamWaitEvent(c->stream2, c->last_frame_done, 0));      // (strips use both)
-	c->last_frame_done = NULL;       // (this call ends with the stream empty)
+	{ const int rc = wait_frames_in_flight(c, s); if(rc != PWN_OK) return rc; }
 	// ---- in row strips, the copies beside the kernels (PWN_OPT_CALL_STRIPS)
 	{
 		int cuts[PWN_CALL_STRIPS_MAX + 1], K = 1;
@@ -1408,6 +1434,96 @@ extern "C" int pwn_trace_screen_centred(pwn_ctx *c, const float cam[16], float s
 	HIPCHK(c, hipEventSynchronize(c->ev[3]));
 	// keep the final frame addressable as d_out for pwn_screen_upscale(NULL,...)
 	if(cur != c->d_out) { c->d_pre = c->d_out; c->d_out = cur; }
+	(void)hipEventElapsedTime(&c->stats.trace_ms, c->ev[0], c->ev[1]);
+	(void)hipEventElapsedTime(&c->stats.blur_ms, c->ev[1], c->ev[2]);
+	(void)hipEventElapsedTime(&c->stats.total_ms, c->ev[0], c->ev[3]);
+	return PWN_OK;
+}
+
+// ---- a batch of views (pwn_trace_views) ----------------------------------------
+
+// Room for n views: the records (PWN_VIEWS_MAX of them, with the first batch) and n planes of each kind.  A larger n moves the
+// depth planes of the slots so far into the new allocation and starts the new slots' planes at 0; the stream is idle behind
+// that before the old planes go (no kernel of an earlier batch reads them: every batch ends with its stream drained).
+static int views_reserve(pwn_ctx *c, int n, hipStream_t s)
+{
+	if(c->h_vrec == NULL)
+	{
+		HIPCHK(c, hipHostMalloc((void **)&c->h_vrec, PWN_VIEWS_MAX * sizeof(pwn_view_rec), hipHostMallocDefault));
+		HIPCHK(c, hipMalloc((void **)&c->d_vrec, PWN_VIEWS_MAX * sizeof(pwn_view_rec)));
+		c->vrec_cap = PWN_VIEWS_MAX;
+	}
+	if(n <= c->views_cap) return PWN_OK;
+	const size_t plane = (size_t)c->w * (size_t)c->h, bytes = (size_t)n * plane * 4;
+	uint32_t *pre = NULL, *out = NULL; float *z = NULL;
+	if(hipMalloc((void **)&pre, bytes) != hipSuccess || hipMalloc((void **)&out, bytes) != hipSuccess || hipMalloc((void **)&z, bytes) != hipSuccess)
+	{
+		(void)hipGetLastError();
+		(void)hipFree(pre); (void)hipFree(out); (void)hipFree(z);
+		snprintf(c->err, sizeof(c->err), "pwn_trace_views: no room for %d views of %d x %d", n, c->w, c->h);
+		return PWN_ENOMEM;
+	}
+	const size_t kept = (size_t)c->views_cap * plane * 4;
+	if(kept > 0) HIPCHK(c, hipMemcpyAsync(z, c->d_vz, kept, hipMemcpyDeviceToDevice, s));
+	HIPCHK(c, hipMemsetAsync((uint8_t *)z + kept, 0, bytes - kept, s));
+	HIPCHK(c, hipStreamSynchronize(s));
+	(void)hipFree(c->d_vpre); (void)hipFree(c->d_vout); (void)hipFree(c->d_vz);
+	c->d_vpre = pre; c->d_vout = out; c->d_vz = z; c->views_cap = n;
+	return PWN_OK;
+}
+
+extern "C" int pwn_trace_views(pwn_ctx *c, int n, const float *cams, const float *secs, uint32_t *sbuf, float *zbuf)
+{
+	GRP_REFUSE(c, "pwn_trace_views");
+	if(c == NULL || cams == NULL || secs == NULL || sbuf == NULL || n < 1 || n > PWN_VIEWS_MAX) return PWN_EINVAL;
+	const size_t plane = (size_t)c->w * (size_t)c->h;
+	if((size_t)n * plane > ((size_t)1 << 28)) return PWN_EINVAL;
+	if(c->blur_passes > 0 && (c->w & 3) != 0) return PWN_EINVAL;
+	if(c->tiled != NULL) return PWN_EBUSY;
+	if(!c->have_level) return PWN_ENOLEVEL;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = c->stream;
+	int rc = wait_frames_in_flight(c, s);
+	if(rc != PWN_OK) return rc;
+	rc = views_reserve(c, n, s);
+	if(rc != PWN_OK) return rc;
+	// every view's record from the blocking call's own set-up (frame_setup: this file's operation order is part of the bit-exact path)
+	bool has_w = false;
+	for(int i = 0; i < n; i++)
+	{
+		const float *cam = cams + 16 * (size_t)i;
+		pwn_trace_params P;
+		frame_setup(c->w, c->h, cam, &P);
+		pwn_view_rec &r = c->h_vrec[i];
+		memcpy(r.rayb, P.rayb, sizeof(r.rayb)); memcpy(r.rdx, P.rdx, sizeof(r.rdx));
+		memcpy(r.rdy, P.rdy, sizeof(r.rdy)); memcpy(r.from, P.from, sizeof(r.from));
+		r.sec_current = secs[i];
+		r.pad_[0] = r.pad_[1] = r.pad_[2] = 0.0f;
+		if(!(cam[3] == 0.0f && cam[7] == 0.0f && cam[11] == 0.0f && cam[15] == 1.0f)) has_w = true;
+	}
+	HIPCHK(c, hipEventRecord(c->ev[0], s));
+	// (the staging is free again: the call before this one ended with the stream drained)
+	HIPCHK(c, pwn_launch_upload(c->h_vrec, c->d_vrec, (size_t)n * sizeof(pwn_view_rec), s));
+	pwn_views_launch V;
+	V.d_recs = c->d_vrec; V.n = n; V.has_w = has_w; V.plane = plane;
+	c->trace_views = &V;
+	rc = pwn_i_launch_trace(c, cams, secs[0], 0, c->h, c->d_vpre, c->d_vz, s);
+	c->trace_views = NULL;
+	if(rc != PWN_OK) return rc;
+	HIPCHK(c, hipEventRecord(c->ev[1], s));
+	uint32_t *cur = c->d_vpre, *other = c->d_vout;
+	for(int p = 0; p < c->blur_passes; p++)
+	{
+		c->blur_views = n;
+		rc = pwn_i_launch_blur(c, 0, c->h, cur, c->d_vz, other, s, 0, 0, NULL, NULL, NULL);
+		if(rc != PWN_OK) return rc;
+		uint32_t *t = cur; cur = other; other = t;
+	}
+	HIPCHK(c, hipEventRecord(c->ev[2], s));
+	HIPCHK(c, hipMemcpyAsync(sbuf, cur, (size_t)n * plane * 4, hipMemcpyDeviceToHost, s));
+	if(zbuf != NULL) HIPCHK(c, hipMemcpyAsync(zbuf, c->d_vz, (size_t)n * plane * 4, hipMemcpyDeviceToHost, s));
+	HIPCHK(c, hipEventRecord(c->ev[3], s));
+	HIPCHK(c, hipEventSynchronize(c->ev[3]));
 	(void)hipEventElapsedTime(&c->stats.trace_ms, c->ev[0], c->ev[1]);
 	(void)hipEventElapsedTime(&c->stats.blur_ms, c->ev[1], c->ev[2]);
 	(void)hipEventElapsedTime(&c->stats.total_ms, c->ev[0], c->ev[3]);

@@ -23,6 +23,18 @@ struct pwn_blur_params
 	int tile_h, tile_w, batch;
 	uint32_t *cost_acc, *cost_out;
 	uint32_t cost_mul, cost_div;   // ... scaled on the way: the resident grid over the grid the trace ran with (PWN_OPT_TRACE_ROOM), so that ranks with and without room compare
+	int views;                     // a batch of views (pwn_trace_views): 0 = one frame; else that many frames, view v's planes at + v * plane
+	unsigned long long plane;
+};
+
+// Set by pwn_trace_views for its next pwn_i_launch_trace only (pwn_ctx.trace_views): the launch traces n views, their records
+// (tables.h pwn_view_rec) already on the device, into planes `plane` pixels apart; has_w: some view's camera has w components
+struct pwn_views_launch
+{
+	const pwn_view_rec *d_recs;
+	int n;
+	bool has_w;
+	unsigned long long plane;
 };
 
 extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream);
@@ -182,6 +194,12 @@ struct pwn_ctx
 	int grid_reserve;                // workgroups the persistent trace grid leaves free (row tiling over RCCL), else 0
 	uint32_t *trace_cost_word;       // likewise: pwn_trace_params.cost_word for the next launch
 	uint32_t *trace_clear_word;      // set by a caller of pwn_i_launch_trace for its next launch: see pwn_trace_params.clear_word
+	const pwn_views_launch *trace_views;   // likewise: the next launch is a batch of views (pwn_trace_views), else NULL
+	int blur_views;                  // ... and the next pwn_i_launch_blur: that many views, planes w * h apart (0 = one frame)
+	// pwn_trace_views: per view slot a pre-blur, a colour and a depth plane (views_cap of each, view-major; the depth planes persist
+	// by slot and are kept when the count grows), the records of the call in pinned staging and on the device
+	uint32_t *d_vpre, *d_vout; float *d_vz; int views_cap;
+	pwn_view_rec *h_vrec, *d_vrec; int vrec_cap;
 	uint32_t *d_tickets; unsigned ticket_set;  // PWN_TICKET_SETS sets of work-queue counters of the trace kernel, used in turn
 	uint32_t *d_scratch; size_t scratch_cap;   // upscale / probe staging
 

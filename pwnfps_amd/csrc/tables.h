@@ -164,7 +164,24 @@ struct pwn_trace_params
 	uint32_t *clear_word;                     // NULL, or a word this launch sets to 0 (the row tiling's miss word of the frame:
 	                                          // the blur of the same frame, behind this launch on the stream, counts in it)
 	uint32_t off_recsph;                      // != 0: the blob holds the per-cell lists with inline sphere records (above); where their "which sphere" array is
+	// A batch of views (pwn_trace_views): NULL, or nviews records below that take the place of rayb ... sec_current per view.  The
+	// launch's units are nviews x the units of one frame, handed out interleaved (trace_kernel.hip); view v's planes start at
+	// sbuf / zbuf + v * plane.  nviews / views_magic / views_shift: unit / nviews as ux_magic / ux_shift divide by tiles_x.
+	const struct pwn_view_rec *views;
+	int nviews;
+	uint32_t views_magic; int views_shift;
+	unsigned long long plane;                 // pixels per view (w * h)
 };
+
+// One view of a batch: the camera set-up of screen.h:43-57 for that view's camera (pwn_api.cpp frame_setup) and its
+// sec_current.  80 bytes; the kernel reads a view's record with scalar loads.
+struct pwn_view_rec
+{
+	float rayb[4], rdx[4], rdy[4], from[4];
+	float sec_current;
+	float pad_[3];
+};
+#define PWN_VIEWS_REC_BYTES 80u
 
 #ifndef PWN_QUEUES
 #define PWN_QUEUES 64u                       /* a power of two <= 64: one lane of a wave looks at each */

@@ -364,7 +364,9 @@ template<bool HAS_W> __device__ __forceinline__ void chain_rounds(Vec<HAS_W> &v,
 // ORDER: the launch writes what every unit cost its wave and / or hands its units out by a table (PWN_OPT_UNIT_ORDER, the
 // wave log).  A template parameter, not a test of the two pointers: as dormant code -- two wave-uniform branches and a
 // clock read per unit -- it cost launches that do not use it 2.5-3 % (profiles/r4/unit_order_dormant_cost.txt).
-template<bool COUNT, bool HAS_W, bool ORDER, bool INL>
+// VIEWS: the launch traces a batch of P.nviews frames of one size (pwn_trace_views): every unit reads its view's camera
+// set-up from P.views and writes that view's planes.  Instantiated with ORDER = false only.
+template<bool COUNT, bool HAS_W, bool ORDER, bool INL, bool VIEWS>
 __global__ void __launch_bounds__(PWN_BLOCK, PWN_MIN_WAVES)
 pwn_trace_kernel(pwn_trace_params P)
 {
@@ -392,6 +394,7 @@ pwn_trace_kernel(pwn_trace_params P)
 	rdx.x = P.rdx[0]; rdx.y = P.rdx[1]; rdx.z = P.rdx[2]; rdx.w = HAS_W ? P.rdx[3] : 0.0f;
 	rdy.x = P.rdy[0]; rdy.y = P.rdy[1]; rdy.z = P.rdy[2]; rdy.w = HAS_W ? P.rdy[3] : 0.0f;
 	from.x = P.from[0]; from.y = P.from[1]; from.z = P.from[2]; from.w = HAS_W ? P.from[3] : 1.0f;
+	float sec_current = P.sec_current;
 
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	const int l16 = lane & 15;
@@ -414,7 +417,7 @@ pwn_trace_kernel(pwn_trace_params P)
 	// the atomic hides behind ~15 us of tracing).  The counters of the NEXT launch of this context
 	// are cleared here (launches of a context are stream-ordered, include/pwnhip.h).
 	const uint32_t units_x = ((uint32_t)P.w + 15u) >> 4;
-	const uint32_t units = units_x * (((uint32_t)(P.y1 - P.y0) + 3u) >> 2);
+	const uint32_t units = units_x * (((uint32_t)(P.y1 - P.y0) + 3u) >> 2) * (VIEWS ? (uint32_t)P.nviews : 1u);
 	if(blockIdx.x == 0 && threadIdx.x < PWN_QUEUES) P.tickets_next[threadIdx.x * PWN_QUEUE_STRIDE] = 0u;
 	if(blockIdx.x == 0 && threadIdx.x == PWN_QUEUES && P.clear_word != NULL) *P.clear_word = 0u;
 	uint32_t q = (blockIdx.x * (PWN_BLOCK / 64) + (uint32_t)wave) % PWN_QUEUES;
@@ -528,12 +531,35 @@ pwn_trace_kernel(pwn_trace_params P)
 		// SLOWER at 4K, three runs -- a wave's scalar instructions issue one at a time and in order)
 		// unit / units_x by the host's reciprocal (pwn_trace_params.ux_magic: exact for every unit < 2^31, pwn_api.cpp
 		// unit_div_magic): two instructions where the compiler's division takes thirteen; frames one unit wide divide
+		// A batch of views: the units are handed out INTERLEAVED, unit = (unit of the frame) * nviews + view, so that the first
+		// tickets of the launch cover every view's middle rows and each view's rows go out middle-out as one frame's do -- the
+		// expensive horizon bands of all views are started first and the cheap edges of all views make up the tail.  (View-major
+		// order would leave the tail to the last views' horizon bands.)  Any order gives the same pixels.  The view number is the
+		// same for the whole wave: its record comes in by scalar loads (constant address space, read-only).
+		uint32_t fu = unit;
+		uint32_t *sbuf = P.sbuf;
+		float *zbuf = P.zbuf;
+		if constexpr(VIEWS)
+		{
+			fu = P.views_shift >= 0 ? __umulhi(unit, P.views_magic) >> P.views_shift : unit;
+			const uint32_t view = (uint32_t)__builtin_amdgcn_readfirstlane((int)(unit - fu * (uint32_t)P.nviews));
+			typedef const __attribute__((address_space(4))) float cfloat;
+			const cfloat *r = (const cfloat *)((uintptr_t)P.views + (uintptr_t)view * PWN_VIEWS_REC_BYTES);
+			rayb.x = r[0]; rayb.y = r[1]; rayb.z = r[2]; rayb.w = HAS_W ? r[3] : 0.0f;
+			rdx.x = r[4]; rdx.y = r[5]; rdx.z = r[6]; rdx.w = HAS_W ? r[7] : 0.0f;
+			rdy.x = r[8]; rdy.y = r[9]; rdy.z = r[10]; rdy.w = HAS_W ? r[11] : 0.0f;
+			from.x = r[12]; from.y = r[13]; from.z = r[14]; from.w = HAS_W ? r[15] : 1.0f;
+			sec_current = r[16];
+			// (the view's planes: 64-bit offsets, a batch may hold 2^28 pixels per plane array)
+			sbuf += (size_t)view * (size_t)P.plane;
+			zbuf += (size_t)view * (size_t)P.plane;
+		}
 		uint32_t k;
 		// (ux_shift < 0 only for units_x == 1, pwn_api.cpp unit_div_magic: then k = unit.  A real division here had its
 		// reciprocal hoisted to the top of the kernel and, in the 4-lane variant, parked in scratch memory)
-		if(P.ux_shift >= 0) k = __umulhi(unit, P.ux_magic) >> P.ux_shift;
-		else k = unit;
-		const uint32_t ux = unit - k * units_x;
+		if(P.ux_shift >= 0) k = __umulhi(fu, P.ux_magic) >> P.ux_shift;
+		else k = fu;
+		const uint32_t ux = fu - k * units_x;
 		const uint32_t rows_u = ((uint32_t)(P.y1 - P.y0) + 3u) >> 2;
 		// ... of the FRAME: a strip of a row tiling starts at its rows nearest the frame's middle row (the strip of
 		// the whole frame at its own middle), not at its own middle
@@ -601,8 +627,8 @@ pwn_trace_kernel(pwn_trace_params P)
 
 			float ox, oy, oz, ow;
 			const uint32_t o = __umul24((uint32_t)y, (uint32_t)P.w) + (uint32_t)x;      // w, h <= 32768 (pwn_init)
-			trace_pixel<COUNT, HAS_W, INL>(L, P.sec_current, seed, from, rayl, ox, oy, oz, ow, P.zbuf + o, cnt);
-			P.sbuf[o] = col_pack4(ox, oy, oz, ow);
+			trace_pixel<COUNT, HAS_W, INL>(L, sec_current, seed, from, rayl, ox, oy, oz, ow, zbuf + o, cnt);
+			sbuf[o] = col_pack4(ox, oy, oz, ow);
 		}
 		// what this unit cost its wave (the add chain and the ticket arithmetic in front of it are the same for every unit)
 		if(ORDER && P.unit_cost != NULL && ln == 0u)
@@ -673,7 +699,7 @@ pwn_trace_kernel(pwn_trace_params P)
 	}
 }
 
-template<bool COUNT, bool HAS_W, bool ORDER, bool INL>
+template<bool COUNT, bool HAS_W, bool ORDER, bool INL, bool VIEWS>
 static hipError_t launch_variant(const pwn_trace_params *P, int grid, size_t lds_bytes, hipStream_t stream)
 {
 	// the dynamic-LDS limit is a per-function attribute: raise it only when the blob grew
@@ -691,28 +717,37 @@ static hipError_t launch_variant(const pwn_trace_params *P, int grid, size_t lds
 			// the kernel addresses its tables from LDS address 0 (trace_common.h): that holds while it has no
 			// static LDS, which would be laid out in front of the dynamic allocation
 			hipFuncAttributes fa;
-			hipError_t e = hipFuncGetAttributes(&fa, (const void *)pwn_trace_kernel<COUNT, HAS_W, ORDER, INL>);
+			hipError_t e = hipFuncGetAttributes(&fa, (const void *)pwn_trace_kernel<COUNT, HAS_W, ORDER, INL, VIEWS>);
 			if(e != hipSuccess) return e;
 			if(fa.sharedSizeBytes != 0) return hipErrorInvalidConfiguration;
-			e = hipFuncSetAttribute((const void *)pwn_trace_kernel<COUNT, HAS_W, ORDER, INL>,
+			e = hipFuncSetAttribute((const void *)pwn_trace_kernel<COUNT, HAS_W, ORDER, INL, VIEWS>,
 				hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
 			if(e != hipSuccess) return e;
 			lds_set = lds_bytes;
 		}
 	}
-	hipLaunchKernelGGL((pwn_trace_kernel<COUNT, HAS_W, ORDER, INL>), dim3(grid), dim3(PWN_BLOCK), lds_bytes, stream, *P);
+	hipLaunchKernelGGL((pwn_trace_kernel<COUNT, HAS_W, ORDER, INL, VIEWS>), dim3(grid), dim3(PWN_BLOCK), lds_bytes, stream, *P);
 	return hipGetLastError();
 }
 
 template<bool ORDER, bool INL>
 static hipError_t launch_ordered(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
 {
-	if(count) return P->has_w ? launch_variant<true, true, ORDER, INL>(P, grid, lds_bytes, stream) : launch_variant<true, false, ORDER, INL>(P, grid, lds_bytes, stream);
-	return P->has_w ? launch_variant<false, true, ORDER, INL>(P, grid, lds_bytes, stream) : launch_variant<false, false, ORDER, INL>(P, grid, lds_bytes, stream);
+	if(count) return P->has_w ? launch_variant<true, true, ORDER, INL, false>(P, grid, lds_bytes, stream) : launch_variant<true, false, ORDER, INL, false>(P, grid, lds_bytes, stream);
+	return P->has_w ? launch_variant<false, true, ORDER, INL, false>(P, grid, lds_bytes, stream) : launch_variant<false, false, ORDER, INL, false>(P, grid, lds_bytes, stream);
+}
+
+// a batch of views (pwn_trace_views): the eight VIEWS variants, never ordered
+template<bool INL>
+static hipError_t launch_views(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
+{
+	if(count) return P->has_w ? launch_variant<true, true, false, INL, true>(P, grid, lds_bytes, stream) : launch_variant<true, false, false, INL, true>(P, grid, lds_bytes, stream);
+	return P->has_w ? launch_variant<false, true, false, INL, true>(P, grid, lds_bytes, stream) : launch_variant<false, false, false, INL, true>(P, grid, lds_bytes, stream);
 }
 
 extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
 {
+	if(P->views != NULL) return P->off_recsph != 0u ? launch_views<true>(P, grid, lds_bytes, count, stream) : launch_views<false>(P, grid, lds_bytes, count, stream);
 	// (the blob says which form its per-cell lists have: pack_blob, pwn_api.cpp)
 	if(P->off_recsph != 0u)
 	{
@@ -736,10 +771,10 @@ extern "C" int pwn_trace_blocks_per_cu(size_t lds_bytes, bool count, bool has_w)
 {
 	int n = 0;
 	hipError_t e;
-	if(count) e = has_w ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pwn_trace_kernel<true, true, false, false>, PWN_BLOCK, lds_bytes)
-	                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pwn_trace_kernel<true, false, false, false>, PWN_BLOCK, lds_bytes);
-	else e = has_w ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pwn_trace_kernel<false, true, false, false>, PWN_BLOCK, lds_bytes)
-	               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pwn_trace_kernel<false, false, false, false>, PWN_BLOCK, lds_bytes);
+	if(count) e = has_w ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pwn_trace_kernel<true, true, false, false, false>, PWN_BLOCK, lds_bytes)
+	                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pwn_trace_kernel<true, false, false, false, false>, PWN_BLOCK, lds_bytes);
+	else e = has_w ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pwn_trace_kernel<false, true, false, false, false>, PWN_BLOCK, lds_bytes)
+	               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pwn_trace_kernel<false, false, false, false, false>, PWN_BLOCK, lds_bytes);
 	if(e != hipSuccess || n < 1) n = 2;
 	return n;
 }

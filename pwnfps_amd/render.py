@@ -229,6 +229,28 @@ class Renderer:
                   "pwn_trace_screen_centred")
         return (sbuf, zbuf) if want_z else sbuf
 
+    def trace_views(self, cams, secs, want_z=True):
+        """pwn_trace_views: n views of this context's size in one call.  cams (n,4,4) or (n,16), secs (n,).  Returns (n,h,w)
+        uint32 colour and, with want_z, (n,h,w) float32 depth; view i as trace_screen_centred(cams[i], secs[i]) renders it."""
+        cams = np.asarray(cams)
+        if cams.ndim == 3 and cams.shape[1:] == (4, 4):
+            cams = cams.reshape(cams.shape[0], 16)
+        if cams.ndim != 2 or cams.shape[1] != 16 or cams.shape[0] < 1:
+            raise ValueError("trace_views: cams must have shape (n,4,4) or (n,16) with n >= 1, not %s" % (cams.shape,))
+        n = cams.shape[0]
+        if n > _lib.PWN_VIEWS_MAX:
+            raise ValueError("trace_views: %d views, at most %d" % (n, _lib.PWN_VIEWS_MAX))
+        secs = np.asarray(secs)
+        if secs.shape != (n,):
+            raise ValueError("trace_views: secs must have shape (%d,), not %s" % (n, secs.shape))
+        cams = np.ascontiguousarray(cams, np.float32)
+        secs = np.ascontiguousarray(secs, np.float32)
+        sbuf = np.empty((n, self.h, self.w), np.uint32)
+        zbuf = np.empty((n, self.h, self.w), np.float32) if want_z else None
+        self._chk(lib.pwn_trace_views(self._ctx, n, cams.ctypes.data, secs.ctypes.data, sbuf.ctypes.data,
+                                      zbuf.ctypes.data if want_z else None), "pwn_trace_views")
+        return (sbuf, zbuf) if want_z else sbuf
+
     def set_call_strips(self, n):
         """PWN_OPT_CALL_STRIPS: -1 = by frame size (default), 0 = one launch per pass, 2..32 = that many row strips"""
         self._chk(lib.pwn_set_option(self._ctx, _lib.PWN_OPT_CALL_STRIPS, int(n)), "pwn_set_option(CALL_STRIPS)")
