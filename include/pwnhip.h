@@ -329,6 +329,58 @@ int pwn_call_strips_state(pwn_ctx *ctx, unsigned long long out[6]);
 int pwn_trace_views(pwn_ctx *ctx, int n, const float *cams, const float *secs, uint32_t *sbuf, float *zbuf);
 
 /*
+ * Caller-supplied rays: trace_ray(0, &seed_i, lv, &depth_i, &origin_i, &dir_i, {1,1,1,1}) (trace.h:186, called as at
+ * screen.h:22-24) for n rays of the caller's choosing, on the context's current level and object table with sec_current:
+ * hitscan and line of sight ("how far along this direction is the first thing, through portals and past spheres"), picking
+ * under the crosshair, projections other than the pinhole (panoramas, fisheyes, cube-map faces: the caller computes the rays).
+ *   ray record     8 floats, 32 B: origin x y z w, then direction x y z w (the two vec4 of trace_ray).  n records, back to back.
+ *   seed           seeds[i] is *seed as trace_ray is entered: pwn_pixel_rays below gives pixel (x, y)'s of a w-wide frame
+ *                  (screen.h:19-21).  The device doubles it internally as the frame path does (lcg2_fs).
+ *   colour         col[i] = col_ftoint of trace_ray's value, BGRA8 as a pixel of sbuf (before any blur: ray batches are not blurred).
+ *   depth          in / out: on entry the value the ray keeps if its primary segment runs out of steps (trace.h:677), on return
+ *                  the primary hit's distance (trace.h:102-105).
+ *   w lanes        a batch whose records all have origin.w == 1 and direction.w == 0 runs the 3-lane kernel variants, any other
+ *                  the 4-lane ones (the rule pwn_trace_screen_centred applies to cameras; PWN_DBG_FORCE_HASW forces 4 lanes and
+ *                  changes no result).  The device form is told which by its flags: without PWN_RAYS_HAS_W the w lanes are
+ *                  taken as 1 and 0, whatever the records hold.
+ *   exactness      ray i is bit-identical, colour and depth, to pixel (x, y) of pwn_trace_screen_centred's pre-blur frame
+ *                  (PWN_OPT_BLUR_PASSES 0) when its record and seed are pwn_pixel_rays' for that pixel and its depth on entry is
+ *                  the frame's depth plane there; the same contract as the frames' with the reference.
+ *   empty batch    n == 0 is PWN_OK once the arguments pass the checks below, and launches nothing.
+ *   ordering       pwn_trace_rays (host memory, blocking) waits behind the frames in flight as pwn_trace_screen_centred does and
+ *                  ends with its stream drained.  pwn_trace_rays_device is ONE trace launch on `stream` (device pointers,
+ *                  stream-ordered, no synchronisation) under the rule for trace launches at the top of this file.
+ *   counters       with PWN_OPT_COUNTERS on, the counting variant runs and pwn_get_stats returns its rays, steps, portals,
+ *                  sphere tests and exhausted rays.  pwn_trace_rays also sets trace_ms (upload and trace) and total_ms; blur_ms 0.
+ *   not followed   always the units scheduler, never refill (PWN_OPT_SCHEDULER); PWN_OPT_UNIT_ORDER, PWN_OPT_WAVE_LOG and
+ *                  PWN_OPT_CALL_STRIPS do not apply; no blur.
+ *   left alone     the blocking call's planes and their depth persistence, pwn_screen_upscale(NULL, ...), the view slots of
+ *                  pwn_trace_views, the unit-order state, the trace-room measurement, the call-strips calibration window.
+ *   cost           pwn_trace_rays keeps 44 B per ray of pinned host memory and as much device memory between calls, grown to
+ *                  the largest batch so far (at least 4096 rays); pwn_destroy frees them.
+ *   errors         PWN_EINVAL: NULL ctx, NULL rays with n > 0, n < 0, n > PWN_RAYS_MAX, col and depth both NULL (host form),
+ *                  d_col or d_depth NULL with n > 0 (device form), flags other than PWN_RAYS_HAS_W, d_rays not 16-byte aligned or d_seeds /
+ *                  d_col / d_depth not 4-byte aligned; PWN_ENOLEVEL before a level; PWN_ENOTSUP on a pwn_init_multi handle;
+ *                  PWN_EBUSY while the context runs a row tiling (pwn_tiled_init); PWN_ENOMEM when the host form's buffers
+ *                  cannot grow.
+ */
+#define PWN_RAYS_HAS_W 1            /* flags of pwn_trace_rays_device: honour the w lanes of the records */
+#define PWN_RAYS_MAX (1 << 28)
+/* Host only, no context and no GPU: the ray record (rays: n x 8 floats) and, unless seeds is NULL, the seed of pixels
+   (xy[2i], xy[2i+1]) of a width x height frame of camera cam, computed exactly as the frame kernel does (frame_setup, then the
+   add chain of screen.h:12-18 in the reference build's order, under FTZ|DAZ as the device and the reference executable).
+   Tracing them reproduces that frame's pre-blur colour and depth at those pixels.  PWN_EINVAL: cam NULL, xy or rays NULL with
+   n > 0, n < 0, n > PWN_RAYS_MAX, a pixel outside the frame, width or height outside pwn_init's 1..32768. */
+int pwn_pixel_rays(int width, int height, const float cam[16], int n, const int32_t *xy, float *rays, uint32_t *seeds);
+/* Blocking, host memory.  seeds NULL: every seed 0.  col or depth may be NULL (not both); depth NULL: every ray starts at 0. */
+int pwn_trace_rays(pwn_ctx *ctx, int n, const float *rays, const uint32_t *seeds, float sec_current,
+	uint32_t *col, float *depth);
+/* Device pointers, stream-ordered on `stream` (a hipStream_t, NULL = default stream) like pwn_trace_rows_device: d_rays 16-byte
+   aligned, d_seeds NULL (every seed 0) or n uint32, d_col n uint32 and d_depth n floats (in / out), both required for n > 0. */
+int pwn_trace_rays_device(pwn_ctx *ctx, int n, const void *d_rays, const void *d_seeds, float sec_current, int flags,
+	void *d_col, void *d_depth, void *stream);
+
+/*
  * Frames in flight.  The reference presents every frame on the host
  * (trace_screen_centred fills sbuf, screen_upscale fills screen->pixels, SDL_Flip:
  * main.c:107-109).  Over PCIe that hand-over takes longer than the kernels of a

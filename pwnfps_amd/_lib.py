@@ -25,6 +25,8 @@ PWN_MAX_SLOTS = 4
 PWN_FRAME_SBUF, PWN_FRAME_ZBUF, PWN_FRAME_SURFACE = 1, 2, 4
 PWN_OBJ_MAX = 10000
 PWN_VIEWS_MAX = 1024
+PWN_RAYS_HAS_W = 1
+PWN_RAYS_MAX = 1 << 28
 (PROBE_RCP, PROBE_RSQRT, PROBE_SINF, PROBE_COSF, PROBE_EXPF, PROBE_SQRT, PROBE_DIV,
  PROBE_FTOINT, PROBE_RANDFS, PROBE_SIN_OF_PAIR, PROBE_COS_OF_PAIR) = range(11)
 
@@ -106,6 +108,9 @@ ABI = [
     ("pwn_host_unregister", _i, [_vp, _vp]),
     ("pwn_call_strips_state", _i, [_vp, _vp]),
     ("pwn_trace_views", _i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    ("pwn_pixel_rays", _i, [_i, _i, _vp, _i, _vp, _vp, _vp]),
+    ("pwn_trace_rays", _i, [_vp, _i, _vp, _vp, _f, _vp, _vp]),
+    ("pwn_trace_rays_device", _i, [_vp, _i, _vp, _vp, _f, _i, _vp, _vp, _vp]),
     ("pwn_frames_config", _i, [_vp, _i, _i, _i, _i]),
     ("pwn_submit_frame", _i, [_vp, _vp, _f, _i]),
     ("pwn_wait_frame", _i, [_vp, _i, C.POINTER(Frame)]),

@@ -10,6 +10,7 @@
 #include <time.h>
 #include <new>
 #include <vector>
+#include <xmmintrin.h>      // pwn_pixel_rays: FTZ|DAZ
 
 #include "pwnhip.h"
 #include "pwn_internal.h"
@@ -92,6 +93,7 @@ extern "C" int pwn_init(pwn_ctx **out, int device, int width, int height)
 	c->trace_clear_word = NULL; c->trace_cost_word = NULL; c->trace_tables_event = NULL; c->grid_reserve = 0;
 	c->trace_views = NULL; c->blur_views = 0;
 	c->d_vpre = c->d_vout = NULL; c->d_vz = NULL; c->views_cap = 0; c->h_vrec = c->d_vrec = NULL; c->vrec_cap = 0;
+	c->trace_rays = NULL; c->h_rays = c->d_rays = NULL; c->rays_cap = 0;
 	memset(&c->room, 0, sizeof(c->room)); c->room.mode = -1; c->launch_room = 0;
 	c->cost_mul = c->cost_div = 1u; c->blur_cost_mul = c->blur_cost_div = 0u;
 	if(const char *e = getenv("PWN_TRACE_ROOM")) if(*e) c->room.mode = atoi(e) < 0 ? -1 : atoi(e);      // (the option's default for every context of a process)
@@ -238,6 +240,8 @@ extern "C" void pwn_destroy(pwn_ctx *c)
 	(void)hipFree(c->d_wave_log);
 	(void)hipFree(c->d_vpre); (void)hipFree(c->d_vout); (void)hipFree(c->d_vz); (void)hipFree(c->d_vrec);
 	if(c->h_vrec) (void)hipHostFree(c->h_vrec);
+	(void)hipFree(c->d_rays);
+	if(c->h_rays) (void)hipHostFree(c->h_rays);
 	for(int i = 0; i < 4; i++) { (void)hipFree(c->order[i].d_cost); (void)hipFree(c->order[i].d_perm); }
 	(void)hipFree(c->d_skip); (void)hipFree(c->d_counters); (void)hipFree(c->d_tickets); (void)hipFree(c->d_scratch);
 	delete c;
@@ -751,6 +755,44 @@ static void frame_setup(int w, int h, const float cam[16], pwn_trace_params *P)
 	}
 }
 
+// The ray record and seed of pixels (x, y) of a frame, exactly as the trace kernel makes them: frame_setup, then screen.h:12-18
+// in the reference build's order, rayl = (cx*rdx + rayb) + y*rdy and one "+= rdx" per pixel of the 32-wide tile up to and
+// including this one.  The chain runs under FTZ|DAZ, as the device does and as the reference executable does (crtfastmath.o), so
+// that a denormal camera gives the frame's rays; frame_setup runs in the default mode, as for the frame launches.
+extern "C" int pwn_pixel_rays(int width, int height, const float cam[16], int n, const int32_t *xy, float *rays, uint32_t *seeds)
+{
+	if(cam == NULL || n < 0 || n > PWN_RAYS_MAX || width <= 0 || height <= 0 || width > 32768 || height > 32768) return PWN_EINVAL;
+	if(n > 0 && (xy == NULL || rays == NULL)) return PWN_EINVAL;
+	for(int i = 0; i < n; i++)
+		if(xy[2 * i] < 0 || xy[2 * i] >= width || xy[2 * i + 1] < 0 || xy[2 * i + 1] >= height) return PWN_EINVAL;
+	pwn_trace_params P;
+	frame_setup(width, height, cam, &P);
+	const unsigned csr = _mm_getcsr();
+	_mm_setcsr(csr | 0x8040u);
+	for(int i = 0; i < n; i++)
+	{
+		const int x = xy[2 * i], y = xy[2 * i + 1], cx0 = x & ~31;
+		float *r = rays + 8 * (size_t)i;
+		for(int k = 0; k < 4; k++)
+		{
+			float v = ((float)cx0 * P.rdx[k] + P.rayb[k]) + (float)y * P.rdy[k];
+			for(int j = cx0; j <= x; j++) v += P.rdx[k];
+			r[k] = P.from[k];
+			r[4 + k] = v;
+		}
+		if(seeds != NULL)
+		{
+			// screen.h:19-21 (uint32 wrap-around)
+			uint32_t sd = (uint32_t)x + (uint32_t)y * (uint32_t)y * ((uint32_t)width + 1u);
+			sd *= sd * sd;
+			sd *= sd * sd;
+			seeds[i] = sd;
+		}
+	}
+	_mm_setcsr(csr);
+	return PWN_OK;
+}
+
 // the unit-order entry of a stream (pwn_internal.h); NULL: none to spare right now
 static pwn_ctx::unit_order_state *order_entry(pwn_ctx *c, hipStream_t stream, bool make)
 {
@@ -803,6 +845,9 @@ int pwn_i_launch_trace(pwn_ctx *c, const float cam[16], float sec, int y0, int y
 	c->trace_tables_event = NULL;
 	const pwn_views_launch *views = c->trace_views;       // (pwn_trace_views)
 	c->trace_views = NULL;
+	const pwn_rays_launch *rays = c->trace_rays;          // (pwn_trace_rays)
+	c->trace_rays = NULL;
+	const bool batch = views != NULL || rays != NULL;
 	if(!c->have_level) return PWN_ENOLEVEL;
 	if(c->blob_dirty) { int rc = pack_blob(c); if(rc != PWN_OK) return rc; }
 	if(y1 == y0) return PWN_OK;
@@ -824,6 +869,12 @@ int pwn_i_launch_trace(pwn_ctx *c, const float cam[16], float sec, int y0, int y
 		P.views = views->d_recs; P.nviews = views->n; P.plane = views->plane;
 		unit_div_magic((uint32_t)views->n, &P.views_magic, &P.views_shift);
 		P.tiles_total *= views->n;
+	}
+	// a batch of rays: 64 to a unit (the camera set-up above is not read)
+	if(rays != NULL)
+	{
+		P.rays = rays->d_rays; P.ray_seeds = rays->d_seeds; P.nrays = rays->n; P.ray_w = rays->has_w ? 1 : 0;
+		P.tiles_total = (int)((rays->n + 63u) / 64u);
 	}
 	P.blob_bytes = (uint32_t)c->blob.size();
 	P.off_sph = c->off_sph;
@@ -854,12 +905,13 @@ int pwn_i_launch_trace(pwn_ctx *c, const float cam[16], float sec, int y0, int y
 	// 3-lane specialisation for them that is arithmetically identical
 	P.has_w = !(cam[3] == 0.0f && cam[7] == 0.0f && cam[11] == 0.0f && cam[15] == 1.0f);
 	if(views != NULL) P.has_w = views->has_w;        // (the same rule over all the batch's cameras)
+	if(rays != NULL) P.has_w = rays->has_w;          // (the rule over the batch's rays: pwn_trace_rays)
 	// test hook (tests/test_gpu_fuzz.py): send every camera through the general variant
 	if(c->dbg_force_hasw) P.has_w = 1;
 	if(c->counters_on) HIPCHK(c, hipMemsetAsync(c->d_counters, 0, PWN_NCOUNTERS * sizeof(unsigned long long), stream));
 	// persistent grid: as many workgroups as are resident at once, each striding over tiles
-	// (a batch of views always runs the units scheduler)
-	const bool refill = c->scheduler == PWN_SCHED_REFILL && views == NULL;
+	// (a batch of views or rays always runs the units scheduler)
+	const bool refill = c->scheduler == PWN_SCHED_REFILL && !batch;
 	const size_t lds_bytes = ((P.blob_bytes + 15u) & ~15u) + (refill ? pwn_trace_refill_lds_extra(P.has_w != 0) : pwn_trace_lds_extra());
 	// resident workgroups per CU depend on (LDS bytes, kernel variant) only: ask once per combination
 	P.scheduler = c->scheduler;
@@ -904,7 +956,7 @@ int pwn_i_launch_trace(pwn_ctx *c, const float cam[16], float sec, int y0, int y
 	}
 	// PWN_OPT_WAVE_LOG: every wave of this launch writes its start and end time; entry 0 is unused, entry
 	// 1 + 4 * workgroup + SIMD is a wave's (the buffer follows the grid of the launch)
-	if(c->wave_log_on && views == NULL)
+	if(c->wave_log_on && !batch)
 	{
 		const size_t entries = (size_t)grid * 4 + 1;
 		if(entries > c->wave_log_cap)
@@ -921,9 +973,9 @@ int pwn_i_launch_trace(pwn_ctx *c, const float cam[16], float sec, int y0, int y
 	// and hands its units out in the order sorted from the last launch of the same rows on this stream
 	// (with the wave log only where the dump is asked for, PWN_DBG_UNIT_COST: the kernel variant that writes the costs is 2-3 % slower,
 	// and the wave log's span and residency are figures of the ordinary launch)
-	// (a batch of views neither writes nor reads nor invalidates any of this)
-	const bool want_cost = !refill && views == NULL && (c->unit_order || (c->wave_log_on && getenv("PWN_DBG_UNIT_COST") != NULL));
-	pwn_ctx::unit_order_state *uop = views != NULL ? NULL : order_entry(c, stream, want_cost);
+	// (a batch of views or rays neither writes nor reads nor invalidates any of this)
+	const bool want_cost = !refill && !batch && (c->unit_order || (c->wave_log_on && getenv("PWN_DBG_UNIT_COST") != NULL));
+	pwn_ctx::unit_order_state *uop = batch ? NULL : order_entry(c, stream, want_cost);
 	if(uop != NULL && want_cost)
 	{
 		pwn_ctx::unit_order_state &uo = *uop;
@@ -1528,6 +1580,107 @@ extern "C" int pwn_trace_views(pwn_ctx *c, int n, const float *cams, const float
 	(void)hipEventElapsedTime(&c->stats.blur_ms, c->ev[1], c->ev[2]);
 	(void)hipEventElapsedTime(&c->stats.total_ms, c->ev[0], c->ev[3]);
 	return PWN_OK;
+}
+
+// ---- a batch of rays (pwn_trace_rays) --------------------------------------------
+
+// (the camera a ray launch hands pwn_i_launch_trace: its set-up is not read)
+static const float rays_no_cam[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
+
+// Room for n rays of the host form, kept across calls: pinned staging and a device buffer of the same layout, for a call of n rays
+// the records at 0, the seeds at 32 n, the depths at 36 n and the colours at 40 n -- one copy up (records, seeds, depths) and one
+// down (depths, colours).  Grows to at least twice the old size; no kernel uses the old buffers (every call ends with its stream drained).
+static int rays_reserve(pwn_ctx *c, size_t n)
+{
+	if(n <= c->rays_cap) return PWN_OK;
+	size_t cap = c->rays_cap * 2;
+	if(cap < 4096) cap = 4096;
+	if(cap > PWN_RAYS_MAX) cap = PWN_RAYS_MAX;
+	if(cap < n) cap = n;
+	const size_t bytes = cap * 44 + 16;            // (+16: the upload kernel copies whole 16-byte words)
+	unsigned char *h = NULL, *d = NULL;
+	if(hipHostMalloc((void **)&h, bytes, hipHostMallocDefault) != hipSuccess || hipMalloc((void **)&d, bytes) != hipSuccess)
+	{
+		(void)hipGetLastError();
+		if(h != NULL) (void)hipHostFree(h);
+		(void)hipFree(d);
+		snprintf(c->err, sizeof(c->err), "pwn_trace_rays: no room for %zu rays", n);
+		return PWN_ENOMEM;
+	}
+	if(c->h_rays != NULL) (void)hipHostFree(c->h_rays);
+	(void)hipFree(c->d_rays);
+	c->h_rays = h; c->d_rays = d; c->rays_cap = cap;
+	return PWN_OK;
+}
+
+// the checks both forms share (include/pwnhip.h)
+static int rays_refuse(pwn_ctx *c)
+{
+	if(c->tiled != NULL) return PWN_EBUSY;
+	if(!c->have_level) return PWN_ENOLEVEL;
+	return PWN_OK;
+}
+
+extern "C" int pwn_trace_rays(pwn_ctx *c, int n, const float *rays, const uint32_t *seeds, float sec, uint32_t *col, float *depth)
+{
+	GRP_REFUSE(c, "pwn_trace_rays");
+	if(c == NULL || n < 0 || n > PWN_RAYS_MAX || (n > 0 && rays == NULL) || (col == NULL && depth == NULL)) return PWN_EINVAL;
+	int rc = rays_refuse(c);
+	if(rc != PWN_OK || n == 0) return rc;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = c->stream;
+	rc = wait_frames_in_flight(c, s);
+	if(rc != PWN_OK) return rc;
+	rc = rays_reserve(c, (size_t)n);
+	if(rc != PWN_OK) return rc;
+	const size_t N = (size_t)n;
+	unsigned char *h = c->h_rays, *d = c->d_rays;
+	memcpy(h, rays, 32 * N);
+	if(seeds != NULL) memcpy(h + 32 * N, seeds, 4 * N); else memset(h + 32 * N, 0, 4 * N);
+	if(depth != NULL) memcpy(h + 36 * N, depth, 4 * N); else memset(h + 36 * N, 0, 4 * N);
+	// the 3-lane variants where every record has the w lanes of an ordinary camera's rays (pwn_i_launch_trace's rule for cameras)
+	bool has_w = false;
+	for(size_t i = 0; i < N && !has_w; i++) has_w = !(rays[8 * i + 3] == 1.0f && rays[8 * i + 7] == 0.0f);
+	HIPCHK(c, hipEventRecord(c->ev[0], s));
+	// (small batches by the upload kernel, as the view records: a DMA copy queues behind other copies of the device)
+	if(40 * N <= 65536) HIPCHK(c, pwn_launch_upload(h, d, 40 * N, s));
+	else HIPCHK(c, hipMemcpyAsync(d, h, 40 * N, hipMemcpyHostToDevice, s));
+	pwn_rays_launch R;
+	R.d_rays = (const float *)d; R.d_seeds = (const uint32_t *)(d + 32 * N); R.n = (uint32_t)n; R.has_w = has_w;
+	c->trace_rays = &R;
+	rc = pwn_i_launch_trace(c, rays_no_cam, sec, 0, 1, (uint32_t *)(d + 40 * N), (float *)(d + 36 * N), s);
+	c->trace_rays = NULL;
+	if(rc != PWN_OK) return rc;
+	HIPCHK(c, hipEventRecord(c->ev[1], s));
+	const size_t lo = depth != NULL ? 36 * N : 40 * N, hi = col != NULL ? 44 * N : 40 * N;
+	HIPCHK(c, hipMemcpyAsync(h + lo, d + lo, hi - lo, hipMemcpyDeviceToHost, s));
+	HIPCHK(c, hipEventRecord(c->ev[3], s));
+	HIPCHK(c, hipEventSynchronize(c->ev[3]));
+	if(depth != NULL) memcpy(depth, h + 36 * N, 4 * N);
+	if(col != NULL) memcpy(col, h + 40 * N, 4 * N);
+	(void)hipEventElapsedTime(&c->stats.trace_ms, c->ev[0], c->ev[1]);
+	c->stats.blur_ms = 0.0f;
+	(void)hipEventElapsedTime(&c->stats.total_ms, c->ev[0], c->ev[3]);
+	return PWN_OK;
+}
+
+extern "C" int pwn_trace_rays_device(pwn_ctx *c, int n, const void *d_rays, const void *d_seeds, float sec, int flags,
+	void *d_col, void *d_depth, void *stream)
+{
+	GRP_REFUSE(c, "pwn_trace_rays_device");
+	if(c == NULL || n < 0 || n > PWN_RAYS_MAX || (n > 0 && (d_rays == NULL || d_col == NULL || d_depth == NULL)) ||
+	   (flags & ~PWN_RAYS_HAS_W) != 0) return PWN_EINVAL;
+	if(((uintptr_t)d_rays & 15u) != 0 || ((uintptr_t)d_seeds & 3u) != 0 || ((uintptr_t)d_col & 3u) != 0 || ((uintptr_t)d_depth & 3u) != 0)
+		return PWN_EINVAL;
+	const int rc = rays_refuse(c);
+	if(rc != PWN_OK || n == 0) return rc;
+	(void)hipSetDevice(c->device);
+	pwn_rays_launch R;
+	R.d_rays = (const float *)d_rays; R.d_seeds = (const uint32_t *)d_seeds; R.n = (uint32_t)n; R.has_w = (flags & PWN_RAYS_HAS_W) != 0;
+	c->trace_rays = &R;
+	const int lrc = pwn_i_launch_trace(c, rays_no_cam, sec, 0, 1, (uint32_t *)d_col, (float *)d_depth, (hipStream_t)stream);
+	c->trace_rays = NULL;
+	return lrc;
 }
 
 // ---- frames in flight ---------------------------------------------------------

@@ -37,6 +37,16 @@ struct pwn_views_launch
 	unsigned long long plane;
 };
 
+// Set by pwn_trace_rays / pwn_trace_rays_device for their next pwn_i_launch_trace only (pwn_ctx.trace_rays): the launch traces n
+// caller-supplied rays (tables.h pwn_trace_params.rays) into d_col / d_depth; has_w: their w lanes count (PWN_RAYS_HAS_W)
+struct pwn_rays_launch
+{
+	const float *d_rays;
+	const uint32_t *d_seeds;
+	uint32_t n;
+	bool has_w;
+};
+
 extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream);
 extern "C" hipError_t pwn_launch_trace_refill(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream);
 extern "C" unsigned pwn_trace_refill_lds_extra(bool has_w);
@@ -200,6 +210,9 @@ struct pwn_ctx
 	// by slot and are kept when the count grows), the records of the call in pinned staging and on the device
 	uint32_t *d_vpre, *d_vout; float *d_vz; int views_cap;
 	pwn_view_rec *h_vrec, *d_vrec; int vrec_cap;
+	const pwn_rays_launch *trace_rays;     // set by a caller of pwn_i_launch_trace: the next launch is a batch of rays (pwn_trace_rays), else NULL
+	// pwn_trace_rays: room for rays_cap rays in pinned staging and on the device, 44 B each (record, seed, depth, colour; pwn_api.cpp rays_reserve)
+	unsigned char *h_rays, *d_rays; size_t rays_cap;
 	uint32_t *d_tickets; unsigned ticket_set;  // PWN_TICKET_SETS sets of work-queue counters of the trace kernel, used in turn
 	uint32_t *d_scratch; size_t scratch_cap;   // upscale / probe staging
 

@@ -171,7 +171,17 @@ struct pwn_trace_params
 	int nviews;
 	uint32_t views_magic; int views_shift;
 	unsigned long long plane;                 // pixels per view (w * h)
+	// A batch of caller-supplied rays (pwn_trace_rays): NULL, or nrays records of 8 fp32 (origin x y z w, direction x y z w; 16-byte
+	// aligned) that take the place of the frame: ray i's seed is ray_seeds[i] (NULL: 0), its colour goes to sbuf[i], its depth is
+	// zbuf[i] (in / out).  ray_w = 0: the w lanes are taken as 1 and 0 (PWN_RAYS_HAS_W not given).
+	const float *rays;
+	const uint32_t *ray_seeds;
+	uint32_t nrays;
+	int ray_w;
 };
+
+// what a launch of the trace kernel traces (its MODE parameter, trace_kernel.hip)
+enum { PWN_KM_FRAME = 0, PWN_KM_VIEWS = 1, PWN_KM_RAYS = 2 };
 
 // One view of a batch: the camera set-up of screen.h:43-57 for that view's camera (pwn_api.cpp frame_setup) and its
 // sec_current.  80 bytes; the kernel reads a view's record with scalar loads.

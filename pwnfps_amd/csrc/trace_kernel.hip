@@ -364,12 +364,15 @@ template<bool HAS_W> __device__ __forceinline__ void chain_rounds(Vec<HAS_W> &v,
 // ORDER: the launch writes what every unit cost its wave and / or hands its units out by a table (PWN_OPT_UNIT_ORDER, the
 // wave log).  A template parameter, not a test of the two pointers: as dormant code -- two wave-uniform branches and a
 // clock read per unit -- it cost launches that do not use it 2.5-3 % (profiles/r4/unit_order_dormant_cost.txt).
-// VIEWS: the launch traces a batch of P.nviews frames of one size (pwn_trace_views): every unit reads its view's camera
-// set-up from P.views and writes that view's planes.  Instantiated with ORDER = false only.
-template<bool COUNT, bool HAS_W, bool ORDER, bool INL, bool VIEWS>
+// MODE (tables.h PWN_KM_*): what the launch traces.  PWN_KM_FRAME: rows of one frame.  PWN_KM_VIEWS: a batch of P.nviews frames
+// of one size (pwn_trace_views): every unit reads its view's camera set-up from P.views and writes that view's planes.
+// PWN_KM_RAYS: P.nrays rays of the caller's (pwn_trace_rays): every lane loads its own origin, direction and seed.  The last two are
+// instantiated with ORDER = false only.
+template<bool COUNT, bool HAS_W, bool ORDER, bool INL, int MODE>
 __global__ void __launch_bounds__(PWN_BLOCK, PWN_MIN_WAVES)
 pwn_trace_kernel(pwn_trace_params P)
 {
+	constexpr bool VIEWS = MODE == PWN_KM_VIEWS, RAYS = MODE == PWN_KM_RAYS;
 	//@R k_prologue
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
 
@@ -417,7 +420,8 @@ pwn_trace_kernel(pwn_trace_params P)
 	// the atomic hides behind ~15 us of tracing).  The counters of the NEXT launch of this context
 	// are cleared here (launches of a context are stream-ordered, include/pwnhip.h).
 	const uint32_t units_x = ((uint32_t)P.w + 15u) >> 4;
-	const uint32_t units = units_x * (((uint32_t)(P.y1 - P.y0) + 3u) >> 2) * (VIEWS ? (uint32_t)P.nviews : 1u);
+	// (a batch of rays: 64 to a unit, P.nrays <= 2^28)
+	const uint32_t units = RAYS ? (P.nrays + 63u) >> 6 : units_x * (((uint32_t)(P.y1 - P.y0) + 3u) >> 2) * (VIEWS ? (uint32_t)P.nviews : 1u);
 	if(blockIdx.x == 0 && threadIdx.x < PWN_QUEUES) P.tickets_next[threadIdx.x * PWN_QUEUE_STRIDE] = 0u;
 	if(blockIdx.x == 0 && threadIdx.x == PWN_QUEUES && P.clear_word != NULL) *P.clear_word = 0u;
 	uint32_t q = (blockIdx.x * (PWN_BLOCK / 64) + (uint32_t)wave) % PWN_QUEUES;
@@ -522,7 +526,43 @@ pwn_trace_kernel(pwn_trace_params P)
 		uint32_t next_raw = ticket + 1u;
 #ifndef PWN_DRAW_PROBE
 		if(draw && ln == 0u) next_raw = atomicAdd(&P.tickets[q * PWN_QUEUE_STRIDE], draw_n) + QBASE(q);
+#else
+		if(RAYS && draw && ln == 0u) next_raw = atomicAdd(&P.tickets[q * PWN_QUEUE_STRIDE], draw_n) + QBASE(q);      // (the probe is of frames)
 #endif
+		if constexpr(RAYS)
+		{
+			// A batch of rays (pwn_trace_rays): unit u is rays [64u, 64u + 64), lane j ray 64u + j, handed out in plain order (the
+			// caller's order is the coherence there is: pwn_pixel_rays can lay a frame's pixels out in the units of a frame).  No add
+			// chain: every lane loads its ray record -- origin x y z w, direction x y z w, two 16-byte loads -- and its seed.
+			//
+			// Any bit pattern in any lane (NaN, +-inf, 1e30, a zero direction, an origin far outside the grid) keeps every address in
+			// range.  Global: i < nrays <= 2^28 and 64-bit offsets, so rays + 32 i, seeds + 4 i, sbuf + 4 i and zbuf + 4 i lie in the
+			// caller's buffers of n entries (pwn_api.cpp checks n and the alignment).  LDS, in trace_pixel: the ray is never an index
+			// by itself.  The table reads take (bits >> 12 or 13) & 2047 of a float (dev_math.h: in range for every bit pattern).  The
+			// starting cell is (int)pos, which saturates (NaN converts to 0), pinned to [-16384, 16383] per axis (cxz_pack_start); a
+			// walk step moves it by one; the cell word is read at min(c, 64) per axis as unsigned 16-bit fields (cellword_pk: a negative
+			// coordinate is a large unsigned one), inside the 65 x 65 table.  Portal, sphere-list and sphere offsets come out of that
+			// word and the blob, never out of the ray.  These are the inputs a frame's reflected segments already start from (a
+			// bounce off a NaN or far-away hit): the frame path meets them at a few pixels of the hard scenes, every lane here.
+			const uint32_t i = unit * 64u + ln;
+			if(i < P.nrays)
+			{
+				const pwn_f4 *rec = (const pwn_f4 *)P.rays + 2u * (size_t)i;
+				const pwn_f4 o = rec[0], d = rec[1];
+				uint32_t seed = P.ray_seeds != NULL ? P.ray_seeds[i] : 0u;
+				seed <<= 1;                               // the generator runs on the doubled state (lcg2_fs, dev_math.h)
+				// (without PWN_RAYS_HAS_W the w lanes are those of an ordinary camera's rays, 1 and 0, whichever variant runs)
+				V org, dir;
+				org.x = o.x; org.y = o.y; org.z = o.z; org.w = HAS_W && P.ray_w ? o.w : 1.0f;
+				dir.x = d.x; dir.y = d.y; dir.z = d.z; dir.w = HAS_W && P.ray_w ? d.w : 0.0f;
+				float ox, oy, oz, ow;
+				trace_pixel<COUNT, HAS_W, INL>(L, sec_current, seed, org, dir, ox, oy, oz, ow, P.zbuf + i, cnt);
+				P.sbuf[i] = col_pack4(ox, oy, oz, ow);
+			}
+			ticket = (uint32_t)__builtin_amdgcn_readfirstlane((int)next_raw);
+			left = draw ? draw_n - 1u : left - 1u;
+			continue;
+		}
 		// rows from the middle outwards: the horizon band, where rays run longest,
 		// is started first and the cheap top and bottom edges make up the tail
 		// (this arithmetic is the same for the whole wave, but the compiler does it per lane because q starts
@@ -699,7 +739,7 @@ pwn_trace_kernel(pwn_trace_params P)
 	}
 }
 
-template<bool COUNT, bool HAS_W, bool ORDER, bool INL, bool VIEWS>
+template<bool COUNT, bool HAS_W, bool ORDER, bool INL, int MODE>
 static hipError_t launch_variant(const pwn_trace_params *P, int grid, size_t lds_bytes, hipStream_t stream)
 {
 	// the dynamic-LDS limit is a per-function attribute: raise it only when the blob grew
@@ -717,37 +757,38 @@ static hipError_t launch_variant(const pwn_trace_params *P, int grid, size_t lds
 			// the kernel addresses its tables from LDS address 0 (trace_common.h): that holds while it has no
 			// static LDS, which would be laid out in front of the dynamic allocation
 			hipFuncAttributes fa;
-			hipError_t e = hipFuncGetAttributes(&fa, (const void *)pwn_trace_kernel<COUNT, HAS_W, ORDER, INL, VIEWS>);
+			hipError_t e = hipFuncGetAttributes(&fa, (const void *)pwn_trace_kernel<COUNT, HAS_W, ORDER, INL, MODE>);
 			if(e != hipSuccess) return e;
 			if(fa.sharedSizeBytes != 0) return hipErrorInvalidConfiguration;
-			e = hipFuncSetAttribute((const void *)pwn_trace_kernel<COUNT, HAS_W, ORDER, INL, VIEWS>,
+			e = hipFuncSetAttribute((const void *)pwn_trace_kernel<COUNT, HAS_W, ORDER, INL, MODE>,
 				hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
 			if(e != hipSuccess) return e;
 			lds_set = lds_bytes;
 		}
 	}
-	hipLaunchKernelGGL((pwn_trace_kernel<COUNT, HAS_W, ORDER, INL, VIEWS>), dim3(grid), dim3(PWN_BLOCK), lds_bytes, stream, *P);
+	hipLaunchKernelGGL((pwn_trace_kernel<COUNT, HAS_W, ORDER, INL, MODE>), dim3(grid), dim3(PWN_BLOCK), lds_bytes, stream, *P);
 	return hipGetLastError();
 }
 
 template<bool ORDER, bool INL>
 static hipError_t launch_ordered(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
 {
-	if(count) return P->has_w ? launch_variant<true, true, ORDER, INL, false>(P, grid, lds_bytes, stream) : launch_variant<true, false, ORDER, INL, false>(P, grid, lds_bytes, stream);
-	return P->has_w ? launch_variant<false, true, ORDER, INL, false>(P, grid, lds_bytes, stream) : launch_variant<false, false, ORDER, INL, false>(P, grid, lds_bytes, stream);
+	if(count) return P->has_w ? launch_variant<true, true, ORDER, INL, PWN_KM_FRAME>(P, grid, lds_bytes, stream) : launch_variant<true, false, ORDER, INL, PWN_KM_FRAME>(P, grid, lds_bytes, stream);
+	return P->has_w ? launch_variant<false, true, ORDER, INL, PWN_KM_FRAME>(P, grid, lds_bytes, stream) : launch_variant<false, false, ORDER, INL, PWN_KM_FRAME>(P, grid, lds_bytes, stream);
 }
 
-// a batch of views (pwn_trace_views): the eight VIEWS variants, never ordered
-template<bool INL>
-static hipError_t launch_views(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
+// a batch of views (pwn_trace_views) or of rays (pwn_trace_rays): eight variants each, never ordered
+template<int MODE, bool INL>
+static hipError_t launch_batch(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
 {
-	if(count) return P->has_w ? launch_variant<true, true, false, INL, true>(P, grid, lds_bytes, stream) : launch_variant<true, false, false, INL, true>(P, grid, lds_bytes, stream);
-	return P->has_w ? launch_variant<false, true, false, INL, true>(P, grid, lds_bytes, stream) : launch_variant<false, false, false, INL, true>(P, grid, lds_bytes, stream);
+	if(count) return P->has_w ? launch_variant<true, true, false, INL, MODE>(P, grid, lds_bytes, stream) : launch_variant<true, false, false, INL, MODE>(P, grid, lds_bytes, stream);
+	return P->has_w ? launch_variant<false, true, false, INL, MODE>(P, grid, lds_bytes, stream) : launch_variant<false, false, false, INL, MODE>(P, grid, lds_bytes, stream);
 }
 
 extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
 {
-	if(P->views != NULL) return P->off_recsph != 0u ? launch_views<true>(P, grid, lds_bytes, count, stream) : launch_views<false>(P, grid, lds_bytes, count, stream);
+	if(P->rays != NULL) return P->off_recsph != 0u ? launch_batch<PWN_KM_RAYS, true>(P, grid, lds_bytes, count, stream) : launch_batch<PWN_KM_RAYS, false>(P, grid, lds_bytes, count, stream);
+	if(P->views != NULL) return P->off_recsph != 0u ? launch_batch<PWN_KM_VIEWS, true>(P, grid, lds_bytes, count, stream) : launch_batch<PWN_KM_VIEWS, false>(P, grid, lds_bytes, count, stream);
 	// (the blob says which form its per-cell lists have: pack_blob, pwn_api.cpp)
 	if(P->off_recsph != 0u)
 	{
@@ -771,10 +812,10 @@ extern "C" int pwn_trace_blocks_per_cu(size_t lds_bytes, bool count, bool has_w)
 {
 	int n = 0;
 	hipError_t e;
-	if(count) e = has_w ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pwn_trace_kernel<true, true, false, false, false>, PWN_BLOCK, lds_bytes)
-	                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pwn_trace_kernel<true, false, false, false, false>, PWN_BLOCK, lds_bytes);
-	else e = has_w ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pwn_trace_kernel<false, true, false, false, false>, PWN_BLOCK, lds_bytes)
-	               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pwn_trace_kernel<false, false, false, false, false>, PWN_BLOCK, lds_bytes);
+	if(count) e = has_w ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pwn_trace_kernel<true, true, false, false, PWN_KM_FRAME>, PWN_BLOCK, lds_bytes)
+	                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pwn_trace_kernel<true, false, false, false, PWN_KM_FRAME>, PWN_BLOCK, lds_bytes);
+	else e = has_w ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pwn_trace_kernel<false, true, false, false, PWN_KM_FRAME>, PWN_BLOCK, lds_bytes)
+	               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pwn_trace_kernel<false, false, false, false, PWN_KM_FRAME>, PWN_BLOCK, lds_bytes);
 	if(e != hipSuccess || n < 1) n = 2;
 	return n;
 }

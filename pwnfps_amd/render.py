@@ -251,6 +251,74 @@ class Renderer:
                                       zbuf.ctypes.data if want_z else None), "pwn_trace_views")
         return (sbuf, zbuf) if want_z else sbuf
 
+    # -- caller-supplied rays (pwn_trace_rays) --------------------------------
+    def pixel_rays(self, cam, xy=None, order="rows"):
+        """pixel_rays() at this context's size"""
+        return pixel_rays(self.w, self.h, cam, xy, order)
+
+    def trace_rays(self, rays, seeds=None, sec_current=0.0, depth=None):
+        """pwn_trace_rays: trace_ray (trace.h:186) for n rays of the caller's on this context's level and objects.  rays: (n,8)
+        records (origin x y z w, direction x y z w) or a pair (origins, directions) of (n,3) or (n,4) arrays, missing w lanes
+        1 and 0; seeds (n,) uint32 or None (0); depth (n,) the depth each ray keeps if it runs out of steps, or None (0).
+        Returns (colour (n,) uint32 BGRA8, depth (n,) float32): the pre-blur pixel and primary depth of each ray."""
+        rays = _ray_records(rays, "trace_rays")
+        n = rays.shape[0]
+        if seeds is not None:
+            seeds = np.asarray(seeds)
+            if seeds.shape != (n,):
+                raise ValueError("trace_rays: seeds must have shape (%d,), not %s" % (n, seeds.shape))
+            seeds = np.ascontiguousarray(seeds.astype(np.uint32, copy=False))
+        if depth is None:
+            z = np.zeros(n, np.float32)
+        else:
+            z = np.array(depth, np.float32)
+            if z.shape != (n,):
+                raise ValueError("trace_rays: depth must have shape (%d,), not %s" % (n, z.shape))
+        col = np.empty(n, np.uint32)
+        self._chk(lib.pwn_trace_rays(self._ctx, n, rays.ctypes.data, seeds.ctypes.data if seeds is not None else None,
+                                     float(sec_current), col.ctypes.data, z.ctypes.data), "pwn_trace_rays")
+        return col, z
+
+    def trace_rays_device(self, rays, col, depth, seeds=None, sec_current=0.0, has_w=False, stream=None, n=None):
+        """pwn_trace_rays_device: one trace launch, stream-ordered, no synchronisation.  rays / col / depth / seeds are torch
+        tensors on this context's GPU -- rays (n,8) float32 16-byte aligned, col (n,) int32 or uint32, depth (n,) float32 (in / out),
+        seeds (n,) int32 or uint32 or None -- or raw device pointers, with n given.  has_w: honour the records' w lanes
+        (PWN_RAYS_HAS_W; else they are taken as 1 and 0).  stream: a torch.cuda.Stream or a raw hipStream_t; None = torch's
+        current stream on this device for tensors, the default stream for pointers."""
+        tensors = [t for t in (rays, col, depth, seeds) if t is not None and not isinstance(t, int)]
+        if tensors:
+            import torch
+            if len(tensors) != sum(t is not None for t in (rays, col, depth, seeds)):
+                raise ValueError("trace_rays_device: give all tensors or all device pointers")
+            rays_n = _tensor_check(torch, rays, "rays", (torch.float32,), 2)
+            if n is not None and int(n) != rays_n:
+                raise ValueError("trace_rays_device: n = %d, but rays has %d rows" % (n, rays_n))
+            n = rays_n
+            if rays.shape[1] != 8 or rays.data_ptr() % 16 != 0:
+                raise ValueError("trace_rays_device: rays must be (n,8) and 16-byte aligned")
+            _tensor_check(torch, col, "col", (torch.int32, getattr(torch, "uint32", torch.int32)), 1, n)
+            _tensor_check(torch, depth, "depth", (torch.float32,), 1, n)
+            if seeds is not None:
+                _tensor_check(torch, seeds, "seeds", (torch.int32, getattr(torch, "uint32", torch.int32)), 1, n)
+            for t in tensors:
+                if t.device != rays.device:
+                    raise ValueError("trace_rays_device: tensors on %s and %s" % (rays.device, t.device))
+            if stream is None:
+                stream = torch.cuda.current_stream(rays.device)
+            p_rays, p_col, p_depth = rays.data_ptr(), col.data_ptr(), depth.data_ptr()
+            p_seeds = seeds.data_ptr() if seeds is not None else None
+        else:
+            if n is None:
+                raise ValueError("trace_rays_device: n is needed with device pointers")
+            p_rays, p_col, p_depth, p_seeds = rays, col, depth, seeds
+        if int(n) < 0 or int(n) > _lib.PWN_RAYS_MAX:
+            raise ValueError("trace_rays_device: n = %d, 0 ... %d" % (n, _lib.PWN_RAYS_MAX))
+        if stream is not None and not isinstance(stream, int):
+            stream = stream.cuda_stream
+        self._chk(lib.pwn_trace_rays_device(self._ctx, int(n), C.c_void_p(p_rays), C.c_void_p(p_seeds), float(sec_current),
+                                            _lib.PWN_RAYS_HAS_W if has_w else 0, C.c_void_p(p_col), C.c_void_p(p_depth),
+                                            C.c_void_p(stream or 0)), "pwn_trace_rays_device")
+
     def set_call_strips(self, n):
         """PWN_OPT_CALL_STRIPS: -1 = by frame size (default), 0 = one launch per pass, 2..32 = that many row strips"""
         self._chk(lib.pwn_set_option(self._ctx, _lib.PWN_OPT_CALL_STRIPS, int(n)), "pwn_set_option(CALL_STRIPS)")
@@ -450,6 +518,76 @@ class Renderer:
         out = np.zeros(n, np.uint32)
         self._chk(lib.pwn_probe(self._ctx, int(op), words.ctypes.data, out.ctypes.data, n), "pwn_probe")
         return out
+
+
+def _ray_records(rays, who):
+    """(n,8) float32 records from an (n,8) array or a pair (origins, directions) of (n,3) / (n,4) arrays (w lanes 1 and 0)"""
+    if isinstance(rays, (tuple, list)) and len(rays) == 2:
+        o, d = np.asarray(rays[0]), np.asarray(rays[1])
+        if o.ndim != 2 or d.ndim != 2 or o.shape[0] != d.shape[0] or o.shape[1] not in (3, 4) or d.shape[1] not in (3, 4):
+            raise ValueError("%s: origins and directions must be (n,3) or (n,4) with the same n, not %s and %s" % (who, o.shape, d.shape))
+        rec = np.zeros((o.shape[0], 8), np.float32)
+        rec[:, 3] = 1.0
+        rec[:, :o.shape[1]] = o
+        rec[:, 4:4 + d.shape[1]] = d
+        return rec
+    rays = np.asarray(rays)
+    if rays.ndim != 2 or rays.shape[1] != 8:
+        raise ValueError("%s: rays must have shape (n,8) or be a pair (origins, directions), not %s" % (who, rays.shape))
+    if rays.shape[0] > _lib.PWN_RAYS_MAX:
+        raise ValueError("%s: %d rays, at most %d" % (who, rays.shape[0], _lib.PWN_RAYS_MAX))
+    return np.ascontiguousarray(rays, np.float32)
+
+
+def _tensor_check(torch, t, name, dtypes, ndim, n=None):
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+        raise ValueError("trace_rays_device: %s must be a GPU tensor" % name)
+    if t.dtype not in dtypes or t.dim() != ndim or (n is not None and t.shape[0] != n) or not t.is_contiguous():
+        raise ValueError("trace_rays_device: %s must be a contiguous %s tensor of %d dimension(s)%s, not %s %s" % (
+            name, "/".join(str(d) for d in dtypes), ndim, "" if n is None else " and %d rows" % n, t.dtype, tuple(t.shape)))
+    if t.data_ptr() % 4 != 0:
+        raise ValueError("trace_rays_device: %s is not 4-byte aligned" % name)
+    return t.shape[0]
+
+
+def unit_order_xy(width, height):
+    """every pixel of a width x height frame in the trace kernel's 16x4-pixel units, units row by row, a unit's pixels row by row
+    (pixels outside the frame left out): (w*h, 2) int32 x, y"""
+    uy, ux, r, c = np.meshgrid(np.arange((height + 3) // 4), np.arange((width + 15) // 16), np.arange(4), np.arange(16), indexing="ij")
+    x, y = (ux * 16 + c).ravel(), (uy * 4 + r).ravel()
+    keep = (x < width) & (y < height)
+    return np.stack([x[keep], y[keep]], 1).astype(np.int32)
+
+
+def pixel_rays(width, height, cam, xy=None, order="rows"):
+    """pwn_pixel_rays (no context, no GPU): (rays (n,8) float32, seeds (n,) uint32, xy (n,2) int32) of pixels xy of camera cam's
+    width x height frame, exactly as the frame kernel makes them; trace_rays on them gives that frame's pre-blur colour and depth.
+    xy=None: every pixel, row-major (order="rows") or in the frame kernel's 16x4-pixel units (order="units", unit_order_xy)."""
+    cam = np.asarray(cam)
+    if cam.size != 16:
+        raise ValueError("pixel_rays: cam must have 16 elements, not %s" % (cam.shape,))
+    cam = np.ascontiguousarray(cam, np.float32).reshape(16)
+    width, height = int(width), int(height)
+    if xy is None:
+        if order == "rows":
+            yy, xx = np.meshgrid(np.arange(height), np.arange(width), indexing="ij")
+            xy = np.stack([xx.ravel(), yy.ravel()], 1).astype(np.int32)
+        elif order == "units":
+            xy = unit_order_xy(width, height)
+        else:
+            raise ValueError('pixel_rays: order must be "rows" or "units", not %r' % (order,))
+    else:
+        xy = np.asarray(xy)
+        if xy.ndim != 2 or xy.shape[1] != 2:
+            raise ValueError("pixel_rays: xy must have shape (n,2), not %s" % (xy.shape,))
+        xy = np.ascontiguousarray(xy, np.int32)
+    n = xy.shape[0]
+    rays = np.empty((n, 8), np.float32)
+    seeds = np.empty(n, np.uint32)
+    rc = lib.pwn_pixel_rays(width, height, cam.ctypes.data, n, xy.ctypes.data, rays.ctypes.data, seeds.ctypes.data)
+    if rc < 0:
+        raise PwnError(rc, "pwn_pixel_rays(%dx%d)" % (width, height))
+    return rays, seeds, xy
 
 
 # camera helpers the host uses to pose the view (util.h:61-110; outside the
