@@ -12,31 +12,7 @@
 // the row seed advanced by 32*g draws, done with the precomputed affine
 // skip-ahead (A_g, C_g): s -> (A_g*s + C_g) mod 2^31  (the LCG is affine mod
 // 2^31 because of the & 0x7FFFFFFF).  Reads: 16 B of depth, 16 scattered 4-B
-// taps from the pre-blur frame; write: one 16-B store.
-struct pwn_blur_params
-{
-	int w, h, y0, y1;
-	int groups;                    // w / 4 (screen.h:91: cx < dimx-3)
-	const uint32_t *pre;           // full pre-blur frame ("tsbuf")
-	const float *zbuf;             // full frame depth
-	uint32_t *out;                 // full frame
-	const uint2 *skip;             // groups x (A_g, C_g)
-	// row tiling with a bounded exchange: only rows [avail_y0, avail_y1) of `pre` hold this
-	// frame; a tap that lands outside them makes the kernel add to *miss (the caller then
-	// repeats the strip with the whole frame present).  miss == NULL: every row is valid.
-	int avail_y0, avail_y1;
-	uint32_t *miss;
-	int tile_h, tile_w, batch;     // a workgroup's tile of output pixels (rows, columns) and the form of its staging loop: pwn_i_launch_blur picks
-	                               // them by the size of the launch, pwn_launch_blur has the instantiations
-	// row tiling with moving cuts: the trace launch in front of this one on the stream added up what its strip cost
-	// in *cost_acc (pwn_trace_params.cost_word); this launch moves the sum to *cost_out, the word that travels with
-	// the frame, and clears the accumulator for the stream's next trace.  Both NULL otherwise.
-	uint32_t *cost_acc, *cost_out;
-	uint32_t cost_mul, cost_div;   // ... scaled on the way: the resident grid over the grid the trace ran with (PWN_OPT_TRACE_ROOM), so that ranks with and without room compare
-	// a batch of views (pwn_trace_views): 0 = one frame; else that many frames of w x h, view v's planes at pre / zbuf / out + v * plane
-	int views;
-	unsigned long long plane;
-};
+// taps from the pre-blur frame; write: one 16-B store.  Arguments: pwn_blur_params (tables.h).
 
 __device__ __forceinline__ uint32_t avg_u8x4(uint32_t a, uint32_t b)
 {

@@ -90,12 +90,10 @@ extern "C" int pwn_init(pwn_ctx **out, int device, int width, int height)
 	}
 	for(int i = 0; i < PWN_NSTAGE; i++) { c->h_stage[i] = NULL; c->ev_stage[i] = NULL; c->stage_used[i] = false; }
 	c->d_pre = c->d_out = NULL; c->d_z = NULL; c->d_skip = NULL; c->d_counters = NULL; c->d_tickets = NULL; c->ticket_set = 0; c->launch_rot = 2; c->launch_waits = 0;
-	c->trace_clear_word = NULL; c->trace_cost_word = NULL; c->trace_tables_event = NULL; c->grid_reserve = 0;
-	c->trace_views = NULL; c->blur_views = 0;
+	c->grid_reserve = 0;
 	c->d_vpre = c->d_vout = NULL; c->d_vz = NULL; c->views_cap = 0; c->h_vrec = c->d_vrec = NULL; c->vrec_cap = 0;
-	c->trace_rays = NULL; c->h_rays = c->d_rays = NULL; c->rays_cap = 0;
-	memset(&c->room, 0, sizeof(c->room)); c->room.mode = -1; c->launch_room = 0;
-	c->cost_mul = c->cost_div = 1u; c->blur_cost_mul = c->blur_cost_div = 0u;
+	c->h_rays = c->d_rays = NULL; c->rays_cap = 0;
+	memset(&c->room, 0, sizeof(c->room)); c->room.mode = -1;
 	if(const char *e = getenv("PWN_TRACE_ROOM")) if(*e) c->room.mode = atoi(e) < 0 ? -1 : atoi(e);      // (the option's default for every context of a process)
 	c->d_scratch = NULL; c->scratch_cap = 0;
 	for(int i = 0; i < 8; i++) { c->occ_lds[i] = 0; c->occ_blocks[i] = 0; }
@@ -834,27 +832,23 @@ int pwn_i_set_launch_rotation(pwn_ctx *c, int rot)
 	return PWN_OK;
 }
 
-int pwn_i_launch_trace(pwn_ctx *c, const float cam[16], float sec, int y0, int y1,
-	uint32_t *d_sbuf, float *d_zbuf, hipStream_t stream)
+int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L)
 {
-	uint32_t *clear_word = c->trace_clear_word;            // for this launch only
-	c->trace_clear_word = NULL;
-	uint32_t *cost_word = c->trace_cost_word;
-	c->trace_cost_word = NULL;
-	hipEvent_t caller_event = c->trace_tables_event;       // (pwn_internal.h)
-	c->trace_tables_event = NULL;
-	const pwn_views_launch *views = c->trace_views;       // (pwn_trace_views)
-	c->trace_views = NULL;
-	const pwn_rays_launch *rays = c->trace_rays;          // (pwn_trace_rays)
-	c->trace_rays = NULL;
+	const pwn_views_launch *views = L->views.n > 0 ? &L->views : NULL;
+	const pwn_rays_launch *rays = L->rays.n > 0 ? &L->rays : NULL;
 	const bool batch = views != NULL || rays != NULL;
+	const int y0 = L->y0, y1 = L->y1;
+	const hipStream_t stream = L->stream;
+	const hipEvent_t caller_event = L->tables_event;
+	L->cost_mul = L->cost_div = 1u;
 	if(!c->have_level) return PWN_ENOLEVEL;
 	if(c->blob_dirty) { int rc = pack_blob(c); if(rc != PWN_OK) return rc; }
-	if(y1 == y0) return PWN_OK;
+	if(y1 == y0 && rays == NULL) return PWN_OK;
 	pwn_trace_params P;
 	memset(&P, 0, sizeof(P));
-	frame_setup(c->w, c->h, cam, &P);
-	P.sec_current = sec;
+	// (a batch has every view's camera set-up and time in its record, every ray's origin and direction in its own)
+	if(!batch) frame_setup(c->w, c->h, L->cam, &P);
+	P.sec_current = L->sec;
 	P.w = c->w; P.h = c->h; P.y0 = y0; P.y1 = y1;
 	const int tw = pwn_trace_tile_w();
 	P.tiles_x = (c->w + tw - 1) / tw;
@@ -863,14 +857,14 @@ int pwn_i_launch_trace(pwn_ctx *c, const float cam[16], float sec, int y0, int y
 	unit_div_magic((uint32_t)P.tiles_x, &P.ux_magic, &P.ux_shift);
 	// (the kernel takes unit / tiles_x = unit where there is no shift: true for one unit per row only)
 	if(P.ux_shift < 0 && P.tiles_x != 1) { snprintf(c->err, sizeof(c->err), "no division constant for %d units per row", P.tiles_x); return PWN_EINVAL; }
-	// a batch of views: the frame's units once per view, every view's camera set-up in its record (the one above is not read)
+	// a batch of views: the frame's units once per view
 	if(views != NULL)
 	{
 		P.views = views->d_recs; P.nviews = views->n; P.plane = views->plane;
 		unit_div_magic((uint32_t)views->n, &P.views_magic, &P.views_shift);
 		P.tiles_total *= views->n;
 	}
-	// a batch of rays: 64 to a unit (the camera set-up above is not read)
+	// a batch of rays: 64 to a unit
 	if(rays != NULL)
 	{
 		P.rays = rays->d_rays; P.ray_seeds = rays->d_seeds; P.nrays = rays->n; P.ray_w = rays->has_w ? 1 : 0;
@@ -879,7 +873,7 @@ int pwn_i_launch_trace(pwn_ctx *c, const float cam[16], float sec, int y0, int y
 	P.blob_bytes = (uint32_t)c->blob.size();
 	P.off_sph = c->off_sph;
 	P.off_recsph = c->off_recsph;
-	P.sbuf = d_sbuf; P.zbuf = d_zbuf;
+	P.sbuf = L->d_sbuf; P.zbuf = L->d_zbuf;
 	const int cur = c->blob_cur;
 	P.blob = (const uint32_t *)c->d_blob[cur];
 	// the upload of these tables runs on its own stream: this launch comes after it
@@ -889,8 +883,8 @@ int pwn_i_launch_trace(pwn_ctx *c, const float cam[16], float sec, int y0, int y
 		else HIPCHK(c, hipStreamWaitEvent(stream, c->ev_upload[cur], 0));
 	}
 	P.counters = c->d_counters;
-	P.clear_word = clear_word;
-	P.cost_word = cost_word;
+	P.clear_word = L->clear_word;
+	P.cost_word = L->cost_word;
 	P.wave_log = NULL;
 	// the kernel's work queues: 2R sets, R = launch_rot; launch n counts in set n mod 2R and clears set (n + R) mod 2R,
 	// the one of the launch R launches on.  Launches of a context are stream-ordered (include/pwnhip.h) -- on ONE stream,
@@ -903,9 +897,9 @@ int pwn_i_launch_trace(pwn_ctx *c, const float cam[16], float sec, int y0, int y
 	// ordinary cameras (rows x,y,z with w = 0, position w = 1: mat4_iden + rotations,
 	// main.c:61-64) never put anything but 0 / 1 into the w lanes; the kernel has a
 	// 3-lane specialisation for them that is arithmetically identical
-	P.has_w = !(cam[3] == 0.0f && cam[7] == 0.0f && cam[11] == 0.0f && cam[15] == 1.0f);
 	if(views != NULL) P.has_w = views->has_w;        // (the same rule over all the batch's cameras)
-	if(rays != NULL) P.has_w = rays->has_w;          // (the rule over the batch's rays: pwn_trace_rays)
+	else if(rays != NULL) P.has_w = rays->has_w;     // (the rule over the batch's rays: pwn_trace_rays)
+	else P.has_w = !(L->cam[3] == 0.0f && L->cam[7] == 0.0f && L->cam[11] == 0.0f && L->cam[15] == 1.0f);
 	// test hook (tests/test_gpu_fuzz.py): send every camera through the general variant
 	if(c->dbg_force_hasw) P.has_w = 1;
 	if(c->counters_on) HIPCHK(c, hipMemsetAsync(c->d_counters, 0, PWN_NCOUNTERS * sizeof(unsigned long long), stream));
@@ -940,12 +934,11 @@ int pwn_i_launch_trace(pwn_ctx *c, const float cam[16], float sec, int y0, int y
 	// kernels; a few workgroups fewer leave room on some CUs (pwn_tiled.cpp sets the number)
 	// ... and frames on two compute streams: room for the other stream's kernels (PWN_OPT_TRACE_ROOM; the caller says how much)
 	{
-		if(c->room.mode >= 0) c->launch_room = c->room.mode;        // (a host that set a number gets it for every launch)
-		const int reserve = c->grid_reserve > c->launch_room ? c->grid_reserve : c->launch_room;
-		c->launch_room = 0;
-		c->cost_mul = c->cost_div = (uint32_t)grid;
+		const int room = c->room.mode >= 0 ? c->room.mode : L->room;        // (a host that set a number gets it for every launch)
+		const int reserve = c->grid_reserve > room ? c->grid_reserve : room;
+		L->cost_mul = (uint32_t)grid;
 		if(reserve > 0 && grid > 2 * reserve) grid -= reserve;
-		c->cost_div = (uint32_t)grid;
+		L->cost_div = (uint32_t)grid;
 	}
 	// fewer units than resident waves (a 320 x 240 frame is 1200 units for 5120 waves): one unit per wave, a
 	// workgroup per four of them -- a workgroup whose waves find nothing still copies the tables into LDS
@@ -1084,21 +1077,17 @@ extern "C" int pwn_unit_order_state(pwn_ctx *c, unsigned long long out[4])
 	return PWN_OK;
 }
 
-int pwn_i_launch_blur(pwn_ctx *c, int y0, int y1, const uint32_t *d_pre, const float *d_z, uint32_t *d_out, hipStream_t stream,
-	int avail_y0, int avail_y1, uint32_t *d_miss, uint32_t *d_cost_acc, uint32_t *d_cost_out)
+int pwn_i_launch_blur(pwn_ctx *c, const pwn_blur_launch *L)
 {
-	const int views = c->blur_views;        // for this launch only (pwn_trace_views)
-	c->blur_views = 0;
 	if((c->w & 3) != 0) return PWN_EINVAL; // screen.h:88,117: aligned 16-B store per group
 	pwn_blur_params B;
-	B.views = views; B.plane = (unsigned long long)c->w * (unsigned long long)c->h;
-	B.w = c->w; B.h = c->h; B.y0 = y0; B.y1 = y1;
+	B.views = L->views; B.plane = (unsigned long long)c->w * (unsigned long long)c->h;
+	B.w = c->w; B.h = c->h; B.y0 = L->y0; B.y1 = L->y1;
 	B.groups = c->w / 4;
-	B.pre = d_pre; B.zbuf = d_z; B.out = d_out; B.skip = c->d_skip;
-	B.avail_y0 = avail_y0; B.avail_y1 = avail_y1; B.miss = d_miss;
-	B.cost_acc = d_cost_acc; B.cost_out = d_cost_out;
-	B.cost_mul = c->blur_cost_mul ? c->blur_cost_mul : 1u; B.cost_div = c->blur_cost_div ? c->blur_cost_div : 1u;
-	c->blur_cost_mul = c->blur_cost_div = 0u;
+	B.pre = L->d_pre; B.zbuf = L->d_z; B.out = L->d_out; B.skip = c->d_skip;
+	B.avail_y0 = L->avail_y0; B.avail_y1 = L->avail_y1; B.miss = L->d_miss;
+	B.cost_acc = L->d_cost_acc; B.cost_out = L->d_cost_out;
+	B.cost_mul = L->cost_mul ? L->cost_mul : 1u; B.cost_div = L->cost_div ? L->cost_div : 1u;
 	// The workgroup's tile of output pixels (post_kernels.hip), chosen by what the frame rate on two streams said
 	// (profiles/r3_blur_sweep.txt): 32 x 32 for wide frames and their strips (256-thread workgroups with 17 KB of LDS find room
 	// beside the trace grid's workgroups that a 1024-thread one with 42 KB does not: 4K +1.9 %, 8K +5.3 %, the strips of an
@@ -1113,7 +1102,7 @@ int pwn_i_launch_blur(pwn_ctx *c, int y0, int y1, const uint32_t *d_pre, const f
 		if(c->dbg_blur_tw > 0) B.tile_w = c->dbg_blur_tw;
 		if(c->dbg_blur_batch >= 0) B.batch = c->dbg_blur_batch;
 	}
-	HIPCHK(c, pwn_launch_blur(&B, stream));
+	HIPCHK(c, pwn_launch_blur(&B, L->stream));
 	return PWN_OK;
 }
 
@@ -1123,7 +1112,8 @@ extern "C" int pwn_trace_rows_device(pwn_ctx *c, const float cam[16], float sec,
 	GRP_REFUSE(c, "pwn_trace_rows_device");
 	if(c == NULL || cam == NULL || d_sbuf == NULL || d_zbuf == NULL || y0 < 0 || y1 > c->h || y0 > y1) return PWN_EINVAL;
 	(void)hipSetDevice(c->device);
-	return pwn_i_launch_trace(c, cam, sec, y0, y1, (uint32_t *)d_sbuf, (float *)d_zbuf, (hipStream_t)stream);
+	pwn_trace_launch L = { .cam = cam, .sec = sec, .y0 = y0, .y1 = y1, .d_sbuf = (uint32_t *)d_sbuf, .d_zbuf = (float *)d_zbuf, .stream = (hipStream_t)stream };
+	return pwn_i_launch_trace(c, &L);
 }
 
 extern "C" int pwn_blur_rows_device(pwn_ctx *c, int y0, int y1, const void *d_pre, const void *d_zbuf, void *d_out, void *stream)
@@ -1131,7 +1121,8 @@ extern "C" int pwn_blur_rows_device(pwn_ctx *c, int y0, int y1, const void *d_pr
 	GRP_REFUSE(c, "pwn_blur_rows_device");
 	if(c == NULL || d_pre == NULL || d_zbuf == NULL || d_out == NULL || y0 < 0 || y1 > c->h || y0 > y1 || d_pre == d_out) return PWN_EINVAL;
 	(void)hipSetDevice(c->device);
-	int rc = pwn_i_launch_blur(c, y0, y1, (const uint32_t *)d_pre, (const float *)d_zbuf, (uint32_t *)d_out, (hipStream_t)stream, 0, 0, NULL, NULL, NULL);
+	const pwn_blur_launch B = { .y0 = y0, .y1 = y1, .d_pre = (const uint32_t *)d_pre, .d_z = (const float *)d_zbuf, .d_out = (uint32_t *)d_out, .stream = (hipStream_t)stream };
+	int rc = pwn_i_launch_blur(c, &B);
 	// PWN_OPT_UNIT_ORDER: a strip's trace and blur on one stream of the caller's -- the order of that stream's next trace of the same rows
 	if(rc == PWN_OK) rc = pwn_i_launch_order(c, (hipStream_t)stream);
 	return rc;
@@ -1144,8 +1135,9 @@ extern "C" int pwn_blur_rows_device_bounded(pwn_ctx *c, int y0, int y1, const vo
 	if(c == NULL || d_pre == NULL || d_zbuf == NULL || d_out == NULL || d_miss == NULL || y0 < 0 || y1 > c->h || y0 > y1 ||
 	   d_pre == d_out || avail_y0 > avail_y1) return PWN_EINVAL;
 	(void)hipSetDevice(c->device);
-	int rc = pwn_i_launch_blur(c, y0, y1, (const uint32_t *)d_pre, (const float *)d_zbuf, (uint32_t *)d_out, (hipStream_t)stream,
-		avail_y0, avail_y1, (uint32_t *)d_miss, NULL, NULL);
+	const pwn_blur_launch B = { .y0 = y0, .y1 = y1, .d_pre = (const uint32_t *)d_pre, .d_z = (const float *)d_zbuf, .d_out = (uint32_t *)d_out, .stream = (hipStream_t)stream,
+		.avail_y0 = avail_y0, .avail_y1 = avail_y1, .d_miss = (uint32_t *)d_miss };
+	int rc = pwn_i_launch_blur(c, &B);
 	if(rc == PWN_OK) rc = pwn_i_launch_order(c, (hipStream_t)stream);
 	return rc;
 }
@@ -1312,10 +1304,11 @@ static int call_in_strips(pwn_ctx *c, const float cam[16], float sec, uint32_t *
 		{
 			const int k = traced;
 			hipStream_t ts = st[k & 1];
-			if(k == 0 && blur) c->trace_clear_word = c->d_strip_miss;      // (cleared by the first strip's launch, in front of every blur)
-			c->trace_tables_event = c->strip_ev[2 * k];                   // recorded right behind the launch; its previous record is a call that returned
-			c->launch_room = room;
-			rc = pwn_i_launch_trace(c, cam, sec, cuts[k], cuts[k + 1], pre, c->d_z, ts);
+			pwn_trace_launch T = { .cam = cam, .sec = sec, .y0 = cuts[k], .y1 = cuts[k + 1], .d_sbuf = pre, .d_zbuf = c->d_z, .stream = ts,
+				.clear_word = (k == 0 && blur) ? c->d_strip_miss : NULL,      // (cleared by the first strip's launch, in front of every blur)
+				.tables_event = c->strip_ev[2 * k],                           // recorded right behind the launch; its previous record is a call that returned
+				.room = room };
+			rc = pwn_i_launch_trace(c, &T);
 			if(rc != PWN_OK) { (void)hipEventRecord(c->strip_ev[2 * k], ts); STRIPS_FAIL(rc); }
 			HIPCHK(c, hipEventRecord(c->strip_ev[2 * k], ts));
 			if(timeline) HIPCHK(c, hipEventRecord(tl[4 * k], ts));
@@ -1332,7 +1325,9 @@ static int call_in_strips(pwn_ctx *c, const float cam[16], float sec, uint32_t *
 				{
 					if(two && k >= 1) HIPCHK(c, hipStreamWaitEvent(ts, c->strip_ev[2 * (k - 1)], 0));
 					const bool whole = traced == K;
-					rc = pwn_i_launch_blur(c, y0, to, pre, c->d_z, fin, ts, 0, whole ? 0 : cuts[traced], whole ? NULL : c->d_strip_miss, NULL, NULL);
+					const pwn_blur_launch B = { .y0 = y0, .y1 = to, .d_pre = pre, .d_z = c->d_z, .d_out = fin, .stream = ts,
+						.avail_y1 = whole ? 0 : cuts[traced], .d_miss = whole ? NULL : c->d_strip_miss };
+					rc = pwn_i_launch_blur(c, &B);
 					if(rc != PWN_OK) STRIPS_FAIL(rc);
 				}
 				else if(!blur && two && k >= 1) HIPCHK(c, hipStreamWaitEvent(ts, c->strip_ev[2 * (k - 1)], 0));      // (the chunk's rows may be the other stream's)
@@ -1407,7 +1402,8 @@ static int call_in_strips(pwn_ctx *c, const float cam[16], float sec, uint32_t *
 		c->strip_redone++;
 		// (the short reach was not enough for this view: the long one from now on; that one too: one-piece calls for a while)
 		if(c->strip_reach == 0) c->strip_reach = 1; else c->strip_backoff = 64;
-		rc = pwn_i_launch_blur(c, 0, c->h, pre, c->d_z, fin, st[0], 0, 0, NULL, NULL, NULL);
+		const pwn_blur_launch B = { .y0 = 0, .y1 = c->h, .d_pre = pre, .d_z = c->d_z, .d_out = fin, .stream = st[0] };
+		rc = pwn_i_launch_blur(c, &B);
 		if(rc != PWN_OK) return rc;
 		HIPCHK(c, hipEventRecord(c->ev[2], st[0]));
 		HIPCHK(c, hipMemcpyAsync(sbuf, fin, n * 4, hipMemcpyDeviceToHost, st[0]));
@@ -1467,12 +1463,14 @@ extern "C" int pwn_trace_screen_centred(pwn_ctx *c, const float cam[16], float s
 	// trace into d_pre; with blur on, d_pre plays tsbuf and d_out plays sbuf
 	// (the memcpy of screen.h:75 becomes a pointer swap per pass)
 	uint32_t *cur = c->d_pre, *other = c->d_out;
-	int rc = pwn_i_launch_trace(c, cam, sec, 0, c->h, cur, c->d_z, s);
+	pwn_trace_launch T = { .cam = cam, .sec = sec, .y0 = 0, .y1 = c->h, .d_sbuf = cur, .d_zbuf = c->d_z, .stream = s };
+	int rc = pwn_i_launch_trace(c, &T);
 	if(rc != PWN_OK) return rc;
 	HIPCHK(c, hipEventRecord(c->ev[1], s));
 	for(int p = 0; p < c->blur_passes; p++)
 	{
-		rc = pwn_i_launch_blur(c, 0, c->h, cur, c->d_z, other, s, 0, 0, NULL, NULL, NULL);
+		const pwn_blur_launch B = { .y0 = 0, .y1 = c->h, .d_pre = cur, .d_z = c->d_z, .d_out = other, .stream = s };
+		rc = pwn_i_launch_blur(c, &B);
 		if(rc != PWN_OK) return rc;
 		uint32_t *t = cur; cur = other; other = t;
 	}
@@ -1556,18 +1554,15 @@ extern "C" int pwn_trace_views(pwn_ctx *c, int n, const float *cams, const float
 	HIPCHK(c, hipEventRecord(c->ev[0], s));
 	// (the staging is free again: the call before this one ended with the stream drained)
 	HIPCHK(c, pwn_launch_upload(c->h_vrec, c->d_vrec, (size_t)n * sizeof(pwn_view_rec), s));
-	pwn_views_launch V;
-	V.d_recs = c->d_vrec; V.n = n; V.has_w = has_w; V.plane = plane;
-	c->trace_views = &V;
-	rc = pwn_i_launch_trace(c, cams, secs[0], 0, c->h, c->d_vpre, c->d_vz, s);
-	c->trace_views = NULL;
+	pwn_trace_launch T = { .y0 = 0, .y1 = c->h, .views = { c->d_vrec, n, has_w, plane }, .d_sbuf = c->d_vpre, .d_zbuf = c->d_vz, .stream = s };
+	rc = pwn_i_launch_trace(c, &T);
 	if(rc != PWN_OK) return rc;
 	HIPCHK(c, hipEventRecord(c->ev[1], s));
 	uint32_t *cur = c->d_vpre, *other = c->d_vout;
 	for(int p = 0; p < c->blur_passes; p++)
 	{
-		c->blur_views = n;
-		rc = pwn_i_launch_blur(c, 0, c->h, cur, c->d_vz, other, s, 0, 0, NULL, NULL, NULL);
+		const pwn_blur_launch B = { .y0 = 0, .y1 = c->h, .d_pre = cur, .d_z = c->d_vz, .d_out = other, .stream = s, .views = n };
+		rc = pwn_i_launch_blur(c, &B);
 		if(rc != PWN_OK) return rc;
 		uint32_t *t = cur; cur = other; other = t;
 	}
@@ -1583,9 +1578,6 @@ extern "C" int pwn_trace_views(pwn_ctx *c, int n, const float *cams, const float
 }
 
 // ---- a batch of rays (pwn_trace_rays) --------------------------------------------
-
-// (the camera a ray launch hands pwn_i_launch_trace: its set-up is not read)
-static const float rays_no_cam[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
 
 // Room for n rays of the host form, kept across calls: pinned staging and a device buffer of the same layout, for a call of n rays
 // the records at 0, the seeds at 32 n, the depths at 36 n and the colours at 40 n -- one copy up (records, seeds, depths) and one
@@ -1645,11 +1637,9 @@ extern "C" int pwn_trace_rays(pwn_ctx *c, int n, const float *rays, const uint32
 	// (small batches by the upload kernel, as the view records: a DMA copy queues behind other copies of the device)
 	if(40 * N <= 65536) HIPCHK(c, pwn_launch_upload(h, d, 40 * N, s));
 	else HIPCHK(c, hipMemcpyAsync(d, h, 40 * N, hipMemcpyHostToDevice, s));
-	pwn_rays_launch R;
-	R.d_rays = (const float *)d; R.d_seeds = (const uint32_t *)(d + 32 * N); R.n = (uint32_t)n; R.has_w = has_w;
-	c->trace_rays = &R;
-	rc = pwn_i_launch_trace(c, rays_no_cam, sec, 0, 1, (uint32_t *)(d + 40 * N), (float *)(d + 36 * N), s);
-	c->trace_rays = NULL;
+	pwn_trace_launch T = { .sec = sec, .rays = { (const float *)d, (const uint32_t *)(d + 32 * N), (uint32_t)n, has_w },
+		.d_sbuf = (uint32_t *)(d + 40 * N), .d_zbuf = (float *)(d + 36 * N), .stream = s };
+	rc = pwn_i_launch_trace(c, &T);
 	if(rc != PWN_OK) return rc;
 	HIPCHK(c, hipEventRecord(c->ev[1], s));
 	const size_t lo = depth != NULL ? 36 * N : 40 * N, hi = col != NULL ? 44 * N : 40 * N;
@@ -1675,12 +1665,9 @@ extern "C" int pwn_trace_rays_device(pwn_ctx *c, int n, const void *d_rays, cons
 	const int rc = rays_refuse(c);
 	if(rc != PWN_OK || n == 0) return rc;
 	(void)hipSetDevice(c->device);
-	pwn_rays_launch R;
-	R.d_rays = (const float *)d_rays; R.d_seeds = (const uint32_t *)d_seeds; R.n = (uint32_t)n; R.has_w = (flags & PWN_RAYS_HAS_W) != 0;
-	c->trace_rays = &R;
-	const int lrc = pwn_i_launch_trace(c, rays_no_cam, sec, 0, 1, (uint32_t *)d_col, (float *)d_depth, (hipStream_t)stream);
-	c->trace_rays = NULL;
-	return lrc;
+	pwn_trace_launch T = { .sec = sec, .rays = { (const float *)d_rays, (const uint32_t *)d_seeds, (uint32_t)n, (flags & PWN_RAYS_HAS_W) != 0 },
+		.d_sbuf = (uint32_t *)d_col, .d_zbuf = (float *)d_depth, .stream = (hipStream_t)stream };
+	return pwn_i_launch_trace(c, &T);
 }
 
 // ---- frames in flight ---------------------------------------------------------
@@ -1702,7 +1689,7 @@ static void slot_release(pwn_slot &sl)
 
 static void frames_release(pwn_ctx *c)
 {
-	// A slot's "kernels done" event may be what an upload would wait for (pwn_ctx.trace_tables_event): no frame
+	// A slot's "kernels done" event may be what an upload would wait for (pwn_trace_launch.tables_event): no frame
 	// is in flight here, so once the compute stream is empty no copy of the tables is in use any more
 	if(c->nslots > 0)
 	{
@@ -1804,15 +1791,17 @@ extern "C" int pwn_submit_frame(pwn_ctx *c, const float cam[16], float sec, int 
 	// the last pass writes into the slot's own plane, which is what the copy stream reads while
 	// the next frame's kernels reuse the context's d_pre / d_out
 	uint32_t *cur = c->blur_passes > 0 ? pre : sl.d_out;
-	c->trace_tables_event = sl.ev_k[2];        // recorded below, behind the frame's last kernel
-	c->launch_room = overlap ? pwn_room_for_launch(c) : 0;
-	int rc = pwn_i_launch_trace(c, cam, sec, 0, c->h, cur, sl.d_z, s);
+	pwn_trace_launch T = { .cam = cam, .sec = sec, .y0 = 0, .y1 = c->h, .d_sbuf = cur, .d_zbuf = sl.d_z, .stream = s,
+		.tables_event = sl.ev_k[2],        // recorded below, behind the frame's last kernel
+		.room = overlap ? pwn_room_for_launch(c) : 0 };
+	int rc = pwn_i_launch_trace(c, &T);
 	if(rc != PWN_OK) return rc;
 	if(timing) HIPCHK(c, hipEventRecord(sl.ev_k[1], s));
 	for(int p = 0; p < c->blur_passes; p++)
 	{
 		uint32_t *dst = (p == c->blur_passes - 1) ? sl.d_out : (cur == c->d_pre ? c->d_out : c->d_pre);      // (several passes: one stream)
-		rc = pwn_i_launch_blur(c, 0, c->h, cur, sl.d_z, dst, s, 0, 0, NULL, NULL, NULL);
+		const pwn_blur_launch B = { .y0 = 0, .y1 = c->h, .d_pre = cur, .d_z = sl.d_z, .d_out = dst, .stream = s };
+		rc = pwn_i_launch_blur(c, &B);
 		if(rc != PWN_OK) { (void)hipEventRecord(sl.ev_k[2], s); return rc; }     // (the trace launch counts on this event)
 		cur = dst;
 	}

@@ -10,25 +10,8 @@
 #include "pwnhip.h"
 #include "tables.h"
 
-struct pwn_blur_params
-{
-	int w, h, y0, y1;
-	int groups;
-	const uint32_t *pre;
-	const float *zbuf;
-	uint32_t *out;
-	const uint2 *skip;
-	int avail_y0, avail_y1;
-	uint32_t *miss;
-	int tile_h, tile_w, batch;
-	uint32_t *cost_acc, *cost_out;
-	uint32_t cost_mul, cost_div;   // ... scaled on the way: the resident grid over the grid the trace ran with (PWN_OPT_TRACE_ROOM), so that ranks with and without room compare
-	int views;                     // a batch of views (pwn_trace_views): 0 = one frame; else that many frames, view v's planes at + v * plane
-	unsigned long long plane;
-};
-
-// Set by pwn_trace_views for its next pwn_i_launch_trace only (pwn_ctx.trace_views): the launch traces n views, their records
-// (tables.h pwn_view_rec) already on the device, into planes `plane` pixels apart; has_w: some view's camera has w components
+// A batch of views (pwn_trace_views) as what a trace launch traces: n views, their records (tables.h pwn_view_rec) already on
+// the device, into planes `plane` pixels apart; has_w: some view's camera has w components.  n = 0: none.
 struct pwn_views_launch
 {
 	const pwn_view_rec *d_recs;
@@ -37,14 +20,45 @@ struct pwn_views_launch
 	unsigned long long plane;
 };
 
-// Set by pwn_trace_rays / pwn_trace_rays_device for their next pwn_i_launch_trace only (pwn_ctx.trace_rays): the launch traces n
-// caller-supplied rays (tables.h pwn_trace_params.rays) into d_col / d_depth; has_w: their w lanes count (PWN_RAYS_HAS_W)
+// A batch of caller-supplied rays (pwn_trace_rays / pwn_trace_rays_device; tables.h pwn_trace_params.rays): n rays into
+// d_sbuf (colour) / d_zbuf (depth) of the launch; has_w: their w lanes count (PWN_RAYS_HAS_W).  n = 0: none.
 struct pwn_rays_launch
 {
 	const float *d_rays;
 	const uint32_t *d_seeds;
 	uint32_t n;
 	bool has_w;
+};
+
+// One trace launch (pwn_i_launch_trace).  All zero but what is traced and where to: a plain launch, nothing cleared or
+// added up, no room, the launcher's own tables event.
+struct pwn_trace_launch
+{
+	const float *cam; float sec; int y0, y1;     // rows [y0, y1) of camera cam[16]'s frame (y0 == y1: nothing is launched) ...
+	pwn_views_launch views;                      // ... or of every view of a batch (cam and sec not read) ...
+	pwn_rays_launch rays;                        // ... or a batch of rays (cam and the rows not read)
+	uint32_t *d_sbuf; float *d_zbuf; hipStream_t stream;
+	uint32_t *clear_word, *cost_word;            // pwn_trace_params.clear_word, .cost_word
+	// An event the caller records itself right behind this launch anyway (its frame's "kernels done").  The launcher
+	// then records none of its own -- every event between two kernels costs the queue a few microseconds.  The caller
+	// must have waited on the host for the frame of the event's previous record (a slot is handed in again only when it
+	// is free): the launcher drops the guards that still point at the event before the caller records it again.
+	hipEvent_t tables_event;
+	int room;                                    // PWN_OPT_TRACE_ROOM: workgroups this launch leaves free (a number set by the host goes first)
+	// out: resident grid / grid launched, what the launch's cost word is to be scaled by (1 / 1 where nothing was launched)
+	uint32_t cost_mul, cost_div;
+};
+
+// One blur launch (pwn_i_launch_blur).  All zero but the rows, the planes and the stream: every row of `d_pre` valid, no
+// cost word, one frame.
+struct pwn_blur_launch
+{
+	int y0, y1;
+	const uint32_t *d_pre; const float *d_z; uint32_t *d_out; hipStream_t stream;
+	int avail_y0, avail_y1; uint32_t *d_miss;    // pwn_blur_params.avail_y0, .avail_y1, .miss
+	uint32_t *d_cost_acc, *d_cost_out;           // pwn_blur_params.cost_acc, .cost_out ...
+	uint32_t cost_mul, cost_div;                 // ... scaled by what the frame's trace launch gave out (0 = 1)
+	int views;                                   // a batch of views (pwn_trace_views): that many, planes w * h apart (0 = one frame)
 };
 
 extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream);
@@ -159,13 +173,7 @@ struct pwn_ctx
 	uint8_t *d_blob[PWN_NBLOB]; int blob_cur;
 	bool blob_has_static[PWN_NBLOB];                                   // the rcp / rsqrt tables are in place
 	hipEvent_t ev_tables[PWN_NBLOB]; bool tables_in_use[PWN_NBLOB];    // behind the last trace launch reading that copy
-	hipEvent_t tables_wait[PWN_NBLOB];                                 // ... the event to wait for: ev_tables[i], or the caller's (below)
-	// Set by a caller of pwn_i_launch_trace for its next launch: an event the caller records itself right behind
-	// that launch anyway (its frame's "kernels done").  The launcher then records none of its own -- every
-	// event between two kernels costs the queue a few microseconds.  The caller must have waited on the host for
-	// the frame of the event's previous record (a slot is handed in again only when it is free): the launcher
-	// drops the guards that still point at the event before the caller records it again.
-	hipEvent_t trace_tables_event;
+	hipEvent_t tables_wait[PWN_NBLOB];                                 // ... the event to wait for: ev_tables[i], or the caller's (pwn_trace_launch.tables_event)
 	hipEvent_t ev_upload[PWN_NBLOB]; bool upload_pending[PWN_NBLOB];   // behind the last upload into that copy
 	uint8_t *h_stage[PWN_NSTAGE]; hipEvent_t ev_stage[PWN_NSTAGE]; bool stage_used[PWN_NSTAGE]; unsigned stage_next;
 	hipStream_t up_stream;
@@ -202,15 +210,10 @@ struct pwn_ctx
 	bool dbg_force_hasw; int dbg_blocks_per_cu;      // PWN_DBG_* hooks, read at pwn_init
 	int dbg_blur_th, dbg_blur_tw, dbg_blur_batch;                 // PWN_DBG_BLUR_TH: tile height of every blur launch (8 / 16 / 32), 0 = the launcher's choice
 	int grid_reserve;                // workgroups the persistent trace grid leaves free (row tiling over RCCL), else 0
-	uint32_t *trace_cost_word;       // likewise: pwn_trace_params.cost_word for the next launch
-	uint32_t *trace_clear_word;      // set by a caller of pwn_i_launch_trace for its next launch: see pwn_trace_params.clear_word
-	const pwn_views_launch *trace_views;   // likewise: the next launch is a batch of views (pwn_trace_views), else NULL
-	int blur_views;                  // ... and the next pwn_i_launch_blur: that many views, planes w * h apart (0 = one frame)
 	// pwn_trace_views: per view slot a pre-blur, a colour and a depth plane (views_cap of each, view-major; the depth planes persist
 	// by slot and are kept when the count grows), the records of the call in pinned staging and on the device
 	uint32_t *d_vpre, *d_vout; float *d_vz; int views_cap;
 	pwn_view_rec *h_vrec, *d_vrec; int vrec_cap;
-	const pwn_rays_launch *trace_rays;     // set by a caller of pwn_i_launch_trace: the next launch is a batch of rays (pwn_trace_rays), else NULL
 	// pwn_trace_rays: room for rays_cap rays in pinned staging and on the device, 44 B each (record, seed, depth, colour; pwn_api.cpp rays_reserve)
 	unsigned char *h_rays, *d_rays; size_t rays_cap;
 	uint32_t *d_tickets; unsigned ticket_set;  // PWN_TICKET_SETS sets of work-queue counters of the trace kernel, used in turn
@@ -219,9 +222,7 @@ struct pwn_ctx
 	hipStream_t stream;              // compute
 	hipStream_t stream2;             // frames in flight alternate between `stream` and this one (PWN_OPT_FRAME_OVERLAP)
 	uint32_t *d_pre2;                // the pre-blur plane of the frames on stream2 (allocated with the first of them)
-	uint32_t cost_mul, cost_div;     // set by pwn_i_launch_trace: resident grid / grid it launched (what its cost word is to be scaled by); read by the tiling
-	uint32_t blur_cost_mul, blur_cost_div;   // ... handed to the next pwn_i_launch_blur by its caller (0 = 1 / 1)
-	pwn_room_ctl room; int launch_room;   // PWN_OPT_TRACE_ROOM; what the next trace launch leaves free (set by its caller, cleared by the launch)
+	pwn_room_ctl room;               // PWN_OPT_TRACE_ROOM
 	int frame_overlap;               // PWN_OPT_FRAME_OVERLAP
 	hipEvent_t last_frame_done; hipStream_t last_frame_stream;   // "kernels done" of the frame submitted last, and its stream
 	hipStream_t copy_stream;         // frames in flight: D2H of finished frames
@@ -266,9 +267,8 @@ struct pwn_ctx
 	snprintf((ctx)->err, sizeof((ctx)->err), "%s: %s", #call, hipGetErrorString(e_)); return PWN_EHIP; } } while(0)
 
 // pwn_api.cpp internals used by pwn_tiled.cpp
-int pwn_i_launch_trace(pwn_ctx *c, const float cam[16], float sec, int y0, int y1, uint32_t *d_sbuf, float *d_zbuf, hipStream_t stream);
-int pwn_i_launch_blur(pwn_ctx *c, int y0, int y1, const uint32_t *d_pre, const float *d_z, uint32_t *d_out, hipStream_t stream,
-	int avail_y0, int avail_y1, uint32_t *d_miss, uint32_t *d_cost_acc, uint32_t *d_cost_out);
+int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L);
+int pwn_i_launch_blur(pwn_ctx *c, const pwn_blur_launch *L);
 void pwn_launch_history_clear(pwn_ctx *c);      // the launch-order events are about to be destroyed (streams idle)
 int pwn_i_set_launch_rotation(pwn_ctx *c, int rot);
 int pwn_i_launch_order(pwn_ctx *c, hipStream_t stream);      // behind a frame's last kernel on `stream`: sort that stream's unit costs (no-op when there are none)

@@ -695,7 +695,7 @@ struct pwn_tiled
 	int want_halo;                      // the halo asked for at init; moving cuts keep every strip at least this tall
 	int halo;                           // rows exchanged with each neighbour; 0 = whole strips to everybody
 	int fhalo[NSLOT];                   // ... as used for the frame in that slot (the mode changes after a miss)
-	uint32_t fcost_mul[NSLOT], fcost_div[NSLOT];   // what the slot's trace launch says its cost word is to be scaled by (pwn_ctx.cost_mul / _div)
+	uint32_t fcost_mul[NSLOT], fcost_div[NSLOT];   // what the slot's trace launch says its cost word is to be scaled by (pwn_trace_launch.cost_mul / _div)
 	int root_mode, froot[NSLOT];     // pwn_tiled_gather_root: PWN_TILED_ROOT_*; the rank the slot's frame is gathered on
 	int balance_every;                  // re-cut every this many delivered frames from the ranks' cost words; 0 = never
 	uint32_t last_cost[MAXW];           // the cost words of the last delivered frame (pwn_tiled_get_cuts)
@@ -948,7 +948,7 @@ void pwn_tiled_destroy(pwn_ctx *c)
 	(void)hipSetDevice(c->device);
 	(void)hipDeviceSynchronize();
 	// (the device is idle: no copy of the tables is in use, and the events that said so -- ev_t, handed to the trace
-	// launches as pwn_ctx.trace_tables_event -- are destroyed below)
+	// launches as their tables_event -- are destroyed below)
 	for(int i = 0; i < PWN_NBLOB; i++) c->tables_in_use[i] = false;
 	pwn_launch_history_clear(c);
 	delete t->tp;
@@ -1458,15 +1458,15 @@ static int enqueue_blur(pwn_ctx *c, pwn_tiled *t, unsigned long long k)
 		// the trace of this frame, in front of this launch on the stream, added up what the strip cost: the blur
 		// moves that into the frame's second word and clears the accumulator for the stream's next trace
 		uint32_t *acc = t->cost_acc + 16 * s;
-		int rc;
-		c->blur_cost_mul = t->fcost_mul[s]; c->blur_cost_div = t->fcost_div[s];
+		pwn_blur_launch B = { .y0 = y0, .y1 = y1, .d_pre = t->pre[s], .d_z = t->fz[s], .d_out = dst, .stream = cs,
+			.d_cost_acc = acc, .d_cost_out = t->missw[s] + 1, .cost_mul = t->fcost_mul[s], .cost_div = t->fcost_div[s] };
 		if(t->fhalo[s])
 		{
 			const int H = t->fhalo[s];
-			const int a0 = t->rank > 0 ? y0 - H : 0, a1 = (t->rank < t->world - 1 && y1 < c->h) ? y1 + H : c->h;
-			rc = pwn_i_launch_blur(c, y0, y1, t->pre[s], t->fz[s], dst, cs, a0, a1, t->missw[s], acc, t->missw[s] + 1);
+			B.avail_y0 = t->rank > 0 ? y0 - H : 0; B.avail_y1 = (t->rank < t->world - 1 && y1 < c->h) ? y1 + H : c->h;
+			B.d_miss = t->missw[s];
 		}
-		else rc = pwn_i_launch_blur(c, y0, y1, t->pre[s], t->fz[s], dst, cs, 0, 0, NULL, acc, t->missw[s] + 1);
+		const int rc = pwn_i_launch_blur(c, &B);
 		if(rc != PWN_OK) return rc;
 		if(t->timed[s]) HIPCHK(c, hipEventRecord(t->ev_k3[s], cs));
 	}
@@ -1609,13 +1609,14 @@ int pwn_i_tiled_submit(pwn_ctx *c, const float cam[16], float sec, uint32_t *hos
 	t->timed[s] = c->frame_timing > 0 && (f % (unsigned long long)c->frame_timing) == 0;
 	t->timed_g2[s] = false;
 	if(t->timed[s]) HIPCHK(c, hipEventRecord(t->ev_k0[s], cs));
-	c->trace_clear_word = t->missw[s];           // the frame's miss word is cleared by its trace launch (no memset between the kernels)
-	c->trace_cost_word = c->blur_passes ? t->cost_acc + 16 * s : NULL;      // (the blur moves it on: enqueue_blur)
-	c->trace_tables_event = t->ev_t[s];          // ... and ev_t, recorded right behind it, also tells when its tables are free again
-	c->launch_room = t->ncs > 1 ? pwn_room_for_launch(c) : 0;          // PWN_OPT_TRACE_ROOM
-	int rc = pwn_i_launch_trace(c, cam, sec, y0, y1, plane, t->fz[s], cs);
+	pwn_trace_launch T = { .cam = cam, .sec = sec, .y0 = y0, .y1 = y1, .d_sbuf = plane, .d_zbuf = t->fz[s], .stream = cs,
+		.clear_word = t->missw[s],           // the frame's miss word is cleared by its trace launch (no memset between the kernels)
+		.cost_word = c->blur_passes ? t->cost_acc + 16 * s : NULL,      // (the blur moves it on: enqueue_blur)
+		.tables_event = t->ev_t[s],          // ... and ev_t, recorded right behind it, also tells when its tables are free again
+		.room = t->ncs > 1 ? pwn_room_for_launch(c) : 0 };          // PWN_OPT_TRACE_ROOM
+	int rc = pwn_i_launch_trace(c, &T);
 	if(rc != PWN_OK) { (void)hipEventRecord(t->ev_t[s], cs); return rc; }
-	t->fcost_mul[s] = c->cost_mul; t->fcost_div[s] = c->cost_div;
+	t->fcost_mul[s] = T.cost_mul; t->fcost_div[s] = T.cost_div;      // (1 / 1 from an empty strip: its blur launches nothing either)
 	if(t->timed[s]) HIPCHK(c, hipEventRecord(t->ev_k1[s], cs));
 	HIPCHK(c, hipEventRecord(t->ev_t[s], cs));
 	double tp0 = 0.0, tp1 = 0.0, tp2 = 0.0;
@@ -1828,7 +1829,8 @@ extern "C" int pwn_tiled_wait(pwn_ctx *c, int flags, pwn_tiled_frame *out)
 		uint32_t *dst = (t->rank == t->froot[s] && !t->sink) ? t->fin[s] : t->out[s];
 		// (this stream's cost accumulator may hold the trace of frame d+2 by now: it is left alone, the frame's
 		// cost word was moved by its first blur)
-		rc = pwn_i_launch_blur(c, y0, y1, t->pre[s], t->fz[s], dst, cs, 0, 0, NULL, NULL, NULL);
+		const pwn_blur_launch B = { .y0 = y0, .y1 = y1, .d_pre = t->pre[s], .d_z = t->fz[s], .d_out = dst, .stream = cs };
+		rc = pwn_i_launch_blur(c, &B);
 		if(rc != PWN_OK) return rc;
 		HIPCHK(c, hipEventRecord(t->ev_b[s], cs));
 		HIPCHK(c, hipStreamWaitEvent(xs, t->ev_b[s], 0));
