@@ -232,7 +232,11 @@ const char *pwn_last_error(pwn_ctx *ctx);
    lower-case portal quirk), build pmap, upload.  */
 int pwn_level_load(pwn_ctx *ctx, const char *path);
 int pwn_level_load_mem(pwn_ctx *ctx, const char *text, int len);
-/* the same tables handed over ready-made: lv->data / lv->pmap (defs.h:103-105) */
+/* the same tables handed over ready-made: lv->data / lv->pmap (defs.h:103-105), also as level_load leaves them (x == -1 for
+   an endpoint never seen, with whatever z).  PWN_EINVAL for a coordinate outside -1 .. 63, and for a hand-made table on which
+   a ray in a cell OUTSIDE the grid, at coordinate -1, would stand on an endpoint and see or do something there: a paired
+   letter with an endpoint at (-1, z) or (x, -1) that stands in the column-0 / row-0 cell read for that cell, or a '#', '&', '"'
+   far side (c1 / c2) behind such an endpoint (level_host.c: pwn_check_portals) */
 int pwn_upload_level(pwn_ctx *ctx, const uint8_t data[4096], const pwn_portal pmap[26]);
 int pwn_get_level(pwn_ctx *ctx, uint8_t data[4096], pwn_portal pmap[26], int32_t spawn[2]);
 

@@ -4,8 +4,11 @@
  *   pwn_parse_level     level_load  (level.h:107-228): the level.txt format
  *   pwn_bin_spheres     level_prepare_render + level_part_add(_bbox)
  *                       (level.h:1-39,64-81): per-cell sphere lists
+ *   pwn_check_portals   which hand-made portal tables pwn_upload_level takes
+ *   pwn_bake_cells      what the walk's portal arms ask of a cell (trace.h:404-413,
+ *                       508-559), decided once per level: cell_bake.h
  *
- * Both produce flat tables that pwn_api.cpp packs into the LDS blob.
+ * All produce flat tables that pwn_api.cpp packs into the LDS blob.
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -108,6 +111,112 @@ int pwn_parse_level(const char *text, int len, uint8_t *cells, pwn_portal *pmap,
 		pm->c2 = flat_cell(cells, pm->x2 + dir_dx[d2], pm->z2 + dir_dz[d2]);
 	}
 	return 0;
+}
+
+/* the look-through class of a cell type (trace.h:404-413: '#' and '&' carry on, '"' shifts y) */
+static uint32_t look_class(int c)
+{
+	if(c == '#' || c == '&') return PWN_C_LT2;
+	if(c == '"') return PWN_C_LTDQ;
+	return 0;
+}
+
+/*
+ * Which portal tables pwn_upload_level takes (1) and which it refuses (0).  The reference compares a letter's
+ * endpoints with the ray's cell as it stands, unclamped (trace.h:404-413, 508-559), while it READS the cell
+ * through get_cell's clamp: a ray in cell (-1, 5), outside the grid, reads cell (0, 5) and stands on an endpoint
+ * that the table gives as (-1, 5).  -1 is the one coordinate outside the grid that a table can hold: x == -1 says
+ * "no endpoint" (level.h:94-99, 149-177), and the z beside it is whatever it was -- level_new sets x1, x2, c1
+ * and c2 only, so level_load leaves (x1, z1, -1, 0) or (-1, 0, -1, 0), or a z left over from the level before.
+ * The baked table (pwn_bake_cells) gives every cell outside the grid the answers of a non-endpoint.  A table is
+ * taken where that is what the reference gives as well:
+ *   - every coordinate lies in -1 .. 63 (as before);
+ *   - for every cell with a coordinate of -1, (-1, t) and (t, -1), the reference's own tests on the cell it reads
+ *     there give what they give for a cell that is no endpoint: looking through sees none of '#', '&', '"'
+ *     behind a matching endpoint, and a matching endpoint does not lead anywhere (x2 == -1: a wall either way).
+ * level_new and level_load leave c1 = c2 = ';' in every letter without endpoint 2: whatever their z, their tables
+ * pass.  What is refused is made by hand: a paired letter with an endpoint at -1 that stands in the row-0 / column-0
+ * cell read for it, or a '#', '&', '"' far side behind such an endpoint.
+ */
+static int outside_cell_differs(const uint8_t *cells, const pwn_portal *pmap, int cx, int cz)
+{
+	const int c = cells[(cz < 0 ? 0 : cz) * 64 + (cx < 0 ? 0 : cx)];    /* util.h:151-158 */
+	if(c < 'A' || c > 'Z') return 0;
+	const pwn_portal *pm = &pmap[c - 'A'];
+	const int at1 = (pm->x1 == cx && pm->z1 == cz), at2 = (pm->x2 == cx && pm->z2 == cz);
+	/* trace.h:404-413: the letter itself is neither 2-high nor a '"' */
+	if(at1) { if(look_class(pm->c2 & 0xff) != 0u) return 1; }
+	else if(at2) { if(look_class(pm->c1 & 0xff) != 0u) return 1; }
+	/* trace.h:514-559: x2 == -1 is a wall before the endpoints are asked */
+	return pm->x2 != -1 && (at1 || at2);
+}
+
+int pwn_check_portals(const uint8_t *cells, const pwn_portal *pmap)
+{
+	for(int i = 0; i < 26; i++)
+	{
+		const int32_t v[4] = { pmap[i].x1, pmap[i].z1, pmap[i].x2, pmap[i].z2 };
+		for(int k = 0; k < 4; k++) if(v[k] < -1 || v[k] > 63) return 0;
+	}
+	/* (no endpoint has a coordinate beyond 63 or below -1: only these cells outside the grid can match one) */
+	for(int t = -1; t < 64; t++)
+		if(outside_cell_differs(cells, pmap, -1, t) || outside_cell_differs(cells, pmap, t, -1)) return 0;
+	return 1;
+}
+
+/* a whole number of magnitude <= 64 as a half float; `neg` gives -0.0 for 0 */
+static uint32_t half_of_int(int v, int neg)
+{
+	uint32_t m = (uint32_t)(v < 0 ? -v : v), sign = (v < 0 || neg) ? 0x8000u : 0u;
+	if(m == 0) return sign;
+	int e = 0;
+	while((m >> e) > 1u) e++;
+	return sign | ((uint32_t)(e + 15) << 10) | ((m - (1u << e)) << (10 - e));
+}
+
+/*
+ * The baked bits of every cell word and the endpoint records (cell_bake.h).  bits[65 * 65] in the
+ * table's own pitch, row / column 64 included; recs[PWN_EP_MAX].  Returns the number of records
+ * used.  The tests on a letter's cell are the reference's, in its order: endpoint 1 before
+ * endpoint 2, x2 == -1 only where it goes somewhere.  c1 / c2 are taken as chars (their low byte).
+ */
+int pwn_bake_cells(const uint8_t *cells, const pwn_portal *pmap, uint16_t *bits, uint32_t *recs)
+{
+	int nrec = 0;
+	memset(bits, 0, 65 * 65 * sizeof(uint16_t));
+	memset(recs, 0, PWN_EP_MAX * sizeof(uint32_t));
+	for(int z = 0; z < 64; z++)
+	for(int x = 0; x < 64; x++)
+	{
+		const int c = cells[z * 64 + x];
+		uint32_t inside = look_class(c), outside = inside;
+		if(c >= 'A' && c <= 'Z')
+		{
+			const pwn_portal *pm = &pmap[c - 'A'];
+			const int at1 = (pm->x1 == x && pm->z1 == z), at2 = (pm->x2 == x && pm->z2 == z);
+			/* trace.h:404-413 */
+			if(at1) inside = look_class(pm->c2 & 0xff);
+			else if(at2) inside = look_class(pm->c1 & 0xff);
+			/* trace.h:514-559 */
+			uint32_t st = pm->x2 == -1 ? PWN_PST_WALL : PWN_PST_MAGENTA;
+			outside |= st << PWN_C_PST_SHIFT;
+			if(pm->x2 != -1 && (at1 || at2))
+			{
+				const int dx = pm->x2 - pm->x1, dz = pm->z2 - pm->z1;
+				recs[nrec] = at1 ? half_of_int(dx, 0) | (half_of_int(dz, 0) << 16)
+				                 : half_of_int(-dx, dx == 0) | (half_of_int(-dz, dz == 0) << 16);
+				inside |= ((at1 ? 0u - (uint32_t)pm->rot12 : (uint32_t)pm->rot12) & 3u) << PWN_C_PROT_SHIFT;
+				st = PWN_PST_REC0 + (uint32_t)nrec++;
+			}
+			inside |= st << PWN_C_PST_SHIFT;
+		}
+		bits[z * 65 + x] = (uint16_t)inside;
+		/* what get_cell returns outside the grid on that axis (util.h:151-158): never at an endpoint */
+		if(x == 0) bits[z * 65 + 64] = (uint16_t)outside;
+		if(z == 0) bits[64 * 65 + x] = (uint16_t)outside;
+		if(x == 0 && z == 0) bits[64 * 65 + 64] = (uint16_t)outside;
+	}
+	return nrec;
 }
 
 /*

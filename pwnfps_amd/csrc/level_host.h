@@ -3,11 +3,14 @@
 #define PWN_LEVEL_HOST_H
 #include <stdint.h>
 #include "pwnhip.h"
+#include "cell_bake.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
 void pwn_level_clear(uint8_t *cells, pwn_portal *pmap, int32_t *spawn);
 int pwn_parse_level(const char *text, int len, uint8_t *cells, pwn_portal *pmap, int32_t *spawn);
+int pwn_check_portals(const uint8_t *cells, const pwn_portal *pmap);
+int pwn_bake_cells(const uint8_t *cells, const pwn_portal *pmap, uint16_t *bits, uint32_t *recs);
 int pwn_bin_spheres(const pwn_sphere *s, int n, int32_t *off, int32_t *idx, int idx_cap);
 #ifdef __cplusplus
 }

@@ -381,19 +381,17 @@ static int pack_blob(pwn_ctx *c)
 	uint8_t *b = c->blob.data();
 	uint32_t *ci = (uint32_t *)(b + PWN_T_CELLINFO);
 	uint16_t *bi = (uint16_t *)(b + PWN_T_BINIDX);
-	// the level's part of the cell words (char + class bits) is the same until the level changes: built once,
-	// copied per upload and patched where a cell has spheres
+	// the level's part of the cell words (class bits + what the portal arms ask of a cell: cell_bake.h) and the endpoint records are the
+	// same until the level or its portal table changes: baked once, the words copied per upload and patched where a cell has spheres
 	if(!c->cell_base_ok)
 	{
-		uint32_t *cb = c->cell_base;
-		memset(cb, 0, sizeof(c->cell_base));
-		for(int z = 0; z < 64; z++)
-		for(int x = 0; x < 64; x++)
-			cb[z * PWN_GRID_PITCH + x] = (uint32_t)c->cells[z * 64 + x] | pwn_cell_class(c->cells[z * 64 + x]);
+		std::vector<uint16_t> bits(65 * 65);
+		pwn_bake_cells(c->cells, c->pmap, bits.data(), c->ep_recs);
 		// row / column 64 = what get_cell returns outside the grid on that axis (util.h:151-158),
 		// never with spheres (the sphere loop runs for in-grid cells only, trace.h:252)
-		for(int z = 0; z < 64; z++) cb[z * PWN_GRID_PITCH + 64] = cb[z * PWN_GRID_PITCH];
-		for(int x = 0; x <= 64; x++) cb[64 * PWN_GRID_PITCH + x] = cb[x];
+		for(int z = 0; z <= 64; z++)
+		for(int x = 0; x <= 64; x++)
+			c->cell_base[z * PWN_GRID_PITCH + x] = (uint32_t)bits[z * PWN_GRID_PITCH + x] | pwn_cell_class(c->cells[(z & 63) * 64 + (x & 63)]);
 		c->cell_base_ok = true;
 	}
 	memcpy(ci, c->cell_base, sizeof(c->cell_base));
@@ -435,13 +433,7 @@ static int pack_blob(pwn_ctx *c)
 	memcpy(b + PWN_T_RCP, c->tabs, 4096);
 	memcpy(b + PWN_T_RSQ, c->tabs + 2048, 4096);
 	pwn_fill_faces((float *)(b + PWN_T_FACES));
-	uint32_t *pm = (uint32_t *)(b + PWN_T_PMAP);
-	for(int i = 0; i < 26; i++)
-	{
-		const pwn_portal &p = c->pmap[i];
-		pm[2 * i] = (uint32_t)(p.x1 & 0xff) | ((uint32_t)(p.z1 & 0xff) << 8) | ((uint32_t)(p.x2 & 0xff) << 16) | ((uint32_t)(p.z2 & 0xff) << 24);
-		pm[2 * i + 1] = (uint32_t)(p.rot12 & 0xff) | ((uint32_t)(p.c1 & 0xff) << 8) | ((uint32_t)(p.c2 & 0xff) << 16);
-	}
+	memcpy(b + PWN_T_EPREC, c->ep_recs, sizeof(c->ep_recs));
 	c->off_sph = inl ? pwn_t_sph_offset_inl(nrec) : pwn_t_sph_offset(nbin);
 	c->off_recsph = inl ? pwn_t_recsph_offset(nrec) : 0u;
 	// the kernels' layout of a sphere (tables.h): position and r*r in one 16-byte half, the rest in the other
@@ -480,20 +472,10 @@ static int pack_blob(pwn_ctx *c)
 	return PWN_OK;
 }
 
-static int valid_portals(const pwn_portal *pm)
-{
-	for(int i = 0; i < 26; i++)
-	{
-		const int32_t v[4] = { pm[i].x1, pm[i].z1, pm[i].x2, pm[i].z2 };
-		for(int k = 0; k < 4; k++) if(v[k] < -1 || v[k] > 63) return 0;
-	}
-	return 1;
-}
-
 extern "C" int pwn_upload_level(pwn_ctx *c, const uint8_t data[4096], const pwn_portal pmap[26])
 {
 	if(GRP_HEAD(c)) return (data == NULL || pmap == NULL) ? PWN_EINVAL : pwn_group_upload_level(c, data, pmap);
-	if(c == NULL || data == NULL || pmap == NULL || !valid_portals(pmap)) return PWN_EINVAL;
+	if(c == NULL || data == NULL || pmap == NULL || !pwn_check_portals(data, pmap)) return PWN_EINVAL;      // (which tables: level_host.c)
 	(void)hipSetDevice(c->device);
 	memcpy(c->cells, data, 4096);
 	memcpy(c->pmap, pmap, sizeof(c->pmap));

@@ -15,20 +15,22 @@
 //                       get_cell's per-axis clamp-to-0 (util.h:151-158) becomes
 //                       min(c, 64) and the in-bounds test in front of the sphere
 //                       loop (trace.h:252) is folded into the word.
-//                       bits 0..7   cell type char        level.data   (defs.h:105)
+//                       bits 0..7   what the walk's portal arms ask of the cell, baked per level (cell_bake.h):
+//                                   PWN_C_LT2 / PWN_C_LTDQ, what a ray leaving a 2-high room sees there (through a
+//                                   portal too); bits 2..7 the portal state of a letter: wall, magenta wall, or
+//                                   2 + the number of its endpoint record
 //                       bit  8      PWN_C_ROOM   ; $ "  #  &   (1-high or 2-high room)
 //                       bit  9      PWN_C_ROOM2  # &
 //                       bit  10     PWN_C_FOG    $ &
 //                       bit  11     PWN_C_DQ     "
 //                       bit  12     PWN_C_RAMP   > < , ^
-//                       bit  13     PWN_C_RAMPX  > <            (tilt along x)
-//                       bit  14     PWN_C_RAMPM  > ,            (ray.y -= ramp*tilt)
+//                       bit  13     PWN_C_RAMPX  > <            (tilt along x)    | in a letter's cell that is an endpoint:
+//                       bit  14     PWN_C_RAMPM  > ,            (ray.y -= ramp*tilt) | the rotation from there, 0..3 (cell_bake.h)
 //                       bit  15     PWN_C_PORTAL A..Z
 //                       bits 16..30 first entry of this cell's sphere list in binidx
 //                       bit  31     PWN_C_SPH    the cell holds >= 1 sphere
-//   [25616  .. 25824)  pmap     2 x u32 [26]      portals         (defs.h:87-94)
-//                       word0 = x1 | z1<<8 | x2<<16 | z2<<24   (0xff = -1)
-//                       word1 = rot12 | c1<<8 | c2<<16
+//   [25616  .. 25824)  eprec    u32 [52]          endpoint records of the portals (cell_bake.h; defs.h:87-94): the way to the other
+//                                                 endpoint as two half floats
 //   [25824  .. +2*nbin pad 16)  binidx u16        per-cell sphere lists (level.h:64-81),
 //                                                 object order, as BYTE offsets into the sphere
 //                                                 array (index * 32), each list closed by 0xffff
@@ -37,6 +39,7 @@
 //                                                 in fp32 like the reference does)
 #pragma once
 #include <stdint.h>
+#include "cell_bake.h"
 
 #define PWN_GRID_PITCH 65u
 #define PWN_T_RCP      0u
@@ -44,7 +47,7 @@
 #define PWN_T_FACES    8192u
 #define PWN_T_EXP2     8448u
 #define PWN_T_CELLINFO 8704u
-#define PWN_T_PMAP     25616u
+#define PWN_T_EPREC    25616u
 #define PWN_T_BINIDX   25824u
 
 // table entry -> fp32 pattern of the result for a zero exponent field (dev_math.h):
@@ -117,7 +120,7 @@ static inline void pwn_fill_faces(float *f)
 }
 
 // class bits of a cell type (trace.h:300-666 switch labels)
-static inline uint32_t pwn_cell_class(uint32_t c)
+static constexpr inline uint32_t pwn_cell_class(uint32_t c)
 {
 	switch(c)
 	{

@@ -37,7 +37,7 @@ struct Lds
 {
 	const PWN_LDS uint32_t *cellinfo;
 	const PWN_LDS uint16_t *rcp, *rsq;
-	const PWN_LDS uint32_t *pmap;
+	const PWN_LDS unsigned char *eprec;   // the portals' endpoint records (cell_bake.h), set back by the two states that have none: see ep_rec
 	const PWN_LDS uint16_t *binidx;
 	const PWN_LDS uint16_t *recsph;       // inline sphere records (tables.h): which sphere a record is of
 	const PWN_LDS float *sph;
@@ -50,7 +50,7 @@ __device__ __forceinline__ Lds lds_tables(uint32_t off_sph, uint32_t off_recsph 
 	L.cellinfo = lds_at<uint32_t>(PWN_T_CELLINFO);
 	L.rcp = lds_at<uint16_t>(PWN_T_RCP);
 	L.rsq = lds_at<uint16_t>(PWN_T_RSQ);
-	L.pmap = lds_at<uint32_t>(PWN_T_PMAP);
+	L.eprec = lds_at<unsigned char>(PWN_T_EPREC - PWN_PST_REC0 * 4u);
 	L.binidx = lds_at<uint16_t>(PWN_T_BINIDX);
 	L.faces = lds_at<pwn_f4>(PWN_T_FACES);
 	L.exp2 = lds_at<uint64_t>(PWN_T_EXP2);
@@ -96,6 +96,21 @@ __device__ __forceinline__ uint32_t cellword_pk(const Lds &L, uint32_t cxz)
 	const pwn_us2 c = __builtin_elementwise_min(__builtin_bit_cast(pwn_us2, cxz), lim);
 	const uint32_t byte = __builtin_amdgcn_udot2(c, pitch, 0u, false);
 	return *(const PWN_LDS uint32_t *)((const PWN_LDS unsigned char *)L.cellinfo + byte);
+}
+
+// The endpoint record of a portal cell whose state says it has one (cell_bake.h): the state field sits at bit 2 of the cell
+// word and a record is 4 bytes -- the field in place is the record's byte offset.  What comes back is what the reference adds
+// to the position on the way to the other endpoint: x, z (two half floats, exact for these whole numbers).
+static_assert(PWN_C_PST_SHIFT == 2u && PWN_T_EPREC + PWN_EP_MAX * 4u <= PWN_T_BINIDX, "ep_rec takes the state field as a byte offset; 52 records fit");
+// The rotation of an endpoint cell (PWN_C_PROT_SHIFT) sits in the two bits that say which way a ramp tilts: they are read behind
+// PWN_C_RAMP only, and a letter's cell has PWN_C_PORTAL and no other class bit.
+static_assert(PWN_C_RAMPX == (1u << PWN_C_PROT_SHIFT) && PWN_C_RAMPM == (2u << PWN_C_PROT_SHIFT), "the rotation takes the place of RAMPX | RAMPM");
+static_assert(pwn_cell_class('A') == PWN_C_PORTAL && pwn_cell_class('M') == PWN_C_PORTAL && pwn_cell_class('Z') == PWN_C_PORTAL, "a letter's cell has no ramp bit");
+static_assert((PWN_C_PST_MASK | PWN_C_LT2 | PWN_C_LTDQ) == 0xffu, "the baked byte lies below the class bits");
+typedef _Float16 pwn_h2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ pwn_h2 ep_rec(const Lds &L, uint32_t pst_in_place)
+{
+	return __builtin_bit_cast(pwn_h2, *(const PWN_LDS uint32_t *)(L.eprec + pst_in_place));
 }
 
 // HAS_W = false: the camera rows x,y,z carry w = 0 and the position w = 1

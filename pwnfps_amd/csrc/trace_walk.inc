@@ -164,20 +164,11 @@ if(cw & PWN_C_ROOM)
 			{
 				//@R w_height_out
 				RG(RG_HC_OUT);
-				// trace.h:404-413: look through a portal at the cell type behind it
-				int xcell = (int)(ncw & 0xffu);
-				if(ncw & PWN_C_PORTAL)
+				// trace.h:404-413: the cell type there, looked at through a portal where the cell is an endpoint -- decided
+				// per level, two bits of the cell word (cell_bake.h)
+				if(!(ncw & PWN_C_LT2))
 				{
-					const int cx = cxz_x(cxz), cz = cxz_z(cxz);
-					uint32_t p0 = L.pmap[2 * (xcell - 'A')], p1 = L.pmap[2 * (xcell - 'A') + 1];
-					int x1 = (int)(int8_t)(p0 & 0xff), z1 = (int)(int8_t)((p0 >> 8) & 0xff);
-					int x2 = (int)(int8_t)((p0 >> 16) & 0xff), z2 = (int)(int8_t)(p0 >> 24);
-					if(x1 == cx && z1 == cz) xcell = (int)((p1 >> 16) & 0xff);
-					else if(x2 == cx && z2 == cz) xcell = (int)((p1 >> 8) & 0xff);
-				}
-				if(!(xcell == '#' || xcell == '&'))
-				{
-					if(xcell == '"')
+					if(ncw & PWN_C_LTDQ)
 					{
 						pos.y += 1.0f;
 						wy -= iay_dn;
@@ -256,49 +247,38 @@ else
 		//@R w_portal
 		WAVE_PATH(5);
 		// trace.h:508-650: portal
-		int cx = cxz_x(cxz), cz = cxz_z(cxz);
-		int gx = cxz_x(sx), gz = cxz_z(sz);
-		const int pi = (int)(cw & 0xffu) - 'A';
-		uint32_t p0 = L.pmap[2 * pi], p1 = L.pmap[2 * pi + 1];
-		int x1 = (int)(int8_t)(p0 & 0xff), z1 = (int)(int8_t)((p0 >> 8) & 0xff);
-		int x2 = (int)(int8_t)((p0 >> 16) & 0xff), z2 = (int)(int8_t)(p0 >> 24);
-		int rot12 = (int)(p1 & 0xff);
-		const bool at1 = (x1 == cx && z1 == cz), at2 = (x2 == cx && z2 == cz);
-		if(x2 == -1 || !(at1 || at2))
+		// which endpoint this cell is, or that it is none, is the cell's portal state (cell_bake.h)
+		const uint32_t pst = cw_in & PWN_C_PST_MASK;
+		if(pst < (PWN_PST_REC0 << PWN_C_PST_SHIFT))
 		{
 			//@R w_portal_wall
 			RG(RG_PORTAL_WALL);
 			// unpaired letter, or a letter standing in a cell that is not one
 			// of its endpoints (trace.h:514-520,551-559)
+			static_assert(BASE_WALL + PWN_PST_WALL == BASE_WALL && BASE_WALL + PWN_PST_MAGENTA == BASE_MAGENTA, "the state is the wall class");
 			if(AUX_HIT()) ev = EV_SPHERE;
-			else { ev = EV_WALL; base = (x2 == -1 ? BASE_WALL : BASE_MAGENTA); }
+			else { ev = EV_WALL; base = BASE_WALL + (int)(pst >> PWN_C_PST_SHIFT); }
 		}
 		else
 		{
 			//@R w_portal_go
 			RG(RG_PORTAL_GO);
-			int rot;
-			if(at1)
-			{
-				cx = x2; cz = z2;
-				pos.x += (float)(x2 - x1);
-				pos.z += (float)(z2 - z1);
-				rot = (-rot12) & 3;
-			}
-			else
-			{
-				cx = x1; cz = z1;
-				pos.x -= (float)(x2 - x1);
-				pos.z -= (float)(z2 - z1);
-				rot = rot12 & 3;
-			}
+			// the way to the other endpoint (its sign applied for THIS endpoint) is one record, the rotation two bits of the cell
+			// word.  The other endpoint's cell is this one plus the same whole numbers, in floats: this cell is inside the grid.
+			const pwn_h2 er = ep_rec(L, pst);
+			const float edx = (float)er.x, edz = (float)er.y;
+			int gx = cxz_x(sx), gz = cxz_z(sz);
+			pos.x += edx;
+			pos.z += edz;
+			const int rot = (int)((cw_in >> PWN_C_PROT_SHIFT) & 3u);
 			if(COUNT) cnt.portals++;
 
 			// trace.h:561-622.  The operation order is the one the reference
 			// build executes (its -ffast-math cancels the +-0.5 terms).
 			const float trx = pos.x, trz = pos.z, trvx = ray.x, trvz = ray.z;
 			const int tgx = gx, tgz = gz;
-			const float fcx = (float)cx, fcz = (float)cz;
+			const float fcx = (float)cxz_x(cxz) + edx, fcz = (float)cxz_z(cxz) + edz;
+			int cx = (int)fcx, cz = (int)fcz;
 			ldir = (ldir - rot) & 3;
 			if(rot & 1)
 			{

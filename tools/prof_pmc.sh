@@ -11,8 +11,11 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p "$OUT"
 pass() { # name counters...
 	local name=$1; shift
-	rocprofv3 --pmc "$@" --output-format csv -d "$OUT/$name" -o "$name" -- python3 tools/prof_frame.py $ARGS > "$OUT/$name.log" 2>&1
-	echo "pass $name rc=$?"
+	timeout -k 10 300 rocprofv3 --pmc "$@" --output-format csv -d "$OUT/$name" -o "$name" -- python3 tools/prof_frame.py $ARGS > "$OUT/$name.log" 2>&1
+	local rc=$?
+	echo "pass $name rc=$rc"
+	# a pass that failed or ran into its time limit ends the run: nothing more is started on that GPU
+	[ $rc -eq 0 ] || exit $rc
 }
 pass valu    SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_INSTS_SALU SQ_INSTS_LDS
 pass wait    SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_INSTS_SMEM
