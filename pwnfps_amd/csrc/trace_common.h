@@ -1,8 +1,18 @@
-// trace_common.h -- types and helpers shared by the two trace kernels
+// trace_common.h -- what the two trace kernels share that is not a ray segment's arithmetic
 // (trace_kernel.hip: a wave64 traces 16x4-pixel units in step; trace_refill.hip: lanes are
-// refilled with new rays by ballot + prefix rank while the others walk on).
+// refilled with new rays by ballot + prefix rank while the others walk on):
+//   - constants, the LDS table pointers, the packed cell coordinates, Vec and its operations, the counters;
+//   - small pieces of the scheduling code as inline functions: pixel_seed, blob_to_lds, next_open_queue,
+//     wave_log_slot, wave_first_lane (each leaves the units kernel's assembly as it was);
+//   - the host side: launch_kernel / kernel_blocks_per_cu for one instantiation, TraceKernels for the four
+//     a launch's count and has_w pick from.
+// The segment's arithmetic itself is one text per piece, textually included by both kernels: trace_setup.inc,
+// trace_walk.inc (with trace_sphere.inc), trace_shade.inc, trace_bounce.inc, trace_jitter.inc,
+// trace_composite.inc; trace_counters.inc flushes the counters.  Each says at its top which names it
+// expects in scope and which it writes.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <mutex>
 #include "dev_math.h"
 #include "tables.h"
 
@@ -171,3 +181,117 @@ struct Counters { uint32_t rays, steps, portals, tests, exhausted, wsteps, wp[8]
 // one count per wave64 that enters a code path with at least one lane (pwn_stats.wave_paths)
 #define WAVE_PATH(k) do { if(COUNT && (__ffsll((long long)__ballot(1)) - 1) == (int)(threadIdx.x & 63)) cnt.wp[k]++; } while(0)
 #define RG(k) do { if(COUNT && (__ffsll((long long)__ballot(1)) - 1) == (int)(threadIdx.x & 63)) cnt.rg[k]++; } while(0)
+
+// ---- pieces of the kernels' scheduling code that both write the same way
+
+// screen.h:19-21 (uint32 wrap-around), doubled: the generator runs on the doubled state (lcg2_fs, dev_math.h)
+__device__ __forceinline__ uint32_t pixel_seed(int x, int y, int w)
+{
+	uint32_t seed = (uint32_t)x + (uint32_t)y * (uint32_t)y * ((uint32_t)w + 1u);
+	seed *= seed * seed;
+	seed *= seed * seed;
+	return seed << 1;
+}
+
+// the level blob HBM -> LDS by the whole workgroup, 16 B per lane per trip (the caller synchronises)
+__device__ __forceinline__ void blob_to_lds(unsigned char *lds, const void *blob, uint32_t blob_bytes)
+{
+	const uint4 *src = (const uint4 *)blob;
+	uint4 *dst = (uint4 *)lds;
+	int n16 = (int)(blob_bytes >> 4);
+	for(int i = threadIdx.x; i < n16; i += PWN_BLOCK) dst[i] = src[i];
+}
+
+// the next open queue after q, cyclically (open: one bit per queue, not 0): bit i of the shifted double mask is queue q+1+i
+__device__ __forceinline__ uint32_t next_open_queue(uint32_t q, unsigned long long open)
+{
+	static_assert(PWN_QUEUES <= 64u && (PWN_QUEUES & (PWN_QUEUES - 1u)) == 0u, "a power of two, one lane per queue");
+	if constexpr(PWN_QUEUES == 64u)
+	{
+		const uint32_t rot = q + 1u;                 // 1..64
+		const unsigned long long r = rot == 64u ? open : ((open >> rot) | (open << (64u - rot)));
+		return (q + 1u + (uint32_t)__builtin_ctzll(r)) & 63u;
+	}
+	else
+		return (q + 1u + (uint32_t)__builtin_ctzll((open | (open << (PWN_QUEUES & 31u))) >> (q + 1u))) & (PWN_QUEUES - 1u);
+}
+
+// PWN_OPT_WAVE_LOG: this wave's two words of the log (pwn_stats.wave_time ..., tools/wave_log.py).
+// Which wave of the workgroup this is comes from the hardware: the four waves of a 256-thread workgroup
+// sit on the four SIMDs of their CU, HW_ID.simd_id is bits 5:4 of hardware register 4.  (Keeping threadIdx.x
+// alive to the end of the kernel costs a scratch slot per lane, and a shared append counter serialises the
+// waves' exits and stretches the very tail it measures.)
+__device__ __forceinline__ unsigned long long *wave_log_slot(unsigned long long *wave_log)
+{
+	static_assert(PWN_BLOCK == 256, "one wave per SIMD: simd_id tells the waves of a workgroup apart");
+	const unsigned simd = __builtin_amdgcn_s_getreg(4 | (4 << 6) | ((2 - 1) << 11));
+	const size_t wid = 1u + (size_t)blockIdx.x * 4u + simd;
+	return wave_log + 2 * wid;
+}
+// lane 0 of the wave without threadIdx.x: the lane number from mbcnt
+__device__ __forceinline__ bool wave_first_lane()
+{
+	return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0u;
+}
+
+// ---- host side: launching the instantiations of a trace kernel
+
+// One instantiation KERNEL (a __global__ void(pwn_trace_params)) with lds_bytes of dynamic LDS.
+template<auto KERNEL>
+static hipError_t launch_kernel(const pwn_trace_params *P, int grid, size_t lds_bytes, hipStream_t stream)
+{
+	// the dynamic-LDS limit is a per-function attribute: raise it only when the blob grew
+	// (high-water mark per device and instantiation; contexts of several threads share it, so the
+	// check and the raise happen under a lock and the mark only ever grows)
+	static size_t lds_mark[64];
+	static std::mutex lds_lock;
+	int dev = 0;
+	(void)hipGetDevice(&dev);
+	{
+		std::lock_guard<std::mutex> g(lds_lock);
+		size_t &lds_set = lds_mark[dev & 63];
+		if(lds_bytes > lds_set)
+		{
+			// the kernel addresses its tables from LDS address 0 (above): that holds while it has no
+			// static LDS, which would be laid out in front of the dynamic allocation
+			hipFuncAttributes fa;
+			hipError_t e = hipFuncGetAttributes(&fa, (const void *)KERNEL);
+			if(e != hipSuccess) return e;
+			if(fa.sharedSizeBytes != 0) return hipErrorInvalidConfiguration;
+			e = hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+			if(e != hipSuccess) return e;
+			lds_set = lds_bytes;
+		}
+	}
+	hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(PWN_BLOCK), lds_bytes, stream, *P);
+	return hipGetLastError();
+}
+
+// resident 256-thread workgroups per CU of one instantiation with this much LDS
+template<auto KERNEL>
+static int kernel_blocks_per_cu(size_t lds_bytes)
+{
+	int n = 0;
+	hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, KERNEL, PWN_BLOCK, lds_bytes);
+	if(e != hipSuccess || n < 1) n = 2;
+	return n;
+}
+
+// The four instantiations of a kernel template for <COUNT, HAS_W> = <1,1>, <1,0>, <0,1>, <0,0>: a launch's
+// count and has_w pick one.  (In an unnamed namespace: the library exports the C ABI only.)
+namespace {
+template<auto K11, auto K10, auto K01, auto K00>
+struct TraceKernels
+{
+	static hipError_t launch(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
+	{
+		if(count) return P->has_w ? launch_kernel<K11>(P, grid, lds_bytes, stream) : launch_kernel<K10>(P, grid, lds_bytes, stream);
+		return P->has_w ? launch_kernel<K01>(P, grid, lds_bytes, stream) : launch_kernel<K00>(P, grid, lds_bytes, stream);
+	}
+	static int blocks_per_cu(size_t lds_bytes, bool count, bool has_w)
+	{
+		if(count) return has_w ? kernel_blocks_per_cu<K11>(lds_bytes) : kernel_blocks_per_cu<K10>(lds_bytes);
+		return has_w ? kernel_blocks_per_cu<K01>(lds_bytes) : kernel_blocks_per_cu<K00>(lds_bytes);
+	}
+};
+}

@@ -26,7 +26,6 @@
 //     is arithmetically identical to the 4-lane SSE code (see HAS_W below),
 //   - no device function calls (dev_math.h) and no SLP packing (Makefile).
 #include <hip/hip_runtime.h>
-#include <mutex>
 #include "trace_common.h"
 
 
@@ -84,85 +83,21 @@ __device__ __forceinline__ void trace_pixel(const Lds &L, float sec_current, uin
 		//@R p_setup
 		RG(RG_SEG);
 		seg = __builtin_amdgcn_readfirstlane(seg);
-		// ------------------------------------------------ trace.h:186-248
-		float cdist = 0.0f, fog = 0.0f;
-		// nearest sphere candidate (trace.h:193-199): distance, hit point, which sphere and
-		// its diffuse factor; normal, colour and reflectivity are rebuilt from these when
-		// the hit is committed
-		// aux_dist: the reference's "none yet" value -1 (trace.h:200) is kept as +inf here, so that
-		// "a candidate exists and lies behind us" is one comparison; a candidate whose distance is
-		// exactly -1.0f counts as none there and is stored as +inf here too
-		// (the candidate's other fields are read only behind aux_dist: they keep what the segment before left in them -- declared in
-		// front of the loop -- instead of five moves per ray)
-		float aux_dist = __builtin_inff();
-		if(COUNT) cnt.rays++;
-
-		// The set-up's table reads (1/sqrt, the first cell's word, three reciprocals) are each issued ahead of work that does not
-		// need them -- the compiler leaves an LDS read where the source has it, directly in front of its use, and sinks one that
-		// only a branch uses into that branch: -0.3 % launch time at 4K, -0.5 % on synth64 (profiles/r5/sphere_lists_ab.txt).
-		const uint32_t lb = __float_as_uint(dot3<HAS_W>(iray, iray));
-		const uint32_t rsq_e = tab_rsqrt_entry(L.rsq, lb);
-		int cx = (int)pos.x, cz = (int)pos.z;
-		// signs of the UN-normalised input (trace.h:225-227)
-		int gx = (iray.x < 0.0f ? -1 : 1);
-		int gz = (iray.z < 0.0f ? -1 : 1);
-		const bool gyp = !(iray.y < 0.0f);          // gy > 0
-		// cell coordinates and steps in the packed form the walk uses (trace_common.h)
-		uint32_t cxz = cxz_pack_start(cx, cz), sx = (uint32_t)gx & 0xffffu, sz = (uint32_t)gz << 16;
-		uint32_t cw = cellword_pk(L, cxz);
-		float wx = pos.x - (float)cx, wy = pos.y, wz = pos.z - (float)cz;
-		const int ldy = gyp ? FYP : FYN;
-		int ldx = (gx < 0 ? FXN : FXP), ldz = (gz < 0 ? FZN : FZP);
-		// util.h:32-46
-		V ray = vscale<HAS_W>(tab_rsqrt_finish(lb, rsq_e), iray);
-		// trace.h:220-222 clamp |ray| to EPSILON, trace.h:230-231 take the three reciprocals.  A normalised ray
-		// has all three magnitudes in [EPSILON, 2^126) unless it is degenerate: ONE test on the bit patterns
-		// (a NaN's is above every number's) and one wave-uniform branch; then nothing is clamped and all three
-		// reciprocals are the one-subtract table path (one LDS round trip, under way while the fractions are turned:
-		// a table index is in range whatever the bits are)
-		float iax, iaz, iay_;
-		{
-			const uint32_t EPSB = __float_as_uint(EPS);
-			const uint32_t bx = __float_as_uint(ray.x) & 0x7fffffffu, by = __float_as_uint(ray.y) & 0x7fffffffu,
-				bz = __float_as_uint(ray.z) & 0x7fffffffu;
-			uint32_t ex = rcp_entry(L.rcp, bx), ey = rcp_entry(L.rcp, by), ez = rcp_entry(L.rcp, bz);
-			const bool plain = max(max(bx - EPSB, by - EPSB), bz - EPSB) < 0x7e800000u - EPSB;
-			if(ray.x >= 0.0f) wx = 1.0f - wx;
-			if(ray.y >= 0.0f) wy = 1.0f - wy;
-			if(ray.z >= 0.0f) wz = 1.0f - wz;
-			// (statements the compiler may not reorder: the fractions first, then the wait for the table.  Not in the 4-lane
-			// variant: its ordered form would need 12 bytes of scratch per lane for them)
-			if constexpr(!HAS_W)
-			{
-				asm volatile("" : "+v"(wx), "+v"(wy), "+v"(wz));
-				asm volatile("" : "+v"(ex), "+v"(ey), "+v"(ez));
-			}
-			if(__builtin_expect(__ballot(!plain) == 0ull, 1))
-			{
-				iax = __uint_as_float(ex - (bx & 0x7f800000u)); iay_ = __uint_as_float(ey - (by & 0x7f800000u));
-				iaz = __uint_as_float(ez - (bz & 0x7f800000u));
-			}
-			else
-			{
-				//@R p_setup_slow
-				RG(RG_SETUP_SLOW);
-				// (the fractions above were turned by the unclamped signs: the clamp keeps ">= 0" as it was -- -0 counts as +)
-				if(fabsf(ray.x) < EPS) ray.x = (ray.x < 0.0f ? -EPS : EPS);
-				if(fabsf(ray.y) < EPS) ray.y = (ray.y < 0.0f ? -EPS : EPS);
-				if(fabsf(ray.z) < EPS) ray.z = (ray.z < 0.0f ? -EPS : EPS);
-				iax = tab_rcp(L.rcp, fabsf(ray.x)); iay_ = tab_rcp(L.rcp, fabsf(ray.y)); iaz = tab_rcp(L.rcp, fabsf(ray.z));
-			}
-		}
-		//@R p_setup
-		const float iay = iay_;
-		wx *= iax; wy *= iay; wz *= iaz;
-		// the "-part of a two-level room shifts the floor by one: wy moves by -+iay
-		// (trace.h:345-349,381-385); iay_dn is the amount added when stepping DOWN into it
-		const float iay_dn = gyp ? iay : -iay;
-		uint32_t iay_up_bits = gyp ? __float_as_uint(iay) : 0u;         // +iay when looking up, else +0
-		asm volatile("" : "+v"(iay_up_bits));        // keep it a register, not a select on gyp per step
-		int ldir = FYN;
-		int ev = EV_NONE, base = BASE_ROOM_Y;
+		// ------------------------------------------------ trace.h:186-248 (trace_setup.inc)
+		// the segment's ray and what the walk keeps of it.  Declared here, without values, because the set-up's text is shared
+		// with the refill kernel, where they outlive the segment.  The ORDER of these declarations is that of the set-up's
+		// first writes and is not a matter of style: in another order the compiler numbers registers differently and this
+		// kernel's assembly is no longer the one that was measured (profiles/shared_segment/asm.txt).
+		float cdist, fog, aux_dist;
+		bool gyp;
+		uint32_t cxz, sx, sz, cw;
+		float wx, wy, wz;
+		int ldy, ldx, ldz;
+		V ray;
+		float iax, iaz, iay, iay_dn;
+		uint32_t iay_up_bits;
+		int ldir, ev, base;
+#include "trace_setup.inc"
 
 		// ------------------------------------------------ trace.h:250-675 (trace_walk.inc)
 		//@R p_walk_ctl
@@ -207,91 +142,19 @@ __device__ __forceinline__ void trace_pixel(const Lds &L, float sec_current, uin
 #define colx vx
 #define coly vy
 #define colz vz
-		if(ev == EV_WALL)
-		{
-			//@R p_wall
-			RG(RG_WALL);
-			// trace.h:108-154, and the axis-aligned mirrors of trace.h:50-75.  Colour by wall class and what
-			// the face does to the ray are two constant tables in LDS (tables.h PWN_T_FACES): three 16-byte
-			// reads instead of two switch trees (which the compiler builds out of lane masks and branches)
-			const pwn_f4 wc = L.faces[base];
-			const pwn_f4 fa = L.faces[4 + 2 * ldir], fb = L.faces[5 + 2 * ldir];
-			float diffuse = (ldir & 1) ? ray.z : ray.x;
-			diffuse = ldir >= FYP ? ray.y : diffuse;
-			diffuse = __uint_as_float(__float_as_uint(diffuse) ^ __float_as_uint(fb.w));      // -ray.c on the N faces
-			if(diffuse < 0.0f) diffuse = 0.0f;
-			const float amb = 0.1f;
-			diffuse = (1.0f - amb) * diffuse + amb;
-			colx = diffuse * (icx * wc.x); coly = diffuse * (icy * wc.y); colz = diffuse * (icz * wc.z);
-			w_acc = __builtin_fmaf(diffuse, 0.0f, w_acc);
-			refl = fa.w;
-			// the mirror: flip the ray component along the face normal, step 0.001 off the surface (the other
-			// axes add -0.0f, which changes nothing); the floor (FYN) takes the step here and its ray from
-			// the rippled normal below
-			ray.x = __uint_as_float(__float_as_uint(ray.x) ^ __float_as_uint(fa.x));
-			ray.y = __uint_as_float(__float_as_uint(ray.y) ^ __float_as_uint(fa.y));
-			ray.z = __uint_as_float(__float_as_uint(ray.z) ^ __float_as_uint(fa.z));
-			pos.x += fb.x; pos.y += fb.y; pos.z += fb.z;
-		}
-		else
-		{
-			//@R p_sphere
-			RG(RG_SPHERE);
-			// trace.h:283-291 for the committed sphere
-			// (inline records: aux_idx is the record's LDS address; which sphere it is of -- a byte offset -- is looked up here, once per hit)
-			if constexpr(INL) aux_idx = L.recsph[(aux_idx - PWN_T_BINIDX) >> 4];
-			const PWN_LDS pwn_f4 *sp = (const PWN_LDS pwn_f4 *)((const PWN_LDS unsigned char *)L.sph + aux_idx);      // (a byte offset)
-			const pwn_f4 s0 = sp[0], s1 = sp[1];
-			V d;
-			d.x = aux_pos.x - s0.x; d.y = aux_pos.y - s0.y; d.z = aux_pos.z - s0.z;
-			if constexpr(HAS_W) d.w = aux_pos.w - 1.0f; else d.w = 0.0f;
-			aux_norm = vnormalise<HAS_W>(L.rsq, d);
-			colx = aux_diff * s1.y; coly = aux_diff * s1.z; colz = aux_diff * s1.w;
-			w_acc = __builtin_fmaf(aux_diff, 0.0f, w_acc);
-			refl = s1.x;
-			ldir = -1;
-			pos = aux_pos;
-		}
+		// trace.h:108-154 / 283-291: the wall's or the sphere's colour, the ray mirrored at a wall
+#include "trace_shade.inc"
 
 		//@R p_post
 		// trace.h:3-7
 		if(seg >= REFLECT_MAX || refl == 0.0f) { vw = 0.0f; depth = seg; break; }
 
-		// trace.h:9-75
-		if(ldir == FYN)
-		{
-			//@R p_floor
-			RG(RG_FLOOR);
-			const float pi = (float)3.14159265358979323846;
-			float ang = (pi * 2.0f) * (
-				(glibc_sincosf((pi * 0.5f) * pos.x, 0) + glibc_sincosf((pi * 0.5f) * pos.z, 1))
-				+ sec_current);
-			const float2 sc = glibc_sincosf_both(ang);
-			V n; n.x = sc.x; n.y = 38.0f; n.z = sc.y; n.w = 0.0f;
-			n = vnormalise<HAS_W>(L.rsq, n);
-			float rmul = -2.0f * ((ray.x * n.x + ray.y * n.y) + ray.z * n.z);
-			ray = vnormalise<HAS_W>(L.rsq, vadd<HAS_W>(vscale<HAS_W>(rmul, n), ray));
-		}
-		else if(ldir < 0)
-		{
-			//@R p_sphrefl
-			RG(RG_SPHREFL);
-			pos = vsub<HAS_W>(pos, vscale<HAS_W>(0.001f, ray));
-			float rmul = -2.0f * ((ray.x * aux_norm.x + ray.y * aux_norm.y) + ray.z * aux_norm.z);
-			ray = vnormalise<HAS_W>(L.rsq, vadd<HAS_W>(vscale<HAS_W>(rmul, aux_norm), ray));
-		}
+		// trace.h:9-84: off the rippled floor or a sphere, then the jitter (straight into the next segment's direction)
+#include "trace_bounce.inc"
+#include "trace_jitter.inc"
 
 		//@R p_jitter
-		RG(RG_JITTER);
-		// trace.h:77-84: five draws, two discarded
-		// (straight into the next segment's direction; the entry below the top is moved down only once there is one)
-		iray.x = ray.x + lcg2_fs(seed) * REFLECT_BLUR_F;
-		iray.y = ray.y + lcg2_fs(seed) * REFLECT_BLUR_F;
-		lcg2_next(seed);
-		iray.z = ray.z + lcg2_fs(seed) * REFLECT_BLUR_F;
-		lcg2_next(seed);
-		if constexpr(HAS_W) iray.w = ray.w;
-
+		// (the entry below the top is moved down only once there is one)
 		if(seg != 0) { st_refl1 = st_refl0; st_fog1 = st_fog0; sc1x = sc0x; sc1y = sc0y; sc1z = sc0z; }
 		st_refl0 = refl; st_fog0 = fog; sc0x = colx; sc0y = coly; sc0z = colz;
 #undef colx
@@ -300,38 +163,8 @@ __device__ __forceinline__ void trace_pixel(const Lds &L, float sec_current, uin
 		seg++;
 	}
 
-	//@R p_comp
-	// trace.h:91-101, innermost first
-	// the top of the stack is the last surface the ray bounced off, the entry below it the one before
-	if(depth >= 1)
-	{
-		//@R p_comp1
-		RG(RG_COMP1);
-		const float r0 = st_refl0, q0 = 1.0f - st_refl0;
-		vx = r0 * vx + q0 * sc0x; vy = r0 * vy + q0 * sc0y; vz = r0 * vz + q0 * sc0z; vw = r0 * vw;
-		if(st_fog0 != 0.0f)
-		{
-			//@R p_comp1_fog
-			RG(RG_COMP1_FOG);
-			float f = glibc_expf(-0.6f * st_fog0, L.exp2), g = 1.0f - f;
-			vx = f * vx + g; vy = f * vy + g; vz = f * vz + g; vw = f * vw + g;
-		}
-	}
-	//@R p_comp
-	if(depth >= 2)
-	{
-		//@R p_comp2
-		RG(RG_COMP2);
-		const float r1 = st_refl1, q1 = 1.0f - st_refl1;
-		vx = r1 * vx + q1 * sc1x; vy = r1 * vy + q1 * sc1y; vz = r1 * vz + q1 * sc1z; vw = r1 * vw;
-		if(st_fog1 != 0.0f)
-		{
-			//@R p_comp2_fog
-			RG(RG_COMP2_FOG);
-			float f = glibc_expf(-0.6f * st_fog1, L.exp2), g = 1.0f - f;
-			vx = f * vx + g; vy = f * vy + g; vz = f * vz + g; vw = f * vw + g;
-		}
-	}
+	// trace.h:91-101
+#include "trace_composite.inc"
 #undef icx
 #undef icy
 #undef icz
@@ -376,15 +209,9 @@ pwn_trace_kernel(pwn_trace_params P)
 	//@R k_prologue
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
 
-	// HBM -> LDS, 16 B per lane per trip
-	{
-		const uint4 *src = (const uint4 *)P.blob;
-		uint4 *dst = (uint4 *)lds_raw;
-		int n16 = (int)(P.blob_bytes >> 4);
-		for(int i = threadIdx.x; i < n16; i += PWN_BLOCK) dst[i] = src[i];
-		// one word behind the tables: the workgroup's share of pwn_trace_params.cost_word (bottom of the kernel)
-		if(threadIdx.x == 0) *(uint32_t *)(lds_raw + ((P.blob_bytes + 15u) & ~15u)) = 0u;
-	}
+	blob_to_lds(lds_raw, P.blob, P.blob_bytes);
+	// one word behind the tables: the workgroup's share of pwn_trace_params.cost_word (bottom of the kernel)
+	if(threadIdx.x == 0) *(uint32_t *)(lds_raw + ((P.blob_bytes + 15u) & ~15u)) = 0u;
 	__syncthreads();
 
 	// (the tables are addressed from LDS address 0 on, trace_common.h; the launcher checks that this kernel has
@@ -474,16 +301,7 @@ pwn_trace_kernel(pwn_trace_params P)
 			const uint32_t len_l = (units + PWN_QUEUES - 1u - (ql & (PWN_QUEUES - 1u))) / PWN_QUEUES;
 			const unsigned long long open = __ballot(ql < PWN_QUEUES && seen < len_l - min(len_l, QBASE(ql & (PWN_QUEUES - 1u))));
 			if(open == 0ull) break;
-			// the next open queue after q, cyclically: bit i of the shifted double mask is queue q+1+i
-			static_assert(PWN_QUEUES <= 64u && (PWN_QUEUES & (PWN_QUEUES - 1u)) == 0u, "a power of two, one lane per queue");
-			if constexpr(PWN_QUEUES == 64u)
-			{
-				const uint32_t rot = q + 1u;                 // 1..64
-				const unsigned long long r = rot == 64u ? open : ((open >> rot) | (open << (64u - rot)));
-				q = (q + 1u + (uint32_t)__builtin_ctzll(r)) & 63u;
-			}
-			else
-				q = (q + 1u + (uint32_t)__builtin_ctzll((open | (open << (PWN_QUEUES & 31u))) >> (q + 1u))) & (PWN_QUEUES - 1u);
+			q = next_open_queue(q, open);
 			uint32_t t = 0;
 			if(lane == 0) t = atomicAdd(&P.tickets[q * PWN_QUEUE_STRIDE], 1u);
 			ticket = (uint32_t)__builtin_amdgcn_readfirstlane((int)t) + QBASE(q);
@@ -659,12 +477,7 @@ pwn_trace_kernel(pwn_trace_params P)
 		if(ORDER && P.unit_cost != NULL) u_begin = __builtin_amdgcn_s_memrealtime();
 		if(x < P.w && y < P.y1)
 		{
-			// screen.h:19-21 (uint32 wrap-around)
-			uint32_t seed = (uint32_t)x + (uint32_t)y * (uint32_t)y * ((uint32_t)P.w + 1u);
-			seed *= seed * seed;
-			seed *= seed * seed;
-			seed <<= 1;                               // the generator runs on the doubled state (lcg2_fs, dev_math.h)
-
+			const uint32_t seed = pixel_seed(x, y, P.w);
 			float ox, oy, oz, ow;
 			const uint32_t o = __umul24((uint32_t)y, (uint32_t)P.w) + (uint32_t)x;      // w, h <= 32768 (pwn_init)
 			trace_pixel<COUNT, HAS_W, INL>(L, sec_current, seed, from, rayl, ox, oy, oz, ow, zbuf + o, cnt);
@@ -695,33 +508,21 @@ pwn_trace_kernel(pwn_trace_params P)
 	//@R k_epilogue
 	if(COUNT)
 	{
-		// wave reduce, one atomic per wave and counter
-		unsigned long long v[16 + RG_N] = { cnt.rays, cnt.steps, cnt.portals, cnt.tests, cnt.exhausted, cnt.wsteps,
-			cnt.wp[0], cnt.wp[1], cnt.wp[2], cnt.wp[3], cnt.wp[4], cnt.wp[5], cnt.wp[6], cnt.wp[7], cnt.apasses, cnt.apass_lanes };
-		for(int i = 0; i < RG_N; i++) v[16 + i] = cnt.rg[i];
-		for(int i = 0; i < 16 + RG_N; i++)
-		{
-			unsigned long long s = v[i];
-			for(int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
-			if(lane == 0 && s) atomicAdd(&P.counters[i], s);
-		}
+		// (the issue model's region counts go behind the first 16)
+#define PWN_CNT_REGIONS RG_N
+#include "trace_counters.inc"
+#undef PWN_CNT_REGIONS
 		// (waves of this launch: the prologue and the epilogue of the issue model)
 		if(lane == 0) atomicAdd(&P.counters[16 + RG_N], 1ull);
 	}
-	// PWN_OPT_WAVE_LOG: every wave's lifetime (pwn_stats.wave_time ..., tools/wave_log.py)
-	// (Which wave of the workgroup this is comes from the hardware: the four waves of a 256-thread workgroup
-	// sit on the four SIMDs of their CU, HW_ID.simd_id is bits 5:4 of hardware register 4; the lane number
-	// comes from mbcnt.  Keeping threadIdx.x alive to the end of the kernel costs a scratch slot per lane,
-	// and a shared append counter serialises the waves' exits and stretches the very tail it measures.)
-	if(P.wave_log != NULL && __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0u)
+	// PWN_OPT_WAVE_LOG: every wave's lifetime
+	if(P.wave_log != NULL && wave_first_lane())
 	{
-		static_assert(PWN_BLOCK == 256, "one wave per SIMD: simd_id tells the waves of a workgroup apart");
-		const unsigned simd = __builtin_amdgcn_s_getreg(4 | (4 << 6) | ((2 - 1) << 11));
-		const size_t wid = 1u + (size_t)blockIdx.x * 4u + simd;
+		unsigned long long *wl = wave_log_slot(P.wave_log);
 #ifdef PWN_DRAW_PROBE
-		P.wave_log[2 * wid] = probe_ticks | (probe_n << 40); P.wave_log[2 * wid + 1] = __builtin_amdgcn_s_memrealtime() - t_begin;
+		wl[0] = probe_ticks | (probe_n << 40); wl[1] = __builtin_amdgcn_s_memrealtime() - t_begin;
 #else
-		P.wave_log[2 * wid] = t_begin; P.wave_log[2 * wid + 1] = __builtin_amdgcn_s_memrealtime();
+		wl[0] = t_begin; wl[1] = __builtin_amdgcn_s_memrealtime();
 #endif
 	}
 	// Row tiling with moving cuts (pwn_tiled.cpp): what this strip COST, as the sum of its waves' lifetimes in ticks of
@@ -729,7 +530,7 @@ pwn_trace_kernel(pwn_trace_params P)
 	// in wave-time, whatever the tail of the launch looked like.  The four waves of a workgroup add up in LDS (one
 	// ds_add_rtn: lifetime in the low 28 bits, a count in the high four) and the last one to leave adds the
 	// workgroup's sum to the word: ~1300 no-return atomics per launch, spread over its tail.
-	if(P.cost_word != NULL && __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0u)
+	if(P.cost_word != NULL && wave_first_lane())
 	{
 		static_assert(PWN_BLOCK == 256, "four waves per workgroup");
 		const uint32_t life = (uint32_t)(__builtin_amdgcn_s_memrealtime() - t_begin) & 0x03ffffffu;
@@ -739,67 +540,23 @@ pwn_trace_kernel(pwn_trace_params P)
 	}
 }
 
-template<bool COUNT, bool HAS_W, bool ORDER, bool INL, int MODE>
-static hipError_t launch_variant(const pwn_trace_params *P, int grid, size_t lds_bytes, hipStream_t stream)
-{
-	// the dynamic-LDS limit is a per-function attribute: raise it only when the blob grew
-	// (high-water mark per device and variant; contexts of several threads share it, so the
-	// check and the raise happen under a lock and the mark only ever grows)
-	static size_t lds_mark[64];
-	static std::mutex lds_lock;
-	int dev = 0;
-	(void)hipGetDevice(&dev);
-	{
-		std::lock_guard<std::mutex> g(lds_lock);
-		size_t &lds_set = lds_mark[dev & 63];
-		if(lds_bytes > lds_set)
-		{
-			// the kernel addresses its tables from LDS address 0 (trace_common.h): that holds while it has no
-			// static LDS, which would be laid out in front of the dynamic allocation
-			hipFuncAttributes fa;
-			hipError_t e = hipFuncGetAttributes(&fa, (const void *)pwn_trace_kernel<COUNT, HAS_W, ORDER, INL, MODE>);
-			if(e != hipSuccess) return e;
-			if(fa.sharedSizeBytes != 0) return hipErrorInvalidConfiguration;
-			e = hipFuncSetAttribute((const void *)pwn_trace_kernel<COUNT, HAS_W, ORDER, INL, MODE>,
-				hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-			if(e != hipSuccess) return e;
-			lds_set = lds_bytes;
-		}
-	}
-	hipLaunchKernelGGL((pwn_trace_kernel<COUNT, HAS_W, ORDER, INL, MODE>), dim3(grid), dim3(PWN_BLOCK), lds_bytes, stream, *P);
-	return hipGetLastError();
-}
-
-template<bool ORDER, bool INL>
-static hipError_t launch_ordered(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
-{
-	if(count) return P->has_w ? launch_variant<true, true, ORDER, INL, PWN_KM_FRAME>(P, grid, lds_bytes, stream) : launch_variant<true, false, ORDER, INL, PWN_KM_FRAME>(P, grid, lds_bytes, stream);
-	return P->has_w ? launch_variant<false, true, ORDER, INL, PWN_KM_FRAME>(P, grid, lds_bytes, stream) : launch_variant<false, false, ORDER, INL, PWN_KM_FRAME>(P, grid, lds_bytes, stream);
-}
-
-// a batch of views (pwn_trace_views) or of rays (pwn_trace_rays): eight variants each, never ordered
-template<int MODE, bool INL>
-static hipError_t launch_batch(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
-{
-	if(count) return P->has_w ? launch_variant<true, true, false, INL, MODE>(P, grid, lds_bytes, stream) : launch_variant<true, false, false, INL, MODE>(P, grid, lds_bytes, stream);
-	return P->has_w ? launch_variant<false, true, false, INL, MODE>(P, grid, lds_bytes, stream) : launch_variant<false, false, false, INL, MODE>(P, grid, lds_bytes, stream);
-}
+// (ORDER, INL, MODE) -> the four kernels a launch's count and has_w pick from (trace_common.h)
+template<bool ORDER, bool INL, int MODE>
+using Units = TraceKernels<pwn_trace_kernel<true, true, ORDER, INL, MODE>, pwn_trace_kernel<true, false, ORDER, INL, MODE>,
+	pwn_trace_kernel<false, true, ORDER, INL, MODE>, pwn_trace_kernel<false, false, ORDER, INL, MODE>>;
 
 extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
 {
-	if(P->rays != NULL) return P->off_recsph != 0u ? launch_batch<PWN_KM_RAYS, true>(P, grid, lds_bytes, count, stream) : launch_batch<PWN_KM_RAYS, false>(P, grid, lds_bytes, count, stream);
-	if(P->views != NULL) return P->off_recsph != 0u ? launch_batch<PWN_KM_VIEWS, true>(P, grid, lds_bytes, count, stream) : launch_batch<PWN_KM_VIEWS, false>(P, grid, lds_bytes, count, stream);
 	// (the blob says which form its per-cell lists have: pack_blob, pwn_api.cpp)
-	if(P->off_recsph != 0u)
-	{
-		if(P->perm != NULL || P->unit_cost != NULL) return launch_ordered<true, true>(P, grid, lds_bytes, count, stream);
-		return launch_ordered<false, true>(P, grid, lds_bytes, count, stream);
-	}
-	if(P->perm != NULL || P->unit_cost != NULL) return launch_ordered<true, false>(P, grid, lds_bytes, count, stream);
-	return launch_ordered<false, false>(P, grid, lds_bytes, count, stream);
+	const bool inl = P->off_recsph != 0u;
+	// a batch of rays (pwn_trace_rays) or of views (pwn_trace_views): eight variants each, never ordered
+	if(P->rays != NULL) return inl ? Units<false, true, PWN_KM_RAYS>::launch(P, grid, lds_bytes, count, stream) : Units<false, false, PWN_KM_RAYS>::launch(P, grid, lds_bytes, count, stream);
+	if(P->views != NULL) return inl ? Units<false, true, PWN_KM_VIEWS>::launch(P, grid, lds_bytes, count, stream) : Units<false, false, PWN_KM_VIEWS>::launch(P, grid, lds_bytes, count, stream);
+	const bool order = P->perm != NULL || P->unit_cost != NULL;
+	if(inl) return order ? Units<true, true, PWN_KM_FRAME>::launch(P, grid, lds_bytes, count, stream) : Units<false, true, PWN_KM_FRAME>::launch(P, grid, lds_bytes, count, stream);
+	return order ? Units<true, false, PWN_KM_FRAME>::launch(P, grid, lds_bytes, count, stream) : Units<false, false, PWN_KM_FRAME>::launch(P, grid, lds_bytes, count, stream);
 }
 
-// resident 256-thread workgroups per CU for this variant and LDS size
 extern "C" int pwn_trace_tile_h(void) { return TILE_H; }
 extern "C" int pwn_trace_tile_w(void) { return TILE_W; }
 // LDS a workgroup needs beyond the table blob
@@ -808,14 +565,8 @@ extern "C" unsigned pwn_trace_lds_extra(void)
 	return 16u;        // the workgroup's cost word (pwn_trace_params.cost_word)
 }
 
+// resident 256-thread workgroups per CU for this variant and LDS size
 extern "C" int pwn_trace_blocks_per_cu(size_t lds_bytes, bool count, bool has_w)
 {
-	int n = 0;
-	hipError_t e;
-	if(count) e = has_w ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pwn_trace_kernel<true, true, false, false, PWN_KM_FRAME>, PWN_BLOCK, lds_bytes)
-	                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pwn_trace_kernel<true, false, false, false, PWN_KM_FRAME>, PWN_BLOCK, lds_bytes);
-	else e = has_w ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pwn_trace_kernel<false, true, false, false, PWN_KM_FRAME>, PWN_BLOCK, lds_bytes)
-	               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pwn_trace_kernel<false, false, false, false, PWN_KM_FRAME>, PWN_BLOCK, lds_bytes);
-	if(e != hipSuccess || n < 1) n = 2;
-	return n;
+	return Units<false, false, PWN_KM_FRAME>::blocks_per_cu(lds_bytes, count, has_w);
 }

@@ -1,7 +1,10 @@
 // trace_refill.hip -- the portal ray-march with wave64 ballot / prefix refill of live rays.
 //
-// Same arithmetic as trace_kernel.hip (trace_ray_prelude, screen.h:1-28, and trace.h; the cell
-// step is the same text, trace_walk.inc), different schedule.  There a wave64 takes a 16x4-pixel
+// Same arithmetic as trace_kernel.hip (trace_ray_prelude, screen.h:1-28, and trace.h), different schedule: a ray
+// segment's set-up, cell step, shading, bounces, jitter and composite are the same text (trace_setup.inc,
+// trace_walk.inc, trace_shade.inc, trace_bounce.inc, trace_jitter.inc, trace_composite.inc); what a kernel does
+// between them -- the composite stack's push, segment and depth bookkeeping, the stores -- is its own.
+// There a wave64 takes a 16x4-pixel
 // unit and its 64 lanes run ray set-up, walk and shading in step, three times per pixel
 // (REFLECT = 2): a lane whose ray ended waits until the slowest ray of the wave has ended, and
 // a lane whose pixel is finished waits for the whole unit.  Rays differ a lot -- portal chains,
@@ -28,7 +31,6 @@
 // lanes when a unit is taken, and parked in LDS (3 or 4 x 64 floats per wave) where the lane that
 // is handed pixel p reads entry p.
 #include <hip/hip_runtime.h>
-#include <mutex>
 #include "trace_common.h"
 
 enum { EV_IDLE = 4, EV_SETUP = 5, EV_DONE = 6 };      // lane states beyond EV_NONE (walking) .. EV_EXHAUSTED
@@ -39,15 +41,10 @@ template<bool COUNT, bool HAS_W>
 __global__ void __launch_bounds__(PWN_BLOCK, PWN_MIN_WAVES)
 pwn_trace_refill_kernel(pwn_trace_params P)
 {
+	constexpr bool INL = false;          // (this scheduler reads the indexed lists: pack_blob packs those for it)
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
 
-	// HBM -> LDS, 16 B per lane per trip
-	{
-		const uint4 *src = (const uint4 *)P.blob;
-		uint4 *dst = (uint4 *)lds_raw;
-		int n16 = (int)(P.blob_bytes >> 4);
-		for(int i = threadIdx.x; i < n16; i += PWN_BLOCK) dst[i] = src[i];
-	}
+	blob_to_lds(lds_raw, P.blob, P.blob_bytes);
 	__syncthreads();
 
 	// (the tables are addressed from LDS address 0 on, trace_common.h; the launcher checks that this kernel has
@@ -60,6 +57,7 @@ pwn_trace_refill_kernel(pwn_trace_params P)
 	rdx.x = P.rdx[0]; rdx.y = P.rdx[1]; rdx.z = P.rdx[2]; rdx.w = HAS_W ? P.rdx[3] : 0.0f;
 	rdy.x = P.rdy[0]; rdy.y = P.rdy[1]; rdy.z = P.rdy[2]; rdy.w = HAS_W ? P.rdy[3] : 0.0f;
 	cam_from.x = P.from[0]; cam_from.y = P.from[1]; cam_from.z = P.from[2]; cam_from.w = HAS_W ? P.from[3] : 1.0f;
+	const float sec_current = P.sec_current;
 
 	const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 	const int l16 = lane & 15;
@@ -133,83 +131,24 @@ pwn_trace_refill_kernel(pwn_trace_params P)
 				// zbuf = the PRIMARY ray's hit distance (trace.h:102-105)
 				if(depth == 0) P.zbuf[o] = (ev == EV_SPHERE ? aux_dist : cdist);
 
-				float colx, coly, colz, refl;
+				// (the segment's colour is computed into the pixel's own registers, as in trace_kernel.hip)
+				float refl;
 				V aux_norm;
 				aux_norm.x = aux_norm.y = aux_norm.z = aux_norm.w = 0.0f;
-				if(ev == EV_WALL)
-				{
-					// trace.h:108-154 and the axis-aligned mirrors of trace.h:50-75 from the constant tables in LDS
-					// (tables.h PWN_T_FACES; trace_kernel.hip has the same block)
-					// (one table entry at a time: this kernel keeps every lane's walk state live across phase A)
-					float diffuse = (ldir & 1) ? ray.z : ray.x;
-					diffuse = ldir >= FYP ? ray.y : diffuse;
-					{
-						const pwn_f4 fb = L.faces[5 + 2 * ldir];
-						diffuse = __uint_as_float(__float_as_uint(diffuse) ^ __float_as_uint(fb.w));      // -ray.c on the N faces
-						pos.x += fb.x; pos.y += fb.y; pos.z += fb.z;
-					}
-					if(diffuse < 0.0f) diffuse = 0.0f;
-					const float amb = 0.1f;
-					diffuse = (1.0f - amb) * diffuse + amb;
-					{
-						const pwn_f4 wc = L.faces[base];
-						colx = diffuse * (icx * wc.x); coly = diffuse * (icy * wc.y); colz = diffuse * (icz * wc.z);
-					}
-					w_acc = __builtin_fmaf(diffuse, 0.0f, w_acc);
-					{
-						const pwn_f4 fa = L.faces[4 + 2 * ldir];
-						refl = fa.w;
-						ray.x = __uint_as_float(__float_as_uint(ray.x) ^ __float_as_uint(fa.x));
-						ray.y = __uint_as_float(__float_as_uint(ray.y) ^ __float_as_uint(fa.y));
-						ray.z = __uint_as_float(__float_as_uint(ray.z) ^ __float_as_uint(fa.z));
-					}
-				}
-				else
-				{
-					// trace.h:283-291 for the committed sphere
-					const PWN_LDS pwn_f4 *sp = (const PWN_LDS pwn_f4 *)((const PWN_LDS unsigned char *)L.sph + aux_idx);      // (a byte offset)
-					const pwn_f4 s0 = sp[0], s1 = sp[1];
-					V d;
-					d.x = aux_pos.x - s0.x; d.y = aux_pos.y - s0.y; d.z = aux_pos.z - s0.z;
-					if constexpr(HAS_W) d.w = aux_pos.w - 1.0f; else d.w = 0.0f;
-					aux_norm = vnormalise<HAS_W>(L.rsq, d);
-					colx = aux_diff * s1.y; coly = aux_diff * s1.z; colz = aux_diff * s1.w;
-					w_acc = __builtin_fmaf(aux_diff, 0.0f, w_acc);
-					refl = s1.x;
-					ldir = -1;
-					pos = aux_pos;
-				}
+#define colx vx
+#define coly vy
+#define colz vz
+#include "trace_shade.inc"
 
 				// trace.h:3-7
-				if(depth >= REFLECT_MAX || refl == 0.0f) { vx = colx; vy = coly; vz = colz; vw = 0.0f; finished = true; }
+				if(depth >= REFLECT_MAX || refl == 0.0f) { vw = 0.0f; finished = true; }
 				else
 				{
-					// trace.h:9-75
-					if(ldir == FYN)
-					{
-						const float pi = (float)3.14159265358979323846;
-						float ang = (pi * 2.0f) * (
-							(glibc_sincosf((pi * 0.5f) * pos.x, 0) + glibc_sincosf((pi * 0.5f) * pos.z, 1))
-							+ P.sec_current);
-						const float2 sc = glibc_sincosf_both(ang);
-						V n; n.x = sc.x; n.y = 38.0f; n.z = sc.y; n.w = 0.0f;
-						n = vnormalise<HAS_W>(L.rsq, n);
-						float rmul = -2.0f * ((ray.x * n.x + ray.y * n.y) + ray.z * n.z);
-						ray = vnormalise<HAS_W>(L.rsq, vadd<HAS_W>(vscale<HAS_W>(rmul, n), ray));
-					}
-					else if(ldir < 0)
-					{
-						pos = vsub<HAS_W>(pos, vscale<HAS_W>(0.001f, ray));
-						float rmul = -2.0f * ((ray.x * aux_norm.x + ray.y * aux_norm.y) + ray.z * aux_norm.z);
-						ray = vnormalise<HAS_W>(L.rsq, vadd<HAS_W>(vscale<HAS_W>(rmul, aux_norm), ray));
-					}
-
-					// trace.h:77-84: five draws, two discarded
-					ray.x += lcg2_fs(seed) * REFLECT_BLUR_F;
-					ray.y += lcg2_fs(seed) * REFLECT_BLUR_F;
-					lcg2_next(seed);
-					ray.z += lcg2_fs(seed) * REFLECT_BLUR_F;
-					lcg2_next(seed);
+#include "trace_bounce.inc"
+					// (the jitter goes into the ray in place: set-up below takes the next segment's direction from there)
+#define iray ray
+#include "trace_jitter.inc"
+#undef iray
 
 					// the composite stack as a shift register; its top entry's colour is the next segment's icol
 					st_refl1 = st_refl0; st_fog1 = st_fog0; sc1x = sc0x; sc1y = sc0y; sc1z = sc0z;
@@ -220,30 +159,14 @@ pwn_trace_refill_kernel(pwn_trace_params P)
 					finished = false;
 					vx = vy = vz = vw = 0.0f;
 				}
+#undef colx
+#undef coly
+#undef colz
 			}
 			if(finished)
 			{
-				// trace.h:91-101, innermost first: the top of the stack, then the entry below it
-				if(depth >= 1)
-				{
-					const float r0 = st_refl0, q0 = 1.0f - st_refl0;
-					vx = r0 * vx + q0 * sc0x; vy = r0 * vy + q0 * sc0y; vz = r0 * vz + q0 * sc0z; vw = r0 * vw;
-					if(st_fog0 != 0.0f)
-					{
-						float f = glibc_expf(-0.6f * st_fog0, L.exp2), g = 1.0f - f;
-						vx = f * vx + g; vy = f * vy + g; vz = f * vz + g; vw = f * vw + g;
-					}
-				}
-				if(depth >= 2)
-				{
-					const float r1 = st_refl1, q1 = 1.0f - st_refl1;
-					vx = r1 * vx + q1 * sc1x; vy = r1 * vy + q1 * sc1y; vz = r1 * vz + q1 * sc1z; vw = r1 * vw;
-					if(st_fog1 != 0.0f)
-					{
-						float f = glibc_expf(-0.6f * st_fog1, L.exp2), g = 1.0f - f;
-						vx = f * vx + g; vy = f * vy + g; vz = f * vz + g; vw = f * vw + g;
-					}
-				}
+				// trace.h:91-101
+#include "trace_composite.inc"
 				// screen.h:22 (col_ftoint, util.h:48-59)
 				P.sbuf[o] = col_pack4(vx, vy, vz, vw + w_acc);
 				ev = EV_IDLE;
@@ -284,15 +207,7 @@ pwn_trace_refill_kernel(pwn_trace_params P)
 							const uint32_t len_l = (units + PWN_QUEUES - 1u - (ql & (PWN_QUEUES - 1u))) / PWN_QUEUES;
 							const unsigned long long open = __ballot(ql < PWN_QUEUES && seen < len_l);
 							if(open == 0ull) break;
-							static_assert(PWN_QUEUES <= 64u && (PWN_QUEUES & (PWN_QUEUES - 1u)) == 0u, "a power of two, one lane per queue");
-							if constexpr(PWN_QUEUES == 64u)
-							{
-								const uint32_t rot = q + 1u;                 // 1..64
-								const unsigned long long r = rot == 64u ? open : ((open >> rot) | (open << (64u - rot)));
-								q = (q + 1u + (uint32_t)__builtin_ctzll(r)) & 63u;
-							}
-							else
-								q = (q + 1u + (uint32_t)__builtin_ctzll((open | (open << (PWN_QUEUES & 31u))) >> (q + 1u))) & (PWN_QUEUES - 1u);
+							q = next_open_queue(q, open);
 							uint32_t t = 0;
 							if(lane == 0) t = atomicAdd(&P.tickets[q * PWN_QUEUE_STRIDE], 1u);
 							ticket = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
@@ -364,11 +279,7 @@ pwn_trace_refill_kernel(pwn_trace_params P)
 						ray.x = rtab[p]; ray.y = rtab[64u + p]; ray.z = rtab[128u + p];
 						if constexpr(HAS_W) ray.w = rtab[192u + p]; else ray.w = 0.0f;
 						o = (uint32_t)y * (uint32_t)P.w + (uint32_t)x;
-						// screen.h:19-21 (uint32 wrap-around)
-						seed = (uint32_t)x + (uint32_t)y * (uint32_t)y * ((uint32_t)P.w + 1u);
-						seed *= seed * seed;
-						seed *= seed * seed;
-						seed <<= 1;                   // the generator runs on the doubled state (lcg2_fs, dev_math.h)
+						seed = pixel_seed(x, y, P.w);
 						depth = 0; sc0x = sc0y = sc0z = 1.0f; w_acc = 0.0f;
 						ev = EV_SETUP;
 					}
@@ -382,51 +293,15 @@ pwn_trace_refill_kernel(pwn_trace_params P)
 		unsigned long long fresh = __ballot(ev == EV_SETUP);
 		if(ev == EV_SETUP)
 		{
-			cdist = 0.0f; fog = 0.0f;
-			// aux_dist: the reference's "none yet" value -1 (trace.h:200) is kept as +inf (trace_kernel.hip)
-			aux_dist = __builtin_inff(); aux_diff = 0.0f; aux_idx = 0u;
+			// (this kernel starts every segment with an empty sphere candidate)
+			aux_diff = 0.0f; aux_idx = 0u;
 			aux_pos.x = aux_pos.y = aux_pos.z = aux_pos.w = 0.0f;
-			if(COUNT) cnt.rays++;
+			// the direction came in `ray` (a new pixel's from the ray table, a bounced ray's from the jitter)
 			const V iray = ray;
-			ray = vnormalise<HAS_W>(L.rsq, iray);
-			const int cx = (int)pos.x, cz = (int)pos.z;
-			// signs of the UN-normalised input (trace.h:225-227)
-			const int gx = (iray.x < 0.0f ? -1 : 1);
-			const int gz = (iray.z < 0.0f ? -1 : 1);
-			const bool gyp = !(iray.y < 0.0f);          // gy > 0
-			// trace.h:220-222 and 230-231: one test on the bit patterns, one wave-uniform branch (trace_kernel.hip)
-			{
-				const uint32_t EPSB = __float_as_uint(EPS);
-				const uint32_t bx = __float_as_uint(ray.x) & 0x7fffffffu, by = __float_as_uint(ray.y) & 0x7fffffffu,
-					bz = __float_as_uint(ray.z) & 0x7fffffffu;
-				const bool plain = max(max(bx - EPSB, by - EPSB), bz - EPSB) < 0x7e800000u - EPSB;
-				if(__builtin_expect(__ballot(!plain) == 0ull, 1))
-				{
-					iax = tab_rcp_pos(L.rcp, __uint_as_float(bx)); iay = tab_rcp_pos(L.rcp, __uint_as_float(by));
-					iaz = tab_rcp_pos(L.rcp, __uint_as_float(bz));
-				}
-				else
-				{
-					if(fabsf(ray.x) < EPS) ray.x = (ray.x < 0.0f ? -EPS : EPS);
-					if(fabsf(ray.y) < EPS) ray.y = (ray.y < 0.0f ? -EPS : EPS);
-					if(fabsf(ray.z) < EPS) ray.z = (ray.z < 0.0f ? -EPS : EPS);
-					iax = tab_rcp(L.rcp, fabsf(ray.x)); iay = tab_rcp(L.rcp, fabsf(ray.y)); iaz = tab_rcp(L.rcp, fabsf(ray.z));
-				}
-			}
-			wx = pos.x - (float)cx; wy = pos.y; wz = pos.z - (float)cz;
-			if(ray.x >= 0.0f) wx = 1.0f - wx;
-			if(ray.y >= 0.0f) wy = 1.0f - wy;
-			if(ray.z >= 0.0f) wz = 1.0f - wz;
-			wx *= iax; wy *= iay; wz *= iaz;
-			iay_dn = gyp ? iay : -iay;
-			ldy = gyp ? FYP : FYN;
-			iay_up_bits = gyp ? __float_as_uint(iay) : 0u;         // +iay when looking up, else +0
-			cxz = cxz_pack_start(cx, cz); sx = (uint32_t)gx & 0xffffu; sz = (uint32_t)gz << 16;
-			cw = cellword_pk(L, cxz);
-			ldx = (gx < 0 ? FXN : FXP); ldz = (gz < 0 ? FZN : FZP);
-			ldir = FYN; base = BASE_ROOM_Y;
+			bool gyp;          // (this kernel keeps ldy)
+#include "trace_setup.inc"
+			(void)gyp;
 			maxsteps = 1000;
-			ev = EV_NONE;
 		}
 
 		// =========================================================== B: the walk (trace.h:250-675)
@@ -454,7 +329,6 @@ pwn_trace_refill_kernel(pwn_trace_params P)
 #pragma unroll 1
 			do
 			{
-			constexpr bool INL = false;          // (this scheduler reads the indexed lists: pack_blob packs those for it)
 #include "trace_walk.inc"
 				// wave-uniform: a young ray still walks, and the ended ones have not waited too long
 				const unsigned long long w = __ballot(ev == EV_NONE);
@@ -472,64 +346,26 @@ pwn_trace_refill_kernel(pwn_trace_params P)
 
 	if(COUNT)
 	{
-		// wave reduce, one atomic per wave and counter
-		unsigned long long v[16] = { cnt.rays, cnt.steps, cnt.portals, cnt.tests, cnt.exhausted, cnt.wsteps,
-			cnt.wp[0], cnt.wp[1], cnt.wp[2], cnt.wp[3], cnt.wp[4], cnt.wp[5], cnt.wp[6], cnt.wp[7], cnt.apasses, cnt.apass_lanes };
-		for(int i = 0; i < 16; i++)
-		{
-			unsigned long long s = v[i];
-			for(int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
-			if(lane == 0 && s) atomicAdd(&P.counters[i], s);
-		}
+		// (no region counts: the issue model maps the units kernel.  The shared texts' RG() still count into cnt.rg[] in this
+		// kernel's counting variants; nothing reads them -- dead work in a diagnostics build, part of its 40 / 20 bytes of scratch)
+#define PWN_CNT_REGIONS 0
+#include "trace_counters.inc"
+#undef PWN_CNT_REGIONS
 	}
-	// PWN_OPT_WAVE_LOG: every wave's lifetime (pwn_stats.wave_time ..., tools/wave_log.py)
-	// (Which wave of the workgroup this is comes from the hardware: the four waves of a 256-thread workgroup
-	// sit on the four SIMDs of their CU, HW_ID.simd_id is bits 5:4 of hardware register 4; the lane number
-	// comes from mbcnt.  Keeping threadIdx.x alive to the end of the kernel costs a scratch slot per lane,
-	// and a shared append counter serialises the waves' exits and stretches the very tail it measures.)
-	if(P.wave_log != NULL && __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0u)
+	// PWN_OPT_WAVE_LOG: every wave's lifetime
+	if(P.wave_log != NULL && wave_first_lane())
 	{
-		static_assert(PWN_BLOCK == 256, "one wave per SIMD: simd_id tells the waves of a workgroup apart");
-		const unsigned simd = __builtin_amdgcn_s_getreg(4 | (4 << 6) | ((2 - 1) << 11));
-		const size_t wid = 1u + (size_t)blockIdx.x * 4u + simd;
-		P.wave_log[2 * wid] = t_begin; P.wave_log[2 * wid + 1] = __builtin_amdgcn_s_memrealtime();
+		unsigned long long *wl = wave_log_slot(P.wave_log);
+		wl[0] = t_begin; wl[1] = __builtin_amdgcn_s_memrealtime();
 	}
 }
 
-template<bool COUNT, bool HAS_W>
-static hipError_t launch_variant(const pwn_trace_params *P, int grid, size_t lds_bytes, hipStream_t stream)
-{
-	// the dynamic-LDS limit is a per-function attribute: raise it only when the blob grew
-	// (high-water mark per device and variant, under a lock: contexts of several threads share it)
-	static size_t lds_mark[64];
-	static std::mutex lds_lock;
-	int dev = 0;
-	(void)hipGetDevice(&dev);
-	{
-		std::lock_guard<std::mutex> g(lds_lock);
-		size_t &lds_set = lds_mark[dev & 63];
-		if(lds_bytes > lds_set)
-		{
-			// the kernel addresses its tables from LDS address 0 (trace_common.h): that holds while it has no
-			// static LDS, which would be laid out in front of the dynamic allocation
-			hipFuncAttributes fa;
-			hipError_t e = hipFuncGetAttributes(&fa, (const void *)pwn_trace_refill_kernel<COUNT, HAS_W>);
-			if(e != hipSuccess) return e;
-			if(fa.sharedSizeBytes != 0) return hipErrorInvalidConfiguration;
-			e = hipFuncSetAttribute((const void *)pwn_trace_refill_kernel<COUNT, HAS_W>,
-				hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-			if(e != hipSuccess) return e;
-			lds_set = lds_bytes;
-		}
-	}
-	hipLaunchKernelGGL((pwn_trace_refill_kernel<COUNT, HAS_W>), dim3(grid), dim3(PWN_BLOCK), lds_bytes, stream, *P);
-	return hipGetLastError();
-}
+typedef TraceKernels<pwn_trace_refill_kernel<true, true>, pwn_trace_refill_kernel<true, false>,
+	pwn_trace_refill_kernel<false, true>, pwn_trace_refill_kernel<false, false>> Refill;
 
 extern "C" hipError_t pwn_launch_trace_refill(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
 {
-	if(count) return P->has_w ? launch_variant<true, true>(P, grid, lds_bytes, stream) : launch_variant<true, false>(P, grid, lds_bytes, stream);
-	return P->has_w ? launch_variant<false, true>(P, grid, lds_bytes, stream) : launch_variant<false, false>(P, grid, lds_bytes, stream);
+	return Refill::launch(P, grid, lds_bytes, count, stream);
 }
 
 // LDS a workgroup needs beyond the table blob: the waves' ray tables
@@ -540,12 +376,5 @@ extern "C" unsigned pwn_trace_refill_lds_extra(bool has_w)
 
 extern "C" int pwn_trace_refill_blocks_per_cu(size_t lds_bytes, bool count, bool has_w)
 {
-	int n = 0;
-	hipError_t e;
-	if(count) e = has_w ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pwn_trace_refill_kernel<true, true>, PWN_BLOCK, lds_bytes)
-	                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pwn_trace_refill_kernel<true, false>, PWN_BLOCK, lds_bytes);
-	else e = has_w ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pwn_trace_refill_kernel<false, true>, PWN_BLOCK, lds_bytes)
-	               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pwn_trace_refill_kernel<false, false>, PWN_BLOCK, lds_bytes);
-	if(e != hipSuccess || n < 1) n = 2;
-	return n;
+	return Refill::blocks_per_cu(lds_bytes, count, has_w);
 }

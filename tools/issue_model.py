@@ -2,7 +2,7 @@
 """Issue model of pwn_trace_kernel<false,false,false,true,0> (frames, no counters, 3 lanes, unit order, inline sphere records): what its instruction stream costs the SIMDs, region by region.
 
     static    the kernel's ISA (hipcc -S with line tables, the Makefile's flags), every instruction attributed to a REGION
-              of the source through its .loc chain (the `//@R name` comments of trace_kernel.hip / trace_walk.inc mark
+              of the source through its .loc chain (the `//@R name` comments of trace_kernel.hip and the .inc files it includes mark
               the regions; an instruction inlined from dev_math.h etc. belongs to the region of its call site) and
               classed by opcode: full-rate VALU, half-rate VALU, quarter-rate VALU (rcp / sqrt / div), scalar ALU,
               branch, LDS, vector memory, other (waitcnt, nop)
@@ -85,7 +85,8 @@ def slow_ranges():
 def region_maps():
     """file -> sorted [(line, region)] from the //@R markers"""
     out = {}
-    for name in ("trace_kernel.hip", "trace_walk.inc", "trace_sphere.inc"):
+    for name in ("trace_kernel.hip", "trace_walk.inc", "trace_sphere.inc", "trace_setup.inc", "trace_shade.inc", "trace_bounce.inc", "trace_jitter.inc",
+                 "trace_composite.inc", "trace_counters.inc"):
         marks = []
         for i, line in enumerate(open(os.path.join(CSRC, name)), 1):
             m = re.search(r"//@R (\w+)", line)

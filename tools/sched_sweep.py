@@ -13,7 +13,8 @@ sys.path.insert(0, ROOT)
 import pwnfps_amd  # noqa: E402
 
 frames = int(sys.argv[1]) if len(sys.argv) > 1 else 30
-limits = [int(v) for v in sys.argv[2:]] or [0, 4, 8, 16, 24, 32, 48]
+# (lane-steps the ended rays of a batch wait, PWN_OPT_REFILL_LIMIT: 1 .. 64000, the library's default is 256)
+limits = [int(v) for v in sys.argv[2:]] or [64, 256, 1024, 64000]
 gold = os.path.join(ROOT, "tests", "golden")
 scenes = [("pwnfps_level", 3840, 2160), ("synth64", 1920, 1080), ("synth256", 7680, 4320), ("pwnfps_level", 1280, 720)]
 if os.environ.get("SWEEP_SCENES"):
