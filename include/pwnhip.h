@@ -385,6 +385,51 @@ int pwn_trace_rays_device(pwn_ctx *ctx, int n, const void *d_rays, const void *d
 	void *d_col, void *d_depth, void *stream);
 
 /*
+ * First hits of caller-supplied rays: what the PRIMARY segment of trace_ray (trace.h:186) ended on, for the rays pwn_trace_rays
+ * takes.  Where pwn_trace_rays answers "what colour, how far", this answers a game loop's questions -- which object, which wall
+ * cell, where, on which side of how many portals -- and stops there: one set-up and one walk per ray, no shading, no bounce, no
+ * second or third segment, no random number (there is no seed) and no floor ripple (there is no sec_current).
+ * Ray records, PWN_RAYS_HAS_W, PWN_RAYS_MAX, the 3-lane / 4-lane rule, the empty batch, the ordering of the two forms, "not
+ * followed", "left alone" and the error rules are pwn_trace_rays' / pwn_trace_rays_device's above, with hits in the place of col and
+ * depth (required for n > 0) and d_hits 16-byte aligned in the place of d_col / d_depth.
+ * A record holds trace.h's variables at the moment trace_ray's primary walk returns:
+ *   kind      PWN_HIT_NONE: the segment ran out of steps (trace.h:677).  Then face = object = -1 and every other field is 0.
+ *   face      ldir, 0..5 = FXP, FZP, FXN, FZN, FYP, FYN (defs.h:25-33); a room cell's floor or ceiling as the frame shades it.  A sphere: -1.
+ *   object    a sphere: its index in the live table -- its place in pwn_upload_spheres' array, in pwn_get_objects' output and in
+ *             pwn_get_object_ids', which names the pwn_obj_new handle.  Otherwise -1.
+ *   portals   portals this segment crossed (trace.h:576).
+ *   dist      what a frame writes to zbuf for this ray: aux_dist for a sphere, cdist otherwise.
+ *   x, y, z   aux_pos for a sphere (the reference's own point, pos + sdist * ray of trace.h:256-294: where it shades the sphere, not
+ *             the geometric intersection), otherwise pos before the 0.001 step off the surface -- in the coordinates of the far
+ *             side of the portals crossed.
+ *   dx,dy,dz  the walked ray as the segment returns it: normalised, clamped to EPSILON, turned by the portals crossed; in a ramp
+ *             cell with the ramp's y skew, as the reference's shading sees it.
+ *   cell_x,z  cx, cz at the return.  A sphere, a floor or a ceiling: the cell the last step began in (a ramp or portal step that the
+ *             reference leaves through trace.h:668 included).  A side wall: the solid cell, which out of a 2-high cell ('#', '&') is
+ *             the cell stepped into.  A ray that starts further than 16383 cells out is pinned there.
+ * Counters: with PWN_OPT_COUNTERS on, pwn_get_stats returns rays (= n), steps, portals, sphere_tests and exhausted of the primary
+ * segments.  pwn_trace_hits keeps 80 B per ray of pinned host memory (32 in, 48 out) and as much device memory between calls,
+ * grown to the largest batch so far (at least 4096 rays); pwn_destroy frees them.  It sets trace_ms and total_ms as pwn_trace_rays does.
+ */
+#define PWN_HIT_NONE   0   /* the primary segment ran out of steps (trace.h:677) */
+#define PWN_HIT_WALL   1   /* wall, floor, ceiling, portal frame */
+#define PWN_HIT_SPHERE 2
+typedef struct pwn_hit {            /* 48 bytes */
+	int32_t kind, face, object, portals;
+	float   dist, x, y, z;
+	float   dx, dy, dz;
+	int16_t cell_x, cell_z;
+} pwn_hit;
+/* Blocking, host memory. */
+int pwn_trace_hits(pwn_ctx *ctx, int n, const float *rays, pwn_hit *hits);
+/* Device pointers, ONE trace launch, stream-ordered on `stream` (NULL = default stream): d_rays and d_hits (n records of 48 B) 16-byte aligned. */
+int pwn_trace_hits_device(pwn_ctx *ctx, int n, const void *d_rays, int flags, void *d_hits, void *stream);
+/* Per live sphere, in the order of the table the kernels read (pwn_hit.object indexes it), the pwn_obj_new handle it came from: after
+   pwn_upload_spheres 0..n-1.  Writes at most cap entries; returns the count, or PWN_EINVAL (an object created but never set, as
+   pwn_get_objects; NULL ctx, cap < 0, NULL ids with cap > 0). */
+int pwn_get_object_ids(pwn_ctx *ctx, int *ids, int cap);
+
+/*
  * Frames in flight.  The reference presents every frame on the host
  * (trace_screen_centred fills sbuf, screen_upscale fills screen->pixels, SDL_Flip:
  * main.c:107-109).  Over PCIe that hand-over takes longer than the kernels of a

@@ -27,6 +27,7 @@ PWN_OBJ_MAX = 10000
 PWN_VIEWS_MAX = 1024
 PWN_RAYS_HAS_W = 1
 PWN_RAYS_MAX = 1 << 28
+PWN_HIT_NONE, PWN_HIT_WALL, PWN_HIT_SPHERE = 0, 1, 2
 (PROBE_RCP, PROBE_RSQRT, PROBE_SINF, PROBE_COSF, PROBE_EXPF, PROBE_SQRT, PROBE_DIV,
  PROBE_FTOINT, PROBE_RANDFS, PROBE_SIN_OF_PAIR, PROBE_COS_OF_PAIR) = range(11)
 
@@ -37,6 +38,12 @@ class Portal(C.Structure):
 
 class Sphere(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("r", "refl", "x", "y", "z", "cb", "cg", "cr")]
+
+
+class Hit(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("kind", "face", "object", "portals")] + \
+               [(n, C.c_float) for n in ("dist", "x", "y", "z", "dx", "dy", "dz")] + \
+               [(n, C.c_int16) for n in ("cell_x", "cell_z")]
 
 
 class Stats(C.Structure):
@@ -111,6 +118,9 @@ ABI = [
     ("pwn_pixel_rays", _i, [_i, _i, _vp, _i, _vp, _vp, _vp]),
     ("pwn_trace_rays", _i, [_vp, _i, _vp, _vp, _f, _vp, _vp]),
     ("pwn_trace_rays_device", _i, [_vp, _i, _vp, _vp, _f, _i, _vp, _vp, _vp]),
+    ("pwn_trace_hits", _i, [_vp, _i, _vp, _vp]),
+    ("pwn_trace_hits_device", _i, [_vp, _i, _vp, _i, _vp, _vp]),
+    ("pwn_get_object_ids", _i, [_vp, _vp, _i]),
     ("pwn_frames_config", _i, [_vp, _i, _i, _i, _i]),
     ("pwn_submit_frame", _i, [_vp, _vp, _f, _i]),
     ("pwn_wait_frame", _i, [_vp, _i, C.POINTER(Frame)]),

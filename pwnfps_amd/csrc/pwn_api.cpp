@@ -93,6 +93,7 @@ extern "C" int pwn_init(pwn_ctx **out, int device, int width, int height)
 	c->grid_reserve = 0;
 	c->d_vpre = c->d_vout = NULL; c->d_vz = NULL; c->views_cap = 0; c->h_vrec = c->d_vrec = NULL; c->vrec_cap = 0;
 	c->h_rays = c->d_rays = NULL; c->rays_cap = 0;
+	c->h_hits = c->d_hits = NULL; c->hits_cap = 0;
 	memset(&c->room, 0, sizeof(c->room)); c->room.mode = -1;
 	if(const char *e = getenv("PWN_TRACE_ROOM")) if(*e) c->room.mode = atoi(e) < 0 ? -1 : atoi(e);      // (the option's default for every context of a process)
 	c->d_scratch = NULL; c->scratch_cap = 0;
@@ -240,6 +241,8 @@ extern "C" void pwn_destroy(pwn_ctx *c)
 	if(c->h_vrec) (void)hipHostFree(c->h_vrec);
 	(void)hipFree(c->d_rays);
 	if(c->h_rays) (void)hipHostFree(c->h_rays);
+	(void)hipFree(c->d_hits);
+	if(c->h_hits) (void)hipHostFree(c->h_hits);
 	for(int i = 0; i < 4; i++) { (void)hipFree(c->order[i].d_cost); (void)hipFree(c->order[i].d_perm); }
 	(void)hipFree(c->d_skip); (void)hipFree(c->d_counters); (void)hipFree(c->d_tickets); (void)hipFree(c->d_scratch);
 	delete c;
@@ -630,6 +633,26 @@ extern "C" int pwn_get_objects(pwn_ctx *c, pwn_sphere *out, int cap)
 	return (int)live.size();
 }
 
+// Which handle each live sphere came from, in live_objects' order: the order of the table the kernels read, so pwn_hit.object indexes it
+extern "C" int pwn_get_object_ids(pwn_ctx *c, int *ids, int cap)
+{
+	if(GRP_HEAD(c)) { const int q = pwn_get_object_ids(GRP_M0(c), ids, cap); if(q < 0) snprintf(c->err, sizeof(c->err), "%s", GRP_M0(c)->err); return q; }
+	if(c == NULL || cap < 0 || (cap > 0 && ids == NULL)) return PWN_EINVAL;
+	int n = 0;
+	for(size_t i = 0; i < c->obj_typ.size(); i++)
+	{
+		if(c->obj_typ[i] == OBJ_FREE) continue;
+		if(c->obj_typ[i] != OBJ_SPHERE)
+		{
+			snprintf(c->err, sizeof(c->err), "object %d was created but never set", (int)i);
+			return PWN_EINVAL;
+		}
+		if(n < cap) ids[n] = (int)i;
+		n++;
+	}
+	return n;
+}
+
 // (a group, pwn_group.cpp: the list is binned once and every member uploads it)
 int pwn_i_bin_spheres(const pwn_sphere *s, int n, pwn_binned *out)
 {
@@ -850,6 +873,7 @@ int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L)
 	if(rays != NULL)
 	{
 		P.rays = rays->d_rays; P.ray_seeds = rays->d_seeds; P.nrays = rays->n; P.ray_w = rays->has_w ? 1 : 0;
+		P.hits = rays->d_hits;
 		P.tiles_total = (int)((rays->n + 63u) / 64u);
 	}
 	P.blob_bytes = (uint32_t)c->blob.size();
@@ -1649,6 +1673,81 @@ extern "C" int pwn_trace_rays_device(pwn_ctx *c, int n, const void *d_rays, cons
 	(void)hipSetDevice(c->device);
 	pwn_trace_launch T = { .sec = sec, .rays = { (const float *)d_rays, (const uint32_t *)d_seeds, (uint32_t)n, (flags & PWN_RAYS_HAS_W) != 0 },
 		.d_sbuf = (uint32_t *)d_col, .d_zbuf = (float *)d_depth, .stream = (hipStream_t)stream };
+	return pwn_i_launch_trace(c, &T);
+}
+
+// ---- first hits of a batch of rays (pwn_trace_hits) ------------------------------
+
+// Room for n rays of the host form, kept across calls as rays_reserve keeps pwn_trace_rays': the records at 0 (32 B a ray), the
+// hit records of a call of n rays behind them at 32 n (48 B a ray; 16-byte aligned) -- one copy up, one down.
+static int hits_reserve(pwn_ctx *c, size_t n)
+{
+	if(n <= c->hits_cap) return PWN_OK;
+	size_t cap = c->hits_cap * 2;
+	if(cap < 4096) cap = 4096;
+	if(cap > PWN_RAYS_MAX) cap = PWN_RAYS_MAX;
+	if(cap < n) cap = n;
+	const size_t bytes = cap * (32 + sizeof(pwn_hit)) + 16;            // (+16: the upload kernel copies whole 16-byte words)
+	unsigned char *h = NULL, *d = NULL;
+	if(hipHostMalloc((void **)&h, bytes, hipHostMallocDefault) != hipSuccess || hipMalloc((void **)&d, bytes) != hipSuccess)
+	{
+		(void)hipGetLastError();
+		if(h != NULL) (void)hipHostFree(h);
+		(void)hipFree(d);
+		snprintf(c->err, sizeof(c->err), "pwn_trace_hits: no room for %zu rays", n);
+		return PWN_ENOMEM;
+	}
+	if(c->h_hits != NULL) (void)hipHostFree(c->h_hits);
+	(void)hipFree(c->d_hits);
+	c->h_hits = h; c->d_hits = d; c->hits_cap = cap;
+	return PWN_OK;
+}
+
+static_assert(sizeof(pwn_hit) == PWN_HIT_REC_BYTES, "the kernel writes a pwn_hit as three 16-byte words (trace_kernel.hip trace_hit)");
+
+extern "C" int pwn_trace_hits(pwn_ctx *c, int n, const float *rays, pwn_hit *hits)
+{
+	GRP_REFUSE(c, "pwn_trace_hits");
+	if(c == NULL || n < 0 || n > PWN_RAYS_MAX || (n > 0 && (rays == NULL || hits == NULL))) return PWN_EINVAL;
+	int rc = rays_refuse(c);
+	if(rc != PWN_OK || n == 0) return rc;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = c->stream;
+	rc = wait_frames_in_flight(c, s);
+	if(rc != PWN_OK) return rc;
+	rc = hits_reserve(c, (size_t)n);
+	if(rc != PWN_OK) return rc;
+	const size_t N = (size_t)n;
+	unsigned char *h = c->h_hits, *d = c->d_hits;
+	memcpy(h, rays, 32 * N);
+	bool has_w = false;          // (pwn_trace_rays' rule)
+	for(size_t i = 0; i < N && !has_w; i++) has_w = !(rays[8 * i + 3] == 1.0f && rays[8 * i + 7] == 0.0f);
+	HIPCHK(c, hipEventRecord(c->ev[0], s));
+	if(32 * N <= 65536) HIPCHK(c, pwn_launch_upload(h, d, 32 * N, s));
+	else HIPCHK(c, hipMemcpyAsync(d, h, 32 * N, hipMemcpyHostToDevice, s));
+	pwn_trace_launch T = { .rays = { (const float *)d, NULL, (uint32_t)n, has_w, d + 32 * N }, .stream = s };
+	rc = pwn_i_launch_trace(c, &T);
+	if(rc != PWN_OK) return rc;
+	HIPCHK(c, hipEventRecord(c->ev[1], s));
+	HIPCHK(c, hipMemcpyAsync(h + 32 * N, d + 32 * N, sizeof(pwn_hit) * N, hipMemcpyDeviceToHost, s));
+	HIPCHK(c, hipEventRecord(c->ev[3], s));
+	HIPCHK(c, hipEventSynchronize(c->ev[3]));
+	memcpy(hits, h + 32 * N, sizeof(pwn_hit) * N);
+	(void)hipEventElapsedTime(&c->stats.trace_ms, c->ev[0], c->ev[1]);
+	c->stats.blur_ms = 0.0f;
+	(void)hipEventElapsedTime(&c->stats.total_ms, c->ev[0], c->ev[3]);
+	return PWN_OK;
+}
+
+extern "C" int pwn_trace_hits_device(pwn_ctx *c, int n, const void *d_rays, int flags, void *d_hits, void *stream)
+{
+	GRP_REFUSE(c, "pwn_trace_hits_device");
+	if(c == NULL || n < 0 || n > PWN_RAYS_MAX || (n > 0 && (d_rays == NULL || d_hits == NULL)) || (flags & ~PWN_RAYS_HAS_W) != 0) return PWN_EINVAL;
+	if(((uintptr_t)d_rays & 15u) != 0 || ((uintptr_t)d_hits & 15u) != 0) return PWN_EINVAL;
+	const int rc = rays_refuse(c);
+	if(rc != PWN_OK || n == 0) return rc;
+	(void)hipSetDevice(c->device);
+	pwn_trace_launch T = { .rays = { (const float *)d_rays, NULL, (uint32_t)n, (flags & PWN_RAYS_HAS_W) != 0, d_hits }, .stream = (hipStream_t)stream };
 	return pwn_i_launch_trace(c, &T);
 }
 

@@ -22,12 +22,15 @@ struct pwn_views_launch
 
 // A batch of caller-supplied rays (pwn_trace_rays / pwn_trace_rays_device; tables.h pwn_trace_params.rays): n rays into
 // d_sbuf (colour) / d_zbuf (depth) of the launch; has_w: their w lanes count (PWN_RAYS_HAS_W).  n = 0: none.
+// d_hits (pwn_trace_hits / pwn_trace_hits_device): not NULL = the launch writes n first-hit records (pwn_hit) there instead,
+// from the primary segments alone; d_seeds, d_sbuf, d_zbuf and sec are then not read.
 struct pwn_rays_launch
 {
 	const float *d_rays;
 	const uint32_t *d_seeds;
 	uint32_t n;
 	bool has_w;
+	void *d_hits;
 };
 
 // One trace launch (pwn_i_launch_trace).  All zero but what is traced and where to: a plain launch, nothing cleared or
@@ -217,6 +220,8 @@ struct pwn_ctx
 	pwn_view_rec *h_vrec, *d_vrec; int vrec_cap;
 	// pwn_trace_rays: room for rays_cap rays in pinned staging and on the device, 44 B each (record, seed, depth, colour; pwn_api.cpp rays_reserve)
 	unsigned char *h_rays, *d_rays; size_t rays_cap;
+	// pwn_trace_hits: the same for hits_cap rays, 32 B in (record) and 48 B out (pwn_hit) each (pwn_api.cpp hits_reserve)
+	unsigned char *h_hits, *d_hits; size_t hits_cap;
 	uint32_t *d_tickets; unsigned ticket_set;  // PWN_TICKET_SETS sets of work-queue counters of the trace kernel, used in turn
 	uint32_t *d_scratch; size_t scratch_cap;   // upscale / probe staging
 

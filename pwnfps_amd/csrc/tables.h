@@ -181,7 +181,11 @@ struct pwn_trace_params
 	const uint32_t *ray_seeds;
 	uint32_t nrays;
 	int ray_w;
+	// First-hit records of a batch of rays (pwn_trace_hits): NULL, or nrays records of PWN_HIT_REC_BYTES (pwn_hit of pwnhip.h; 16-byte
+	// aligned) that ray i's primary segment is written to.  Then sbuf, zbuf, ray_seeds and sec_current are not read.
+	void *hits;
 };
+#define PWN_HIT_REC_BYTES 48u
 
 // kernel arguments of one blur launch (post_kernels.hip; rows [y0,y1) of a w x h frame)
 struct pwn_blur_params
@@ -210,7 +214,7 @@ struct pwn_blur_params
 };
 
 // what a launch of the trace kernel traces (its MODE parameter, trace_kernel.hip)
-enum { PWN_KM_FRAME = 0, PWN_KM_VIEWS = 1, PWN_KM_RAYS = 2 };
+enum { PWN_KM_FRAME = 0, PWN_KM_VIEWS = 1, PWN_KM_RAYS = 2, PWN_KM_HITS = 3 };
 
 // One view of a batch: the camera set-up of screen.h:43-57 for that view's camera (pwn_api.cpp frame_setup) and its
 // sec_current.  80 bytes; the kernel reads a view's record with scalar loads.

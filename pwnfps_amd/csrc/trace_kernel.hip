@@ -36,6 +36,10 @@ __device__ __forceinline__ void trace_pixel(const Lds &L, float sec_current, uin
 	float *zpix, Counters &cnt)
 {
 	typedef Vec<HAS_W> V;
+	// (trace_walk.inc: nothing is kept for hit records here; the two names it would write are never touched)
+	constexpr bool HITREC = false;
+	[[maybe_unused]] uint32_t hit_cxz;
+	[[maybe_unused]] int hit_portals;
 	// icol (screen.h:24).  Its w lane, and the w lane of every surface colour, is
 	// x * 0.0f (COL_* have a = 0, defs.h:17-19; spheres get b,g,r only, script.h:30-32):
 	// +-0 for any finite input, and the sign of a zero never reaches a pixel, so the
@@ -172,6 +176,83 @@ __device__ __forceinline__ void trace_pixel(const Lds &L, float sec_current, uin
 	out_x = vx; out_y = vy; out_z = vz; out_w = vw + w_acc;
 }
 
+// One ray's PRIMARY segment for pwn_trace_hits: the set-up and the walk of trace_pixel's first pass through its loop -- the same
+// two texts -- and then, where trace_pixel shades, the walk's state written out as a 48-byte record (pwn_hit, pwnhip.h):
+//   word 0..3    kind (EV_WALL = PWN_HIT_WALL, EV_SPHERE = PWN_HIT_SPHERE, out of steps = PWN_HIT_NONE), face, object, portals
+//   word 4..7    dist (what the frame writes to zbuf), x, y, z (pos, or the sphere candidate's aux_pos)
+//   word 8..11   the walked ray x, y, z;  cell x | cell z << 16 (hit_cxz as the walk packs it: two int16)
+// No shading, bounce, jitter or composite, no composite stack, no random number, no sec_current.
+template<bool COUNT, bool HAS_W, bool INL>
+__device__ __forceinline__ void trace_hit(const Lds &L, Vec<HAS_W> from, Vec<HAS_W> iray, uint4 *out, Counters &cnt)
+{
+	typedef Vec<HAS_W> V;
+	constexpr bool HITREC = true;
+	uint32_t hit_cxz;
+	int hit_portals = 0;
+	V pos = from;
+	[[maybe_unused]] float aux_diff = 0.0f;      // (trace_sphere.inc writes the candidate's diffuse factor; nothing here reads it)
+	uint32_t aux_idx = 0;
+	V aux_pos;
+	aux_pos.x = aux_pos.y = aux_pos.z = aux_pos.w = 0.0f;
+	//@R p_setup
+	// (declared as in trace_pixel: trace_setup.inc writes them, trace_walk.inc walks with them)
+	float cdist, fog, aux_dist;
+	bool gyp;
+	uint32_t cxz, sx, sz, cw;
+	float wx, wy, wz;
+	int ldy, ldx, ldz;
+	V ray;
+	float iax, iaz, iay, iay_dn;
+	uint32_t iay_up_bits;
+	int ldir, ev, base;
+#include "trace_setup.inc"
+	//@R p_walk_ctl
+	int maxsteps = 1000;
+#pragma unroll 1
+	do
+	{
+#include "trace_walk.inc"
+		// trace.h:250,677: out of steps
+		if(--maxsteps == 0 && ev == 0) ev = EV_EXHAUSTED;
+	} while(ev == 0);
+	asm volatile("" : "+v"(ev));
+
+	//@R p_post
+	static_assert(EV_WALL == 1 && EV_SPHERE == 2, "pwnhip.h PWN_HIT_WALL, PWN_HIT_SPHERE");
+	uint4 r0, r1, r2;
+	if(ev == EV_EXHAUSTED)
+	{
+		// trace.h:677: nothing was hit.  face = object = -1, every other field 0
+		if(COUNT) cnt.exhausted++;
+		r0 = make_uint4(0u, 0xffffffffu, 0xffffffffu, 0u);
+		r1 = make_uint4(0u, 0u, 0u, 0u);
+		r2 = r1;
+	}
+	else
+	{
+		// (the frame kernel's patch of a room's y exit, in front of its shading)
+		if(ev == EV_WALL && base == BASE_ROOM_Y) ldir = ldy;
+		int object = -1;
+		float dist = cdist;
+		V at = pos;
+		if(ev == EV_SPHERE)
+		{
+			// which sphere: its byte offset in the blob's sphere array (32 bytes a sphere, in the order of the live table) is what an
+			// indexed list holds per entry; an inline record's comes from the "which sphere" array, as trace_shade.inc looks it up
+			if constexpr(INL) aux_idx = L.recsph[(aux_idx - PWN_T_BINIDX) >> 4];
+			object = (int)(aux_idx >> 5);
+			ldir = -1;
+			dist = aux_dist;
+			at = aux_pos;
+		}
+		r0 = make_uint4((uint32_t)ev, (uint32_t)ldir, (uint32_t)object, (uint32_t)hit_portals);
+		r1 = make_uint4(__float_as_uint(dist), __float_as_uint(at.x), __float_as_uint(at.y), __float_as_uint(at.z));
+		r2 = make_uint4(__float_as_uint(ray.x), __float_as_uint(ray.y), __float_as_uint(ray.z), hit_cxz);
+	}
+	// three 16-byte stores (the record is 16-byte aligned: pwn_api.cpp checks the array)
+	out[0] = r0; out[1] = r1; out[2] = r2;
+}
+
 // Rounds 1..15 of the add chain of screen.h:12-18 (see the unit loop): in round k the lanes k..15 of every 16-lane row add
 // rdx once more, so lane j ends with j adds on top of the row's start value -- the same sequence of fp32 additions for
 // every pixel as the reference's "+= rdx" per pixel of the tile.  Written with the execution mask set by hand: a
@@ -199,13 +280,14 @@ template<bool HAS_W> __device__ __forceinline__ void chain_rounds(Vec<HAS_W> &v,
 // clock read per unit -- it cost launches that do not use it 2.5-3 % (profiles/r4/unit_order_dormant_cost.txt).
 // MODE (tables.h PWN_KM_*): what the launch traces.  PWN_KM_FRAME: rows of one frame.  PWN_KM_VIEWS: a batch of P.nviews frames
 // of one size (pwn_trace_views): every unit reads its view's camera set-up from P.views and writes that view's planes.
-// PWN_KM_RAYS: P.nrays rays of the caller's (pwn_trace_rays): every lane loads its own origin, direction and seed.  The last two are
-// instantiated with ORDER = false only.
+// PWN_KM_RAYS: P.nrays rays of the caller's (pwn_trace_rays): every lane loads its own origin, direction and seed.  PWN_KM_HITS: the
+// same batch of rays (pwn_trace_hits), of which every lane traces the primary segment only and writes a first-hit record
+// (trace_hit) instead of a colour and a depth.  The last three are instantiated with ORDER = false only.
 template<bool COUNT, bool HAS_W, bool ORDER, bool INL, int MODE>
 __global__ void __launch_bounds__(PWN_BLOCK, PWN_MIN_WAVES)
 pwn_trace_kernel(pwn_trace_params P)
 {
-	constexpr bool VIEWS = MODE == PWN_KM_VIEWS, RAYS = MODE == PWN_KM_RAYS;
+	constexpr bool VIEWS = MODE == PWN_KM_VIEWS, HITS = MODE == PWN_KM_HITS, RAYS = MODE == PWN_KM_RAYS || HITS;
 	//@R k_prologue
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
 
@@ -367,15 +449,31 @@ pwn_trace_kernel(pwn_trace_params P)
 			{
 				const pwn_f4 *rec = (const pwn_f4 *)P.rays + 2u * (size_t)i;
 				const pwn_f4 o = rec[0], d = rec[1];
-				uint32_t seed = P.ray_seeds != NULL ? P.ray_seeds[i] : 0u;
-				seed <<= 1;                               // the generator runs on the doubled state (lcg2_fs, dev_math.h)
+				uint32_t seed = 0u;
+				if constexpr(!HITS)
+				{
+					seed = P.ray_seeds != NULL ? P.ray_seeds[i] : 0u;
+					seed <<= 1;                           // the generator runs on the doubled state (lcg2_fs, dev_math.h)
+				}
 				// (without PWN_RAYS_HAS_W the w lanes are those of an ordinary camera's rays, 1 and 0, whichever variant runs)
 				V org, dir;
 				org.x = o.x; org.y = o.y; org.z = o.z; org.w = HAS_W && P.ray_w ? o.w : 1.0f;
 				dir.x = d.x; dir.y = d.y; dir.z = d.z; dir.w = HAS_W && P.ray_w ? d.w : 0.0f;
-				float ox, oy, oz, ow;
-				trace_pixel<COUNT, HAS_W, INL>(L, sec_current, seed, org, dir, ox, oy, oz, ow, P.zbuf + i, cnt);
-				P.sbuf[i] = col_pack4(ox, oy, oz, ow);
+				if constexpr(HITS)
+				{
+					// First-hit records (pwn_trace_hits): the same lane, the same record, the same argument as above for every LDS address --
+					// trace_hit runs trace_pixel's set-up and walk texts and reads one more table, the inline lists' "which sphere" array,
+					// at the index trace_shade.inc reads it at (aux_idx is a list record's LDS address, written by the walk from the cell
+					// word's list offset; never the ray's).  Global: hits + 48 i for i < nrays <= 2^28 in 64-bit arithmetic lies in the
+					// caller's array of n records; a lane with i >= nrays stores nothing.  No seed, colour or depth is touched.
+					trace_hit<COUNT, HAS_W, INL>(L, org, dir, (uint4 *)((unsigned char *)P.hits + (size_t)i * PWN_HIT_REC_BYTES), cnt);
+				}
+				else
+				{
+					float ox, oy, oz, ow;
+					trace_pixel<COUNT, HAS_W, INL>(L, sec_current, seed, org, dir, ox, oy, oz, ow, P.zbuf + i, cnt);
+					P.sbuf[i] = col_pack4(ox, oy, oz, ow);
+				}
 			}
 			ticket = (uint32_t)__builtin_amdgcn_readfirstlane((int)next_raw);
 			left = draw ? draw_n - 1u : left - 1u;
@@ -549,7 +647,8 @@ extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size
 {
 	// (the blob says which form its per-cell lists have: pack_blob, pwn_api.cpp)
 	const bool inl = P->off_recsph != 0u;
-	// a batch of rays (pwn_trace_rays) or of views (pwn_trace_views): eight variants each, never ordered
+	// a batch of rays (pwn_trace_rays), of their first hits (pwn_trace_hits) or of views (pwn_trace_views): eight variants each, never ordered
+	if(P->hits != NULL) return inl ? Units<false, true, PWN_KM_HITS>::launch(P, grid, lds_bytes, count, stream) : Units<false, false, PWN_KM_HITS>::launch(P, grid, lds_bytes, count, stream);
 	if(P->rays != NULL) return inl ? Units<false, true, PWN_KM_RAYS>::launch(P, grid, lds_bytes, count, stream) : Units<false, false, PWN_KM_RAYS>::launch(P, grid, lds_bytes, count, stream);
 	if(P->views != NULL) return inl ? Units<false, true, PWN_KM_VIEWS>::launch(P, grid, lds_bytes, count, stream) : Units<false, false, PWN_KM_VIEWS>::launch(P, grid, lds_bytes, count, stream);
 	const bool order = P->perm != NULL || P->unit_cost != NULL;

@@ -42,6 +42,9 @@ __global__ void __launch_bounds__(PWN_BLOCK, PWN_MIN_WAVES)
 pwn_trace_refill_kernel(pwn_trace_params P)
 {
 	constexpr bool INL = false;          // (this scheduler reads the indexed lists: pack_blob packs those for it)
+	constexpr bool HITREC = false;       // (trace_walk.inc: nothing kept for hit records; the two names it would write, never touched)
+	[[maybe_unused]] uint32_t hit_cxz;
+	[[maybe_unused]] int hit_portals;
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
 
 	blob_to_lds(lds_raw, P.blob, P.blob_bytes);

@@ -3,7 +3,10 @@
 //   L (Lds), COUNT, HAS_W, INL (the per-cell lists hold inline sphere records: tables.h), V, cnt;  the ray: pos, ray, cxz (cell x | z << 16), sx, sz (the steps (gx, 0) and
 //   (0, gz) in the same packing: trace_common.h), ldx, ldz, ldy, gyp,
 //   wx, wy, wz, iax, iay, iaz, iay_dn, iay_up_bits, cw, cdist, fog, ldir, ev, base, maxsteps;
-//   the nearest sphere candidate: aux_dist, aux_diff, aux_idx, aux_pos.
+//   the nearest sphere candidate: aux_dist, aux_diff, aux_idx, aux_pos;
+//   HITREC (compile-time; false in every kernel that shades): the walk also keeps what a first-hit record needs and the
+//   shading never asks for -- hit_cxz, the reference's cx, cz when the segment returns, and hit_portals, the portals
+//   this lane crossed.  With HITREC false the two names are not touched and no instruction is made for them.
 // One cell per iteration, one loop exit at the bottom.  The cell class is a bit test on the
 // LDS word (tables.h).  The room body - by far the most frequent - is written with selects;
 // lanes whose ray ended in it carry on through the (then meaningless) cell advance and leave
@@ -16,6 +19,10 @@ if(COUNT)
 	// once per wave and iteration: the lowest active lane
 	if((__ffsll((long long)__ballot(1)) - 1) == (int)(threadIdx.x & 63)) cnt.wsteps++;
 }
+
+// HITREC: the cell this step begins in.  Behind the walk cxz is not it: the room body's ended lanes have advanced, a portal
+// step has crossed, a ramp step has moved on before trace.h:668 sees the sphere.
+if constexpr(HITREC) hit_cxz = cxz;
 
 #ifdef PWN_PLAIN_STATS
 // measurement build: in how many wave iterations is no lane in a special cell?
@@ -174,6 +181,8 @@ if(cw & PWN_C_ROOM)
 						wy -= iay_dn;
 					}
 					ev = EV_WALL; base = BASE_WALL;
+					// (the one return behind the reference's own cell advance, trace.h:393-441: the wall is the cell stepped into)
+					if constexpr(HITREC) hit_cxz = cxz;
 				}
 			}
 		}
@@ -272,6 +281,7 @@ else
 			pos.z += edz;
 			const int rot = (int)((cw_in >> PWN_C_PROT_SHIFT) & 3u);
 			if(COUNT) cnt.portals++;
+			if constexpr(HITREC) hit_portals++;
 
 			// trace.h:561-622.  The operation order is the one the reference
 			// build executes (its -ffast-math cancels the +-0.5 terms).

@@ -12,6 +12,10 @@ import numpy as np
 from . import _lib
 from ._lib import lib
 
+# pwn_hit (pwnhip.h): a first-hit record of trace_hits, 48 bytes
+HIT_DTYPE = np.dtype([("kind", "<i4"), ("face", "<i4"), ("object", "<i4"), ("portals", "<i4"),
+                      ("dist", "<f4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4"),
+                      ("dx", "<f4"), ("dy", "<f4"), ("dz", "<f4"), ("cell_x", "<i2"), ("cell_z", "<i2")])
 SPHERE_DTYPE = np.dtype([("r", "<f4"), ("refl", "<f4"), ("x", "<f4"), ("y", "<f4"),
                          ("z", "<f4"), ("cb", "<f4"), ("cg", "<f4"), ("cr", "<f4")])
 PORTAL_DTYPE = np.dtype([(n, "<i4") for n in ("x1", "z1", "x2", "z2", "rot12", "c1", "c2")])
@@ -318,6 +322,59 @@ class Renderer:
         self._chk(lib.pwn_trace_rays_device(self._ctx, int(n), C.c_void_p(p_rays), C.c_void_p(p_seeds), float(sec_current),
                                             _lib.PWN_RAYS_HAS_W if has_w else 0, C.c_void_p(p_col), C.c_void_p(p_depth),
                                             C.c_void_p(stream or 0)), "pwn_trace_rays_device")
+
+    # -- first hits of caller-supplied rays (pwn_trace_hits) -------------------
+    def trace_hits(self, rays):
+        """pwn_trace_hits: what the primary segment of each ray ends on.  rays as trace_rays takes them: (n,8) records or a pair
+        (origins, directions).  Returns (n,) HIT_DTYPE records: kind (PWN_HIT_NONE / WALL / SPHERE), face, object (index into
+        get_objects() / object_ids()), portals crossed, dist, the point x y z, the walked direction dx dy dz, the cell."""
+        rays = _ray_records(rays, "trace_hits")
+        n = rays.shape[0]
+        hits = np.zeros(n, HIT_DTYPE)
+        self._chk(lib.pwn_trace_hits(self._ctx, n, rays.ctypes.data if n else None, hits.ctypes.data if n else None), "pwn_trace_hits")
+        return hits
+
+    def trace_hits_device(self, rays, hits, has_w=False, stream=None, n=None):
+        """pwn_trace_hits_device: one trace launch, stream-ordered, no synchronisation.  rays (n,8) float32 and hits -- (n,12) int32
+        or float32, or (n,48) uint8: n records of HIT_DTYPE -- are torch tensors on this context's GPU, both 16-byte aligned, or
+        raw device pointers with n given.  has_w and stream as trace_rays_device takes them."""
+        tensors = [t for t in (rays, hits) if not isinstance(t, int)]
+        if tensors:
+            import torch
+            if len(tensors) != 2:
+                raise ValueError("trace_hits_device: give both tensors or both device pointers")
+            rays_n = _tensor_check(torch, rays, "rays", (torch.float32,), 2)
+            if n is not None and int(n) != rays_n:
+                raise ValueError("trace_hits_device: n = %d, but rays has %d rows" % (n, rays_n))
+            n = rays_n
+            if rays.shape[1] != 8 or rays.data_ptr() % 16 != 0:
+                raise ValueError("trace_hits_device: rays must be (n,8) and 16-byte aligned")
+            _tensor_check(torch, hits, "hits", (torch.int32, torch.float32, torch.uint8), 2, n)
+            if hits.shape[1] * hits.element_size() != HIT_DTYPE.itemsize or hits.data_ptr() % 16 != 0:
+                raise ValueError("trace_hits_device: hits must hold %d bytes a row and be 16-byte aligned" % HIT_DTYPE.itemsize)
+            if hits.device != rays.device:
+                raise ValueError("trace_hits_device: tensors on %s and %s" % (rays.device, hits.device))
+            if stream is None:
+                stream = torch.cuda.current_stream(rays.device)
+            p_rays, p_hits = rays.data_ptr(), hits.data_ptr()
+        else:
+            if n is None:
+                raise ValueError("trace_hits_device: n is needed with device pointers")
+            p_rays, p_hits = rays, hits
+        if int(n) < 0 or int(n) > _lib.PWN_RAYS_MAX:
+            raise ValueError("trace_hits_device: n = %d, 0 ... %d" % (n, _lib.PWN_RAYS_MAX))
+        if stream is not None and not isinstance(stream, int):
+            stream = stream.cuda_stream
+        self._chk(lib.pwn_trace_hits_device(self._ctx, int(n), C.c_void_p(p_rays), _lib.PWN_RAYS_HAS_W if has_w else 0,
+                                            C.c_void_p(p_hits), C.c_void_p(stream or 0)), "pwn_trace_hits_device")
+
+    def object_ids(self):
+        """pwn_get_object_ids: per live sphere, in get_objects()' order (what a hit's `object` indexes), the obj_new handle"""
+        n = self._chk(lib.pwn_get_object_ids(self._ctx, None, 0), "pwn_get_object_ids")
+        ids = np.zeros(n, np.int32)
+        if n:
+            self._chk(lib.pwn_get_object_ids(self._ctx, ids.ctypes.data, n), "pwn_get_object_ids")
+        return ids
 
     def set_call_strips(self, n):
         """PWN_OPT_CALL_STRIPS: -1 = by frame size (default), 0 = one launch per pass, 2..32 = that many row strips"""
