@@ -35,7 +35,9 @@ extern "C" {
 #define PWN_EIO          -4  /* level file could not be read (level.h:110-115) */
 #define PWN_EHIP         -5  /* a HIP runtime call failed; see pwn_last_error() */
 #define PWN_ENOLEVEL     -6  /* render called before a level was uploaded */
-#define PWN_ETOOBIG      -7  /* sphere tables exceed the on-chip (LDS) budget */
+#define PWN_ETOOBIG      -7  /* sphere tables exceed PWN_TABLES_MAX (or one cell's list PWN_LIST_MAX): the per-cell lists of these spheres, kept in device memory where they outgrow
+                                the on-chip (LDS) budget, would take more than 16 MiB -- 10000 spheres that each touch 3 x 3 cells need
+                                about 2 MB, a sphere whose box covers the whole grid alone makes 4096 entries (pwn_sphere_tables_plan) */
 #define PWN_EBUSY        -8  /* the frame slot is still in flight (pwn_wait_frame it first) */
 #define PWN_ENOTSUP      -9  /* not available here (RCCL could not be loaded; not configured) */
 #define PWN_ETIMEDOUT    -10 /* the row tiling waited longer than its deadline for a peer (pwn_tiled_set_timeouts); the tiling is
@@ -92,6 +94,8 @@ typedef struct pwn_stats
 #define PWN_SCHED_UNITS     0  /*   a wave traces 16x4-pixel units, all 64 lanes in step (ray set-up, walk, shading) */
 #define PWN_SCHED_REFILL    1  /*   lanes whose ray ended are refilled by ballot + prefix rank while the rest walk on */
 #define PWN_SCHED_DEFAULT   PWN_SCHED_UNITS
+                               /*   While the sphere tables are in their device-memory form (pwn_sphere_tables_state: form 2) every launch runs
+                                    the units kernel whatever this option says -- the refill kernel reads on-chip lists only.  Same frames. */
 #define PWN_OPT_REFILL_LIMIT 4 /* PWN_SCHED_REFILL: lane-steps (1..64000) the ended rays of a batch may wait, in sum, for
                                   the batch's other rays before they are shaded and replaced; rays still walking
                                   then walk on beside the next batches */
@@ -210,6 +214,8 @@ typedef struct pwn_group_info
 int pwn_init_multi(pwn_ctx **out, const int *devices, int ndev, int width, int height);
 int pwn_group_info_get(pwn_ctx *ctx, pwn_group_info *out);
 int pwn_set_option(pwn_ctx *ctx, int option, int value);
+/* (PWN_OPT_UNIT_ORDER is ignored while the sphere tables are in their device-memory form, pwn_sphere_tables_state: form 2 -- those
+   kernels hand their units out in arithmetic order and write no costs.  Same frames.) */
 /* PWN_OPT_UNIT_ORDER as it stands: out[0] the option, out[1] trace launches so far that handed their units out in a sorted order,
    out[2] sorts launched (one behind every frame whose trace wrote its units' costs), out[3] units the first compute stream's
    current order covers (0: none yet). */
@@ -241,9 +247,34 @@ int pwn_upload_level(pwn_ctx *ctx, const uint8_t data[4096], const pwn_portal pm
 int pwn_get_level(pwn_ctx *ctx, uint8_t data[4096], pwn_portal pmap[26], int32_t spawn[2]);
 
 /* level_prepare_render (level.h:64-81) + level_part_add_bbox (level.h:1-19):
-   bins the live spheres per cell in object order and uploads the lists */
+   bins the live spheres per cell in object order and uploads the lists.
+   Any table up to PWN_OBJ_MAX spheres loads, as in the reference.  Lists that fit the on-chip budget are copied into LDS by every
+   workgroup, in the form and with the kernels they always had; lists that do not (more than 2047 spheres, more than 32767 list
+   entries, more than 72 KiB in all) stay in device memory and are read from there by kernels of their own, for every call of this
+   file -- frames, frames in flight, strips, views, rays, hits, the row tiling, groups -- with the same pixels, depths, records and
+   counters.  Only tables whose device-memory part would exceed PWN_TABLES_MAX, or with more than PWN_LIST_MAX spheres binned to one
+   cell, are refused (PWN_ETOOBIG); a refused or failed
+   upload leaves the previous tables in force.  The device-memory part and its pinned staging are allocated with the first tables
+   that need them and grown to the largest so far; an upload that has to grow a device buffer synchronises the device once (a
+   launch in flight may still read the buffer it replaces), one that fits waits for nothing, as before. */
 int pwn_upload_spheres(pwn_ctx *ctx, const pwn_sphere *spheres, int n);
 int pwn_get_bins(pwn_ctx *ctx, uint16_t counts[4096], int32_t *idx, int cap);
+#define PWN_TABLES_MAX (16u << 20)   /* bytes of the sphere tables' device-memory part at most */
+#define PWN_LIST_MAX 4096            /* ... and spheres binned to ONE cell at most, for tables in device memory: every step of every ray through a
+                                        cell tests the cell's whole list (trace.h:252-296), up to 1000 steps a segment, so a list bounds how long a
+                                        launch can run.  Thousands of spheres piled into one cell stay PWN_ETOOBIG, as they always were; the reference's
+                                        scenes and 10000 spheres spread over a level are nowhere near (pwn_sphere_tables_plan: out[5]) */
+/* What an upload of these n spheres would do, under the default scheduler (and PWN_SPHERE_LISTS=indexed|inline|global of the
+   environment, which every context of the process follows: tests, experiments).  Host only: no context, no device.
+     out[0]  form of the per-cell lists: 0 indexed, 1 inline records (both in LDS), 2 in device memory
+     out[1]  LDS bytes per workgroup of the units kernel (the tables' on-chip part and the kernel's own 16 bytes)
+     out[2]  bytes in device memory beside that (0 for forms 0 and 1): 16 per (cell, sphere) pair and 16 more, 4 per pair, 32 per
+             sphere, each section rounded up to 16
+     out[3]  (cell, sphere) pairs    out[4]  non-empty cells    out[5]  the longest cell list
+   PWN_OK; PWN_ETOOBIG (out is filled in all the same); PWN_EINVAL for NULL spheres or out, n < 0, n > PWN_OBJ_MAX. */
+int pwn_sphere_tables_plan(const pwn_sphere *spheres, int n, unsigned long long out[6]);
+/* The same six values for the tables in force in this context, under its scheduler (a pwn_init_multi handle: member 0's). */
+int pwn_sphere_tables_state(pwn_ctx *ctx, unsigned long long out[6]);
 
 /*
  * The object table behind those lists, driven the way game.lua drives the
@@ -261,7 +292,8 @@ int pwn_get_bins(pwn_ctx *ctx, uint16_t counts[4096], int32_t *idx, int cap);
  *   pwn_level_get      level_get(cx, cz) (script.h:53-64): the cell character
  *                      under get_cell's clamp (util.h:151-158)
  *   pwn_prepare_render level_prepare_render (level.h:64-81): bin every object
- *                      that is not free, in table order, and upload; an object
+ *                      that is not free, in table order, and upload (all PWN_OBJ_MAX
+ *                      of them if need be: see pwn_upload_spheres); an object
  *                      that was created but never set is PWN_EINVAL (the
  *                      reference aborts, level.h:34-37)
  *   pwn_get_objects    the live spheres in table order (at most cap); returns

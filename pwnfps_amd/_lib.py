@@ -24,6 +24,7 @@ PWN_SCHED_UNITS, PWN_SCHED_REFILL = 0, 1
 PWN_MAX_SLOTS = 4
 PWN_FRAME_SBUF, PWN_FRAME_ZBUF, PWN_FRAME_SURFACE = 1, 2, 4
 PWN_OBJ_MAX = 10000
+PWN_TABLES_MAX = 16 << 20
 PWN_VIEWS_MAX = 1024
 PWN_RAYS_HAS_W = 1
 PWN_RAYS_MAX = 1 << 28
@@ -104,6 +105,8 @@ ABI = [
     ("pwn_get_level", _i, [_vp, _vp, _vp, _vp]),
     ("pwn_upload_spheres", _i, [_vp, _vp, _i]),
     ("pwn_get_bins", _i, [_vp, _vp, _vp, _i]),
+    ("pwn_sphere_tables_plan", _i, [_vp, _i, _vp]),
+    ("pwn_sphere_tables_state", _i, [_vp, _vp]),
     ("pwn_obj_new", _i, [_vp]),
     ("pwn_obj_set_sphere", _i, [_vp, _i, _d, _d, _d, _d, _d, _d, _d, _d]),
     ("pwn_obj_free", _i, [_vp, _i]),

@@ -28,7 +28,7 @@ extern "C" const char *pwn_strerror(int code)
 		case PWN_EIO: return "level file could not be read";
 		case PWN_EHIP: return "HIP runtime error";
 		case PWN_ENOLEVEL: return "no level uploaded";
-		case PWN_ETOOBIG: return "sphere tables exceed the LDS budget";
+		case PWN_ETOOBIG: return "sphere tables exceed PWN_TABLES_MAX";
 		case PWN_EBUSY: return "frame slot still in flight";
 		case PWN_ENOTSUP: return "not available (RCCL missing, or not configured)";
 		case PWN_ETIMEDOUT: return "the row tiling's deadline passed waiting for a peer";
@@ -76,7 +76,10 @@ extern "C" int pwn_init(pwn_ctx **out, int device, int width, int height)
 	c->dbg_blur_th = 0;
 	if(const char *e = getenv("PWN_DBG_BLUR_TH")) c->dbg_blur_th = atoi(e);
 	c->dbg_sphere_lists = 0; c->off_recsph = 0;
-	if(const char *e = getenv("PWN_SPHERE_LISTS")) c->dbg_sphere_lists = strcmp(e, "indexed") == 0 ? 1 : (strcmp(e, "inline") == 0 ? 2 : 0);
+	c->dbg_sphere_lists = pwn_i_forced_lists();
+	c->lists_form = PWN_LF_INDEXED; c->big_which = c->big_sph = 0; c->big_high = 0;
+	for(int i = 0; i < PWN_NBLOB; i++) { c->d_big[i] = NULL; c->d_big_cap[i] = 0; }
+	for(int i = 0; i < PWN_NSTAGE; i++) { c->h_big[i] = NULL; c->h_big_cap[i] = 0; }
 	c->dbg_blur_tw = 0; c->dbg_blur_batch = -1;          // (sweeps with a -DPWN_BLUR_SWEEP build: tools/r3/run_w.sh)
 	if(const char *e = getenv("PWN_DBG_BLUR_TW")) c->dbg_blur_tw = atoi(e);
 	if(const char *e = getenv("PWN_DBG_BLUR_BATCH")) if(*e) c->dbg_blur_batch = atoi(e);
@@ -97,7 +100,7 @@ extern "C" int pwn_init(pwn_ctx **out, int device, int width, int height)
 	memset(&c->room, 0, sizeof(c->room)); c->room.mode = -1;
 	if(const char *e = getenv("PWN_TRACE_ROOM")) if(*e) c->room.mode = atoi(e) < 0 ? -1 : atoi(e);      // (the option's default for every context of a process)
 	c->d_scratch = NULL; c->scratch_cap = 0;
-	for(int i = 0; i < 8; i++) { c->occ_lds[i] = 0; c->occ_blocks[i] = 0; }
+	for(int i = 0; i < 12; i++) { c->occ_lds[i] = 0; c->occ_blocks[i] = 0; }
 	c->stream = NULL; c->copy_stream = NULL; c->copy_stream2 = NULL; c->stream2 = NULL; c->d_pre2 = NULL;
 	c->frame_overlap = 1; c->last_frame_done = NULL; c->last_frame_stream = NULL;
 	if(const char *e = getenv("PWN_FRAME_OVERLAP")) c->frame_overlap = atoi(e) != 0;
@@ -224,11 +227,13 @@ extern "C" void pwn_destroy(pwn_ctx *c)
 		if(c->ev_tables[i]) (void)hipEventDestroy(c->ev_tables[i]);
 		if(c->ev_upload[i]) (void)hipEventDestroy(c->ev_upload[i]);
 		(void)hipFree(c->d_blob[i]);
+		(void)hipFree(c->d_big[i]);
 	}
 	for(int i = 0; i < PWN_NSTAGE; i++)
 	{
 		if(c->ev_stage[i]) (void)hipEventDestroy(c->ev_stage[i]);
 		if(c->h_stage[i]) (void)hipHostFree(c->h_stage[i]);
+		if(c->h_big[i]) (void)hipHostFree(c->h_big[i]);
 	}
 	if(c->stream) (void)hipStreamDestroy(c->stream);
 	if(c->stream2) (void)hipStreamDestroy(c->stream2);
@@ -352,34 +357,94 @@ static void expand_tables(uint16_t *rcp, uint16_t *rsq)
 	}
 }
 
-static int pack_blob(pwn_ctx *c)
+int pwn_i_forced_lists(void)
 {
-	// per-cell sphere lists, each closed by PWN_LIST_END; only non-empty cells get one
-	uint32_t nsph = (uint32_t)c->spheres.size();
-	uint32_t nbin = 0;
+	const char *e = getenv("PWN_SPHERE_LISTS");
+	if(e == NULL) return 0;
+	return strcmp(e, "indexed") == 0 ? 1 : (strcmp(e, "inline") == 0 ? 2 : (strcmp(e, "global") == 0 ? 3 : 0));
+}
+
+// The size rules (pwn_internal.h): pack_blob, pwn_i_bin_spheres, upload_live and pwn_sphere_tables_plan all ask here.
+int pwn_i_tables_plan(const int32_t off[4097], uint32_t nsph, int scheduler, int forced, pwn_tables_plan *out)
+{
+	pwn_tables_plan p;
+	memset(&p, 0, sizeof(p));
+	p.nsph = nsph;
+	// per-cell sphere lists, each closed by PWN_LIST_END in the indexed form; only non-empty cells get one
+	uint64_t nbin = 0;
 	for(int i = 0; i < 4096; i++)
 	{
-		uint32_t cnt = (uint32_t)(c->bin_off[i + 1] - c->bin_off[i]);
-		if(cnt) nbin += cnt + 1u;
+		const uint32_t cnt = (uint32_t)(off[i + 1] - off[i]);
+		if(cnt) { nbin += cnt + 1u; p.ncell++; if(cnt > p.longest) p.longest = cnt; }
 	}
-	if(nbin > 32767u || nsph * 32u >= PWN_LIST_END) return PWN_ETOOBIG;      // list entries are byte offsets (index * 32) in 16 bits
-	uint32_t total = (pwn_t_total(nbin, nsph) + 15u) & ~15u;
-	if(total > PWN_BLOB_MAX) return PWN_ETOOBIG;
-	// Which form the per-cell lists take (tables.h): inline sphere records -- one LDS read per test instead of two dependent ones --
-	// for the unit scheduler's kernels wherever the bigger blob leaves as many workgroups per CU as the indexed one (2 KiB granules of
-	// 152 KiB: pwn_i_launch_trace); level.txt 26.5 against 26.3 KB, synth64 30.0 against 28.3 (both five), synth256 32.8 against
-	// 30.5 (four against five: indexed).  PWN_SPHERE_LISTS=indexed|inline in the environment forces one (experiments, tests).
-	uint32_t nrec = (uint32_t)c->bin_off[4096];
-	bool inl = false;
+	p.nrec = (uint32_t)off[4096];
+	p.nbin = (uint32_t)nbin;
+	// The forms that live in LDS: list entries are byte offsets (index * 32) in 16 bits, the cell word has 15 bits for a list's
+	// start, and the blob is copied whole into every workgroup's LDS.
+	const uint32_t total_idx = nbin > 32767u ? 0u : (pwn_t_total(p.nbin, nsph) + 15u) & ~15u;
+	const bool in_lds = !(nbin > 32767u || nsph * 32u >= PWN_LIST_END || total_idx > PWN_BLOB_MAX);
+	if(in_lds && forced != 3)
 	{
+		// Which of the two (tables.h): inline sphere records -- one LDS read per test instead of two dependent ones --
+		// for the unit scheduler's kernels wherever the bigger blob leaves as many workgroups per CU as the indexed one (2 KiB granules of
+		// 152 KiB: pwn_i_launch_trace); level.txt 26.5 against 26.3 KB, synth64 30.0 against 28.3 (both five), synth256 32.8 against
+		// 30.5 (four against five: indexed).  PWN_SPHERE_LISTS=indexed|inline in the environment forces one (experiments, tests).
+		const uint32_t nrec = p.nrec;
 		const uint32_t total_inl = (pwn_t_total_inl(nrec, nsph) + 15u) & ~15u;
 		const uint32_t extra = pwn_trace_lds_extra();
-		const uint32_t fit_idx = 155648u / ((total + extra + 2047u) & ~2047u), fit_inl = 155648u / ((total_inl + extra + 2047u) & ~2047u);
-		inl = c->scheduler == PWN_SCHED_UNITS && nrec > 0u && total_inl <= PWN_BLOB_MAX && fit_inl >= (fit_idx < 5u ? fit_idx : 5u);
-		if(c->dbg_sphere_lists == 1) inl = false;
-		if(c->dbg_sphere_lists == 2) inl = c->scheduler == PWN_SCHED_UNITS && nrec > 0u && total_inl <= PWN_BLOB_MAX;
-		if(inl) total = total_inl;
+		const uint32_t fit_idx = 155648u / ((total_idx + extra + 2047u) & ~2047u), fit_inl = 155648u / ((total_inl + extra + 2047u) & ~2047u);
+		bool inl = scheduler == PWN_SCHED_UNITS && nrec > 0u && total_inl <= PWN_BLOB_MAX && fit_inl >= (fit_idx < 5u ? fit_idx : 5u);
+		if(forced == 1) inl = false;
+		if(forced == 2) inl = scheduler == PWN_SCHED_UNITS && nrec > 0u && total_inl <= PWN_BLOB_MAX;
+		p.form = inl ? PWN_LF_INLINE : PWN_LF_INDEXED;
+		p.blob_bytes = inl ? total_inl : total_idx;
 	}
+	else
+	{
+		// The lists in device memory (tables.h): whatever the LDS forms refuse, or PWN_SPHERE_LISTS=global (tests: small scenes
+		// through those kernels).  Any scheduler: pwn_i_launch_trace runs the units kernel on such tables.
+		p.form = PWN_LF_GLOBAL;
+		p.blob_bytes = pwn_t_total_glb(p.ncell);
+		p.big_bytes = pwn_g_total(p.nrec, nsph);
+	}
+	*out = p;
+	// (pwnhip.h: the two things that bound tables in device memory -- their bytes, and how long a ray can be held in one cell)
+	return (p.big_bytes > PWN_TABLES_MAX || (p.form == PWN_LF_GLOBAL && p.longest > PWN_LIST_MAX)) ? PWN_ETOOBIG : PWN_OK;
+}
+
+// Room for `need` bytes of the device-memory part in copy nb of the tables and in staging buffer st.  Buffers grow to the largest
+// part so far and never shrink.  A device buffer that grows may still be read by a launch in flight (copy nb's, four uploads
+// ago) and is freed here: the device is synchronised first -- on growth only, an upload that fits waits for nothing.  The staging
+// buffer is free already (pack_blob has waited for its event).
+static int big_reserve(pwn_ctx *c, int nb, unsigned st, size_t need)
+{
+	if(need > c->big_high) c->big_high = (need + 65535u) & ~(size_t)65535u;
+	if(need > c->d_big_cap[nb])
+	{
+		if(c->d_big[nb] != NULL) { HIPCHK(c, hipDeviceSynchronize()); (void)hipFree(c->d_big[nb]); c->d_big[nb] = NULL; c->d_big_cap[nb] = 0; }
+		if(hipMalloc((void **)&c->d_big[nb], c->big_high) != hipSuccess) { (void)hipGetLastError(); c->d_big[nb] = NULL; return PWN_ENOMEM; }
+		c->d_big_cap[nb] = c->big_high;
+	}
+	if(need > c->h_big_cap[st])
+	{
+		if(c->h_big[st] != NULL) { (void)hipHostFree(c->h_big[st]); c->h_big[st] = NULL; c->h_big_cap[st] = 0; }
+		if(hipHostMalloc((void **)&c->h_big[st], c->big_high, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); c->h_big[st] = NULL; return PWN_ENOMEM; }
+		c->h_big_cap[st] = c->big_high;
+	}
+	return PWN_OK;
+}
+
+static int pack_blob(pwn_ctx *c)
+{
+	const uint32_t nsph = (uint32_t)c->spheres.size();
+	pwn_tables_plan plan;
+	{
+		const int rc = pwn_i_tables_plan(c->bin_off.data(), nsph, c->scheduler, c->dbg_sphere_lists, &plan);
+		if(rc != PWN_OK) return rc;
+	}
+	const uint32_t nbin = plan.nbin, nrec = plan.nrec;
+	const uint32_t total = plan.blob_bytes;
+	const bool inl = plan.form == PWN_LF_INLINE, glb = plan.form == PWN_LF_GLOBAL;
 	c->blob.assign(total, 0);        // (nothing has changed up to here: a failed call leaves the context as it was)
 	uint8_t *b = c->blob.data();
 	uint32_t *ci = (uint32_t *)(b + PWN_T_CELLINFO);
@@ -399,7 +464,7 @@ static int pack_blob(pwn_ctx *c)
 	}
 	memcpy(ci, c->cell_base, sizeof(c->cell_base));
 	uint32_t at = 0;
-	for(int i = 0; i < 4096 && !inl; i++)
+	for(int i = 0; i < 4096 && !inl && !glb; i++)
 	{
 		int32_t k0 = c->bin_off[i], k1 = c->bin_off[i + 1];
 		if(k1 > k0)
@@ -433,15 +498,46 @@ static int pack_blob(pwn_ctx *c)
 			}
 		}
 	}
+	c->big.clear();
+	if(glb)
+	{
+		// the global form (tables.h): the records are the inline form's, in device memory; LDS gets one u32 per non-empty cell
+		c->big.assign((size_t)plan.big_bytes, 0);
+		c->big_which = pwn_g_which_offset(nrec); c->big_sph = pwn_g_sph_offset(nrec);
+		uint32_t *start = (uint32_t *)(b + PWN_T_BINIDX);
+		float *rec = (float *)c->big.data();
+		uint32_t *which = (uint32_t *)(c->big.data() + c->big_which);
+		uint32_t ord = 0;
+		for(int i = 0; i < 4096; i++)
+		{
+			const int32_t k0 = c->bin_off[i], k1 = c->bin_off[i + 1];
+			if(k1 <= k0) continue;
+			ci[(i >> 6) * PWN_GRID_PITCH + (i & 63)] |= PWN_C_SPH | (ord << 16);
+			start[ord++] = (uint32_t)k0;
+			for(int32_t k = k0; k < k1; k++)
+			{
+				const pwn_sphere &q = c->spheres[(size_t)c->bin_idx[k]];
+				float r2 = q.r * q.r;
+				if(r2 < 1.17549435e-38f) r2 = 0.0f;          // (as below: the reference build's flush to zero)
+				rec[4 * (size_t)k + 0] = q.x; rec[4 * (size_t)k + 1] = q.y; rec[4 * (size_t)k + 2] = q.z;
+				uint32_t wbits;
+				memcpy(&wbits, &r2, 4);
+				if(k == k1 - 1) wbits |= 0x80000000u;
+				memcpy(&rec[4 * (size_t)k + 3], &wbits, 4);
+				which[k] = (uint32_t)c->bin_idx[k];
+			}
+		}
+	}
 	memcpy(b + PWN_T_RCP, c->tabs, 4096);
 	memcpy(b + PWN_T_RSQ, c->tabs + 2048, 4096);
 	pwn_fill_faces((float *)(b + PWN_T_FACES));
 	memcpy(b + PWN_T_EPREC, c->ep_recs, sizeof(c->ep_recs));
-	c->off_sph = inl ? pwn_t_sph_offset_inl(nrec) : pwn_t_sph_offset(nbin);
+	c->off_sph = glb ? 0u : (inl ? pwn_t_sph_offset_inl(nrec) : pwn_t_sph_offset(nbin));
 	c->off_recsph = inl ? pwn_t_recsph_offset(nrec) : 0u;
+	c->lists_form = plan.form;
 	// the kernels' layout of a sphere (tables.h): position and r*r in one 16-byte half, the rest in the other
 	{
-		float *sp = (float *)(b + c->off_sph);
+		float *sp = glb ? (float *)(c->big.data() + c->big_sph) : (float *)(b + c->off_sph);
 		for(uint32_t i = 0; i < nsph; i++, sp += 8)
 		{
 			const pwn_sphere &q = c->spheres[i];
@@ -461,10 +557,18 @@ static int pack_blob(pwn_ctx *c)
 	const unsigned st = c->stage_next++ % PWN_NSTAGE;
 	if(c->stage_used[st]) HIPCHK(c, hipEventSynchronize(c->ev_stage[st]));
 	memcpy(c->h_stage[st], b + from, total - from);
+	// the global form: the device-memory part travels with the same upload -- the same copy number, staging slot, stream and events
+	if(glb)
+	{
+		const int rc = big_reserve(c, nb, st, c->big.size());
+		if(rc != PWN_OK) return rc;
+		memcpy(c->h_big[st], c->big.data(), c->big.size());
+	}
 	// launches still reading that copy (two uploads ago) finish first -- a wait between streams
 	if(c->tables_in_use[nb]) HIPCHK(c, hipStreamWaitEvent(c->up_stream, c->tables_wait[nb], 0));
 	// (a kernel that reads the pinned buffer, not a DMA copy: see pwn_upload_kernel; total and from are multiples of 16)
 	HIPCHK(c, pwn_launch_upload(c->h_stage[st], c->d_blob[nb] + from, total - from, c->up_stream));
+	if(glb) HIPCHK(c, pwn_launch_upload(c->h_big[st], c->d_big[nb], c->big.size(), c->up_stream));
 	HIPCHK(c, hipEventRecord(c->ev_stage[st], c->up_stream));
 	HIPCHK(c, hipEventRecord(c->ev_upload[nb], c->up_stream));
 	c->stage_used[st] = true;
@@ -659,13 +763,12 @@ int pwn_i_bin_spheres(const pwn_sphere *s, int n, pwn_binned *out)
 	out->off.assign(4097, 0);
 	const int nb = pwn_bin_spheres(s, n, out->off.data(), NULL, 0);
 	if(nb < 0) return PWN_ENOMEM;
+	// what pack_blob would refuse (no scheduler or forced form changes that), before the lists themselves are made
+	pwn_tables_plan plan;
+	if(pwn_i_tables_plan(out->off.data(), (uint32_t)n, PWN_SCHED_DEFAULT, 0, &plan) != PWN_OK) return PWN_ETOOBIG;
 	out->idx.assign((size_t)(nb > 0 ? nb : 1), 0);
 	if(pwn_bin_spheres(s, n, out->off.data(), out->idx.data(), nb) != nb) return PWN_ENOMEM;
 	out->s.assign(s, s + n);
-	// what pack_blob would refuse
-	uint32_t nbin = 0;
-	for(int i = 0; i < 4096; i++) { const uint32_t cnt = (uint32_t)(out->off[i + 1] - out->off[i]); if(cnt) nbin += cnt + 1u; }
-	if(nbin > 32767u || (uint32_t)n * 32u >= PWN_LIST_END || ((pwn_t_total(nbin, (uint32_t)n) + 15u) & ~15u) > PWN_BLOB_MAX) return PWN_ETOOBIG;
 	return PWN_OK;
 }
 
@@ -689,6 +792,12 @@ static int upload_live(pwn_ctx *c, const pwn_sphere *s, int n)
 	std::vector<int32_t> off(4097, 0);
 	int nb = pwn_bin_spheres(s, n, off.data(), NULL, 0);
 	if(nb < 0) return PWN_ENOMEM;
+	// (tables that no form holds are refused on their size alone: a sphere's box may cover every cell)
+	{
+		pwn_tables_plan plan;
+		const int rc = pwn_i_tables_plan(off.data(), (uint32_t)n, c->scheduler, c->dbg_sphere_lists, &plan);
+		if(rc != PWN_OK) return rc;
+	}
 	std::vector<int32_t> idx((size_t)(nb > 0 ? nb : 1));
 	if(pwn_bin_spheres(s, n, off.data(), idx.data(), nb) != nb) return PWN_ENOMEM;
 	std::vector<pwn_sphere> keep_s(c->spheres);
@@ -720,6 +829,36 @@ extern "C" int pwn_get_bins(pwn_ctx *c, uint16_t counts[4096], int32_t *idx, int
 		for(int i = 0; i < n; i++) idx[i] = c->bin_idx[i];
 	}
 	return n;
+}
+
+static void plan_out(const pwn_tables_plan &p, unsigned long long out[6])
+{
+	out[0] = (unsigned long long)p.form;
+	out[1] = (unsigned long long)p.blob_bytes + pwn_trace_lds_extra();
+	out[2] = p.big_bytes;
+	out[3] = p.nrec; out[4] = p.ncell; out[5] = p.longest;
+}
+
+extern "C" int pwn_sphere_tables_plan(const pwn_sphere *s, int n, unsigned long long out[6])
+{
+	if(out == NULL || n < 0 || n > PWN_OBJ_MAX || s == NULL) return PWN_EINVAL;
+	std::vector<int32_t> off(4097, 0);
+	if(pwn_bin_spheres(s, n, off.data(), NULL, 0) < 0) return PWN_ENOMEM;
+	pwn_tables_plan p;
+	const int rc = pwn_i_tables_plan(off.data(), (uint32_t)n, PWN_SCHED_DEFAULT, pwn_i_forced_lists(), &p);
+	plan_out(p, out);
+	return rc;
+}
+
+extern "C" int pwn_sphere_tables_state(pwn_ctx *c, unsigned long long out[6])
+{
+	if(GRP_HEAD(c)) { const int rc = pwn_group_sync(c); return rc != PWN_OK ? rc : pwn_sphere_tables_state(GRP_M0(c), out); }      // (as pwn_get_bins)
+	if(c == NULL || out == NULL) return PWN_EINVAL;
+	// (the lists in force are the context's bins: a refused upload has put the previous ones back)
+	pwn_tables_plan p;
+	const int rc = pwn_i_tables_plan(c->bin_off.data(), (uint32_t)c->spheres.size(), c->scheduler, c->dbg_sphere_lists, &p);
+	plan_out(p, out);
+	return rc;
 }
 
 // ---- frame ------------------------------------------------------------------
@@ -882,6 +1021,15 @@ int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L)
 	P.sbuf = L->d_sbuf; P.zbuf = L->d_zbuf;
 	const int cur = c->blob_cur;
 	P.blob = (const uint32_t *)c->d_blob[cur];
+	// the lists' global form (tables.h): blob_bytes is the LDS part, the rest is read where it lies.  Nothing below but the choice
+	// of the kernel knows the form.
+	const bool glb = c->lists_form == PWN_LF_GLOBAL;
+	if(glb)
+	{
+		P.g_rec = (const float *)c->d_big[cur];
+		P.g_which = (const uint32_t *)(c->d_big[cur] + c->big_which);
+		P.g_sph = (const float *)(c->d_big[cur] + c->big_sph);
+	}
 	// the upload of these tables runs on its own stream: this launch comes after it
 	if(c->upload_pending[cur])
 	{
@@ -911,16 +1059,18 @@ int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L)
 	if(c->counters_on) HIPCHK(c, hipMemsetAsync(c->d_counters, 0, PWN_NCOUNTERS * sizeof(unsigned long long), stream));
 	// persistent grid: as many workgroups as are resident at once, each striding over tiles
 	// (a batch of views or rays always runs the units scheduler)
-	const bool refill = c->scheduler == PWN_SCHED_REFILL && !batch;
+	// (so do tables in the global form: the refill kernel has none)
+	const bool refill = c->scheduler == PWN_SCHED_REFILL && !batch && !glb;
 	const size_t lds_bytes = ((P.blob_bytes + 15u) & ~15u) + (refill ? pwn_trace_refill_lds_extra(P.has_w != 0) : pwn_trace_lds_extra());
 	// resident workgroups per CU depend on (LDS bytes, kernel variant) only: ask once per combination
 	P.scheduler = c->scheduler;
 	P.refill_limit = c->refill_limit;
-	const int variant = (refill ? 4 : 0) | (c->counters_on ? 2 : 0) | (P.has_w ? 1 : 0);
+	const int variant = (glb ? 8 : 0) | (refill ? 4 : 0) | (c->counters_on ? 2 : 0) | (P.has_w ? 1 : 0);
 	if(c->occ_lds[variant] != lds_bytes)
 	{
 		c->occ_blocks[variant] = refill ? pwn_trace_refill_blocks_per_cu(lds_bytes, c->counters_on != 0, P.has_w != 0)
-		                                : pwn_trace_blocks_per_cu(lds_bytes, c->counters_on != 0, P.has_w != 0);
+		                       : glb ? pwn_trace_global_blocks_per_cu(lds_bytes, c->counters_on != 0, P.has_w != 0)
+		                             : pwn_trace_blocks_per_cu(lds_bytes, c->counters_on != 0, P.has_w != 0);
 		c->occ_lds[variant] = lds_bytes;
 	}
 	int per_cu = c->occ_blocks[variant];
@@ -973,7 +1123,8 @@ int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L)
 	// (with the wave log only where the dump is asked for, PWN_DBG_UNIT_COST: the kernel variant that writes the costs is 2-3 % slower,
 	// and the wave log's span and residency are figures of the ordinary launch)
 	// (a batch of views or rays neither writes nor reads nor invalidates any of this)
-	const bool want_cost = !refill && !batch && (c->unit_order || (c->wave_log_on && getenv("PWN_DBG_UNIT_COST") != NULL));
+	// (nor do tables in the global form: their kernels have no ordered variant, PWN_OPT_UNIT_ORDER is ignored)
+	const bool want_cost = !refill && !batch && !glb && (c->unit_order || (c->wave_log_on && getenv("PWN_DBG_UNIT_COST") != NULL));
 	pwn_ctx::unit_order_state *uop = batch ? NULL : order_entry(c, stream, want_cost);
 	if(uop != NULL && want_cost)
 	{

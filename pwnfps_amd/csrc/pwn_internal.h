@@ -69,6 +69,7 @@ extern "C" hipError_t pwn_launch_trace_refill(const pwn_trace_params *P, int gri
 extern "C" unsigned pwn_trace_refill_lds_extra(bool has_w);
 extern "C" int pwn_trace_refill_blocks_per_cu(size_t lds_bytes, bool count, bool has_w);
 extern "C" int pwn_trace_blocks_per_cu(size_t lds_bytes, bool count, bool has_w);
+extern "C" int pwn_trace_global_blocks_per_cu(size_t lds_bytes, bool count, bool has_w);
 extern "C" int pwn_trace_tile_h(void);
 extern "C" int pwn_trace_tile_w(void);
 extern "C" unsigned pwn_trace_lds_extra(void);
@@ -82,6 +83,9 @@ extern "C" hipError_t pwn_launch_probe(int op, const uint32_t *in, uint32_t *out
 // LDS budget for the table blob: leave room so that at least two workgroups
 // fit per CU (160 KiB LDS per CU on gfx950)
 #define PWN_BLOB_MAX (72u * 1024u)
+// ... and for the device-memory part of tables whose lists do not fit there (tables.h PWN_LF_GLOBAL).  10000 spheres with boxes
+// of 3 x 3 cells need about 2 MB; the limit exists because a sphere's box may cover all 4096 cells.
+#define PWN_TABLES_MAX (16u << 20)
 #ifndef PWN_NBLOB
 #define PWN_NBLOB 4       // device copies of the blob: an upload never touches one that launches in flight read.  With two, the upload
                           // of frame f+1's tables had to wait for the end of frame f-1 and so ran right where trace f starts;
@@ -184,8 +188,17 @@ struct pwn_ctx
 	uint16_t tabs[4096];             // expanded rcp + rsqrt tables (never change)
 	uint32_t off_sph;
 	uint32_t off_recsph; int dbg_sphere_lists;      // inline sphere records in the per-cell lists (tables.h): where their "which sphere" array is, 0 = indexed lists; PWN_SPHERE_LISTS
+	// The lists' global form (tables.h PWN_LF_GLOBAL): `blob` is then the LDS part alone and `big` the host image of the device-memory
+	// part, big_which / big_sph its sections.  Copy i of the tables has d_big[i] beside d_blob[i], under the same events; staging
+	// buffer i of the ring has h_big[i] beside h_stage[i].  All of them are allocated with the first tables that need them and
+	// grown to the largest so far (big_high); pack_blob says what growing waits for.
+	int lists_form;                  // PWN_LF_* of the tables in force
+	std::vector<uint8_t> big; uint64_t big_which, big_sph;
+	uint8_t *d_big[PWN_NBLOB]; size_t d_big_cap[PWN_NBLOB];
+	uint8_t *h_big[PWN_NSTAGE]; size_t h_big_cap[PWN_NSTAGE];
+	size_t big_high;
 	bool blob_dirty;
-	size_t occ_lds[8]; int occ_blocks[8];    // cached occupancy query per kernel variant
+	size_t occ_lds[12]; int occ_blocks[12];    // cached occupancy query per kernel variant
 
 	uint32_t *d_pre, *d_out;         // pre-blur ("tsbuf") and final ("sbuf") frames
 	float *d_z;
@@ -289,6 +302,17 @@ int pwn_i_tiled_ready(pwn_ctx *c, int ahead);
 // pwn_api.cpp: level_prepare_render's binning of a compact list of live spheres (no context: PWN_ETOOBIG where the lists would not
 // fit on chip), and its upload into one context; the object table of pwn_upload_spheres by itself
 struct pwn_binned { std::vector<pwn_sphere> s; std::vector<int32_t> off, idx; };
+// The size rules of the sphere tables, in one place: which form the per-cell lists of these bins take under this scheduler
+// (PWN_SCHED_*) and this PWN_SPHERE_LISTS setting (0 none, 1 indexed, 2 inline, 3 global), and what that costs.  PWN_ETOOBIG: no form holds them.
+struct pwn_tables_plan
+{
+	int form;                        // PWN_LF_*
+	uint32_t nsph, nrec, nbin, ncell, longest;      // spheres; (cell, sphere) pairs; entries of the indexed lists; non-empty cells; the longest list
+	uint32_t blob_bytes;             // the blob = the LDS part, a multiple of 16
+	uint64_t big_bytes;              // the device-memory part (0 unless form == PWN_LF_GLOBAL)
+};
+int pwn_i_tables_plan(const int32_t off[4097], uint32_t nsph, int scheduler, int forced, pwn_tables_plan *out);
+int pwn_i_forced_lists(void);        // PWN_SPHERE_LISTS of the environment
 int pwn_i_bin_spheres(const pwn_sphere *s, int n, pwn_binned *out);
 int pwn_i_upload_binned(pwn_ctx *c, const pwn_binned &b);
 void pwn_i_set_object_table(pwn_ctx *c, const pwn_sphere *s, int n);

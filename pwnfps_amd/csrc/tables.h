@@ -37,6 +37,8 @@
 //   [...    .. +32*nsph)        spheres 8 x f32   x, y, z, r*r | refl, cb, cg, cr: what a test reads is ONE 16-byte
 //                                                 load (r only ever enters as r*r, trace.h:262,270; the host squares it
 //                                                 in fp32 like the reference does)
+// A sphere set whose lists outgrow LDS takes the lists' GLOBAL form (below, PWN_LF_GLOBAL): LDS ends with a u32 per non-empty
+// cell at PWN_T_BINIDX; records, "which sphere" and spheres lie in a device-memory buffer of their own.
 #pragma once
 #include <stdint.h>
 #include "cell_bake.h"
@@ -83,6 +85,21 @@ static inline uint32_t pwn_t_total(uint32_t nbin, uint32_t nsph)
 static inline uint32_t pwn_t_recsph_offset(uint32_t nrec) { return PWN_T_BINIDX + nrec * 16u; }
 static inline uint32_t pwn_t_sph_offset_inl(uint32_t nrec) { return pwn_t_recsph_offset(nrec) + ((nrec * 2u + 15u) & ~15u); }
 static inline uint32_t pwn_t_total_inl(uint32_t nrec, uint32_t nsph) { return pwn_t_sph_offset_inl(nrec) + nsph * 32u; }
+
+// The per-cell lists in DEVICE MEMORY (sphere sets whose lists outgrow LDS, up to PWN_OBJ_MAX spheres: pwn_tables_plan, pwn_api.cpp).
+// LDS holds the blob up to and including eprec and, at PWN_T_BINIDX, `liststart`: one u32 per NON-EMPTY cell, the index of that
+// cell's first record.  The cell word keeps PWN_C_SPH; its bits 16..30 hold the non-empty cell's ordinal (at most 4096 cells,
+// however many records there are).  A buffer apart from the blob, in 16-byte aligned sections, nothing in it 16-bit:
+//   nrec + 1 records of 16 bytes, exactly the inline form's (x, y, z, r*r; the sign of r*r set on a cell's last record) -- the one
+//            more is what the walk's read-ahead behind the very last record lands on;
+//   nrec u32 "which sphere": the sphere's INDEX, read when a hit is shaded or recorded (pwn_hit.object is it);
+//   nsph spheres of 32 bytes, as in the blob.
+// The units kernel only (trace_kernel.hip, its LISTS parameter); a test is one 16-byte global load, the next record requested first.
+enum { PWN_LF_INDEXED = 0, PWN_LF_INLINE = 1, PWN_LF_GLOBAL = 2 };
+static inline uint32_t pwn_t_total_glb(uint32_t ncell) { return PWN_T_BINIDX + ((ncell * 4u + 15u) & ~15u); }
+static inline uint64_t pwn_g_which_offset(uint64_t nrec) { return (nrec + 1u) * 16u; }
+static inline uint64_t pwn_g_sph_offset(uint64_t nrec) { return pwn_g_which_offset(nrec) + ((nrec * 4u + 15u) & ~(uint64_t)15u); }
+static inline uint64_t pwn_g_total(uint64_t nrec, uint64_t nsph) { return pwn_g_sph_offset(nrec) + nsph * 32u; }
 
 // glibc 2.35 e_expf.c / exp2f_data: 2^(i/32) as double bit patterns with the exponent adjusted (N = 32)
 #define PWN_EXP2F_TAB_INIT { \
@@ -184,6 +201,11 @@ struct pwn_trace_params
 	// First-hit records of a batch of rays (pwn_trace_hits): NULL, or nrays records of PWN_HIT_REC_BYTES (pwn_hit of pwnhip.h; 16-byte
 	// aligned) that ray i's primary segment is written to.  Then sbuf, zbuf, ray_seeds and sec_current are not read.
 	void *hits;
+	// The lists' global form (above): NULL, or the three sections of the device-memory part of the tables.  Then blob_bytes is the LDS
+	// part alone, and off_sph / off_recsph are not read.
+	const float *g_rec;
+	const uint32_t *g_which;
+	const float *g_sph;
 };
 #define PWN_HIT_REC_BYTES 48u
 

@@ -53,6 +53,11 @@ struct Lds
 	const PWN_LDS float *sph;
 	const PWN_LDS uint64_t *exp2;         // tables.h PWN_T_EXP2
 	const PWN_LDS pwn_f4 *faces;           // tables.h PWN_T_FACES: [0..4) wall colours, [4 + 2 * face ..] face constants
+	// the lists' global form (tables.h PWN_LF_GLOBAL; lds_tables_global): binidx is then `liststart`, u32 per non-empty cell, and
+	// these three are the device-memory sections -- records, which sphere (an index), spheres.  Not set otherwise.
+	const pwn_f4 *g_rec;
+	const uint32_t *g_which;
+	const pwn_f4 *g_sph;
 };
 __device__ __forceinline__ Lds lds_tables(uint32_t off_sph, uint32_t off_recsph = 0u)
 {
@@ -66,6 +71,13 @@ __device__ __forceinline__ Lds lds_tables(uint32_t off_sph, uint32_t off_recsph 
 	L.exp2 = lds_at<uint64_t>(PWN_T_EXP2);
 	L.sph = lds_at<float>(off_sph);
 	L.recsph = lds_at<uint16_t>(off_recsph);
+	L.g_rec = nullptr; L.g_which = nullptr; L.g_sph = nullptr;
+	return L;
+}
+__device__ __forceinline__ Lds lds_tables_global(const pwn_trace_params &P)
+{
+	Lds L = lds_tables(0u);
+	L.g_rec = (const pwn_f4 *)P.g_rec; L.g_which = P.g_which; L.g_sph = (const pwn_f4 *)P.g_sph;
 	return L;
 }
 

@@ -30,7 +30,7 @@
 
 
 // One pixel = trace_ray(0, ...) of screen.h:22-24 with the recursion unrolled.
-template<bool COUNT, bool HAS_W, bool INL>
+template<bool COUNT, bool HAS_W, int LISTS>
 __device__ __forceinline__ void trace_pixel(const Lds &L, float sec_current, uint32_t seed,
 	Vec<HAS_W> from, Vec<HAS_W> iray, float &out_x, float &out_y, float &out_z, float &out_w,
 	float *zpix, Counters &cnt)
@@ -182,7 +182,7 @@ __device__ __forceinline__ void trace_pixel(const Lds &L, float sec_current, uin
 //   word 4..7    dist (what the frame writes to zbuf), x, y, z (pos, or the sphere candidate's aux_pos)
 //   word 8..11   the walked ray x, y, z;  cell x | cell z << 16 (hit_cxz as the walk packs it: two int16)
 // No shading, bounce, jitter or composite, no composite stack, no random number, no sec_current.
-template<bool COUNT, bool HAS_W, bool INL>
+template<bool COUNT, bool HAS_W, int LISTS>
 __device__ __forceinline__ void trace_hit(const Lds &L, Vec<HAS_W> from, Vec<HAS_W> iray, uint4 *out, Counters &cnt)
 {
 	typedef Vec<HAS_W> V;
@@ -239,8 +239,9 @@ __device__ __forceinline__ void trace_hit(const Lds &L, Vec<HAS_W> from, Vec<HAS
 		{
 			// which sphere: its byte offset in the blob's sphere array (32 bytes a sphere, in the order of the live table) is what an
 			// indexed list holds per entry; an inline record's comes from the "which sphere" array, as trace_shade.inc looks it up
-			if constexpr(INL) aux_idx = L.recsph[(aux_idx - PWN_T_BINIDX) >> 4];
-			object = (int)(aux_idx >> 5);
+			// (the global form's record index leads to the sphere's index itself, in device memory: tables.h)
+			if constexpr(LISTS == PWN_LF_INLINE) aux_idx = L.recsph[(aux_idx - PWN_T_BINIDX) >> 4];
+			object = LISTS == PWN_LF_GLOBAL ? (int)L.g_which[aux_idx] : (int)(aux_idx >> 5);
 			ldir = -1;
 			dist = aux_dist;
 			at = aux_pos;
@@ -283,7 +284,9 @@ template<bool HAS_W> __device__ __forceinline__ void chain_rounds(Vec<HAS_W> &v,
 // PWN_KM_RAYS: P.nrays rays of the caller's (pwn_trace_rays): every lane loads its own origin, direction and seed.  PWN_KM_HITS: the
 // same batch of rays (pwn_trace_hits), of which every lane traces the primary segment only and writes a first-hit record
 // (trace_hit) instead of a colour and a depth.  The last three are instantiated with ORDER = false only.
-template<bool COUNT, bool HAS_W, bool ORDER, bool INL, int MODE>
+// LISTS (tables.h PWN_LF_*): the form of the per-cell sphere lists -- indexed or inline records in LDS, or, for sphere sets whose
+// lists outgrow LDS, records in device memory (PWN_LF_GLOBAL: instantiated with ORDER = false only).
+template<bool COUNT, bool HAS_W, bool ORDER, int LISTS, int MODE>
 __global__ void __launch_bounds__(PWN_BLOCK, PWN_MIN_WAVES)
 pwn_trace_kernel(pwn_trace_params P)
 {
@@ -298,7 +301,7 @@ pwn_trace_kernel(pwn_trace_params P)
 
 	// (the tables are addressed from LDS address 0 on, trace_common.h; the launcher checks that this kernel has
 	// no static LDS in front of the dynamic allocation)
-	const Lds L = lds_tables(P.off_sph, P.off_recsph);
+	const Lds L = LISTS == PWN_LF_GLOBAL ? lds_tables_global(P) : lds_tables(P.off_sph, P.off_recsph);
 
 	typedef Vec<HAS_W> V;
 	V rayb, rdx, rdy, from;
@@ -464,14 +467,16 @@ pwn_trace_kernel(pwn_trace_params P)
 					// First-hit records (pwn_trace_hits): the same lane, the same record, the same argument as above for every LDS address --
 					// trace_hit runs trace_pixel's set-up and walk texts and reads one more table, the inline lists' "which sphere" array,
 					// at the index trace_shade.inc reads it at (aux_idx is a list record's LDS address, written by the walk from the cell
-					// word's list offset; never the ray's).  Global: hits + 48 i for i < nrays <= 2^28 in 64-bit arithmetic lies in the
+					// word's list offset; never the ray's; in the lists' global form a record's index in device memory, which the walk counts up
+					// from the cell's liststart entry to the record with the end mark: inside the nrec records the host packed).
+					// Global: hits + 48 i for i < nrays <= 2^28 in 64-bit arithmetic lies in the
 					// caller's array of n records; a lane with i >= nrays stores nothing.  No seed, colour or depth is touched.
-					trace_hit<COUNT, HAS_W, INL>(L, org, dir, (uint4 *)((unsigned char *)P.hits + (size_t)i * PWN_HIT_REC_BYTES), cnt);
+					trace_hit<COUNT, HAS_W, LISTS>(L, org, dir, (uint4 *)((unsigned char *)P.hits + (size_t)i * PWN_HIT_REC_BYTES), cnt);
 				}
 				else
 				{
 					float ox, oy, oz, ow;
-					trace_pixel<COUNT, HAS_W, INL>(L, sec_current, seed, org, dir, ox, oy, oz, ow, P.zbuf + i, cnt);
+					trace_pixel<COUNT, HAS_W, LISTS>(L, sec_current, seed, org, dir, ox, oy, oz, ow, P.zbuf + i, cnt);
 					P.sbuf[i] = col_pack4(ox, oy, oz, ow);
 				}
 			}
@@ -578,7 +583,7 @@ pwn_trace_kernel(pwn_trace_params P)
 			const uint32_t seed = pixel_seed(x, y, P.w);
 			float ox, oy, oz, ow;
 			const uint32_t o = __umul24((uint32_t)y, (uint32_t)P.w) + (uint32_t)x;      // w, h <= 32768 (pwn_init)
-			trace_pixel<COUNT, HAS_W, INL>(L, sec_current, seed, from, rayl, ox, oy, oz, ow, zbuf + o, cnt);
+			trace_pixel<COUNT, HAS_W, LISTS>(L, sec_current, seed, from, rayl, ox, oy, oz, ow, zbuf + o, cnt);
 			sbuf[o] = col_pack4(ox, oy, oz, ow);
 		}
 		// what this unit cost its wave (the add chain and the ticket arithmetic in front of it are the same for every unit)
@@ -638,22 +643,32 @@ pwn_trace_kernel(pwn_trace_params P)
 	}
 }
 
-// (ORDER, INL, MODE) -> the four kernels a launch's count and has_w pick from (trace_common.h)
-template<bool ORDER, bool INL, int MODE>
-using Units = TraceKernels<pwn_trace_kernel<true, true, ORDER, INL, MODE>, pwn_trace_kernel<true, false, ORDER, INL, MODE>,
-	pwn_trace_kernel<false, true, ORDER, INL, MODE>, pwn_trace_kernel<false, false, ORDER, INL, MODE>>;
+// (ORDER, LISTS, MODE) -> the four kernels a launch's count and has_w pick from (trace_common.h)
+template<bool ORDER, int LISTS, int MODE>
+using Units = TraceKernels<pwn_trace_kernel<true, true, ORDER, LISTS, MODE>, pwn_trace_kernel<true, false, ORDER, LISTS, MODE>,
+	pwn_trace_kernel<false, true, ORDER, LISTS, MODE>, pwn_trace_kernel<false, false, ORDER, LISTS, MODE>>;
 
 extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
 {
 	// (the blob says which form its per-cell lists have: pack_blob, pwn_api.cpp)
+	// The global form: sixteen variants, MODE x COUNT x HAS_W, never ordered (pwn_i_launch_trace hands such a launch neither an
+	// order nor a cost array).
+	if(P->g_rec != NULL)
+	{
+		if(P->hits != NULL) return Units<false, PWN_LF_GLOBAL, PWN_KM_HITS>::launch(P, grid, lds_bytes, count, stream);
+		if(P->rays != NULL) return Units<false, PWN_LF_GLOBAL, PWN_KM_RAYS>::launch(P, grid, lds_bytes, count, stream);
+		if(P->views != NULL) return Units<false, PWN_LF_GLOBAL, PWN_KM_VIEWS>::launch(P, grid, lds_bytes, count, stream);
+		if(P->perm != NULL || P->unit_cost != NULL) return hipErrorInvalidValue;
+		return Units<false, PWN_LF_GLOBAL, PWN_KM_FRAME>::launch(P, grid, lds_bytes, count, stream);
+	}
 	const bool inl = P->off_recsph != 0u;
 	// a batch of rays (pwn_trace_rays), of their first hits (pwn_trace_hits) or of views (pwn_trace_views): eight variants each, never ordered
-	if(P->hits != NULL) return inl ? Units<false, true, PWN_KM_HITS>::launch(P, grid, lds_bytes, count, stream) : Units<false, false, PWN_KM_HITS>::launch(P, grid, lds_bytes, count, stream);
-	if(P->rays != NULL) return inl ? Units<false, true, PWN_KM_RAYS>::launch(P, grid, lds_bytes, count, stream) : Units<false, false, PWN_KM_RAYS>::launch(P, grid, lds_bytes, count, stream);
-	if(P->views != NULL) return inl ? Units<false, true, PWN_KM_VIEWS>::launch(P, grid, lds_bytes, count, stream) : Units<false, false, PWN_KM_VIEWS>::launch(P, grid, lds_bytes, count, stream);
+	if(P->hits != NULL) return inl ? Units<false, PWN_LF_INLINE, PWN_KM_HITS>::launch(P, grid, lds_bytes, count, stream) : Units<false, PWN_LF_INDEXED, PWN_KM_HITS>::launch(P, grid, lds_bytes, count, stream);
+	if(P->rays != NULL) return inl ? Units<false, PWN_LF_INLINE, PWN_KM_RAYS>::launch(P, grid, lds_bytes, count, stream) : Units<false, PWN_LF_INDEXED, PWN_KM_RAYS>::launch(P, grid, lds_bytes, count, stream);
+	if(P->views != NULL) return inl ? Units<false, PWN_LF_INLINE, PWN_KM_VIEWS>::launch(P, grid, lds_bytes, count, stream) : Units<false, PWN_LF_INDEXED, PWN_KM_VIEWS>::launch(P, grid, lds_bytes, count, stream);
 	const bool order = P->perm != NULL || P->unit_cost != NULL;
-	if(inl) return order ? Units<true, true, PWN_KM_FRAME>::launch(P, grid, lds_bytes, count, stream) : Units<false, true, PWN_KM_FRAME>::launch(P, grid, lds_bytes, count, stream);
-	return order ? Units<true, false, PWN_KM_FRAME>::launch(P, grid, lds_bytes, count, stream) : Units<false, false, PWN_KM_FRAME>::launch(P, grid, lds_bytes, count, stream);
+	if(inl) return order ? Units<true, PWN_LF_INLINE, PWN_KM_FRAME>::launch(P, grid, lds_bytes, count, stream) : Units<false, PWN_LF_INLINE, PWN_KM_FRAME>::launch(P, grid, lds_bytes, count, stream);
+	return order ? Units<true, PWN_LF_INDEXED, PWN_KM_FRAME>::launch(P, grid, lds_bytes, count, stream) : Units<false, PWN_LF_INDEXED, PWN_KM_FRAME>::launch(P, grid, lds_bytes, count, stream);
 }
 
 extern "C" int pwn_trace_tile_h(void) { return TILE_H; }
@@ -667,5 +682,10 @@ extern "C" unsigned pwn_trace_lds_extra(void)
 // resident 256-thread workgroups per CU for this variant and LDS size
 extern "C" int pwn_trace_blocks_per_cu(size_t lds_bytes, bool count, bool has_w)
 {
-	return Units<false, false, PWN_KM_FRAME>::blocks_per_cu(lds_bytes, count, has_w);
+	return Units<false, PWN_LF_INDEXED, PWN_KM_FRAME>::blocks_per_cu(lds_bytes, count, has_w);
+}
+// ... for the variants that read the lists from device memory
+extern "C" int pwn_trace_global_blocks_per_cu(size_t lds_bytes, bool count, bool has_w)
+{
+	return Units<false, PWN_LF_GLOBAL, PWN_KM_FRAME>::blocks_per_cu(lds_bytes, count, has_w);
 }

@@ -2,7 +2,7 @@
 // (trace.h:108-154 and the axis-aligned mirrors of trace.h:50-75) or the committed sphere (trace.h:283-291).
 // Textually included by both trace kernels behind their walk, for the lanes whose segment ended on a surface.
 // Names it uses from the including scope:
-//   L (Lds), COUNT, HAS_W, INL, V, cnt;  ev (EV_WALL, else the sphere), base, ray;  the colour the segment is lit with:
+//   L (Lds), COUNT, HAS_W, LISTS (tables.h PWN_LF_*), V, cnt;  ev (EV_WALL, else the sphere), base, ray;  the colour the segment is lit with:
 //   icx, icy, icz;  the sphere candidate: aux_idx, aux_pos, aux_diff.
 // Names it writes:
 //   colx, coly, colz (the segment's colour), refl (the surface's reflectivity), w_acc;  pos (moved off the surface);
@@ -41,9 +41,19 @@ else
 	RG(RG_SPHERE);
 	// trace.h:283-291 for the committed sphere
 	// (inline records: aux_idx is the record's LDS address; which sphere it is of -- a byte offset -- is looked up here, once per hit)
-	if constexpr(INL) aux_idx = L.recsph[(aux_idx - PWN_T_BINIDX) >> 4];
-	const PWN_LDS pwn_f4 *sp = (const PWN_LDS pwn_f4 *)((const PWN_LDS unsigned char *)L.sph + aux_idx);      // (a byte offset)
-	const pwn_f4 s0 = sp[0], s1 = sp[1];
+	// (the global form: aux_idx is the record's index; which sphere -- an index -- and the sphere itself come from device memory)
+	pwn_f4 s0, s1;
+	if constexpr(LISTS == PWN_LF_GLOBAL)
+	{
+		const pwn_f4 *sp = L.g_sph + 2u * (size_t)L.g_which[aux_idx];
+		s0 = sp[0]; s1 = sp[1];
+	}
+	else
+	{
+		if constexpr(LISTS == PWN_LF_INLINE) aux_idx = L.recsph[(aux_idx - PWN_T_BINIDX) >> 4];
+		const PWN_LDS pwn_f4 *sp = (const PWN_LDS pwn_f4 *)((const PWN_LDS unsigned char *)L.sph + aux_idx);      // (a byte offset)
+		s0 = sp[0]; s1 = sp[1];
+	}
 	V d;
 	d.x = aux_pos.x - s0.x; d.y = aux_pos.y - s0.y; d.z = aux_pos.z - s0.z;
 	if constexpr(HAS_W) d.w = aux_pos.w - 1.0f; else d.w = 0.0f;

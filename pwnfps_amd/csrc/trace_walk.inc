@@ -1,6 +1,6 @@
 // trace_walk.inc -- ONE cell step of the walk (trace.h:250-675), textually included by both
 // trace kernels inside their walk loop.  Names it uses from the including scope:
-//   L (Lds), COUNT, HAS_W, INL (the per-cell lists hold inline sphere records: tables.h), V, cnt;  the ray: pos, ray, cxz (cell x | z << 16), sx, sz (the steps (gx, 0) and
+//   L (Lds), COUNT, HAS_W, LISTS (the form of the per-cell lists, PWN_LF_*: tables.h), V, cnt;  the ray: pos, ray, cxz (cell x | z << 16), sx, sz (the steps (gx, 0) and
 //   (0, gz) in the same packing: trace_common.h), ldx, ldz, ldy, gyp,
 //   wx, wy, wz, iax, iay, iaz, iay_dn, iay_up_bits, cw, cdist, fog, ldir, ev, base, maxsteps;
 //   the nearest sphere candidate: aux_dist, aux_diff, aux_idx, aux_pos;
@@ -41,7 +41,34 @@ if((int)cw < 0)
 {
 	//@R w_sphlist
 	WAVE_PATH(0);
-	if constexpr(INL)
+	if constexpr(LISTS == PWN_LF_GLOBAL)
+	{
+		// The records in device memory (tables.h): as the inline arm below, with one 16-byte GLOBAL load per test where that makes an
+		// LDS read.  The cell word names the non-empty cell, liststart (one LDS read per list) the index of its first record;
+		// aux_idx = the record's index.  The next record is asked for before this one is tested (behind the very last record lies
+		// one more that the host packed for this read).  Plain, cached loads: no copy of the tables is written while a launch
+		// reads it (pwn_api.cpp).  Every index here comes out of the tables the host packed -- the cell word, liststart, the end
+		// mark of a list -- and none out of a ray: no input bit pattern reaches an address (as argued at the ray modes' loads,
+		// trace_kernel.hip).
+		uint32_t ri = ((const PWN_LDS uint32_t *)L.binidx)[(cw >> 16) & 0x7fffu];
+		pwn_f4 nx = L.g_rec[(size_t)ri];
+		for(;;)
+		{
+			//@R w_sphtest
+			RG(RG_SPHTEST);
+			const pwn_f4 s0 = nx;
+			const uint32_t wb = __float_as_uint(s0.w);
+			nx = L.g_rec[(size_t)ri + 1u];
+#define PWN_ST_RAD2 __uint_as_float(wb & 0x7fffffffu)
+#define PWN_ST_WHICH ri
+#include "trace_sphere.inc"
+#undef PWN_ST_RAD2
+#undef PWN_ST_WHICH
+			if((int)wb < 0) break;
+			ri++;
+		}
+	}
+	else if constexpr(LISTS == PWN_LF_INLINE)
 	{
 		// inline records (tables.h): one 16-byte read per test; the last record of the cell's list carries the sign bit in r*r.
 		// aux_idx = the record's LDS address (which sphere: looked up when shaded).  The NEXT record is asked for before this one

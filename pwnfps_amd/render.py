@@ -221,6 +221,12 @@ class Renderer:
         self._chk(lib.pwn_get_bins(self._ctx, counts.ctypes.data, idx.ctypes.data, n), "pwn_get_bins")
         return counts, idx[:n]
 
+    def sphere_tables(self):
+        """pwn_sphere_tables_state: form, size and shape of the sphere tables in force (see sphere_tables_plan)"""
+        out = (C.c_uint64 * 6)()
+        self._chk(lib.pwn_sphere_tables_state(self._ctx, out), "pwn_sphere_tables_state")
+        return _tables_dict(out)
+
     # -- frame (screen.h:31-124) ---------------------------------------------
     def trace_screen_centred(self, cam, sec_current=0.0, want_z=True, sbuf=None, zbuf=None):
         cam = np.ascontiguousarray(cam, np.float32).reshape(16)
@@ -575,6 +581,24 @@ class Renderer:
         out = np.zeros(n, np.uint32)
         self._chk(lib.pwn_probe(self._ctx, int(op), words.ctypes.data, out.ctypes.data, n), "pwn_probe")
         return out
+
+
+def _tables_dict(out):
+    return {"form": int(out[0]), "lds_bytes": int(out[1]), "device_bytes": int(out[2]), "pairs": int(out[3]),
+            "cells": int(out[4]), "longest": int(out[5])}
+
+
+def sphere_tables_plan(spheres):
+    """pwn_sphere_tables_plan: what an upload of these spheres would do -- the form of the per-cell lists (0 indexed, 1 inline,
+    2 in device memory), LDS bytes per workgroup, bytes in device memory, (cell, sphere) pairs, non-empty cells, the longest
+    list.  No context, no device.  Raises PwnError(PWN_ETOOBIG) for tables that no form holds."""
+    spheres = np.ascontiguousarray(spheres, SPHERE_DTYPE)
+    out = (C.c_uint64 * 6)()
+    buf = spheres if len(spheres) else np.zeros(1, SPHERE_DTYPE)
+    rc = lib.pwn_sphere_tables_plan(buf.ctypes.data, len(spheres), out)
+    if rc < 0:
+        raise PwnError(rc, "pwn_sphere_tables_plan")
+    return _tables_dict(out)
 
 
 def _ray_records(rays, who):
