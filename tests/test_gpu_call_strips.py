@@ -202,10 +202,11 @@ def test_strips_mixed_with_frames_in_flight(oracle_lib, cases):
     r.close()
 
 
-@pytest.mark.parametrize("lists", ["indexed", "inline"])
-def test_both_forms_of_the_sphere_lists_give_the_goldens(oracle_lib, cases, monkeypatch, lists):
-    """the per-cell sphere lists (trace.h:252-296) as u16 indices into the sphere array or with the sphere records inline (tables.h, round 5):
-    chosen by the size of the tables, here forced each way -- every level, both lane forms, counters included"""
+@pytest.mark.parametrize("lists", ["indexed", "inline", "global"])
+def test_every_form_of_the_sphere_lists_gives_the_goldens(oracle_lib, cases, monkeypatch, lists):
+    """the per-cell sphere lists (trace.h:252-296) as u16 indices into the sphere array, with the sphere records inline (tables.h, round 5)
+    or with the records in device memory (tables.h PWN_LF_GLOBAL): chosen by the size of the tables, here forced each way -- every level,
+    both lane forms, counters included"""
     monkeypatch.setenv("PWN_SPHERE_LISTS", lists)
     names = ("level_spawn_1280x720", "level_pose1_1280x720", "synth64_cam1_1920x1080", "synth256_cam1_480x272", "level_spawn_320x200", "level_spawn_nosph_320x240")
     for hasw in (False, True):
@@ -225,6 +226,7 @@ def test_both_forms_of_the_sphere_lists_give_the_goldens(oracle_lib, cases, monk
             post2, _ = r.trace_screen_centred(cam, c["sec"])
             assert (post2 == post).all()
             # the other scheduler reads indexed lists: the tables are packed again behind the option
+            # (tables in device memory stay there, and the units kernel runs whatever the option says: pwn_i_launch_trace)
             r.set_scheduler("refill")
             post3, _ = r.trace_screen_centred(cam, c["sec"])
             assert (post3 == post).all(), (lists, hasw, name)

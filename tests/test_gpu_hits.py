@@ -1,7 +1,8 @@
 """pwn_trace_hits: first-hit records of caller-supplied rays.  A record is the state of trace_ray's primary walk (trace.h:186) at
 its return; the reference is the oracle's event chain of the same ray, read by tests/hit_chain.py (pinned on the oracle alone in
 tests/test_hits_oracle.py), and the oracle's depth plane for `kind` and `dist` of whole frames.  Every check runs the kernel
-variants a context can pick: 3-lane and 4-lane (PWN_DBG_FORCE_HASW), inline and indexed sphere lists (PWN_SPHERE_LISTS).
+variants a context can pick: 3-lane and 4-lane (PWN_DBG_FORCE_HASW), and the sphere lists inline, indexed or in device memory
+(PWN_SPHERE_LISTS; global: tables.h PWN_LF_GLOBAL, forced on scenes that would fit on chip).
 """
 import contextlib
 import os
@@ -20,7 +21,8 @@ SCENES = HS.scenes(SPHERE_DTYPE)
 IDS = [s.name for s in SCENES]
 PWN_EINVAL, PWN_ENOLEVEL, PWN_EBUSY, PWN_ENOTSUP = -1, -6, -8, -9
 VARIANTS = {"plain": {}, "force_hasw": {"PWN_DBG_FORCE_HASW": "1"}, "inline": {"PWN_SPHERE_LISTS": "inline"},
-            "indexed": {"PWN_SPHERE_LISTS": "indexed"}}
+            "indexed": {"PWN_SPHERE_LISTS": "indexed"}, "global": {"PWN_SPHERE_LISTS": "global"}}
+ON_CHIP = ("plain", "force_hasw", "inline", "indexed")
 SENTINEL = np.uint32(0x7fc12345)          # a NaN pattern no computation makes
 
 
@@ -57,6 +59,12 @@ def _bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
+def _form_is_forced(r, variant, what):
+    """global: the context really holds its tables in device memory (a misspelt variable would leave them on chip)"""
+    if variant == "global":
+        assert r.sphere_tables()["form"] == 2, (what, r.sphere_tables())
+
+
 def _report(got, want, bad, rays=None):
     return [(int(i), got[i].tolist(), want[i].tolist(), None if rays is None else rays[i].tolist()) for i in bad[:3]]
 
@@ -84,6 +92,7 @@ def test_hard_scene_depths(oracle_lib, sc, variant):
     zb = _depth_plane(oracle_lib, sc)
     r = _renderer(variant)
     HS.load_renderer(r, sc)
+    _form_is_forced(r, variant, sc.name)
     rays, _, xy = pwnfps_amd.pixel_rays(sc.w, sc.h, sc.cam)
     hits = r.trace_hits(rays)
     r.close()
@@ -97,26 +106,45 @@ def test_hard_scene_depths(oracle_lib, sc, variant):
 
 # ---------------------------------------------------------------- 2. every field against the reader ----
 
-@pytest.mark.parametrize("sc", SCENES, ids=IDS)
-def test_hard_scene_records(oracle_lib, sc):
-    """512 seeded pixels and the four corners of each hard scene (all pixels of a smaller one): every field, every variant"""
+_record_refs = {}
+
+
+def _record_ref(oracle_lib, sc):
+    """(the pixels, their rays, what hit_chain.Reader reads off the oracle with marked spheres): computed once per scene, shared"""
     import pwnfps_amd
+    if sc.name not in _record_refs:
+        O = oracle_lib.Oracle()
+        HS.load_oracle(O, sc._replace(spheres=HC.mark_spheres(sc.spheres)))
+        n = sc.w * sc.h
+        if n <= 516:
+            xy = HC.all_pixels(sc.w, sc.h)
+        else:
+            rng = np.random.default_rng(1000 + len(sc.name))
+            pick = rng.choice(n, 512, replace=False)
+            xy = np.stack([pick % sc.w, pick // sc.w], 1).astype(np.int32)
+            xy = np.concatenate([xy, np.array([[0, 0], [sc.w - 1, 0], [0, sc.h - 1], [sc.w - 1, sc.h - 1]], np.int32)])
+        ref = HC.Reader(O).pixels(sc.w, sc.h, sc.cam, xy)
+        rays, _, _ = pwnfps_amd.pixel_rays(sc.w, sc.h, sc.cam, xy)
+        _record_refs[sc.name] = (xy, rays, ref)
+    return _record_refs[sc.name]
+
+
+# (the case without a suffix is the one this test has always had: the contexts whose tables lie on chip)
+RECORD_CASES = [pytest.param(sc, lists, id=sc.name if lists == "plain" else sc.name + "-" + lists)
+                for sc in SCENES for lists in ("plain", "global")]
+
+
+@pytest.mark.parametrize("sc,lists", RECORD_CASES)
+def test_hard_scene_records(oracle_lib, sc, lists):
+    """512 seeded pixels and the four corners of each hard scene (all pixels of a smaller one): every field of every record
+    against hit_chain.Reader.  plain: the four variants of a context with the lists on chip; global: the lists in device
+    memory (`object` then comes out of the device buffer's which[])"""
     marked = sc._replace(spheres=HC.mark_spheres(sc.spheres))
-    O = oracle_lib.Oracle()
-    HS.load_oracle(O, marked)
-    n = sc.w * sc.h
-    if n <= 516:
-        xy = HC.all_pixels(sc.w, sc.h)
-    else:
-        rng = np.random.default_rng(1000 + len(sc.name))
-        pick = rng.choice(n, 512, replace=False)
-        xy = np.stack([pick % sc.w, pick // sc.w], 1).astype(np.int32)
-        xy = np.concatenate([xy, np.array([[0, 0], [sc.w - 1, 0], [0, sc.h - 1], [sc.w - 1, sc.h - 1]], np.int32)])
-    ref = HC.Reader(O).pixels(sc.w, sc.h, sc.cam, xy)
-    rays, _, _ = pwnfps_amd.pixel_rays(sc.w, sc.h, sc.cam, xy)
-    for variant in VARIANTS:
+    xy, rays, ref = _record_ref(oracle_lib, sc)
+    for variant in (ON_CHIP if lists == "plain" else ("global",)):
         r = _renderer(variant)
         HS.load_renderer(r, marked)
+        _form_is_forced(r, variant, sc.name)
         hits = r.trace_hits(rays)
         r.close()
         bad = HC.mismatches(hits, ref.want, ref.cmp_dy)
@@ -197,7 +225,8 @@ def test_loop_corridor(oracle_lib):
 @pytest.mark.parametrize("w_lanes", [False, True], ids=["w01", "w_lanes"])
 def test_hostile_records(variant, w_lanes):
     """NaN, +-inf, 1e30, zero directions, origins at +-16384 and beyond: kind and dist are what pwn_trace_rays leaves in a
-    sentinel-filled depth array for the same rays and variant"""
+    sentinel-filled depth array for the same rays and variant.  global: the walk reads its sphere records from device memory at
+    indices that come out of the packed tables alone (trace_walk.inc), so these rays end as cleanly as on the other four"""
     from test_gpu_rays import _hostile_rays
     rng = np.random.default_rng(5150 + w_lanes)
     n = 512
@@ -208,6 +237,7 @@ def test_hostile_records(variant, w_lanes):
         rec[8 * k + 7 + 80, 2] = v
         rec[8 * k + 7 + 80, 0] = -v
     r = _level_renderer(variant)
+    _form_is_forced(r, variant, w_lanes)
     zin = np.full(n, SENTINEL, np.uint32).view(np.float32)
     _, z = r.trace_rays(rec, None, 0.0, depth=zin)
     hits = r.trace_hits(rec)

@@ -94,19 +94,22 @@ def test_golden_frames_as_rays(oracle_lib, cases, order, force_hasw):
 
 # ---------------------------------------------------------------- hard scenes ----
 
-@pytest.mark.parametrize("variant", ["plain", "force_hasw", "inline", "indexed"])
+@pytest.mark.parametrize("variant", ["plain", "force_hasw", "inline", "indexed", "global"])
 @pytest.mark.parametrize("sc", SCENES, ids=IDS)
 def test_hard_scenes_as_rays(oracle_lib, sc, variant):
     """all 42 hard scenes: every pixel's ray against the oracle's pre-blur frame, colour, depth and counters, carrying the
-    depth of a first frame into a second (rays that run out of steps keep it)"""
+    depth of a first frame into a second (rays that run out of steps keep it); global: the sphere lists in device memory
+    (tables.h PWN_LF_GLOBAL), forced on these small scenes"""
     import pwnfps_amd
     env = {"plain": {}, "force_hasw": {"PWN_DBG_FORCE_HASW": "1"}, "inline": {"PWN_SPHERE_LISTS": "inline"},
-           "indexed": {"PWN_SPHERE_LISTS": "indexed"}}[variant]
+           "indexed": {"PWN_SPHERE_LISTS": "indexed"}, "global": {"PWN_SPHERE_LISTS": "global"}}[variant]
     O = HS.oracle(oracle_lib, sc)
     plane = HS.Plane(O, sc.w, sc.h)
     with _env(**env):
         r = pwnfps_amd.Renderer(8, 8)
     HS.load_renderer(r, sc)
+    if variant == "global":
+        assert r.sphere_tables()["form"] == 2, (sc.name, r.sphere_tables())
     r.set_counters(True)
     for k, (cam, sec) in enumerate(((sc.cam, sc.sec), (pwnfps_amd.mat4_roty(sc.cam, 0.4), sc.sec + 0.5))):
         rays, seeds, xy = pwnfps_amd.pixel_rays(sc.w, sc.h, cam, order="units" if k else "rows")

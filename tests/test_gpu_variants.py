@@ -1,8 +1,8 @@
 """Every shipped kernel variant and call path on the hard scenes (tests/hard_scenes.py) and on hostile depths.
 
 The default blocking call already runs the hard scenes (test_gpu_parity.py, test_nonfinite.py).  Here the same scenes go
-through the other compiled variants of the trace kernel (COUNT, HAS_W, both sphere-list forms, ORDER with a sorted hand-out,
-VIEWS) and of the blur (the 32x32 tile, the CHECK forms of row strips and groups, the VIEWS tiles), and through the other
+through the other compiled variants of the trace kernel (COUNT, HAS_W, all three sphere-list forms -- indexed, inline, and the
+records in device memory --, ORDER with a sorted hand-out, VIEWS) and of the blur (the 32x32 tile, the CHECK forms of row strips and groups, the VIEWS tiles), and through the other
 entry points: pwn_trace_views, forced call strips, frames in flight on two streams, a three-member group, the refill
 scheduler.  Colour and depth are compared bit for bit with the oracle, counters where they are on; a path that cannot take a
 scene must refuse it with its documented error.
@@ -155,17 +155,22 @@ def test_blocking_call_variants(sc, oracle_lib):
     r.close()
 
 
-@pytest.mark.parametrize("variant", ["force_hasw", "indexed", "inline"])
+@pytest.mark.parametrize("variant", ["force_hasw", "indexed", "inline", "global"])
 @pytest.mark.parametrize("sc", SCENES, ids=IDS)
 def test_context_variants(sc, variant, oracle_lib):
     """Variants chosen when the context is created: HAS_W forced (PWN_DBG_FORCE_HASW), and each sphere-list form
-    (PWN_SPHERE_LISTS, the INL template parameter): the blocking call with and without counters, the 32x32 tile, a batch
-    of views."""
+    (PWN_SPHERE_LISTS, the LISTS template parameter; global: the records in device memory, tables.h PWN_LF_GLOBAL, which
+    every scene plans when forced, one whose spheres bin into no cell too): the blocking call with and without counters,
+    the 32x32 tile, a batch of views."""
     env = {"force_hasw": {"PWN_DBG_FORCE_HASW": "1"}, "indexed": {"PWN_SPHERE_LISTS": "indexed"},
-           "inline": {"PWN_SPHERE_LISTS": "inline"}}[variant]
+           "inline": {"PWN_SPHERE_LISTS": "inline"}, "global": {"PWN_SPHERE_LISTS": "global"}}[variant]
     O = HS.oracle(oracle_lib, sc)
     plane = HS.Plane(O, sc.w, sc.h)
     r = _ctx(sc, env=env)
+    if variant == "global":
+        assert r.sphere_tables()["form"] == 2, (sc.name, r.sphere_tables())
+        if not sc.blur_ok:
+            _refuses_blur(r, sc, lambda: r.trace_screen_centred(sc.cam, sc.sec))
     _set_blur(r, _blur(sc))
     _blocking(r, plane, sc, variant)
     r.set_counters(True)

@@ -5,6 +5,10 @@ Not part of the test suite (minutes of oracle time); run on the GPU box:
     python3 tools/fuzz_parity.py [N_SCENES [SEED]]
 Prints one line per mismatch and a summary; exit code 1 on any mismatch.
 
+--expect-form F (with a variable that forces the form of the sphere lists, e.g. PWN_SPHERE_LISTS=global and F = 2): every
+context must report form F (Renderer.sphere_tables) once its spheres are loaded; one that does not counts as a mismatch, and
+the summary line ends with ", form F in force on K of K contexts" -- a misspelt variable would otherwise pass in silence.
+
 --lattice draws degenerate poses instead of generic ones: axis-aligned or 45-degree
 headings, camera and sphere coordinates on the integer / half / quarter lattice.  Rays
 then have exactly rational slopes: zero components (the EPSILON clamp, trace.h:220-222),
@@ -37,6 +41,11 @@ FORCE_SIZE = None                 # --size WxH: every scene at this frame size (
 if "--size" in sys.argv:
     i = sys.argv.index("--size")
     FORCE_SIZE = tuple(int(v) for v in sys.argv[i + 1].lower().split("x"))
+    del sys.argv[i:i + 2]
+EXPECT_FORM = None               # --expect-form F: every context's sphere tables have this form (0 indexed, 1 inline, 2 device memory)
+if "--expect-form" in sys.argv:
+    i = sys.argv.index("--expect-form")
+    EXPECT_FORM = int(sys.argv[i + 1])
     del sys.argv[i:i + 2]
 LATTICE = "--lattice" in sys.argv
 if LATTICE:
@@ -81,6 +90,7 @@ def random_level():
 
 
 bad = 0
+contexts = form_ok = 0
 sizes = [(64, 32), (36, 20), (128, 72), (33, 9), (256, 64), (8, 8), (100, 52), (160, 96)]
 # every 16th scene: a frame larger than one blur tile, so that deep pixels send taps outside
 # the staged halo (post_kernels.hip) and several tiles / XCD bands take part
@@ -175,6 +185,9 @@ for it in range(n):
     r = pwnfps_amd.Renderer(w, h)
     r.level_load_text(text)
     r.set_objects(sph)
+    contexts += 1
+    form = r.sphere_tables()["form"]
+    form_ok += form == EXPECT_FORM
     r.set_blur_passes(blur)
     r.set_counters(True)
     a, za = r.trace_screen_centred(cam, sec)
@@ -182,7 +195,10 @@ for it in range(n):
     b, zb, ost = O.render(w, h, cam, sec=sec, blur=blur, stats=True)
     ok = (a == b).all() and (za.view(np.uint32) == zb.view(np.uint32)).all()
     cnt_ok = (st["rays"], st["steps"], st["portals"], st["sphere_tests"], st["exhausted"]) == (ost.rays, ost.steps, ost.portals, ost.sphere_tests, ost.exhausted)
-    if not (ok and cnt_ok):
+    if EXPECT_FORM is not None and form != EXPECT_FORM:
+        bad += 1
+        print("FORM scene %d seed %d: the sphere tables have form %d, not %d" % (it, seed, form, EXPECT_FORM))
+    elif not (ok and cnt_ok):
         bad += 1
         print("MISMATCH scene %d seed %d: %dx%d blur %d sec %r pixels %d depth %d counters %s" % (
             it, seed, w, h, blur, sec, int((a != b).sum()), int((za.view(np.uint32) != zb.view(np.uint32)).sum()), cnt_ok))
@@ -196,5 +212,6 @@ for it in range(n):
                  gpu_cnt=np.array([st["rays"], st["steps"], st["portals"], st["sphere_tests"], st["exhausted"]]),
                  ora_cnt=np.array([ost.rays, ost.steps, ost.portals, ost.sphere_tests, ost.exhausted]))
     r.close()
-print("fuzz_parity: %d scenes, %d mismatches (seed %d)" % (n, bad, seed))
+print("fuzz_parity: %d scenes, %d mismatches (seed %d)" % (n, bad, seed)
+      + ("" if EXPECT_FORM is None or REF_MODE else ", form %d in force on %d of %d contexts" % (EXPECT_FORM, form_ok, contexts)))
 sys.exit(1 if bad else 0)
