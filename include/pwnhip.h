@@ -365,6 +365,51 @@ int pwn_call_strips_state(pwn_ctx *ctx, unsigned long long out[6]);
 int pwn_trace_views(pwn_ctx *ctx, int n, const float *cams, const float *secs, uint32_t *sbuf, float *zbuf);
 
 /*
+ * trace_screen_centred(lv, x1, y1, x2, y2, cam) (screen.h:31-40) for n views of their OWN sizes, composited on the device into
+ * one frame of the context's W x H: split-screen (two half-height views), picture-in-picture (a small preview beside the main
+ * view), dynamic resolution (the same rectangle rendered smaller this frame).  Blocking; one trace launch and one blur launch
+ * per pass for all the rectangles, one copy to the host.  vp = n rectangles of the frame, cams = n x 16 floats, secs = n
+ * sec_current as for pwn_trace_views; sbuf and zbuf (or NULL) are ONE W x H frame each, pitch W.
+ *   exactness            the w_i x h_i pixels of rectangle i are bit-identical, colour and depth, to what
+ *                        pwn_trace_screen_centred(cams[i], secs[i]) returns on a context of size w_i x h_i with the same level,
+ *                        objects and PWN_OPT_BLUR_PASSES.  The view is a frame of its own: the camera set-up of a w_i x h_i frame,
+ *                        the pixel seed of (x_local, y_local) in a frame w_i wide (screen.h:19-21 with rwidth = w_i), the 32-pixel
+ *                        add chain (screen.h:12-18) from the view's local column 0, blur strength 0.002 * h_i, row seeds from the
+ *                        local row, taps clamped to the view's own rectangle (screen.h:103-106 with dimx = w_i, dimy = h_i): a tap
+ *                        never reads a neighbouring rectangle.
+ *   depth                the call family owns one pre-blur plane, one colour plane (the two take turns under several blur passes)
+ *                        and one depth plane of W x H,
+ *                        apart from the blocking call's planes and from the view slots of pwn_trace_views.  The depth plane is zero
+ *                        when first allocated and persists across calls BY DESTINATION PIXEL: a primary ray that runs out of steps
+ *                        keeps what the plane holds at the pixel it is composited to (trace.h:677), whichever rectangle wrote it.
+ *                        Cost: 12 B x W x H on the device, allocated by the first call; pwn_destroy frees them.
+ *   outside the rectangles  colour reads 0; zbuf is the depth plane as it stands.
+ *   blur                 PWN_OPT_BLUR_PASSES as the blocking call.  With blur on, PWN_EINVAL unless W % 4 == 0 and every x_i % 4 == 0
+ *                        and w_i % 4 == 0 (the w % 4 rule of the blocking call, and 16-byte groups in a pitch-W plane); with blur
+ *                        off any rectangle is accepted.
+ *   counters, timings, ordering, not followed, left alone
+ *                        as pwn_trace_views (counters summed over the views; behind the frames in flight; always the units
+ *                        scheduler, never in row strips; the unit-order state, the trace-room measurement and the blocking call's
+ *                        planes are left alone) -- and so are the view slots of pwn_trace_views.
+ *   errors               PWN_EINVAL for NULL ctx / vp / cams / secs / sbuf, n < 1, n > PWN_VIEWS_MAX, a rectangle with w < 1 or
+ *                        h < 1, a rectangle not inside W x H, two rectangles that overlap (touching edges is fine), the blur rules
+ *                        above; PWN_ENOLEVEL before a level; PWN_ENOTSUP on a pwn_init_multi handle; PWN_EBUSY while the context runs
+ *                        a row tiling (pwn_tiled_init).
+ * pwn_viewports_plan applies the checks of that list that need no context -- host only, no context, no device (like
+ * pwn_sphere_tables_plan); pwn_trace_viewports calls the same function, so the two cannot disagree.  PWN_OK or PWN_EINVAL, and
+ * out is filled in both cases (PWN_EINVAL alone for a NULL out):
+ *     out[0]  16 x 4-pixel units of the launch: the sum over the views of ceil(w / 16) * ceil(h / 4)
+ *     out[1]  pixels covered            out[2]  the largest view's units
+ *     out[3]  index of the first offending rectangle (of two that overlap: the later one), or n if there is none -- also when
+ *             what is wrong is not a rectangle: n itself, a NULL vp, W or H outside pwn_init's 1..32768, W % 4 with blur on
+ *   (out[0..2] count the rectangles that lie inside a valid frame; 0 where vp, n or the frame is refused)
+ */
+typedef struct pwn_viewport { int32_t x, y, w, h; } pwn_viewport;   /* a rectangle of the context's W x H frame */
+int pwn_viewports_plan(int W, int H, int blur_passes, int n, const pwn_viewport *vp, unsigned long long out[4]);
+int pwn_trace_viewports(pwn_ctx *ctx, int n, const pwn_viewport *vp, const float *cams, const float *secs,
+	uint32_t *sbuf, float *zbuf);
+
+/*
  * Caller-supplied rays: trace_ray(0, &seed_i, lv, &depth_i, &origin_i, &dir_i, {1,1,1,1}) (trace.h:186, called as at
  * screen.h:22-24) for n rays of the caller's choosing, on the context's current level and object table with sec_current:
  * hitscan and line of sight ("how far along this direction is the first thing, through portals and past spheres"), picking

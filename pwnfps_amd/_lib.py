@@ -41,6 +41,10 @@ class Sphere(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("r", "refl", "x", "y", "z", "cb", "cg", "cr")]
 
 
+class Viewport(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("x", "y", "w", "h")]
+
+
 class Hit(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("kind", "face", "object", "portals")] + \
                [(n, C.c_float) for n in ("dist", "x", "y", "z", "dx", "dy", "dz")] + \
@@ -118,6 +122,8 @@ ABI = [
     ("pwn_host_unregister", _i, [_vp, _vp]),
     ("pwn_call_strips_state", _i, [_vp, _vp]),
     ("pwn_trace_views", _i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    ("pwn_viewports_plan", _i, [_i, _i, _i, _i, _vp, _vp]),
+    ("pwn_trace_viewports", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     ("pwn_pixel_rays", _i, [_i, _i, _vp, _i, _vp, _vp, _vp]),
     ("pwn_trace_rays", _i, [_vp, _i, _vp, _vp, _f, _vp, _vp]),
     ("pwn_trace_rays_device", _i, [_vp, _i, _vp, _vp, _f, _i, _vp, _vp, _vp]),

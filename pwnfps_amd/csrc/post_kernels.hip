@@ -108,6 +108,14 @@ pwn_blur_kernel(pwn_blur_params P)
 // (profiles/r3_blur_sweep.txt).
 // VIEWS: a batch of views in one launch (pwn_trace_views), blockIdx.y = the view.  Every view is blurred as a frame of its own --
 // its row seeds (cy*cy + 415135) and edge clamps are those of one frame -- so the batch is not one tall frame.
+// VIEWS == 2: views of their own sizes in rectangles of ONE frame (pwn_trace_viewports), blockIdx.y = the view again.  The view's
+// record (tables.h pwn_viewport_rec) gives its rectangle; the kernel then blurs a frame of w_i x h_i whose rows happen to lie
+// `pitch` = the whole frame's width apart: the plane pointers move to the rectangle's first pixel, P.w / P.h / P.groups / the rows
+// become the view's, and every use of the width as a distance between rows below is `pitch`.  So the staging clamp, the tap
+// clamp and the plain fall-back load are bounded by the view's rectangle (a tap never reads a neighbour's pixel), the row seed
+// and the skip-ahead entry are those of the local row and the local 4-pixel group, fstr is 0.002 * h_i.  The grid is sized by
+// the view with the most tiles; workgroups beyond a view's own tiles return.  x_i, w_i and the pitch are multiples of 4
+// (pwn_viewports_plan), so every uint4 of the view is 16-byte aligned.
 #ifndef BLUR_HALO
 #define BLUR_HALO 16        // measured 8 / 16 / 24 / 32: 45.6 / 45.4 / 46.6 / 48.0 us at 4K (less staging beats fewer fall-backs)
 #endif
@@ -116,15 +124,25 @@ pwn_blur_kernel(pwn_blur_params P)
 #define BLUR_PITCH (BLUR_LW + (BATCH == 2 ? 0 : 4)) // words; +4 keeps rows 16-B aligned and off one bank (direct-to-LDS staging: rows back to back)
 #define BLUR_THREADS (BLUR_TW / 4 * BLUR_TH)       // one thread per 4-pixel group
 
-template<bool CHECK, int BLUR_TW, int BLUR_TH, int BATCH, bool VIEWS>
+template<bool CHECK, int BLUR_TW, int BLUR_TH, int BATCH, int VIEWS>
 __global__ void __launch_bounds__(BLUR_THREADS)
 pwn_blur_tiled_kernel(pwn_blur_params P)
 {
 	extern __shared__ __attribute__((aligned(16))) uint32_t tile[];
-	if constexpr(VIEWS)
+	if constexpr(VIEWS == 1)
 	{
 		const size_t off = (size_t)blockIdx.y * (size_t)P.plane;
 		P.pre += off; P.zbuf += off; P.out += off;
+	}
+	// words between two rows of the planes
+	const int pitch = P.w;
+	if constexpr(VIEWS == 2)
+	{
+		typedef const __attribute__((address_space(4))) int32_t ci32;
+		ci32 *r = (ci32 *)((uintptr_t)P.vps + (uintptr_t)blockIdx.y * PWN_VP_REC_BYTES);
+		const size_t off = (size_t)r[18] * (size_t)pitch + (size_t)r[17];
+		P.pre += off; P.zbuf += off; P.out += off;
+		P.w = r[19]; P.h = r[20]; P.y0 = 0; P.y1 = P.h; P.groups = P.w >> 2;
 	}
 	// Workgroup w runs on XCD w % 8 (round-robin dispatch) and every XCD has its
 	// own L2.  Neighbouring tiles share their halos, so XCD k takes the k-th
@@ -137,6 +155,8 @@ pwn_blur_tiled_kernel(pwn_blur_params P)
 	const int per_xcd = (ntiles + 7) >> 3;
 	const int t = (int)(blockIdx.x & 7u) * per_xcd + (int)(blockIdx.x >> 3);
 	if(t >= ntiles) return;
+	// (a grid sized by a larger view: the workgroups behind this XCD's share would do the next XCD's tiles again)
+	if constexpr(VIEWS == 2) { if((int)(blockIdx.x >> 3) >= per_xcd) return; }
 	const int x0 = (t % tiles_x) * BLUR_TW, y0 = P.y0 + (t / tiles_x) * BLUR_TH;
 	const int lx0 = x0 - BLUR_HALO, ly0 = y0 - BLUR_HALO;
 
@@ -155,12 +175,12 @@ pwn_blur_tiled_kernel(pwn_blur_params P)
 			const int row = i / (BLUR_LW / 4), c4 = i - row * (BLUR_LW / 4);
 			const int gy = ly0 + row, gx = lx0 + c4 * 4;
 			if((unsigned)gy < (unsigned)P.h && (unsigned)gx < (unsigned)P.w)
-				*(uint4 *)(tile + row * BLUR_PITCH + c4 * 4) = *(const uint4 *)(P.pre + (size_t)gy * (size_t)P.w + (size_t)gx);
+				*(uint4 *)(tile + row * BLUR_PITCH + c4 * 4) = *(const uint4 *)(P.pre + (size_t)gy * (size_t)pitch + (size_t)gx);
 		}
 		__syncthreads();
 		if(!mine) return;
 		ac = P.skip[g];
-		zv = *(const float4 *)(P.zbuf + (size_t)cy * (size_t)P.w + (size_t)(g * 4));
+		zv = *(const float4 *)(P.zbuf + (size_t)cy * (size_t)pitch + (size_t)(g * 4));
 	}
 	else if constexpr(BATCH == 2)
 	{
@@ -172,7 +192,7 @@ pwn_blur_tiled_kernel(pwn_blur_params P)
 		// the frame; what lies outside is loaded from there and never read (tap coordinates are clamped into the frame).
 		const int gq = mine ? g : 0, cyq = mine ? cy : P.y0;
 		ac = P.skip[gq];
-		zv = *(const float4 *)(P.zbuf + (size_t)cyq * (size_t)P.w + (size_t)(gq * 4));
+		zv = *(const float4 *)(P.zbuf + (size_t)cyq * (size_t)pitch + (size_t)(gq * 4));
 		constexpr int NL = (NV + 63) / 64;                         // wave-loads in all
 		constexpr int NW = BLUR_THREADS / 64;
 		const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
@@ -185,7 +205,7 @@ pwn_blur_tiled_kernel(pwn_blur_params P)
 				const int i = min(l * 64 + lane, NV - 1);
 				const int row = i / (BLUR_LW / 4), c4 = i - row * (BLUR_LW / 4);
 				const int gyc = min(max(ly0 + row, 0), P.h - 1), gxc = min(max(lx0 + c4 * 4, 0), P.w - 4);
-				__builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(P.pre + (size_t)gyc * (size_t)P.w + (size_t)gxc),
+				__builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(P.pre + (size_t)gyc * (size_t)pitch + (size_t)gxc),
 					(__attribute__((address_space(3))) void *)(tile + l * 256), 16, 0, 0);
 			}
 		}
@@ -203,7 +223,7 @@ pwn_blur_tiled_kernel(pwn_blur_params P)
 		// r3_blur_sweep.txt: batch 1 against batch 0).
 		const int gq = mine ? g : 0, cyq = mine ? cy : P.y0;
 		ac = P.skip[gq];
-		zv = *(const float4 *)(P.zbuf + (size_t)cyq * (size_t)P.w + (size_t)(gq * 4));
+		zv = *(const float4 *)(P.zbuf + (size_t)cyq * (size_t)pitch + (size_t)(gq * 4));
 		typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 		constexpr int NT = (NV + BLUR_THREADS - 1) / BLUR_THREADS;
 		static_assert(NT >= 1 && NT <= 8, "the barrier below names its operands");
@@ -221,7 +241,7 @@ pwn_blur_tiled_kernel(pwn_blur_params P)
 			// the rectangle
 			dst[k] = i < NV ? row * BLUR_PITCH + c4 * 4 : -4;
 			const int gyc = min(max(gy, 0), P.h - 1), gxc = min(max(gx, 0), P.w - 4);
-			r[k] = *(const u32x4 *)(P.pre + (size_t)gyc * (size_t)P.w + (size_t)gxc);
+			r[k] = *(const u32x4 *)(P.pre + (size_t)gyc * (size_t)pitch + (size_t)gxc);
 			edge[k] = gx < 0 ? 1 : (gx >= P.w ? 2 : 0);
 		}
 		// (all of them live at one point: the loads cannot be sunk to their stores one by one)
@@ -251,7 +271,7 @@ pwn_blur_tiled_kernel(pwn_blur_params P)
 
 	const float fstr = 0.002f * (float)P.h;
 	const int cx = g * 4;
-	const size_t row = (size_t)cy * (size_t)P.w;
+	const size_t row = (size_t)cy * (size_t)pitch;
 	const float z[4] = { zv.x - 1.0f, zv.y - 1.0f, zv.z - 1.0f, zv.w - 1.0f };
 	const float fcx[4] = { (float)cx, (float)(cx + 1), (float)(cx + 2), (float)(cx + 3) };
 	const float fcy = (float)cy;
@@ -261,7 +281,7 @@ pwn_blur_tiled_kernel(pwn_blur_params P)
 	// until the offset of a real tap, >= w + 1, has been added).
 	int lx1 = lx0 + 1, ly1 = ly0 + 1;
 	asm volatile("" : "+s"(lx1), "+s"(ly1));       // (one scalar each: left to itself the compiler subtracts the tile's origin and adds the constant per tap)
-	const uint32_t w1 = (uint32_t)P.w + 1u;
+	const uint32_t w1 = (uint32_t)pitch + 1u;
 	const uintptr_t pre1 = (uintptr_t)P.pre - (uintptr_t)w1 * 4u;
 	uint32_t t2 = seed << 1;                               // the LCG state doubled (lcg2_fs, dev_math.h)
 	// (the frame's width and height once in vector registers: blur_coord1's v_med3_i32 takes its bound from one, and handed a
@@ -278,7 +298,7 @@ pwn_blur_tiled_kernel(pwn_blur_params P)
 	const bool tame = fabsf(z[0]) < 1.0e6f && fabsf(z[1]) < 1.0e6f && fabsf(z[2]) < 1.0e6f && fabsf(z[3]) < 1.0e6f;
 	if(__builtin_expect(__ballot(!tame) == 0ull, 1))
 	{
-		const uint32_t w0 = (uint32_t)P.w;
+		const uint32_t w0 = (uint32_t)pitch;
 		const uintptr_t pre0 = (uintptr_t)P.pre;
 		int vw1 = P.w - 1, vh1 = P.h - 1;
 		asm volatile("" : "+v"(vw1), "+v"(vh1));
@@ -363,7 +383,7 @@ pwn_blur_tiled_kernel(pwn_blur_params P)
 			if(!(tx < (unsigned)BLUR_LW && ty < (unsigned)BLUR_LH))
 			{
 				asm volatile("");
-				p = (const uint32_t *)(pre1 + ((uintptr_t)__umul24((unsigned)y1, (unsigned)P.w) + (uintptr_t)(unsigned)x1) * 4u);
+				p = (const uint32_t *)(pre1 + ((uintptr_t)__umul24((unsigned)y1, (unsigned)pitch) + (uintptr_t)(unsigned)x1) * 4u);
 			}
 			const uint32_t v = *p;
 			tap[i][j] = v;
@@ -379,7 +399,7 @@ pwn_blur_tiled_kernel(pwn_blur_params P)
 	if(CHECK) { if(missed) atomicAdd(P.miss, 1u); }
 }
 
-template<bool CHECK, int TW, int TH, int BATCH, bool VIEWS = false>
+template<bool CHECK, int TW, int TH, int BATCH, int VIEWS = 0>
 static hipError_t launch_blur_variant(const pwn_blur_params *P, hipStream_t stream)
 {
 	const int BLUR_TW = TW, BLUR_TH = TH;
@@ -399,8 +419,8 @@ static hipError_t launch_blur_variant(const pwn_blur_params *P, hipStream_t stre
 			lds_set = true;
 		}
 	}
-	const int ntiles = ((P->w + BLUR_TW - 1) / BLUR_TW) * ((P->y1 - P->y0 + BLUR_TH - 1) / BLUR_TH);
-	dim3 grid(((ntiles + 7) / 8) * 8, VIEWS ? P->views : 1);
+	const int ntiles = VIEWS == 2 ? P->vp_tiles : ((P->w + BLUR_TW - 1) / BLUR_TW) * ((P->y1 - P->y0 + BLUR_TH - 1) / BLUR_TH);
+	dim3 grid(((ntiles + 7) / 8) * 8, VIEWS == 2 ? P->nvp : VIEWS == 1 ? P->views : 1);
 	hipLaunchKernelGGL((pwn_blur_tiled_kernel<CHECK, TW, TH, BATCH, VIEWS>), grid, dim3(BLUR_THREADS), lds, stream, *P);
 	return hipGetLastError();
 }
@@ -419,8 +439,17 @@ extern "C" hipError_t pwn_launch_blur(const pwn_blur_params *P, hipStream_t stre
 	{
 		if(P->miss != NULL || P->cost_acc != NULL) return hipErrorInvalidValue;
 		const int key = P->tile_w * 1000 + P->tile_h * 10 + P->batch;
-		if(key == 128161) return launch_blur_variant<false, 128, 16, 1, true>(P, stream);
-		if(key == 32321) return launch_blur_variant<false, 32, 32, 1, true>(P, stream);
+		if(key == 128161) return launch_blur_variant<false, 128, 16, 1, 1>(P, stream);
+		if(key == 32321) return launch_blur_variant<false, 32, 32, 1, 1>(P, stream);
+		return hipErrorInvalidValue;
+	}
+	// views of their own sizes in one frame: the same two shapes (vp_tiles is the host's count for the shape it chose)
+	if(P->vps != NULL)
+	{
+		if(P->miss != NULL || P->cost_acc != NULL || P->nvp < 1 || P->vp_tiles < 1) return hipErrorInvalidValue;
+		const int key = P->tile_w * 1000 + P->tile_h * 10 + P->batch;
+		if(key == 128161) return launch_blur_variant<false, 128, 16, 1, 2>(P, stream);
+		if(key == 32321) return launch_blur_variant<false, 32, 32, 1, 2>(P, stream);
 		return hipErrorInvalidValue;
 	}
 #ifdef PWN_BLUR_PLAIN

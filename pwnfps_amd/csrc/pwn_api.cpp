@@ -9,6 +9,7 @@
 #include <string.h>
 #include <time.h>
 #include <new>
+#include <algorithm>
 #include <vector>
 #include <xmmintrin.h>      // pwn_pixel_rays: FTZ|DAZ
 
@@ -95,6 +96,7 @@ extern "C" int pwn_init(pwn_ctx **out, int device, int width, int height)
 	c->d_pre = c->d_out = NULL; c->d_z = NULL; c->d_skip = NULL; c->d_counters = NULL; c->d_tickets = NULL; c->ticket_set = 0; c->launch_rot = 2; c->launch_waits = 0;
 	c->grid_reserve = 0;
 	c->d_vpre = c->d_vout = NULL; c->d_vz = NULL; c->views_cap = 0; c->h_vrec = c->d_vrec = NULL; c->vrec_cap = 0;
+	c->d_ppre = c->d_pout = NULL; c->d_pz = NULL; c->h_prec = c->d_prec = NULL;
 	c->h_rays = c->d_rays = NULL; c->rays_cap = 0;
 	c->h_hits = c->d_hits = NULL; c->hits_cap = 0;
 	memset(&c->room, 0, sizeof(c->room)); c->room.mode = -1;
@@ -244,6 +246,8 @@ extern "C" void pwn_destroy(pwn_ctx *c)
 	(void)hipFree(c->d_wave_log);
 	(void)hipFree(c->d_vpre); (void)hipFree(c->d_vout); (void)hipFree(c->d_vz); (void)hipFree(c->d_vrec);
 	if(c->h_vrec) (void)hipHostFree(c->h_vrec);
+	(void)hipFree(c->d_ppre); (void)hipFree(c->d_pout); (void)hipFree(c->d_pz); (void)hipFree(c->d_prec);
+	if(c->h_prec) (void)hipHostFree(c->h_prec);
 	(void)hipFree(c->d_rays);
 	if(c->h_rays) (void)hipHostFree(c->h_rays);
 	(void)hipFree(c->d_hits);
@@ -980,7 +984,8 @@ int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L)
 {
 	const pwn_views_launch *views = L->views.n > 0 ? &L->views : NULL;
 	const pwn_rays_launch *rays = L->rays.n > 0 ? &L->rays : NULL;
-	const bool batch = views != NULL || rays != NULL;
+	const pwn_vps_launch *vps = L->vps.n > 0 ? &L->vps : NULL;
+	const bool batch = views != NULL || rays != NULL || vps != NULL;
 	const int y0 = L->y0, y1 = L->y1;
 	const hipStream_t stream = L->stream;
 	const hipEvent_t caller_event = L->tables_event;
@@ -1007,6 +1012,14 @@ int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L)
 		P.views = views->d_recs; P.nviews = views->n; P.plane = views->plane;
 		unit_div_magic((uint32_t)views->n, &P.views_magic, &P.views_shift);
 		P.tiles_total *= views->n;
+	}
+	// views of their own sizes into this one frame: the units of all of them, found by the kernel from the records
+	if(vps != NULL)
+	{
+		P.vps = vps->d_recs; P.nvp = vps->n; P.tiles_total = (int)vps->units;
+		// (the kernel's search: strides from the largest power of two below n down to 1)
+		P.vp_step0 = 0u;
+		if(vps->n > 1) { P.vp_step0 = 1u; while(2u * P.vp_step0 <= (uint32_t)vps->n - 1u) P.vp_step0 *= 2u; }
 	}
 	// a batch of rays: 64 to a unit
 	if(rays != NULL)
@@ -1053,6 +1066,7 @@ int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L)
 	// 3-lane specialisation for them that is arithmetically identical
 	if(views != NULL) P.has_w = views->has_w;        // (the same rule over all the batch's cameras)
 	else if(rays != NULL) P.has_w = rays->has_w;     // (the rule over the batch's rays: pwn_trace_rays)
+	else if(vps != NULL) P.has_w = vps->has_w;
 	else P.has_w = !(L->cam[3] == 0.0f && L->cam[7] == 0.0f && L->cam[11] == 0.0f && L->cam[15] == 1.0f);
 	// test hook (tests/test_gpu_fuzz.py): send every camera through the general variant
 	if(c->dbg_force_hasw) P.has_w = 1;
@@ -1239,6 +1253,8 @@ int pwn_i_launch_blur(pwn_ctx *c, const pwn_blur_launch *L)
 	if((c->w & 3) != 0) return PWN_EINVAL; // screen.h:88,117: aligned 16-B store per group
 	pwn_blur_params B;
 	B.views = L->views; B.plane = (unsigned long long)c->w * (unsigned long long)c->h;
+	const pwn_vps_launch *vps = L->vps.n > 0 ? &L->vps : NULL;
+	B.vps = vps != NULL ? vps->d_recs : NULL; B.nvp = vps != NULL ? vps->n : 0; B.vp_tiles = 0;
 	B.w = c->w; B.h = c->h; B.y0 = L->y0; B.y1 = L->y1;
 	B.groups = c->w / 4;
 	B.pre = L->d_pre; B.zbuf = L->d_z; B.out = L->d_out; B.skip = c->d_skip;
@@ -1254,10 +1270,20 @@ int pwn_i_launch_blur(pwn_ctx *c, const pwn_blur_launch *L)
 		// With room beside the trace grid (PWN_OPT_TRACE_ROOM, what level.txt-like scenes settle on) 32 x 32 wins on narrow frames
 		// too: 720p 16.4-17.5 -> 19.4 Gpixels/s (profiles/r3_blur_sweep.txt, last block).
 		B.tile_w = 32; B.tile_h = 32; B.batch = 1;
-		if(c->w < 2560 && pwn_room_for_launch(c) == 0) { B.tile_w = 128; B.tile_h = 16; }
+		// (views of their own sizes: the widest view decides, as it would on a context of its size)
+		int wide = c->w;
+		if(vps != NULL) { wide = 0; for(int i = 0; i < vps->n; i++) if(vps->h_recs[i].w > wide) wide = vps->h_recs[i].w; }
+		if(wide < 2560 && pwn_room_for_launch(c) == 0) { B.tile_w = 128; B.tile_h = 16; }
 		if(c->dbg_blur_th > 0) B.tile_h = c->dbg_blur_th;          // (a shape without an instantiation: the launch fails with hipErrorInvalidValue)
 		if(c->dbg_blur_tw > 0) B.tile_w = c->dbg_blur_tw;
 		if(c->dbg_blur_batch >= 0) B.batch = c->dbg_blur_batch;
+		// ... and the grid is that of the view with the most tiles of this shape
+		if(vps != NULL && B.tile_w > 0 && B.tile_h > 0)
+			for(int i = 0; i < vps->n; i++)
+			{
+				const int t = ((vps->h_recs[i].w + B.tile_w - 1) / B.tile_w) * ((vps->h_recs[i].h + B.tile_h - 1) / B.tile_h);
+				if(t > B.vp_tiles) B.vp_tiles = t;
+			}
 	}
 	HIPCHK(c, pwn_launch_blur(&B, L->stream));
 	return PWN_OK;
@@ -1726,6 +1752,116 @@ extern "C" int pwn_trace_views(pwn_ctx *c, int n, const float *cams, const float
 	HIPCHK(c, hipEventRecord(c->ev[2], s));
 	HIPCHK(c, hipMemcpyAsync(sbuf, cur, (size_t)n * plane * 4, hipMemcpyDeviceToHost, s));
 	if(zbuf != NULL) HIPCHK(c, hipMemcpyAsync(zbuf, c->d_vz, (size_t)n * plane * 4, hipMemcpyDeviceToHost, s));
+	HIPCHK(c, hipEventRecord(c->ev[3], s));
+	HIPCHK(c, hipEventSynchronize(c->ev[3]));
+	(void)hipEventElapsedTime(&c->stats.trace_ms, c->ev[0], c->ev[1]);
+	(void)hipEventElapsedTime(&c->stats.blur_ms, c->ev[1], c->ev[2]);
+	(void)hipEventElapsedTime(&c->stats.total_ms, c->ev[0], c->ev[3]);
+	return PWN_OK;
+}
+
+// ---- views of their own sizes in one frame (pwn_trace_viewports) ----------------
+
+// The records (PWN_VIEWS_MAX of them) and the three planes of w x h, with the first call.  The depth plane starts at zero and
+// is never cleared again: it persists by destination pixel.
+static int viewports_reserve(pwn_ctx *c, hipStream_t s)
+{
+	if(c->h_prec == NULL)
+	{
+		HIPCHK(c, hipHostMalloc((void **)&c->h_prec, PWN_VIEWS_MAX * sizeof(pwn_viewport_rec), hipHostMallocDefault));
+		HIPCHK(c, hipMalloc((void **)&c->d_prec, PWN_VIEWS_MAX * sizeof(pwn_viewport_rec)));
+	}
+	if(c->d_pz != NULL) return PWN_OK;
+	const size_t bytes = (size_t)c->w * (size_t)c->h * 4;
+	uint32_t *pre = NULL, *out = NULL; float *z = NULL;
+	if(hipMalloc((void **)&pre, bytes) != hipSuccess || hipMalloc((void **)&out, bytes) != hipSuccess || hipMalloc((void **)&z, bytes) != hipSuccess)
+	{
+		(void)hipGetLastError();
+		(void)hipFree(pre); (void)hipFree(out); (void)hipFree(z);
+		snprintf(c->err, sizeof(c->err), "pwn_trace_viewports: no room for three planes of %d x %d", c->w, c->h);
+		return PWN_ENOMEM;
+	}
+	c->d_ppre = pre; c->d_pout = out; c->d_pz = z;
+	HIPCHK(c, hipMemsetAsync(z, 0, bytes, s));
+	return PWN_OK;
+}
+
+extern "C" int pwn_trace_viewports(pwn_ctx *c, int n, const pwn_viewport *vp, const float *cams, const float *secs, uint32_t *sbuf, float *zbuf)
+{
+	GRP_REFUSE(c, "pwn_trace_viewports");
+	if(c == NULL || vp == NULL || cams == NULL || secs == NULL || sbuf == NULL) return PWN_EINVAL;
+	// (the rules that need no context: the one function a host can ask beforehand)
+	unsigned long long plan[4];
+	if(pwn_viewports_plan(c->w, c->h, c->blur_passes, n, vp, plan) != PWN_OK)
+	{
+		snprintf(c->err, sizeof(c->err), "pwn_trace_viewports: %d rectangles of a %d x %d frame refused (the first offender: %llu)", n, c->w, c->h, plan[3]);
+		return PWN_EINVAL;
+	}
+	if(c->tiled != NULL) return PWN_EBUSY;
+	if(!c->have_level) return PWN_ENOLEVEL;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = c->stream;
+	int rc = wait_frames_in_flight(c, s);
+	if(rc != PWN_OK) return rc;
+	rc = viewports_reserve(c, s);
+	if(rc != PWN_OK) return rc;
+	// The records, in order of rising units (tables.h pwn_viewport_rec: the kernel's rounds), each view's set-up from the blocking
+	// call's own frame_setup for a frame of the VIEW's size (this file's operation order is part of the bit-exact path).
+	// (the staging is free: the call before this one ended with the stream drained)
+	int ord[PWN_VIEWS_MAX];
+	uint32_t vu[PWN_VIEWS_MAX];
+	for(int i = 0; i < n; i++) { ord[i] = i; vu[i] = (uint32_t)((vp[i].w + 15) / 16) * (uint32_t)((vp[i].h + 3) / 4); }
+	std::stable_sort(ord, ord + n, [&vu](int a, int b) { return vu[a] < vu[b]; });
+	bool has_w = false;
+	uint32_t first = 0u, prev = 0u;
+	for(int j = 0; j < n; j++)
+	{
+		const int i = ord[j];
+		const float *cam = cams + 16 * (size_t)i;
+		pwn_trace_params P;
+		frame_setup(vp[i].w, vp[i].h, cam, &P);
+		pwn_viewport_rec &r = c->h_prec[j];
+		memcpy(r.rayb, P.rayb, sizeof(r.rayb)); memcpy(r.rdx, P.rdx, sizeof(r.rdx));
+		memcpy(r.rdy, P.rdy, sizeof(r.rdy)); memcpy(r.from, P.from, sizeof(r.from));
+		r.sec_current = secs[i];
+		r.x = vp[i].x; r.y = vp[i].y; r.w = vp[i].w; r.h = vp[i].h;
+		r.units_x = (uint32_t)((vp[i].w + 15) / 16); r.rows_u = (uint32_t)((vp[i].h + 3) / 4); r.units = vu[i];
+		int sh;
+		unit_div_magic(r.units_x, &r.ux_magic, &sh); r.ux_shift = sh;
+		// segment j: rounds [prev, units) of the views j .. n-1
+		r.seg_first = first; r.seg_round = prev;
+		unit_div_magic((uint32_t)(n - j), &r.seg_magic, &sh); r.seg_shift = sh;
+		first += (uint32_t)(n - j) * (r.units - prev); prev = r.units;
+		r.pad_[0] = r.pad_[1] = 0u;
+		if(!(cam[3] == 0.0f && cam[7] == 0.0f && cam[11] == 0.0f && cam[15] == 1.0f)) has_w = true;
+	}
+	if((unsigned long long)first != plan[0]) { snprintf(c->err, sizeof(c->err), "pwn_trace_viewports: %u units in the records, %llu planned", first, plan[0]); return PWN_EINVAL; }
+	HIPCHK(c, hipEventRecord(c->ev[0], s));
+	HIPCHK(c, pwn_launch_upload(c->h_prec, c->d_prec, (size_t)n * sizeof(pwn_viewport_rec), s));
+	// where no rectangle covers the frame colour reads 0: in the plane the trace writes and in the one the blur passes write
+	// (with several passes the two take turns)
+	const size_t plane = (size_t)c->w * (size_t)c->h;
+	if(plan[1] < (unsigned long long)plane)
+	{
+		HIPCHK(c, hipMemsetAsync(c->d_ppre, 0, plane * 4, s));
+		if(c->blur_passes > 0) HIPCHK(c, hipMemsetAsync(c->d_pout, 0, plane * 4, s));
+	}
+	const pwn_vps_launch V = { c->d_prec, c->h_prec, n, has_w, first };
+	pwn_trace_launch T = { .y0 = 0, .y1 = c->h, .vps = V, .d_sbuf = c->d_ppre, .d_zbuf = c->d_pz, .stream = s };
+	rc = pwn_i_launch_trace(c, &T);
+	if(rc != PWN_OK) return rc;
+	HIPCHK(c, hipEventRecord(c->ev[1], s));
+	uint32_t *cur = c->d_ppre, *other = c->d_pout;
+	for(int p = 0; p < c->blur_passes; p++)
+	{
+		const pwn_blur_launch B = { .y0 = 0, .y1 = c->h, .d_pre = cur, .d_z = c->d_pz, .d_out = other, .stream = s, .vps = V };
+		rc = pwn_i_launch_blur(c, &B);
+		if(rc != PWN_OK) return rc;
+		uint32_t *t = cur; cur = other; other = t;
+	}
+	HIPCHK(c, hipEventRecord(c->ev[2], s));
+	HIPCHK(c, hipMemcpyAsync(sbuf, cur, plane * 4, hipMemcpyDeviceToHost, s));
+	if(zbuf != NULL) HIPCHK(c, hipMemcpyAsync(zbuf, c->d_pz, plane * 4, hipMemcpyDeviceToHost, s));
 	HIPCHK(c, hipEventRecord(c->ev[3], s));
 	HIPCHK(c, hipEventSynchronize(c->ev[3]));
 	(void)hipEventElapsedTime(&c->stats.trace_ms, c->ev[0], c->ev[1]);

@@ -20,6 +20,17 @@ struct pwn_views_launch
 	unsigned long long plane;
 };
 
+// Views of their own sizes in rectangles of one frame (pwn_trace_viewports) as what a launch traces or blurs: n records (tables.h
+// pwn_viewport_rec) on the device, in the order the trace kernel expects, and the same records on the host (the blur launcher
+// counts the tiles of the shape it picks); units = the launch's 16 x 4 units over all views.  n = 0: none.
+struct pwn_vps_launch
+{
+	const pwn_viewport_rec *d_recs, *h_recs;
+	int n;
+	bool has_w;
+	uint32_t units;
+};
+
 // A batch of caller-supplied rays (pwn_trace_rays / pwn_trace_rays_device; tables.h pwn_trace_params.rays): n rays into
 // d_sbuf (colour) / d_zbuf (depth) of the launch; has_w: their w lanes count (PWN_RAYS_HAS_W).  n = 0: none.
 // d_hits (pwn_trace_hits / pwn_trace_hits_device): not NULL = the launch writes n first-hit records (pwn_hit) there instead,
@@ -40,6 +51,7 @@ struct pwn_trace_launch
 	const float *cam; float sec; int y0, y1;     // rows [y0, y1) of camera cam[16]'s frame (y0 == y1: nothing is launched) ...
 	pwn_views_launch views;                      // ... or of every view of a batch (cam and sec not read) ...
 	pwn_rays_launch rays;                        // ... or a batch of rays (cam and the rows not read)
+	pwn_vps_launch vps;                          // ... or views of their own sizes into one frame (cam, sec and the rows not read)
 	uint32_t *d_sbuf; float *d_zbuf; hipStream_t stream;
 	uint32_t *clear_word, *cost_word;            // pwn_trace_params.clear_word, .cost_word
 	// An event the caller records itself right behind this launch anyway (its frame's "kernels done").  The launcher
@@ -62,6 +74,7 @@ struct pwn_blur_launch
 	uint32_t *d_cost_acc, *d_cost_out;           // pwn_blur_params.cost_acc, .cost_out ...
 	uint32_t cost_mul, cost_div;                 // ... scaled by what the frame's trace launch gave out (0 = 1)
 	int views;                                   // a batch of views (pwn_trace_views): that many, planes w * h apart (0 = one frame)
+	pwn_vps_launch vps;                          // views of their own sizes in one frame (pwn_trace_viewports): each rectangle a frame of its own (rows not read)
 };
 
 extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream);
@@ -231,6 +244,10 @@ struct pwn_ctx
 	// by slot and are kept when the count grows), the records of the call in pinned staging and on the device
 	uint32_t *d_vpre, *d_vout; float *d_vz; int views_cap;
 	pwn_view_rec *h_vrec, *d_vrec; int vrec_cap;
+	// pwn_trace_viewports: one pre-blur, one colour and one depth plane of w x h (the depth plane persists by pixel), the records
+	// of the call in pinned staging and on the device (PWN_VIEWS_MAX of them)
+	uint32_t *d_ppre, *d_pout; float *d_pz;
+	pwn_viewport_rec *h_prec, *d_prec;
 	// pwn_trace_rays: room for rays_cap rays in pinned staging and on the device, 44 B each (record, seed, depth, colour; pwn_api.cpp rays_reserve)
 	unsigned char *h_rays, *d_rays; size_t rays_cap;
 	// pwn_trace_hits: the same for hits_cap rays, 32 B in (record) and 48 B out (pwn_hit) each (pwn_api.cpp hits_reserve)

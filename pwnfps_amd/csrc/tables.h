@@ -206,6 +206,13 @@ struct pwn_trace_params
 	const float *g_rec;
 	const uint32_t *g_which;
 	const float *g_sph;
+	// Views of their own sizes composited into one frame (pwn_trace_viewports): NULL, or nvp records (pwn_viewport_rec below) that
+	// take the place of rayb ... sec_current AND of w, h, y0, y1, tiles_x, ux_magic per view; w is then the pitch of sbuf / zbuf
+	// alone.  tiles_total = the units of all views; vp_step0 = the first stride of the kernel's search for a ticket's segment, the
+	// largest power of two below nvp (0 for one view).
+	const struct pwn_viewport_rec *vps;
+	int nvp;
+	uint32_t vp_step0;
 };
 #define PWN_HIT_REC_BYTES 48u
 
@@ -233,10 +240,14 @@ struct pwn_blur_params
 	// a batch of views (pwn_trace_views): 0 = one frame; else that many frames of w x h, view v's planes at pre / zbuf / out + v * plane
 	int views;
 	unsigned long long plane;
+	// views of their own sizes in one frame (pwn_trace_viewports): NULL, or nvp records -- blockIdx.y = the view, whose rectangle
+	// of the pitch-w planes is blurred as a frame of its own; vp_tiles = the tiles of the view that has most (the launch's grid)
+	const struct pwn_viewport_rec *vps;
+	int nvp, vp_tiles;
 };
 
 // what a launch of the trace kernel traces (its MODE parameter, trace_kernel.hip)
-enum { PWN_KM_FRAME = 0, PWN_KM_VIEWS = 1, PWN_KM_RAYS = 2, PWN_KM_HITS = 3 };
+enum { PWN_KM_FRAME = 0, PWN_KM_VIEWS = 1, PWN_KM_RAYS = 2, PWN_KM_HITS = 3, PWN_KM_VIEWPORTS = 4 };
 
 // One view of a batch: the camera set-up of screen.h:43-57 for that view's camera (pwn_api.cpp frame_setup) and its
 // sec_current.  80 bytes; the kernel reads a view's record with scalar loads.
@@ -247,6 +258,26 @@ struct pwn_view_rec
 	float pad_[3];
 };
 #define PWN_VIEWS_REC_BYTES 80u
+
+// One view of pwn_trace_viewports: pwn_view_rec's fields for a frame of the view's OWN size, then its rectangle of the context's
+// frame and what turns a unit number of the view into a place in it.  128 bytes; scalar loads, as a view record.
+// The records are in order of rising `units`.  The launch hands its units out in ROUNDS: round r is unit r of every view that
+// has more than r units, so all views advance together, each from its middle row outwards, and a view drops out when it is done.
+// Views s .. nvp-1 take part in rounds [units of record s-1, units of record s): "segment" s, whose fields sit in record s --
+// seg_first = the launch's first ticket of the segment (rising with s; equal for an empty segment), seg_round = its first round,
+// seg_magic / seg_shift = the division by its nvp - s participants (unit_div_magic; shift < 0: one participant).
+struct pwn_viewport_rec
+{
+	float rayb[4], rdx[4], rdy[4], from[4];
+	float sec_current;
+	int32_t x, y, w, h;                       // the rectangle
+	uint32_t units_x; uint32_t ux_magic; int32_t ux_shift;     // ceil(w / 16) and unit / units_x (pwn_trace_params.ux_magic)
+	uint32_t rows_u;                          // ceil(h / 4)
+	uint32_t units;                           // units_x * rows_u
+	uint32_t seg_first, seg_round, seg_magic; int32_t seg_shift;
+	uint32_t pad_[2];
+};
+#define PWN_VP_REC_BYTES 128u
 
 #ifndef PWN_QUEUES
 #define PWN_QUEUES 64u                       /* a power of two <= 64: one lane of a wave looks at each */

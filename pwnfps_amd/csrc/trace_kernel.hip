@@ -283,14 +283,16 @@ template<bool HAS_W> __device__ __forceinline__ void chain_rounds(Vec<HAS_W> &v,
 // of one size (pwn_trace_views): every unit reads its view's camera set-up from P.views and writes that view's planes.
 // PWN_KM_RAYS: P.nrays rays of the caller's (pwn_trace_rays): every lane loads its own origin, direction and seed.  PWN_KM_HITS: the
 // same batch of rays (pwn_trace_hits), of which every lane traces the primary segment only and writes a first-hit record
-// (trace_hit) instead of a colour and a depth.  The last three are instantiated with ORDER = false only.
+// (trace_hit) instead of a colour and a depth.  PWN_KM_VIEWPORTS: P.nvp views of their own sizes, each a frame of its own, into
+// rectangles of ONE pitch-P.w frame (pwn_trace_viewports): every unit finds its view and reads that view's set-up, size and
+// place from P.vps.  The last four are instantiated with ORDER = false only.
 // LISTS (tables.h PWN_LF_*): the form of the per-cell sphere lists -- indexed or inline records in LDS, or, for sphere sets whose
 // lists outgrow LDS, records in device memory (PWN_LF_GLOBAL: instantiated with ORDER = false only).
 template<bool COUNT, bool HAS_W, bool ORDER, int LISTS, int MODE>
 __global__ void __launch_bounds__(PWN_BLOCK, PWN_MIN_WAVES)
 pwn_trace_kernel(pwn_trace_params P)
 {
-	constexpr bool VIEWS = MODE == PWN_KM_VIEWS, HITS = MODE == PWN_KM_HITS, RAYS = MODE == PWN_KM_RAYS || HITS;
+	constexpr bool VIEWS = MODE == PWN_KM_VIEWS, HITS = MODE == PWN_KM_HITS, RAYS = MODE == PWN_KM_RAYS || HITS, VPS = MODE == PWN_KM_VIEWPORTS;
 	//@R k_prologue
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
 
@@ -333,7 +335,8 @@ pwn_trace_kernel(pwn_trace_params P)
 	// are cleared here (launches of a context are stream-ordered, include/pwnhip.h).
 	const uint32_t units_x = ((uint32_t)P.w + 15u) >> 4;
 	// (a batch of rays: 64 to a unit, P.nrays <= 2^28)
-	const uint32_t units = RAYS ? (P.nrays + 63u) >> 6 : units_x * (((uint32_t)(P.y1 - P.y0) + 3u) >> 2) * (VIEWS ? (uint32_t)P.nviews : 1u);
+	// (views of their own sizes: the host's sum over the views)
+	const uint32_t units = VPS ? (uint32_t)P.tiles_total : RAYS ? (P.nrays + 63u) >> 6 : units_x * (((uint32_t)(P.y1 - P.y0) + 3u) >> 2) * (VIEWS ? (uint32_t)P.nviews : 1u);
 	if(blockIdx.x == 0 && threadIdx.x < PWN_QUEUES) P.tickets_next[threadIdx.x * PWN_QUEUE_STRIDE] = 0u;
 	if(blockIdx.x == 0 && threadIdx.x == PWN_QUEUES && P.clear_word != NULL) *P.clear_word = 0u;
 	uint32_t q = (blockIdx.x * (PWN_BLOCK / 64) + (uint32_t)wave) % PWN_QUEUES;
@@ -515,16 +518,61 @@ pwn_trace_kernel(pwn_trace_params P)
 			sbuf += (size_t)view * (size_t)P.plane;
 			zbuf += (size_t)view * (size_t)P.plane;
 		}
+		// The frame this unit belongs to: the launch's -- or, views of their own sizes (pwn_trace_viewports), the view's own, from
+		// its record: width and height (bounds, pixel seed, middle row), units per row with their division constant, rows of
+		// units, and `org`, where the view's pixel (0, 0) lies in the pitch-P.w planes.  x and y below are LOCAL to the view, so
+		// the 32-pixel add chain starts at the view's column 0 and the seed is that of a frame fw wide; only the store adds org.
+		int fw = P.w, fh = P.h, fy0 = P.y0, fy1 = P.y1;
+		uint32_t fux = units_x, fmagic = P.ux_magic;
+		int fshift = P.ux_shift;
+		uint32_t rows_u = ((uint32_t)(P.y1 - P.y0) + 3u) >> 2;
+		uint32_t org = 0u;
+		if constexpr(VPS)
+		{
+			// Which view, which of its units (tables.h pwn_viewport_rec): the launch goes in rounds -- round r = unit r of every
+			// view that has more than r -- so ticket t lies in the segment s with the largest seg_first <= t, is the
+			// (t - seg_first) mod (nvp - s)-th of the views s .. nvp-1 there and that view's unit seg_round + (t - seg_first) / (nvp - s),
+			// which is below the view's units because the records are in order of rising units.  All of it is the same for the
+			// whole wave: scalar arithmetic and scalar loads from the constant address space (read-only), at most ten steps of
+			// the search for PWN_VIEWS_MAX views.  Any order gives the same pixels.
+			typedef const __attribute__((address_space(4))) uint32_t cu32;
+			typedef const __attribute__((address_space(4))) float cfloat;
+			const uintptr_t base = (uintptr_t)P.vps;
+			const uint32_t t = (uint32_t)__builtin_amdgcn_readfirstlane((int)unit), nvp = (uint32_t)P.nvp;
+			uint32_t s = 0u;
+			for(uint32_t step = P.vp_step0; step != 0u; step >>= 1)
+			{
+				const uint32_t c = min(s + step, nvp - 1u);
+				const uint32_t first = ((cu32 *)(base + (uintptr_t)c * PWN_VP_REC_BYTES))[26];
+				if(s + step < nvp && first <= t) s += step;
+			}
+			cu32 *sr = (cu32 *)(base + (uintptr_t)s * PWN_VP_REC_BYTES);
+			const uint32_t d = t - sr[26], cnt = nvp - s;
+			const int sshift = (int)sr[29];
+			const uint32_t rr = sshift >= 0 ? __umulhi(d, sr[28]) >> sshift : d;
+			const uint32_t view = s + (d - rr * cnt);
+			fu = sr[27] + rr;
+			cu32 *ri = (cu32 *)(base + (uintptr_t)view * PWN_VP_REC_BYTES);
+			const cfloat *r = (const cfloat *)ri;
+			rayb.x = r[0]; rayb.y = r[1]; rayb.z = r[2]; rayb.w = HAS_W ? r[3] : 0.0f;
+			rdx.x = r[4]; rdx.y = r[5]; rdx.z = r[6]; rdx.w = HAS_W ? r[7] : 0.0f;
+			rdy.x = r[8]; rdy.y = r[9]; rdy.z = r[10]; rdy.w = HAS_W ? r[11] : 0.0f;
+			from.x = r[12]; from.y = r[13]; from.z = r[14]; from.w = HAS_W ? r[15] : 1.0f;
+			sec_current = r[16];
+			fw = (int)ri[19]; fh = (int)ri[20]; fy0 = 0; fy1 = fh;
+			fux = ri[21]; fmagic = ri[22]; fshift = (int)ri[23]; rows_u = ri[24];
+			// (the rectangle lies inside the w x h <= 2^30 pixels of the planes: pwn_viewports_plan)
+			org = ri[18] * (uint32_t)P.w + ri[17];
+		}
 		uint32_t k;
 		// (ux_shift < 0 only for units_x == 1, pwn_api.cpp unit_div_magic: then k = unit.  A real division here had its
 		// reciprocal hoisted to the top of the kernel and, in the 4-lane variant, parked in scratch memory)
-		if(P.ux_shift >= 0) k = __umulhi(fu, P.ux_magic) >> P.ux_shift;
+		if(fshift >= 0) k = __umulhi(fu, fmagic) >> fshift;
 		else k = fu;
-		const uint32_t ux = fu - k * units_x;
-		const uint32_t rows_u = ((uint32_t)(P.y1 - P.y0) + 3u) >> 2;
+		const uint32_t ux = fu - k * fux;
 		// ... of the FRAME: a strip of a row tiling starts at its rows nearest the frame's middle row (the strip of
 		// the whole frame at its own middle), not at its own middle
-		const int hrow = ((P.h >> 1) - P.y0) >> 2;
+		const int hrow = ((fh >> 1) - fy0) >> 2;
 		const uint32_t mid = (uint32_t)min(max(hrow, 0), (int)rows_u - 1);
 		// k = 0,1,2,3,... -> mid, mid-1, mid+1, mid-2, ... while there are rows on both sides (a above, b below),
 		// then the rest of the longer side in order
@@ -537,7 +585,7 @@ pwn_trace_kernel(pwn_trace_params P)
 		}
 		const int half = (int)(ux & 1u);                  // left / right half of the 32-wide tile
 		const int cx0 = (int)(ux >> 1) * 32;              // the 32-pixel tile of screen.h:6-7 this wave is in
-		const int x = (int)ux * 16 + (HAS_W ? (int)(ln & 15u) : l16), y = P.y0 + (int)uy * 4 + (HAS_W ? (int)(ln >> 4) : (lane >> 4));
+		const int x = (int)ux * 16 + (HAS_W ? (int)(ln & 15u) : l16), y = fy0 + (int)uy * 4 + (HAS_W ? (int)(ln >> 4) : (lane >> 4));
 
 		// screen.h:12-18, in the order the reference build evaluates it:
 		// rayl = (cx*rdx + rayb) + y*rdy, then one "+= rdx" per pixel of the
@@ -578,11 +626,11 @@ pwn_trace_kernel(pwn_trace_params P)
 
 		unsigned long long u_begin = 0ull;
 		if(ORDER && P.unit_cost != NULL) u_begin = __builtin_amdgcn_s_memrealtime();
-		if(x < P.w && y < P.y1)
+		if(x < fw && y < fy1)
 		{
-			const uint32_t seed = pixel_seed(x, y, P.w);
+			const uint32_t seed = pixel_seed(x, y, fw);
 			float ox, oy, oz, ow;
-			const uint32_t o = __umul24((uint32_t)y, (uint32_t)P.w) + (uint32_t)x;      // w, h <= 32768 (pwn_init)
+			const uint32_t o = __umul24((uint32_t)y, (uint32_t)P.w) + (uint32_t)x + org;      // w, h <= 32768 (pwn_init)
 			trace_pixel<COUNT, HAS_W, LISTS>(L, sec_current, seed, from, rayl, ox, oy, oz, ow, zbuf + o, cnt);
 			sbuf[o] = col_pack4(ox, oy, oz, ow);
 		}
@@ -658,14 +706,17 @@ extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size
 		if(P->hits != NULL) return Units<false, PWN_LF_GLOBAL, PWN_KM_HITS>::launch(P, grid, lds_bytes, count, stream);
 		if(P->rays != NULL) return Units<false, PWN_LF_GLOBAL, PWN_KM_RAYS>::launch(P, grid, lds_bytes, count, stream);
 		if(P->views != NULL) return Units<false, PWN_LF_GLOBAL, PWN_KM_VIEWS>::launch(P, grid, lds_bytes, count, stream);
+		if(P->vps != NULL) return Units<false, PWN_LF_GLOBAL, PWN_KM_VIEWPORTS>::launch(P, grid, lds_bytes, count, stream);
 		if(P->perm != NULL || P->unit_cost != NULL) return hipErrorInvalidValue;
 		return Units<false, PWN_LF_GLOBAL, PWN_KM_FRAME>::launch(P, grid, lds_bytes, count, stream);
 	}
 	const bool inl = P->off_recsph != 0u;
-	// a batch of rays (pwn_trace_rays), of their first hits (pwn_trace_hits) or of views (pwn_trace_views): eight variants each, never ordered
+	// a batch of rays (pwn_trace_rays), of their first hits (pwn_trace_hits), of views (pwn_trace_views) or of views of their own sizes
+	// (pwn_trace_viewports): eight variants each, never ordered
 	if(P->hits != NULL) return inl ? Units<false, PWN_LF_INLINE, PWN_KM_HITS>::launch(P, grid, lds_bytes, count, stream) : Units<false, PWN_LF_INDEXED, PWN_KM_HITS>::launch(P, grid, lds_bytes, count, stream);
 	if(P->rays != NULL) return inl ? Units<false, PWN_LF_INLINE, PWN_KM_RAYS>::launch(P, grid, lds_bytes, count, stream) : Units<false, PWN_LF_INDEXED, PWN_KM_RAYS>::launch(P, grid, lds_bytes, count, stream);
 	if(P->views != NULL) return inl ? Units<false, PWN_LF_INLINE, PWN_KM_VIEWS>::launch(P, grid, lds_bytes, count, stream) : Units<false, PWN_LF_INDEXED, PWN_KM_VIEWS>::launch(P, grid, lds_bytes, count, stream);
+	if(P->vps != NULL) return inl ? Units<false, PWN_LF_INLINE, PWN_KM_VIEWPORTS>::launch(P, grid, lds_bytes, count, stream) : Units<false, PWN_LF_INDEXED, PWN_KM_VIEWPORTS>::launch(P, grid, lds_bytes, count, stream);
 	const bool order = P->perm != NULL || P->unit_cost != NULL;
 	if(inl) return order ? Units<true, PWN_LF_INLINE, PWN_KM_FRAME>::launch(P, grid, lds_bytes, count, stream) : Units<false, PWN_LF_INLINE, PWN_KM_FRAME>::launch(P, grid, lds_bytes, count, stream);
 	return order ? Units<true, PWN_LF_INDEXED, PWN_KM_FRAME>::launch(P, grid, lds_bytes, count, stream) : Units<false, PWN_LF_INDEXED, PWN_KM_FRAME>::launch(P, grid, lds_bytes, count, stream);

@@ -261,6 +261,33 @@ class Renderer:
                                       zbuf.ctypes.data if want_z else None), "pwn_trace_views")
         return (sbuf, zbuf) if want_z else sbuf
 
+    def trace_viewports(self, rects, cams, secs, want_z=True, sbuf=None, zbuf=None):
+        """pwn_trace_viewports: n views of their own sizes composited into ONE frame of this context's size in one call.  rects
+        (n,4) int (x, y, w, h), cams (n,4,4) or (n,16), secs (n,).  Returns (h,w) uint32 colour and, with want_z, (h,w) float32
+        depth (else None): rectangle i as trace_screen_centred(cams[i], secs[i]) renders it on a context of w_i x h_i.
+        sbuf / zbuf: the caller's own frame buffers (host_register makes their copies plain DMA)."""
+        rects = _rect_records(rects, "trace_viewports")
+        n = rects.shape[0]
+        cams = np.asarray(cams)
+        if cams.ndim == 3 and cams.shape[1:] == (4, 4):
+            cams = cams.reshape(cams.shape[0], 16)
+        if cams.shape != (n, 16):
+            raise ValueError("trace_viewports: cams must have shape (%d,4,4) or (%d,16), not %s" % (n, n, cams.shape))
+        secs = np.asarray(secs)
+        if secs.shape != (n,):
+            raise ValueError("trace_viewports: secs must have shape (%d,), not %s" % (n, secs.shape))
+        cams = np.ascontiguousarray(cams, np.float32)
+        secs = np.ascontiguousarray(secs, np.float32)
+        if sbuf is None:
+            sbuf = np.empty((self.h, self.w), np.uint32)
+        if not want_z:
+            zbuf = None
+        elif zbuf is None:
+            zbuf = np.empty((self.h, self.w), np.float32)
+        self._chk(lib.pwn_trace_viewports(self._ctx, n, rects.ctypes.data, cams.ctypes.data, secs.ctypes.data, sbuf.ctypes.data,
+                                          zbuf.ctypes.data if want_z else None), "pwn_trace_viewports")
+        return sbuf, zbuf
+
     # -- caller-supplied rays (pwn_trace_rays) --------------------------------
     def pixel_rays(self, cam, xy=None, order="rows"):
         """pixel_rays() at this context's size"""
@@ -599,6 +626,28 @@ def sphere_tables_plan(spheres):
     if rc < 0:
         raise PwnError(rc, "pwn_sphere_tables_plan")
     return _tables_dict(out)
+
+
+def _rect_records(rects, who):
+    """(n,4) int32 rectangles (x, y, w, h), the layout of pwn_viewport"""
+    rects = np.asarray(rects)
+    if rects.ndim != 2 or rects.shape[1] != 4 or rects.shape[0] < 1:
+        raise ValueError("%s: rects must have shape (n,4) with n >= 1, not %s" % (who, rects.shape))
+    if rects.shape[0] > _lib.PWN_VIEWS_MAX:
+        raise ValueError("%s: %d rectangles, at most %d" % (who, rects.shape[0], _lib.PWN_VIEWS_MAX))
+    return np.ascontiguousarray(rects, np.int32)
+
+
+def viewports_plan(W, H, rects, blur):
+    """pwn_viewports_plan: what pwn_trace_viewports would make of these rectangles (n,4: x, y, w, h) in a W x H frame under `blur`
+    passes.  No context, no device.  Returns a dict: ok (the call would accept them), units (16 x 4 units of the launch), pixels
+    (covered), largest (units of the largest view), offender (index of the first rectangle that breaks a rule, or n)."""
+    rects = _rect_records(rects, "viewports_plan")
+    out = (C.c_uint64 * 4)()
+    rc = lib.pwn_viewports_plan(int(W), int(H), int(blur), rects.shape[0], rects.ctypes.data, out)
+    if rc not in (_lib.PWN_OK, _lib.PWN_EINVAL):
+        raise PwnError(rc, "pwn_viewports_plan")
+    return {"ok": rc == _lib.PWN_OK, "units": int(out[0]), "pixels": int(out[1]), "largest": int(out[2]), "offender": int(out[3])}
 
 
 def _ray_records(rays, who):
