@@ -363,6 +363,43 @@ int pwn_call_strips_state(pwn_ctx *ctx, unsigned long long out[6]);
  */
 #define PWN_VIEWS_MAX 1024
 int pwn_trace_views(pwn_ctx *ctx, int n, const float *cams, const float *secs, uint32_t *sbuf, float *zbuf);
+/*
+ * The device form: the same n views from cameras in device memory into planes in device memory, stream-ordered on `stream` (a
+ * hipStream_t, NULL = default stream) like pwn_trace_rays_device -- no synchronisation, no host copy.  Observations of many agents
+ * as tensors, previews composited on the device.
+ *   d_cams, d_secs       n x 16 floats (rows x,y,z,w as above) and n floats.
+ *   d_sbuf               n x h x w BGRA8, view-major: the finished views.
+ *   d_zbuf               n x h x w floats, required, in / out: the CALLER's depth planes stand where the host form has its view
+ *                        slots.  A primary ray that runs out of steps keeps what the plane holds (trace.h:677), as a ray of
+ *                        pwn_trace_rays keeps its depth.
+ *   d_work               n x h x w words of scratch: required when PWN_OPT_BLUR_PASSES > 0, may be NULL when it is 0.  The trace
+ *                        writes whichever of d_work / d_sbuf makes the last blur pass land in d_sbuf (d_work for an odd number of
+ *                        passes); what d_work holds afterwards is unspecified.
+ *                        All five pointers are 16-byte aligned.
+ *   launches             one camera set-up launch, one trace launch, one blur launch per pass, all on `stream`.  The trace launch
+ *                        falls under the rule for trace launches at the top of this file.
+ *   exactness            view i is bit-identical, colour and depth, to view i of pwn_trace_views with the same cameras, times and
+ *                        PWN_OPT_BLUR_PASSES, provided d_zbuf on entry holds what that call's view slots held (zero for a fresh
+ *                        context) -- and so to pwn_trace_screen_centred.  The camera set-up runs on the device with the host's
+ *                        arithmetic, operation for operation, denormals kept.
+ *   w lanes              cameras with w components need PWN_VIEWS_HAS_W; without it the w lanes are taken as 0, 0, 0, 1 whatever
+ *                        the cameras hold (as PWN_RAYS_HAS_W).  PWN_DBG_FORCE_HASW forces the 4-lane variants and changes nothing.
+ *   records              the view records are the library's: PWN_VIEWS_MAX per set of work-queue counters (480 KB in all), allocated
+ *                        by the first call, freed by pwn_destroy.  A launch uses the records of the counter set it counts in, so a
+ *                        launch that may run beside it on the other stream never shares them.
+ *   counters             as pwn_trace_rays_device: with PWN_OPT_COUNTERS on the counting variant runs, summed over the views.  The
+ *                        call sets no timings.
+ *   not followed         as pwn_trace_views.
+ *   left alone           what pwn_trace_views leaves alone, and its view slots, the planes of pwn_trace_viewports and the
+ *                        call-strips calibration window.
+ *   errors               PWN_EINVAL for NULL ctx / d_cams / d_secs / d_sbuf / d_zbuf, NULL d_work with blur on, n < 1,
+ *                        n > PWN_VIEWS_MAX, n x w x h > 2^28, flags other than PWN_VIEWS_HAS_W, a pointer that is not 16-byte
+ *                        aligned, w % 4 != 0 with blur on, any two of the plane ranges d_work / d_sbuf / d_zbuf overlapping;
+ *                        PWN_ENOLEVEL, PWN_ENOTSUP and PWN_EBUSY as pwn_trace_views.  A refused call launches nothing.
+ */
+#define PWN_VIEWS_HAS_W 1           /* flags of pwn_trace_views_device: honour the w lanes of the cameras */
+int pwn_trace_views_device(pwn_ctx *ctx, int n, const void *d_cams, const void *d_secs, int flags,
+	void *d_work, void *d_sbuf, void *d_zbuf, void *stream);
 
 /*
  * trace_screen_centred(lv, x1, y1, x2, y2, cam) (screen.h:31-40) for n views of their OWN sizes, composited on the device into

@@ -27,6 +27,7 @@ PWN_OBJ_MAX = 10000
 PWN_TABLES_MAX = 16 << 20
 PWN_VIEWS_MAX = 1024
 PWN_RAYS_HAS_W = 1
+PWN_VIEWS_HAS_W = 1
 PWN_RAYS_MAX = 1 << 28
 PWN_HIT_NONE, PWN_HIT_WALL, PWN_HIT_SPHERE = 0, 1, 2
 (PROBE_RCP, PROBE_RSQRT, PROBE_SINF, PROBE_COSF, PROBE_EXPF, PROBE_SQRT, PROBE_DIV,
@@ -122,6 +123,7 @@ ABI = [
     ("pwn_host_unregister", _i, [_vp, _vp]),
     ("pwn_call_strips_state", _i, [_vp, _vp]),
     ("pwn_trace_views", _i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    ("pwn_trace_views_device", _i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     ("pwn_viewports_plan", _i, [_i, _i, _i, _i, _vp, _vp]),
     ("pwn_trace_viewports", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     ("pwn_pixel_rays", _i, [_i, _i, _vp, _i, _vp, _vp, _vp]),

@@ -95,7 +95,7 @@ extern "C" int pwn_init(pwn_ctx **out, int device, int width, int height)
 	for(int i = 0; i < PWN_NSTAGE; i++) { c->h_stage[i] = NULL; c->ev_stage[i] = NULL; c->stage_used[i] = false; }
 	c->d_pre = c->d_out = NULL; c->d_z = NULL; c->d_skip = NULL; c->d_counters = NULL; c->d_tickets = NULL; c->ticket_set = 0; c->launch_rot = 2; c->launch_waits = 0;
 	c->grid_reserve = 0;
-	c->d_vpre = c->d_vout = NULL; c->d_vz = NULL; c->views_cap = 0; c->h_vrec = c->d_vrec = NULL; c->vrec_cap = 0;
+	c->d_vpre = c->d_vout = NULL; c->d_vz = NULL; c->views_cap = 0; c->h_vrec = c->d_vrec = NULL; c->vrec_cap = 0; c->d_vrec_dev = NULL;
 	c->d_ppre = c->d_pout = NULL; c->d_pz = NULL; c->h_prec = c->d_prec = NULL;
 	c->h_rays = c->d_rays = NULL; c->rays_cap = 0;
 	c->h_hits = c->d_hits = NULL; c->hits_cap = 0;
@@ -244,7 +244,7 @@ extern "C" void pwn_destroy(pwn_ctx *c)
 	if(c->up_stream) (void)hipStreamDestroy(c->up_stream);
 	(void)hipFree(c->d_pre); (void)hipFree(c->d_out); (void)hipFree(c->d_z); (void)hipFree(c->d_pre2);
 	(void)hipFree(c->d_wave_log);
-	(void)hipFree(c->d_vpre); (void)hipFree(c->d_vout); (void)hipFree(c->d_vz); (void)hipFree(c->d_vrec);
+	(void)hipFree(c->d_vpre); (void)hipFree(c->d_vout); (void)hipFree(c->d_vz); (void)hipFree(c->d_vrec); (void)hipFree(c->d_vrec_dev);
 	if(c->h_vrec) (void)hipHostFree(c->h_vrec);
 	(void)hipFree(c->d_ppre); (void)hipFree(c->d_pout); (void)hipFree(c->d_pz); (void)hipFree(c->d_prec);
 	if(c->h_prec) (void)hipHostFree(c->h_prec);
@@ -888,10 +888,8 @@ static void unit_div_magic(uint32_t d, uint32_t *magic, int *shift)
 
 static void frame_setup(int w, int h, const float cam[16], pwn_trace_params *P)
 {
-	float dimx = (float)w, dimy = (float)h;
-	float yrat = (-dimy) / dimx;
-	float xsrat = -2.0f / dimx;
-	float ysrat = (yrat + yrat) / dimy;
+	const pwn_setup_scalars S = pwn_frame_setup_scalars(w, h);
+	const float yrat = S.yrat, xsrat = S.xsrat, ysrat = S.ysrat;
 	for(int i = 0; i < 4; i++)
 	{
 		P->rayb[i] = (cam[0 + i] + cam[8 + i]) + (-yrat) * cam[4 + i];
@@ -1757,6 +1755,53 @@ extern "C" int pwn_trace_views(pwn_ctx *c, int n, const float *cams, const float
 	(void)hipEventElapsedTime(&c->stats.trace_ms, c->ev[0], c->ev[1]);
 	(void)hipEventElapsedTime(&c->stats.blur_ms, c->ev[1], c->ev[2]);
 	(void)hipEventElapsedTime(&c->stats.total_ms, c->ev[0], c->ev[3]);
+	return PWN_OK;
+}
+
+// The device form: cameras and planes of the caller's in device memory, everything on the caller's stream, nothing waited for.
+// frame_setup runs on the device (view_setup.hip), into records of the library's.
+extern "C" int pwn_trace_views_device(pwn_ctx *c, int n, const void *d_cams, const void *d_secs, int flags,
+	void *d_work, void *d_sbuf, void *d_zbuf, void *stream)
+{
+	GRP_REFUSE(c, "pwn_trace_views_device");
+	if(c == NULL || d_cams == NULL || d_secs == NULL || d_sbuf == NULL || d_zbuf == NULL || n < 1 || n > PWN_VIEWS_MAX ||
+	   (flags & ~PWN_VIEWS_HAS_W) != 0) return PWN_EINVAL;
+	const size_t plane = (size_t)c->w * (size_t)c->h;
+	if((size_t)n * plane > ((size_t)1 << 28)) return PWN_EINVAL;
+	if(c->blur_passes > 0 && ((c->w & 3) != 0 || d_work == NULL)) return PWN_EINVAL;
+	if((((uintptr_t)d_cams | (uintptr_t)d_secs | (uintptr_t)d_work | (uintptr_t)d_sbuf | (uintptr_t)d_zbuf) & 15u) != 0) return PWN_EINVAL;
+	{
+		const uintptr_t bytes = (uintptr_t)n * plane * 4, p[3] = { (uintptr_t)d_sbuf, (uintptr_t)d_zbuf, (uintptr_t)d_work };
+		for(int i = 0; i < 3; i++) for(int k = i + 1; k < 3; k++)
+			if(p[i] != 0 && p[k] != 0 && p[i] < p[k] + bytes && p[k] < p[i] + bytes) return PWN_EINVAL;
+	}
+	if(c->tiled != NULL) return PWN_EBUSY;
+	if(!c->have_level) return PWN_ENOLEVEL;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	// (tables that cannot be packed refuse the call before anything is launched)
+	if(c->blob_dirty) { const int rc = pack_blob(c); if(rc != PWN_OK) return rc; }
+	if(c->d_vrec_dev == NULL) HIPCHK(c, hipMalloc((void **)&c->d_vrec_dev, (size_t)PWN_TICKET_SETS * PWN_VIEWS_MAX * sizeof(pwn_view_rec)));
+	// The records of the ticket set the trace launch below counts in (pwn_i_launch_trace): the launch that read them last is the
+	// one 2R launches back, and launch n - R is behind it.  On one stream and in the rotation over R this stream is behind launch
+	// n - R by itself; a call that leaves the pattern is put there before its set-up kernel writes, as its trace launch will be.
+	const unsigned rot = (unsigned)c->launch_rot;
+	if(c->launch_event[rot - 1] != NULL && c->launch_stream[rot - 1] != s) HIPCHK(c, hipStreamWaitEvent(s, c->launch_event[rot - 1], 0));
+	pwn_view_rec *recs = c->d_vrec_dev + (size_t)(c->ticket_set % (2u * rot)) * PWN_VIEWS_MAX;
+	HIPCHK(c, pwn_launch_view_setup((const float *)d_cams, (const float *)d_secs, recs, n, c->w, c->h, s));
+	// the trace into the plane from which the last blur pass lands in d_sbuf
+	uint32_t *cur = (c->blur_passes & 1) ? (uint32_t *)d_work : (uint32_t *)d_sbuf;
+	uint32_t *other = (c->blur_passes & 1) ? (uint32_t *)d_sbuf : (uint32_t *)d_work;
+	pwn_trace_launch T = { .y0 = 0, .y1 = c->h, .views = { recs, n, (flags & PWN_VIEWS_HAS_W) != 0, plane }, .d_sbuf = cur, .d_zbuf = (float *)d_zbuf, .stream = s };
+	int rc = pwn_i_launch_trace(c, &T);
+	if(rc != PWN_OK) return rc;
+	for(int p = 0; p < c->blur_passes; p++)
+	{
+		const pwn_blur_launch B = { .y0 = 0, .y1 = c->h, .d_pre = cur, .d_z = (const float *)d_zbuf, .d_out = other, .stream = s, .views = n };
+		rc = pwn_i_launch_blur(c, &B);
+		if(rc != PWN_OK) return rc;
+		uint32_t *t = cur; cur = other; other = t;
+	}
 	return PWN_OK;
 }
 

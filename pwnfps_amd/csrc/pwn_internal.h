@@ -90,8 +90,23 @@ extern "C" hipError_t pwn_launch_blur(const pwn_blur_params *P, hipStream_t stre
 extern "C" hipError_t pwn_launch_order(const uint16_t *cost, uint32_t units, uint32_t cap, uint32_t *perm, hipStream_t stream);
 extern "C" hipError_t pwn_launch_upscale(const uint32_t *src, uint32_t *dst, int w, int h, int scale, int pitch, hipStream_t stream);
 extern "C" hipError_t pwn_launch_upload(const void *h_pinned_src, void *d_dst, size_t bytes, hipStream_t stream);
+// the camera set-up of n views from device memory (view_setup.hip): d_cams n x 16 floats and d_out 16-byte aligned
+extern "C" hipError_t pwn_launch_view_setup(const float *d_cams, const float *d_secs, pwn_view_rec *d_out, int n, int w, int h, hipStream_t stream);
 extern "C" hipError_t pwn_launch_words(const uint32_t *d_all, const uint32_t *d_own, uint32_t *h_pinned_dst, int world, hipStream_t stream);
 extern "C" hipError_t pwn_launch_probe(int op, const uint32_t *in, uint32_t *out, int n, const uint16_t *tabs, hipStream_t stream);
+
+// The camera-independent scalars of the camera set-up (screen.h:43-57) of a w x h frame, in the reference build's operation
+// order: frame_setup (pwn_api.cpp) and the device's set-up (view_setup.hip) both take them from here, computed on the host.
+struct pwn_setup_scalars { float yrat, xsrat, ysrat; };
+static inline pwn_setup_scalars pwn_frame_setup_scalars(int w, int h)
+{
+	float dimx = (float)w, dimy = (float)h;
+	pwn_setup_scalars s;
+	s.yrat = (-dimy) / dimx;
+	s.xsrat = -2.0f / dimx;
+	s.ysrat = (s.yrat + s.yrat) / dimy;
+	return s;
+}
 
 // LDS budget for the table blob: leave room so that at least two workgroups
 // fit per CU (160 KiB LDS per CU on gfx950)
@@ -244,6 +259,9 @@ struct pwn_ctx
 	// by slot and are kept when the count grows), the records of the call in pinned staging and on the device
 	uint32_t *d_vpre, *d_vout; float *d_vz; int views_cap;
 	pwn_view_rec *h_vrec, *d_vrec; int vrec_cap;
+	// pwn_trace_views_device: PWN_VIEWS_MAX records per ticket set, written by the set-up kernel of the call whose trace launch
+	// counts in that set (so reuse is ordered as the sets' is); allocated by the first call
+	pwn_view_rec *d_vrec_dev;
 	// pwn_trace_viewports: one pre-blur, one colour and one depth plane of w x h (the depth plane persists by pixel), the records
 	// of the call in pinned staging and on the device (PWN_VIEWS_MAX of them)
 	uint32_t *d_ppre, *d_pout; float *d_pz;

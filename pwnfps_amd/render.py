@@ -261,6 +261,39 @@ class Renderer:
                                       zbuf.ctypes.data if want_z else None), "pwn_trace_views")
         return (sbuf, zbuf) if want_z else sbuf
 
+    def trace_views_device(self, cams, secs, sbuf, zbuf, work=None, has_w=False, stream=None):
+        """pwn_trace_views_device: the batch of trace_views from cameras on the GPU into planes on the GPU, stream-ordered, no
+        synchronisation and no host copy.  All torch tensors on this context's GPU, contiguous: cams (n,16) or (n,4,4) float32,
+        secs (n,) float32, sbuf (n,h,w) int32 or uint32 (the finished views), zbuf (n,h,w) float32 (in / out: a primary ray that
+        runs out of steps keeps what it holds), work (n,h,w) int32 or uint32 scratch, needed with blur on.  has_w: honour the
+        cameras' w lanes (PWN_VIEWS_HAS_W; else they are taken as 0, 0, 0, 1).  stream: a torch.cuda.Stream or a raw hipStream_t;
+        None = torch's current stream on the tensors' device."""
+        import torch
+        who = "trace_views_device"
+        words = (torch.int32, getattr(torch, "uint32", torch.int32))
+        if isinstance(cams, torch.Tensor) and cams.dim() == 3 and tuple(cams.shape[1:]) == (4, 4) and cams.is_contiguous():
+            cams = cams.view(cams.shape[0], 16)
+        n = _tensor_check(torch, cams, "cams", (torch.float32,), 2, who=who)
+        if cams.shape[1] != 16 or n < 1 or n > _lib.PWN_VIEWS_MAX:
+            raise ValueError("%s: cams must have shape (n,4,4) or (n,16) with 1 <= n <= %d, not %s" % (who, _lib.PWN_VIEWS_MAX, tuple(cams.shape)))
+        _tensor_check(torch, secs, "secs", (torch.float32,), 1, n, who=who)
+        planes = [("sbuf", sbuf, words), ("zbuf", zbuf, (torch.float32,))] + ([("work", work, words)] if work is not None else [])
+        for name, t, dtypes in planes:
+            _tensor_check(torch, t, name, dtypes, 3, n, who=who)
+            if tuple(t.shape) != (n, self.h, self.w):
+                raise ValueError("%s: %s must have shape (%d,%d,%d), not %s" % (who, name, n, self.h, self.w, tuple(t.shape)))
+        for name, t in [("secs", secs)] + [(name, t) for name, t, _ in planes]:
+            if t.device != cams.device:
+                raise ValueError("%s: tensors on %s and %s" % (who, cams.device, t.device))
+        if stream is None:
+            stream = torch.cuda.current_stream(cams.device)
+        if not isinstance(stream, int):
+            stream = stream.cuda_stream
+        self._chk(lib.pwn_trace_views_device(self._ctx, n, C.c_void_p(cams.data_ptr()), C.c_void_p(secs.data_ptr()),
+                                             _lib.PWN_VIEWS_HAS_W if has_w else 0,
+                                             C.c_void_p(work.data_ptr() if work is not None else None), C.c_void_p(sbuf.data_ptr()),
+                                             C.c_void_p(zbuf.data_ptr()), C.c_void_p(stream or 0)), "pwn_trace_views_device")
+
     def trace_viewports(self, rects, cams, secs, want_z=True, sbuf=None, zbuf=None):
         """pwn_trace_viewports: n views of their own sizes composited into ONE frame of this context's size in one call.  rects
         (n,4) int (x, y, w, h), cams (n,4,4) or (n,16), secs (n,).  Returns (h,w) uint32 colour and, with want_z, (h,w) float32
@@ -669,14 +702,14 @@ def _ray_records(rays, who):
     return np.ascontiguousarray(rays, np.float32)
 
 
-def _tensor_check(torch, t, name, dtypes, ndim, n=None):
+def _tensor_check(torch, t, name, dtypes, ndim, n=None, who="trace_rays_device"):
     if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-        raise ValueError("trace_rays_device: %s must be a GPU tensor" % name)
+        raise ValueError("%s: %s must be a GPU tensor" % (who, name))
     if t.dtype not in dtypes or t.dim() != ndim or (n is not None and t.shape[0] != n) or not t.is_contiguous():
-        raise ValueError("trace_rays_device: %s must be a contiguous %s tensor of %d dimension(s)%s, not %s %s" % (
-            name, "/".join(str(d) for d in dtypes), ndim, "" if n is None else " and %d rows" % n, t.dtype, tuple(t.shape)))
+        raise ValueError("%s: %s must be a contiguous %s tensor of %d dimension(s)%s, not %s %s" % (
+            who, name, "/".join(str(d) for d in dtypes), ndim, "" if n is None else " and %d rows" % n, t.dtype, tuple(t.shape)))
     if t.data_ptr() % 4 != 0:
-        raise ValueError("trace_rays_device: %s is not 4-byte aligned" % name)
+        raise ValueError("%s: %s is not 4-byte aligned" % (who, name))
     return t.shape[0]
 
 

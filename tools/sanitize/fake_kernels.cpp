@@ -74,6 +74,27 @@ extern "C" hipError_t pwn_launch_upscale(const uint32_t *src, uint32_t *dst, int
 	return hipSuccess;
 }
 extern "C" hipError_t pwn_launch_upload(const void *src, void *dst, size_t bytes, hipStream_t) { memcpy(dst, src, bytes); return hipSuccess; }
+// (the camera set-up of pwn_trace_views_device: view_setup.hip's arithmetic, on "device" memory that is host memory here)
+extern "C" hipError_t pwn_launch_view_setup(const float *cams, const float *secs, pwn_view_rec *out, int n, int w, int h, hipStream_t)
+{
+	const pwn_setup_scalars S = pwn_frame_setup_scalars(w, h);
+	for(int v = 0; v < n; v++)
+	{
+		const float *cam = cams + 16 * (size_t)v;
+		pwn_view_rec r;
+		memset(&r, 0, sizeof(r));
+		for(int i = 0; i < 4; i++)
+		{
+			r.rayb[i] = (cam[0 + i] + cam[8 + i]) + (-S.yrat) * cam[4 + i];
+			r.rdx[i] = S.xsrat * cam[0 + i];
+			r.rdy[i] = S.ysrat * cam[4 + i];
+			r.from[i] = cam[12 + i];
+		}
+		r.sec_current = secs[v];
+		out[v] = r;
+	}
+	return hipSuccess;
+}
 extern "C" hipError_t pwn_launch_words(const uint32_t *all, const uint32_t *own, uint32_t *h, int world, hipStream_t)
 {
 	for(int i = 0; i < 2 * world + 2; i++) h[i] = i < 2 * world ? all[i] : own[i - 2 * world];
