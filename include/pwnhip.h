@@ -273,6 +273,17 @@ int pwn_get_bins(pwn_ctx *ctx, uint16_t counts[4096], int32_t *idx, int cap);
      out[3]  (cell, sphere) pairs    out[4]  non-empty cells    out[5]  the longest cell list
    PWN_OK; PWN_ETOOBIG (out is filled in all the same); PWN_EINVAL for NULL spheres or out, n < 0, n > PWN_OBJ_MAX. */
 int pwn_sphere_tables_plan(const pwn_sphere *spheres, int n, unsigned long long out[6]);
+/* The bounding balls the next upload of these n spheres would make, under the default scheduler (and PWN_SPHERE_LISTS, as above): the
+   trace kernels skip a cell's whole sphere list for a wave none of whose rays can meet the list's ball.  At most PWN_BOUNDS_MAX
+   lists get one -- those with the most records, of equally long ones the lower cell first, none shorter than four records; a list
+   with a member that is not finite, further out than 1024 on an axis, or more than 1.5 from the members' mean including its
+   radius gets none.  Host only.  Returns how many balls there are (out[i] for the rest is zero), or PWN_EINVAL / PWN_ETOOBIG /
+   PWN_ENOMEM as pwn_sphere_tables_plan.  PWN_SPHERE_BOUNDS=0 in the environment makes every context of the process launch without
+   them (tests, A/B); this function reports them all the same.
+     out[i][0]  the list's cell, z * 64 + x    out[i][1]  its records    out[i][2]  the list's id in the cell word (bits 16..30)
+     out[i][3..5]  centre x, y, z (fp32 values)    out[i][6]  effective radius    out[i][7]  its square as the kernel compares it */
+#define PWN_BOUNDS_MAX 4
+int pwn_sphere_bounds_plan(const pwn_sphere *spheres, int n, double out[PWN_BOUNDS_MAX][8]);
 /* The same six values for the tables in force in this context, under its scheduler (a pwn_init_multi handle: member 0's). */
 int pwn_sphere_tables_state(pwn_ctx *ctx, unsigned long long out[6]);
 

@@ -111,6 +111,7 @@ ABI = [
     ("pwn_upload_spheres", _i, [_vp, _vp, _i]),
     ("pwn_get_bins", _i, [_vp, _vp, _vp, _i]),
     ("pwn_sphere_tables_plan", _i, [_vp, _i, _vp]),
+    ("pwn_sphere_bounds_plan", _i, [_vp, _i, _vp]),
     ("pwn_sphere_tables_state", _i, [_vp, _vp]),
     ("pwn_obj_new", _i, [_vp]),
     ("pwn_obj_set_sphere", _i, [_vp, _i, _d, _d, _d, _d, _d, _d, _d, _d]),

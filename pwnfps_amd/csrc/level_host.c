@@ -8,11 +8,14 @@
  *   pwn_bake_cells      what the walk's portal arms ask of a cell (trace.h:404-413,
  *                       508-559), decided once per level: cell_bake.h
  *
+ *   pwn_sphere_bounds_build   a bounding ball for the longest per-cell lists (sphere_bound.h)
+ *
  * All produce flat tables that pwn_api.cpp packs into the LDS blob.
  */
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
+#include <math.h>
 #include "level_host.h"
 
 enum { DIR_XP = 0, DIR_ZP, DIR_XN, DIR_ZN };
@@ -268,4 +271,71 @@ int pwn_bin_spheres(const pwn_sphere *s, int n, int32_t *off, int32_t *idx, int 
 	}
 	free(fill);
 	return off[4096];
+}
+
+/* Bounding balls for the longest per-cell lists (sphere_bound.h has the predicate, the proof and the constants).
+   off / idx: the lists as pwn_bin_spheres made them; form: PWN_LF_* of the tables they go into (tables.h: 0 indexed, 1 inline, 2 global), which decides what a list's id is
+   (bits 16..30 of its cell's word: tables.h, pack_blob).  The PWN_BOUNDS_MAX lists with the most records are taken, of equally long
+   ones the lower cell first, none shorter than PWN_BOUND_MIN_RECORDS; of those a list gets no ball (and no other list takes its
+   place) when a member is not finite or far out, or its ball would be large.  Returns how many balls it wrote, longest list first. */
+int pwn_sphere_bounds_build(const pwn_sphere *s, const int32_t *off, const int32_t *idx, int form, pwn_sphere_bound *out)
+{
+	int pick[PWN_BOUNDS_MAX], npick = 0;
+	for(int k = 0; k < PWN_BOUNDS_MAX; k++)
+	{
+		int best = -1, best_n = PWN_BOUND_MIN_RECORDS - 1;
+		for(int c = 0; c < 4096; c++)
+		{
+			const int n = off[c + 1] - off[c];
+			if(n <= best_n) continue;
+			int taken = 0;
+			for(int j = 0; j < npick; j++) taken |= pick[j] == c;
+			if(!taken) { best = c; best_n = n; }
+		}
+		if(best < 0) break;
+		pick[npick++] = best;
+	}
+	int nout = 0;
+	for(int k = 0; k < npick; k++)
+	{
+		const int cell = pick[k], k0 = off[cell], k1 = off[cell + 1], n = k1 - k0;
+		/* the list's id in this form: its first entry among the indexed lists (each closed by an end mark), its first record,
+		   or its place among the non-empty cells */
+		uint32_t id = 0;
+		for(int c = 0; c < cell; c++)
+		{
+			const int m = off[c + 1] - off[c];
+			if(m > 0) id += form == 0 ? (uint32_t)m + 1u : (form == 1 ? (uint32_t)m : 1u);
+		}
+		int ok = 1;
+		double mx = 0.0, my = 0.0, mz = 0.0;
+		for(int i = k0; i < k1; i++)
+		{
+			const pwn_sphere *q = &s[idx[i]];
+			const double v[4] = { q->x, q->y, q->z, q->r };
+			for(int j = 0; j < 4; j++) if(!(fabs(v[j]) <= PWN_SB_COORD_LIMIT)) ok = 0;       /* (NaN and the infinities fail this too) */
+			mx += q->x; my += q->y; mz += q->z;
+		}
+		if(!ok) continue;
+		/* the centre the kernel will use: the mean, in fp32 -- the members' distances are taken from THAT point */
+		const float cx = (float)(mx / n), cy = (float)(my / n), cz = (float)(mz / n);
+		double reff = 0.0;
+		for(int i = k0; i < k1; i++)
+		{
+			const pwn_sphere *q = &s[idx[i]];
+			const double dx = (double)q->x - cx, dy = (double)q->y - cy, dz = (double)q->z - cz;
+			const double rho = sqrt(dx * dx + dy * dy + dz * dz) * (1.0 + 1e-12), r = fabs((double)q->r);
+			if(!(rho + r <= PWN_SB_R_LIMIT)) ok = 0;
+			const double a = PWN_SB_D_MAX + rho;
+			const double r0 = rho + sqrt(r * r + PWN_SB_EPS_PROOF * a * a + PWN_SB_ETA);
+			if(r0 > reff) reff = r0;
+		}
+		if(!ok) continue;
+		/* rounded outwards: R_eff up, RR = R_eff^2 up */
+		const float rf = nextafterf((float)(reff * (1.0 + 1.0 / 1048576.0)), INFINITY);
+		const float rr = nextafterf((float)((double)rf * (double)rf), INFINITY);
+		pwn_sphere_bound *b = &out[nout++];
+		b->id = id; b->count = (uint32_t)n; b->cx = cx; b->cy = cy; b->cz = cz; b->rr = rr; b->neg_r = -rf; b->cell = (uint32_t)cell;
+	}
+	return nout;
 }

@@ -78,6 +78,8 @@ extern "C" int pwn_init(pwn_ctx **out, int device, int width, int height)
 	if(const char *e = getenv("PWN_DBG_BLUR_TH")) c->dbg_blur_th = atoi(e);
 	c->dbg_sphere_lists = 0; c->off_recsph = 0;
 	c->dbg_sphere_lists = pwn_i_forced_lists();
+	c->nbounds = 0;
+	{ const char *e = getenv("PWN_SPHERE_BOUNDS"); c->dbg_sphere_bounds = (e != NULL && strcmp(e, "0") == 0) ? 0 : 1; }
 	c->lists_form = PWN_LF_INDEXED; c->big_which = c->big_sph = 0; c->big_high = 0;
 	for(int i = 0; i < PWN_NBLOB; i++) { c->d_big[i] = NULL; c->d_big_cap[i] = 0; }
 	for(int i = 0; i < PWN_NSTAGE; i++) { c->h_big[i] = NULL; c->h_big_cap[i] = 0; }
@@ -539,6 +541,10 @@ static int pack_blob(pwn_ctx *c)
 	c->off_sph = glb ? 0u : (inl ? pwn_t_sph_offset_inl(nrec) : pwn_t_sph_offset(nbin));
 	c->off_recsph = inl ? pwn_t_recsph_offset(nrec) : 0u;
 	c->lists_form = plan.form;
+	// the balls of the longest lists (sphere_bound.h), with the ids these very tables give the lists: they travel in every launch's
+	// arguments (pwn_i_launch_trace)
+	static_assert(PWN_LF_INDEXED == 0 && PWN_LF_INLINE == 1 && PWN_LF_GLOBAL == 2, "pwn_sphere_bounds_build takes the form as a number");
+	c->nbounds = nsph > 0u ? pwn_sphere_bounds_build(c->spheres.data(), c->bin_off.data(), c->bin_idx.data(), plan.form, c->bounds) : 0;
 	// the kernels' layout of a sphere (tables.h): position and r*r in one 16-byte half, the rest in the other
 	{
 		float *sp = glb ? (float *)(c->big.data() + c->big_sph) : (float *)(b + c->off_sph);
@@ -854,6 +860,29 @@ extern "C" int pwn_sphere_tables_plan(const pwn_sphere *s, int n, unsigned long 
 	return rc;
 }
 
+extern "C" int pwn_sphere_bounds_plan(const pwn_sphere *s, int n, double out[PWN_BOUNDS_MAX][8])
+{
+	if(out == NULL || n < 0 || n > PWN_OBJ_MAX || s == NULL) return PWN_EINVAL;
+	std::vector<int32_t> off(4097, 0);
+	const int nb = pwn_bin_spheres(s, n, off.data(), NULL, 0);
+	if(nb < 0) return PWN_ENOMEM;
+	pwn_tables_plan p;
+	const int rc = pwn_i_tables_plan(off.data(), (uint32_t)n, PWN_SCHED_DEFAULT, pwn_i_forced_lists(), &p);
+	if(rc != PWN_OK) return rc;
+	std::vector<int32_t> idx((size_t)(nb > 0 ? nb : 1));
+	if(pwn_bin_spheres(s, n, off.data(), idx.data(), nb) != nb) return PWN_ENOMEM;
+	pwn_sphere_bound b[PWN_BOUNDS_MAX];
+	const int k = n > 0 ? pwn_sphere_bounds_build(s, off.data(), idx.data(), p.form, b) : 0;
+	memset(out, 0, sizeof(double) * PWN_BOUNDS_MAX * 8);
+	for(int i = 0; i < k; i++)
+	{
+		double *o = out[i];
+		o[0] = (double)b[i].cell; o[1] = (double)b[i].count; o[2] = (double)b[i].id;
+		o[3] = b[i].cx; o[4] = b[i].cy; o[5] = b[i].cz; o[6] = -(double)b[i].neg_r; o[7] = b[i].rr;
+	}
+	return k;
+}
+
 extern "C" int pwn_sphere_tables_state(pwn_ctx *c, unsigned long long out[6])
 {
 	if(GRP_HEAD(c)) { const int rc = pwn_group_sync(c); return rc != PWN_OK ? rc : pwn_sphere_tables_state(GRP_M0(c), out); }      // (as pwn_get_bins)
@@ -1040,6 +1069,13 @@ int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L)
 		P.g_rec = (const float *)c->d_big[cur];
 		P.g_which = (const uint32_t *)(c->d_big[cur] + c->big_which);
 		P.g_sph = (const float *)(c->d_big[cur] + c->big_sph);
+	}
+	// the balls of these tables' longest lists (pack_blob made them with the tables; a launch reads no tables but c->blob_cur's)
+	P.nbounds = c->dbg_sphere_bounds ? c->nbounds : 0;
+	for(int i = 0; i < PWN_BOUNDS_MAX; i++)
+	{
+		P.bound_ids[i] = 0xffffffffu;
+		if(i < P.nbounds) { P.bounds[i] = c->bounds[i]; P.bound_ids[i] = c->bounds[i].id; }
 	}
 	// the upload of these tables runs on its own stream: this launch comes after it
 	if(c->upload_pending[cur])

@@ -119,7 +119,7 @@ static inline pwn_setup_scalars pwn_frame_setup_scalars(int w, int h)
                           // of frame f+1's tables had to wait for the end of frame f-1 and so ran right where trace f starts;
                           // with three or four it runs at once, somewhere beside the trace grid: 0.3823 -> 0.3790 ms per 4K frame
 #endif
-#define PWN_NCOUNTERS 48     // device counters of the counting kernel variants: 16 (pwn_stats) + 24 regions + spare
+#define PWN_NCOUNTERS 48     // device counters of the counting kernel variants: 16 (pwn_stats) + 26 regions + waves + spare
 #define PWN_TILED_STREAMS_DEFAULT 2
 #define PWN_TICKET_SETS 6u  // launch n counts in set n mod 2R and clears set (n + R) mod 2R, R = pwn_ctx.launch_rot streams in rotation, 2 or 3 (pwn_i_launch_trace)
 #define PWN_NSTAGE 4      // pinned staging buffers for those uploads
@@ -221,6 +221,8 @@ struct pwn_ctx
 	// buffer i of the ring has h_big[i] beside h_stage[i].  All of them are allocated with the first tables that need them and
 	// grown to the largest so far (big_high); pack_blob says what growing waits for.
 	int lists_form;                  // PWN_LF_* of the tables in force
+	pwn_sphere_bound bounds[PWN_BOUNDS_MAX]; int nbounds;      // the balls of their longest lists (sphere_bound.h), made with them by pack_blob
+	int dbg_sphere_bounds;           // PWN_SPHERE_BOUNDS of the environment: 0 = launches are sent no balls (tests, A/B in one process)
 	std::vector<uint8_t> big; uint64_t big_which, big_sph;
 	uint8_t *d_big[PWN_NBLOB]; size_t d_big_cap[PWN_NBLOB];
 	uint8_t *h_big[PWN_NSTAGE]; size_t h_big_cap[PWN_NSTAGE];

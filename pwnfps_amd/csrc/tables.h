@@ -42,6 +42,7 @@
 #pragma once
 #include <stdint.h>
 #include "cell_bake.h"
+#include "sphere_bound.h"
 
 #define PWN_GRID_PITCH 65u
 #define PWN_T_RCP      0u
@@ -213,6 +214,15 @@ struct pwn_trace_params
 	const struct pwn_viewport_rec *vps;
 	int nvp;
 	uint32_t vp_step0;
+	// Bounding balls of the longest per-cell lists (sphere_bound.h; pwn_sphere_bounds_build): nbounds of them, made from the lists
+	// that THIS launch's copy of the tables was packed from.  By value in the launch's arguments, so that launches in flight on two
+	// streams and the copies of the tables stay consistent, and because no form of the tables has room for them (their byte sizes are
+	// pinned: pwn_sphere_tables_plan).  The walk reads them with scalar loads from the kernel's arguments (trace_walk.inc): the four ids at
+	// once -- bound_ids[k] = bounds[k].id, 0xffffffff where there is none -- then the one record.  nbounds = 0: PWN_SPHERE_BOUNDS=0, or no list
+	// long enough.
+	int nbounds;
+	uint32_t bound_ids[PWN_BOUNDS_MAX];
+	pwn_sphere_bound bounds[PWN_BOUNDS_MAX];
 };
 #define PWN_HIT_REC_BYTES 48u
 

@@ -40,6 +40,8 @@ enum { FXP = 0, FZP, FXN, FZN, FYP, FYN };   // defs.h:25-33
 // access is a ds_read with an immediate offset; through the `extern __shared__` symbol every access adds that
 // symbol's address (0, but known too late to fold): 21 `v_add_u32 v, 0, v` in the kernel, one per cell step.
 #define PWN_LDS __attribute__((address_space(3)))
+// (the kernel's arguments where the hardware puts them: pwn_trace_params is the one argument of both trace kernels, at offset 0)
+#define PWN_KARGS __attribute__((address_space(4)))
 template<class T> __device__ __forceinline__ const PWN_LDS T *lds_at(uint32_t byte) { return (const PWN_LDS T *)(uintptr_t)byte; }
 // (16-byte LDS loads as a built-in vector type: HIP's float4 class has no constructor from another address space)
 typedef float pwn_f4 __attribute__((ext_vector_type(4)));
@@ -188,7 +190,9 @@ enum { BASE_CEIL = 0, BASE_FLOOR, BASE_WALL, BASE_MAGENTA, BASE_ROOM_Y };
 // (pwn_stats.regions).  The walk's own paths are the older wave_paths counters (WAVE_PATH) and wave_steps.
 enum { RG_SEG = 0, RG_SETUP_SLOW, RG_EXHAUSTED, RG_WALL, RG_SPHERE, RG_FLOOR, RG_SPHREFL, RG_JITTER, RG_COMP1, RG_COMP1_FOG,
 	RG_COMP2, RG_COMP2_FOG, RG_HELP, RG_UNIT, RG_SPHTEST, RG_SPHUPD, RG_ELSE,
-	RG_UNIT_HALF, RG_HC_R2, RG_HC_OUT, RG_PORTAL_WALL, RG_PORTAL_GO, RG_PORTAL_ODD, RG_PORTAL_ROT2, RG_N };
+	RG_UNIT_HALF, RG_HC_R2, RG_HC_OUT, RG_PORTAL_WALL, RG_PORTAL_GO, RG_PORTAL_ODD, RG_PORTAL_ROT2,
+	RG_SPHBOUND, RG_SPHSKIP,       // a list's ball is tested by the wave (trace_walk.inc, sphere_bound.h); ... and the list skipped
+	RG_N };
 struct Counters { uint32_t rays, steps, portals, tests, exhausted, wsteps, wp[8], apasses, apass_lanes, rg[RG_N]; };
 // one count per wave64 that enters a code path with at least one lane (pwn_stats.wave_paths)
 #define WAVE_PATH(k) do { if(COUNT && (__ffsll((long long)__ballot(1)) - 1) == (int)(threadIdx.x & 63)) cnt.wp[k]++; } while(0)

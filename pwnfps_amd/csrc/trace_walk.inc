@@ -41,7 +41,44 @@ if((int)cw < 0)
 {
 	//@R w_sphlist
 	WAVE_PATH(0);
-	if constexpr(LISTS == PWN_LF_GLOBAL)
+	// A list that no lane of the wave can hit is not run (sphere_bound.h: the ball of a long list, the predicate and why a miss of
+	// the ball is a miss of every member).  The balls come with the launch's arguments (tables.h) and are read from there with scalar
+	// loads where they are needed: the id of the first active lane's list; all active lanes on that list (one ballot); that list one
+	// of the launch's few (scalar compares with the four ids); then the lanes' test with the ball as scalar operands -- no register
+	// holds a ball outside this block.  Lanes that stand on different lists, or on a list without a ball, run theirs as ever.
+	// A skipped lane keeps pos, cdist and the candidate aux_* as they are; the sphere-test counter moves on by the list's length, as
+	// if the tests had been made (the counters are the reference's counts).
+	bool sb_skip = false;
+	{
+		//@R w_sphbound
+		const PWN_KARGS pwn_trace_params *KP = (const PWN_KARGS pwn_trace_params *)__builtin_amdgcn_kernarg_segment_ptr();
+		if(KP->nbounds != 0)
+		{
+			const uint32_t lid = (cw >> 16) & 0x7fffu;
+			const uint32_t id0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)lid);
+			if(__ballot(lid != id0) == 0ull)
+			{
+				int k = -1;
+#pragma unroll
+				for(int i = PWN_BOUNDS_MAX - 1; i >= 0; i--) if(KP->bound_ids[i] == id0) k = i;
+				if(k >= 0)
+				{
+					RG(RG_SPHBOUND);
+					const PWN_KARGS pwn_sphere_bound *sb = &KP->bounds[k];
+					const int pass = pwn_sb_pass(HAS_W, pos.x, pos.y, pos.z, pos.w, ray.x, ray.y, ray.z, ray.w, sb->cx, sb->cy, sb->cz, sb->rr, sb->neg_r);
+					if(__ballot(pass) == 0ull)
+					{
+						RG(RG_SPHSKIP);
+						sb_skip = true;
+						if(COUNT) cnt.tests += sb->count;
+					}
+				}
+			}
+		}
+	}
+	//@R w_sphlist
+	if(sb_skip) { }
+	else if constexpr(LISTS == PWN_LF_GLOBAL)
 	{
 		// The records in device memory (tables.h): as the inline arm below, with one 16-byte GLOBAL load per test where that makes an
 		// LDS read.  The cell word names the non-empty cell, liststart (one LDS read per list) the index of its first record;
@@ -50,6 +87,7 @@ if((int)cw < 0)
 		// reads it (pwn_api.cpp).  Every index here comes out of the tables the host packed -- the cell word, liststart, the end
 		// mark of a list -- and none out of a ray: no input bit pattern reaches an address (as argued at the ray modes' loads,
 		// trace_kernel.hip).
+		//@R w_sphrun
 		uint32_t ri = ((const PWN_LDS uint32_t *)L.binidx)[(cw >> 16) & 0x7fffu];
 		pwn_f4 nx = L.g_rec[(size_t)ri];
 		for(;;)
@@ -75,6 +113,7 @@ if((int)cw < 0)
 		// is tested, so that the read's latency passes during the test (behind a list's last record lie the next list or the
 		// "which sphere" array: read, never used).  Two register moves per test more and 0.9 % less launch time at 4K, 2 % at
 		// 720p (profiles/r5/sphere_lists_ab.txt) -- the compiler leaves the read where the source has it, in front of its use.
+		//@R w_sphrun
 		const PWN_LDS pwn_f4 *rp = (const PWN_LDS pwn_f4 *)L.binidx + ((cw >> 16) & 0x7fffu);
 		pwn_f4 nx = *rp;
 		for(;;)
@@ -95,6 +134,7 @@ if((int)cw < 0)
 	}
 	else
 	{
+		//@R w_sphrun
 		const PWN_LDS uint16_t *lp = L.binidx + ((cw >> 16) & 0x7fffu);
 		for(uint32_t si = *lp; si != PWN_LIST_END; si = *++lp)
 		{

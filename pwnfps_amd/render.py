@@ -661,6 +661,20 @@ def sphere_tables_plan(spheres):
     return _tables_dict(out)
 
 
+def sphere_bounds_plan(spheres):
+    """pwn_sphere_bounds_plan: the bounding balls the next upload of these spheres would make for its longest per-cell lists (the
+    trace kernels skip a list whose ball no ray of a wave can meet).  No context, no device.  A list of dicts, longest list first:
+    cell (z * 64 + x), records, id (the list's id in its cell's word), centre (x, y, z), r_eff, rr."""
+    spheres = np.ascontiguousarray(spheres, SPHERE_DTYPE)
+    out = np.zeros((4, 8), np.float64)
+    buf = spheres if len(spheres) else np.zeros(1, SPHERE_DTYPE)
+    rc = lib.pwn_sphere_bounds_plan(buf.ctypes.data, len(spheres), out.ctypes.data)
+    if rc < 0:
+        raise PwnError(rc, "pwn_sphere_bounds_plan")
+    return [{"cell": int(o[0]), "records": int(o[1]), "id": int(o[2]), "centre": (float(o[3]), float(o[4]), float(o[5])),
+             "r_eff": float(o[6]), "rr": float(o[7])} for o in out[:rc]]
+
+
 def _rect_records(rects, who):
     """(n,4) int32 rectangles (x, y, w, h), the layout of pwn_viewport"""
     rects = np.asarray(rects)

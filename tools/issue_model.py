@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Issue model of pwn_trace_kernel<false,false,false,true,0> (frames, no counters, 3 lanes, unit order, inline sphere records): what its instruction stream costs the SIMDs, region by region.
+"""Issue model of pwn_trace_kernel<false, false, false, 1, 0> (frames, no counters, 3 lanes, unit order, inline sphere records): what its instruction stream costs the SIMDs, region by region.
 
     static    the kernel's ISA (hipcc -S with line tables, the Makefile's flags), every instruction attributed to a REGION
               of the source through its .loc chain (the `//@R name` comments of trace_kernel.hip and the .inc files it includes mark
@@ -30,7 +30,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "pwnfps_amd", "csrc")
-KERNEL = "_Z16pwn_trace_kernelILb0ELb0ELb0ELb1ELi0EEv16pwn_trace_params"
+KERNEL = "_Z16pwn_trace_kernelILb0ELb0ELb0ELi1ELi0EEv16pwn_trace_params"
 
 FULL = {"v_add_f32", "v_sub_f32", "v_subrev_f32", "v_mul_f32", "v_fma_f32", "v_fmac_f32", "v_mac_f32", "v_add_u32", "v_sub_u32",
         "v_subrev_u32", "v_and_b32", "v_or_b32", "v_xor_b32", "v_mov_b32", "v_bitop3_b32", "v_not_b32", "v_add_co_u32", "v_addc_co_u32",
@@ -195,7 +195,7 @@ COUNT_OF = {        # region -> key of the counts
     "p_setup": "segs", "p_setup_slow": "setup_slow", "p_walk_ctl": "wave_steps", "p_post": "segs", "p_exhausted": "exhausted_w",
     "p_wall": "wall", "p_sphere": "sphere", "p_floor": "floor", "p_sphrefl": "sphrefl", "p_jitter": "jitter",
     "p_comp": "units", "p_comp1": "comp1", "p_comp1_fog": "comp1_fog", "p_comp2": "comp2", "p_comp2_fog": "comp2_fog",
-    "w_head": "wave_steps", "w_sphlist": "wp0", "w_sphtest": "sphtest", "w_sphhit": "wp7", "w_sphupd": "sphupd",
+    "w_head": "wave_steps", "w_sphlist": "wp0", "w_sphbound": "sphbound", "w_sphrun": "sphrun", "w_sphtest": "sphtest", "w_sphhit": "wp7", "w_sphupd": "sphupd",
     "w_room": "wp1", "w_fog": "wp2", "w_height": "wp3", "w_height_r2": "hc_r2", "w_height_out": "hc_out", "w_else": "else", "w_ramp": "wp4",
     "w_portal": "wp5", "w_portal_wall": "portal_wall", "w_portal_go": "portal_go", "w_portal_odd": "portal_odd", "w_portal_rot2": "portal_rot2",
     "w_solid": "wp6", "k_unit_half": "unit_half",
@@ -222,7 +222,7 @@ def main():
         blocks[reg].add(b)
     lines = []
     P = lines.append
-    P("# issue model of pwn_trace_kernel<false,false,false,true,0> (tools/issue_model.py); static part: %d instructions in %d regions" % (len(ins), len(per)))
+    P("# issue model of pwn_trace_kernel<false, false, false, 1, 0> (tools/issue_model.py); static part: %d instructions in %d regions" % (len(ins), len(per)))
     P("# costs per wave-instruction and SIMD at 5 waves / SIMD (profiles/r3_valu_rate.txt): full-rate VALU %.2f ns, half-rate %.2f ns, quarter-rate %.2f ns"
       % (COST["full"], COST["half"], COST["quarter"]))
     P("")
@@ -244,7 +244,7 @@ def main():
     # the instruction counters of the 4K level.txt launch: the committed PMC summary of the same build
     try:
         rows = [ln.rstrip("\n").rsplit(",", 3) for ln in open(os.path.join(ROOT, "profiles", "pmc_latest.csv"))]
-        v = {r[1]: float(r[3]) for r in rows if len(r) == 4 and "pwn_trace_kernel<false, false, false, true, 0>" in r[0]}
+        v = {r[1]: float(r[3]) for r in rows if len(r) == 4 and "pwn_trace_kernel<false, false, false, 1, 0>" in r[0]}
         for sc in scenes:
             if (sc["level"], sc["w"], sc["h"]) == ("pwnfps_level", 3840, 2160):
                 sc["pmc"] = {k: v[k] for k in ("SQ_INSTS_VALU", "SQ_INSTS_SALU", "SQ_INSTS_BRANCH", "SQ_INSTS_LDS")}
@@ -252,6 +252,8 @@ def main():
         pass
 
     def totals(cnt):
+        # a list's set-up (w_sphrun) runs in the visits that are not skipped: no counter of its own
+        cnt = dict(cnt, sphrun=cnt.get("wp0", 0) - cnt.get("sphskip", 0))
         t = collections.Counter()
         by_region = {}
         for reg, c in per.items():
@@ -262,7 +264,8 @@ def main():
             by_region[reg] = (n, n * (c["full"] + c["half"] + c["quarter"]), sc, valu_ns, n * c["half"])
             t["valu"] += n * (c["full"] + c["half"] + c["quarter"])
             t["half"] += n * c["half"]
-            t["salu"] += n * (c["salu"] + c["smem"])
+            t["salu"] += n * c["salu"]                          # (scalar loads are SQ_INSTS_SMEM to the counters, not SALU)
+            t["smem"] += n * c["smem"]
             t["branch"] += n * c["branch"]
             t["lds"] += n * c["lds"]
             t["valu_ns"] += valu_ns
@@ -289,7 +292,7 @@ def main():
         P("")
         P("## %s %dx%d: launch span %.4f ms (wave stamps; %.4f ms between HIP events around a blocking frame), mean wave residency %.3f -> busy %.4f ms" % (
             sc["level"], sc["w"], sc["h"], span, sc["trace_ms"], res, busy))
-        P("   wave-instructions by the model: VALU %.4g (half-rate %.4g), SALU %.4g, branch %.4g, LDS %.4g" % (t["valu"], t["half"], t["salu"], t["branch"], t["lds"]))
+        P("   wave-instructions by the model: VALU %.4g (half-rate %.4g), SALU %.4g (and %.4g scalar loads), branch %.4g, LDS %.4g" % (t["valu"], t["half"], t["salu"], t["smem"], t["branch"], t["lds"]))
         if sc.get("pmc"):
             pm = sc["pmc"]
             P("   PMC of the same launch:         VALU %.4g, SALU %.4g, branch %.4g, LDS %.4g   (model / PMC: %.3f %.3f %.3f %.3f)" % (
