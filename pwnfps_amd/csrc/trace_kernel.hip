@@ -28,6 +28,13 @@
 #include <hip/hip_runtime.h>
 #include "trace_common.h"
 
+// The walk loops of this file count a segment's cell steps in ev itself (trace_pixel: "How the walk loop ends"): below zero while
+// the ray walks, and what a ray that made WALK_STEPS steps (trace.h:250) without an event leaves the loop with is this file's
+// "out of steps" -- the shared enum's 0, not its EV_EXHAUSTED, which is the refill kernel's.
+#define WALK_STEPS 1000
+#define EV_OUT_OF_STEPS 0
+#define WALK_EV_KEEP ev
+#define WALK_EV_OPEN(e) ((e) <= 0)
 
 // One pixel = trace_ray(0, ...) of screen.h:22-24 with the recursion unrolled.
 template<bool COUNT, bool HAS_W, int LISTS>
@@ -105,27 +112,30 @@ __device__ __forceinline__ void trace_pixel(const Lds &L, float sec_current, uin
 
 		// ------------------------------------------------ trace.h:250-675 (trace_walk.inc)
 		//@R p_walk_ctl
-		// How the walk loop ends: ev per step -- two selects in the room body (sphere hit / floor-ceiling / neither), the
-		// step limit (trace.h:250) folded into it with three more VALU instructions, one compare of ev for the exit.
+		// How the walk loop ends: ev is the step count and the event in one register.  It starts a segment at -WALK_STEPS, is counted up
+		// at the top of every iteration, and a step without an event leaves it as it is (trace_walk.inc WALK_EV_KEEP: the room body's two
+		// selects -- sphere hit / floor-ceiling / neither); the loop runs while ev < 0, one compare.  A lane that leaves with ev == 0 has made
+		// WALK_STEPS steps without an event: out of steps (trace.h:250,677); an event in the last step still wins.  The limit in a counter
+		// of its own, folded into ev at the bottom, was three more VALU and one more scalar instruction per step
+		// (profiles/walk_exit/ab.txt, with both latches as compiled).
 		// Two other forms were built and measured in round 3 (profiles/r3_walk_exit.txt; the code is in commit 2b36426):
 		// the step limit as a scalar count with a branch of its own (-3 VALU, +2 scalar per step: +3.9 % time at 4K), and a
 		// lane mask `done` = hit || ymin with WHICH of the two read off cdist against aux_dist after the walk (-4 VALU,
 		// +10 scalar mask instructions per step as compiled: +5.3 %).  Scalar instructions are not free here.
-		int maxsteps = 1000;
+		ev = -WALK_STEPS;
 #pragma unroll 1
 		do
 		{
+			ev++;
 #include "trace_walk.inc"
-			// trace.h:250,677: out of steps
-			if(--maxsteps == 0 && ev == 0) ev = EV_EXHAUSTED;
-		} while(ev == 0);
+		} while(ev < 0);
 		// what the ray ended on is read back from the register: without this the compiler keeps
-		// "ev == EV_EXHAUSTED" as a lane mask that it updates in every iteration of the walk
+		// "ev == EV_OUT_OF_STEPS" as a lane mask that it updates in every iteration of the walk
 		// (5 of ~85 instructions per step)
 		asm volatile("" : "+v"(ev));
 
 		//@R p_post
-		if(ev == EV_EXHAUSTED)
+		if(ev == EV_OUT_OF_STEPS)
 		{
 			//@R p_exhausted
 			RG(RG_EXHAUSTED);
@@ -207,20 +217,20 @@ __device__ __forceinline__ void trace_hit(const Lds &L, Vec<HAS_W> from, Vec<HAS
 	int ldir, ev, base;
 #include "trace_setup.inc"
 	//@R p_walk_ctl
-	int maxsteps = 1000;
+	// (the step limit is carried in ev: trace_pixel)
+	ev = -WALK_STEPS;
 #pragma unroll 1
 	do
 	{
+		ev++;
 #include "trace_walk.inc"
-		// trace.h:250,677: out of steps
-		if(--maxsteps == 0 && ev == 0) ev = EV_EXHAUSTED;
-	} while(ev == 0);
+	} while(ev < 0);
 	asm volatile("" : "+v"(ev));
 
 	//@R p_post
 	static_assert(EV_WALL == 1 && EV_SPHERE == 2, "pwnhip.h PWN_HIT_WALL, PWN_HIT_SPHERE");
 	uint4 r0, r1, r2;
-	if(ev == EV_EXHAUSTED)
+	if(ev == EV_OUT_OF_STEPS)
 	{
 		// trace.h:677: nothing was hit.  face = object = -1, every other field 0
 		if(COUNT) cnt.exhausted++;

@@ -332,7 +332,11 @@ pwn_trace_refill_kernel(pwn_trace_params P)
 #pragma unroll 1
 			do
 			{
+#define WALK_EV_KEEP 0
+#define WALK_EV_OPEN(e) ((e) == 0)
 #include "trace_walk.inc"
+#undef WALK_EV_KEEP
+#undef WALK_EV_OPEN
 				// wave-uniform: a young ray still walks, and the ended ones have not waited too long
 				const unsigned long long w = __ballot(ev == EV_NONE);
 				waited += (int)__builtin_popcountll(walking0 & ~w);

@@ -2,7 +2,10 @@
 // trace kernels inside their walk loop.  Names it uses from the including scope:
 //   L (Lds), COUNT, HAS_W, LISTS (the form of the per-cell lists, PWN_LF_*: tables.h), V, cnt;  the ray: pos, ray, cxz (cell x | z << 16), sx, sz (the steps (gx, 0) and
 //   (0, gz) in the same packing: trace_common.h), ldx, ldz, ldy, gyp,
-//   wx, wy, wz, iax, iay, iaz, iay_dn, iay_up_bits, cw, cdist, fog, ldir, ev, base, maxsteps;
+//   wx, wy, wz, iax, iay, iaz, iay_dn, iay_up_bits, cw, cdist, fog, ldir, ev, base;
+//   how the including loop spells "no event yet" in ev, which it alone reads for its exit: WALK_EV_KEEP, the value a step without an
+//   event leaves in ev, and WALK_EV_OPEN(ev), true while none has been recorded (trace_refill.hip: 0 and == 0; trace_kernel.hip
+//   carries its step count in ev below zero: ev itself and <= 0);
 //   the nearest sphere candidate: aux_dist, aux_diff, aux_idx, aux_pos;
 //   HITREC (compile-time; false in every kernel that shades): the walk also keeps what a first-hit record needs and the
 //   shading never asks for -- hit_cxz, the reference's cx, cz when the segment returns, and hit_portals, the portals
@@ -199,7 +202,7 @@ if(cw & PWN_C_ROOM)
 	// the mask made by one v_cndmask -- measured 0.5-1 % slower at 4K: five instructions where there are four.  Code in
 	// commit fe41695, profiles/r4/walk_variants.txt.)
 	ldir = xlt ? ldx : ldz;                      // a y exit is patched in after the walk
-	ev = hit ? EV_SPHERE : (ymin ? EV_WALL : 0);
+	ev = hit ? EV_SPHERE : (ymin ? EV_WALL : WALK_EV_KEEP);
 	wy = (wy - txz) - up2;
 	wz = xlt ? wz - txz : iaz;
 	wx = xlt ? iax : wx - txz;
@@ -213,7 +216,7 @@ if(cw & PWN_C_ROOM)
 	// next is 2-high ? current is " : current is 2-high  (DQ sits two bits above ROOM2)
 	static_assert(PWN_C_DQ == (PWN_C_ROOM2 << 2), "the shift below lines DQ up with ROOM2");
 	const uint32_t height_changes = (((cw >> 2) & ncw) | (cw & ~ncw)) & PWN_C_ROOM2;
-	if(height_changes != 0u && !(hit || ymin))          // (ev == 0, from the masks instead of a compare)
+	if(height_changes != 0u && !(hit || ymin))          // (no event, from the masks instead of a compare)
 	{
 		//@R w_height
 		WAVE_PATH(3);
@@ -409,7 +412,7 @@ else
 	}
 	//@R w_else
 	// trace.h:668-673 (in the room body the same test sits right after the step)
-	if(ev == 0 && AUX_HIT()) ev = EV_SPHERE;
+	if(WALK_EV_OPEN(ev) && AUX_HIT()) ev = EV_SPHERE;
 }
-// (trace.h:250,677, running out of steps, is the including loop's business: maxsteps)
+// (trace.h:250,677, running out of steps, is the including loop's business)
 #undef AUX_HIT
