@@ -97,7 +97,7 @@ extern "C" int pwn_init(pwn_ctx **out, int device, int width, int height)
 	for(int i = 0; i < PWN_NSTAGE; i++) { c->h_stage[i] = NULL; c->ev_stage[i] = NULL; c->stage_used[i] = false; }
 	c->d_pre = c->d_out = NULL; c->d_z = NULL; c->d_skip = NULL; c->d_counters = NULL; c->d_tickets = NULL; c->ticket_set = 0; c->launch_rot = 2; c->launch_waits = 0;
 	c->grid_reserve = 0;
-	c->d_vpre = c->d_vout = NULL; c->d_vz = NULL; c->views_cap = 0; c->h_vrec = c->d_vrec = NULL; c->vrec_cap = 0; c->d_vrec_dev = NULL;
+	c->d_vpre = c->d_vout = NULL; c->d_vz = NULL; c->views_cap = 0; c->h_vrec = c->d_vrec = NULL; c->d_vrec_dev = NULL;
 	c->d_ppre = c->d_pout = NULL; c->d_pz = NULL; c->h_prec = c->d_prec = NULL;
 	c->h_rays = c->d_rays = NULL; c->rays_cap = 0;
 	c->h_hits = c->d_hits = NULL; c->hits_cap = 0;
@@ -915,7 +915,8 @@ static void unit_div_magic(uint32_t d, uint32_t *magic, int *shift)
 	*magic = (uint32_t)M; *shift = s;
 }
 
-static void frame_setup(int w, int h, const float cam[16], pwn_trace_params *P)
+// (into a launch's parameters, or into the head that a view's record shares with them: pwn_view_rec, pwn_viewport_rec)
+template<class T> static void frame_setup(int w, int h, const float cam[16], T *P)
 {
 	const pwn_setup_scalars S = pwn_frame_setup_scalars(w, h);
 	const float yrat = S.yrat, xsrat = S.xsrat, ysrat = S.ysrat;
@@ -927,6 +928,11 @@ static void frame_setup(int w, int h, const float cam[16], pwn_trace_params *P)
 		P->from[i] = cam[12 + i];
 	}
 }
+
+// ordinary cameras (rows x,y,z with w = 0, position w = 1: mat4_iden + rotations,
+// main.c:61-64) never put anything but 0 / 1 into the w lanes; the kernel has a
+// 3-lane specialisation for them that is arithmetically identical
+static bool camera_has_w(const float cam[16]) { return !(cam[3] == 0.0f && cam[7] == 0.0f && cam[11] == 0.0f && cam[15] == 1.0f); }
 
 // The ray record and seed of pixels (x, y) of a frame, exactly as the trace kernel makes them: frame_setup, then screen.h:12-18
 // in the reference build's order, rayl = (cx*rdx + rayb) + y*rdy and one "+= rdx" per pixel of the 32-wide tile up to and
@@ -1087,21 +1093,15 @@ int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L)
 	P.clear_word = L->clear_word;
 	P.cost_word = L->cost_word;
 	P.wave_log = NULL;
-	// the kernel's work queues: 2R sets, R = launch_rot; launch n counts in set n mod 2R and clears set (n + R) mod 2R,
-	// the one of the launch R launches on.  Launches of a context are stream-ordered (include/pwnhip.h) -- on ONE stream,
-	// or rotating over the R = 2 compute streams of the frames in flight (pwn_submit_frame) or the R = 2 or 3 of a row
-	// tiling, where launch n + R is behind launch n on its stream and the launches between may run beside it with sets
-	// of their own.
+	// the kernel's work queues: this launch's set and the one it clears (the rotation over 2R sets: pwn_internal.h, launch_stream)
 	const unsigned rot = (unsigned)c->launch_rot, nsets = 2u * rot;
 	P.tickets = c->d_tickets + (c->ticket_set % nsets) * PWN_QUEUES * PWN_QUEUE_STRIDE;
 	P.tickets_next = c->d_tickets + ((c->ticket_set + rot) % nsets) * PWN_QUEUES * PWN_QUEUE_STRIDE;
-	// ordinary cameras (rows x,y,z with w = 0, position w = 1: mat4_iden + rotations,
-	// main.c:61-64) never put anything but 0 / 1 into the w lanes; the kernel has a
-	// 3-lane specialisation for them that is arithmetically identical
+	// the 3-lane or the 4-lane variants (camera_has_w)
 	if(views != NULL) P.has_w = views->has_w;        // (the same rule over all the batch's cameras)
 	else if(rays != NULL) P.has_w = rays->has_w;     // (the rule over the batch's rays: pwn_trace_rays)
 	else if(vps != NULL) P.has_w = vps->has_w;
-	else P.has_w = !(L->cam[3] == 0.0f && L->cam[7] == 0.0f && L->cam[11] == 0.0f && L->cam[15] == 1.0f);
+	else P.has_w = camera_has_w(L->cam);
 	// test hook (tests/test_gpu_fuzz.py): send every camera through the general variant
 	if(c->dbg_force_hasw) P.has_w = 1;
 	if(c->counters_on) HIPCHK(c, hipMemsetAsync(c->d_counters, 0, PWN_NCOUNTERS * sizeof(unsigned long long), stream));
@@ -1357,6 +1357,71 @@ extern "C" int pwn_blur_rows_device_bounded(pwn_ctx *c, int y0, int y1, const vo
 	int rc = pwn_i_launch_blur(c, &B);
 	if(rc == PWN_OK) rc = pwn_i_launch_order(c, (hipStream_t)stream);
 	return rc;
+}
+
+// ---- what the blocking call, the batch calls and the frames in flight share -----
+// (tests/golden/host_calls.txt has, per entry point, what these send to the runtime and the launchers: tools/sanitize/calls_driver.cpp)
+
+// The blocking calls (pwn_trace_screen_centred, pwn_trace_views) on compute stream s: behind the frames in flight, whichever
+// compute stream their kernels are on
+static int wait_frames_in_flight(pwn_ctx *c, hipStream_t s)
+{
+	if(c->last_frame_done != NULL && c->last_frame_stream != s) HIPCHK(c, hipStreamWaitEvent(s, c->last_frame_done, 0));
+	if(c->last_frame_done != NULL && c->stream2 != NULL && c->last_frame_stream != c->stream2) HIPCHK(c, hipStreamWaitEvent(c->stream2, c->last_frame_done, 0));      // (strips use both)
+	c->last_frame_done = NULL;       // (the call ends with the stream empty)
+	return PWN_OK;
+}
+
+// What refuses a batch call once its own arguments are in order (include/pwnhip.h), in the order that decides which code a caller
+// with two faults gets.  views > 0: a call that traces that many views of w x h and blurs them, with the two rules of those.
+static int batch_refuse(const pwn_ctx *c, int views = 0)
+{
+	if(views > 0 && (size_t)views * (size_t)c->w * (size_t)c->h > ((size_t)1 << 28)) return PWN_EINVAL;
+	if(views > 0 && c->blur_passes > 0 && (c->w & 3) != 0) return PWN_EINVAL;
+	if(c->tiled != NULL) return PWN_EBUSY;
+	if(!c->have_level) return PWN_ENOLEVEL;
+	return PWN_OK;
+}
+
+// The blur passes behind a trace into *cur: each pass is B (its rows, depth, stream and views as given) from the plane that holds
+// the frame into the other of the two, which take turns (the memcpy of screen.h:75 becomes a pointer swap per pass); the last pass
+// into `last` where one is given.  *cur is left at the plane that holds the result.
+static int blur_passes_run(pwn_ctx *c, pwn_blur_launch B, uint32_t **cur, uint32_t *other, uint32_t *last = NULL)
+{
+	for(int p = 0; p < c->blur_passes; p++)
+	{
+		B.d_pre = *cur; B.d_out = (last != NULL && p == c->blur_passes - 1) ? last : other;
+		const int rc = pwn_i_launch_blur(c, &B);
+		if(rc != PWN_OK) return rc;
+		other = *cur; *cur = B.d_out;
+	}
+	return PWN_OK;
+}
+
+// The end of a blocking call on stream s, in two steps: "kernels done" (ev[2]), `bytes` of colour and, where the caller wants it,
+// of depth on their way down, "all done" (ev[3]) ...
+static int blocking_copies(pwn_ctx *c, hipStream_t s, uint32_t *sbuf, const uint32_t *d_col, float *zbuf, const float *d_z, size_t bytes)
+{
+	HIPCHK(c, hipEventRecord(c->ev[2], s));
+	HIPCHK(c, hipMemcpyAsync(sbuf, d_col, bytes, hipMemcpyDeviceToHost, s));
+	if(zbuf != NULL) HIPCHK(c, hipMemcpyAsync(zbuf, d_z, bytes, hipMemcpyDeviceToHost, s));
+	HIPCHK(c, hipEventRecord(c->ev[3], s));
+	return PWN_OK;
+}
+// ... the call's times from its events: ev[0] start, [1] traced, [2] blurred (a call that does not blur records none), [3] all done
+static void stats_from_events(pwn_ctx *c, bool blurred)
+{
+	(void)hipEventElapsedTime(&c->stats.trace_ms, c->ev[0], c->ev[1]);
+	if(blurred) (void)hipEventElapsedTime(&c->stats.blur_ms, c->ev[1], c->ev[2]);
+	else c->stats.blur_ms = 0.0f;
+	(void)hipEventElapsedTime(&c->stats.total_ms, c->ev[0], c->ev[3]);
+}
+// ... and the wait for "all done" (what a call launches between the two steps it does not wait for)
+static int blocking_wait(pwn_ctx *c, bool blurred)
+{
+	HIPCHK(c, hipEventSynchronize(c->ev[3]));
+	stats_from_events(c, blurred);
+	return PWN_OK;
 }
 
 // ---- the blocking call in row strips (PWN_OPT_CALL_STRIPS, include/pwnhip.h) ----
@@ -1622,22 +1687,11 @@ static int call_in_strips(pwn_ctx *c, const float cam[16], float sec, uint32_t *
 		const pwn_blur_launch B = { .y0 = 0, .y1 = c->h, .d_pre = pre, .d_z = c->d_z, .d_out = fin, .stream = st[0] };
 		rc = pwn_i_launch_blur(c, &B);
 		if(rc != PWN_OK) return rc;
-		HIPCHK(c, hipEventRecord(c->ev[2], st[0]));
-		HIPCHK(c, hipMemcpyAsync(sbuf, fin, n * 4, hipMemcpyDeviceToHost, st[0]));
-		HIPCHK(c, hipEventRecord(c->ev[3], st[0]));
+		rc = blocking_copies(c, st[0], sbuf, fin, NULL, NULL, n * 4);
+		if(rc != PWN_OK) return rc;
 		HIPCHK(c, hipEventSynchronize(c->ev[3]));
 	}
 #undef STRIPS_FAIL
-	return PWN_OK;
-}
-
-// The blocking calls (pwn_trace_screen_centred, pwn_trace_views) on compute stream s: behind the frames in flight, whichever
-// compute stream their kernels are on
-static int wait_frames_in_flight(pwn_ctx *c, hipStream_t s)
-{
-	if(c->last_frame_done != NULL && c->last_frame_stream != s) HIPCHK(c, hipStreamWaitEvent(s, c->last_frame_done, 0));
-	if(c->last_frame_done != NULL && c->stream2 != NULL && c->last_frame_stream != c->stream2) HIPCHK(c, hipStreamWaitEvent(c->stream2, c->last_frame_done, 0));      // (strips use both)
-	c->last_frame_done = NULL;       // (the call ends with the stream empty)
 	return PWN_OK;
 }
 
@@ -1670,9 +1724,7 @@ extern "C" int pwn_trace_screen_centred(pwn_ctx *c, const float cam[16], float s
 			const int rc = call_in_strips(c, cam, sec, sbuf, zbuf, cuts, K);
 			if(rc != PWN_OK) return rc;
 			if(c->blur_passes == 0) { uint32_t *t = c->d_pre; c->d_pre = c->d_out; c->d_out = t; }      // (the final frame stays addressable as d_out)
-			(void)hipEventElapsedTime(&c->stats.trace_ms, c->ev[0], c->ev[1]);
-			(void)hipEventElapsedTime(&c->stats.blur_ms, c->ev[1], c->ev[2]);
-			(void)hipEventElapsedTime(&c->stats.total_ms, c->ev[0], c->ev[3]);
+			stats_from_events(c, true);
 			return PWN_OK;
 		}
 	}
@@ -1709,6 +1761,16 @@ extern "C" int pwn_trace_screen_centred(pwn_ctx *c, const float cam[16], float s
 
 // ---- a batch of views (pwn_trace_views) ----------------------------------------
 
+// Three planes of `bytes` (pre-blur, colour, depth) or none: PWN_ENOMEM with nothing kept, the message is the caller's
+static int planes3_alloc(size_t bytes, uint32_t **pre, uint32_t **out, float **z)
+{
+	*pre = *out = NULL; *z = NULL;
+	if(hipMalloc((void **)pre, bytes) == hipSuccess && hipMalloc((void **)out, bytes) == hipSuccess && hipMalloc((void **)z, bytes) == hipSuccess) return PWN_OK;
+	(void)hipGetLastError();
+	(void)hipFree(*pre); (void)hipFree(*out); (void)hipFree(*z);
+	return PWN_ENOMEM;
+}
+
 // Room for n views: the records (PWN_VIEWS_MAX of them, with the first batch) and n planes of each kind.  A larger n moves the
 // depth planes of the slots so far into the new allocation and starts the new slots' planes at 0; the stream is idle behind
 // that before the old planes go (no kernel of an earlier batch reads them: every batch ends with its stream drained).
@@ -1718,15 +1780,12 @@ static int views_reserve(pwn_ctx *c, int n, hipStream_t s)
 	{
 		HIPCHK(c, hipHostMalloc((void **)&c->h_vrec, PWN_VIEWS_MAX * sizeof(pwn_view_rec), hipHostMallocDefault));
 		HIPCHK(c, hipMalloc((void **)&c->d_vrec, PWN_VIEWS_MAX * sizeof(pwn_view_rec)));
-		c->vrec_cap = PWN_VIEWS_MAX;
 	}
 	if(n <= c->views_cap) return PWN_OK;
 	const size_t plane = (size_t)c->w * (size_t)c->h, bytes = (size_t)n * plane * 4;
-	uint32_t *pre = NULL, *out = NULL; float *z = NULL;
-	if(hipMalloc((void **)&pre, bytes) != hipSuccess || hipMalloc((void **)&out, bytes) != hipSuccess || hipMalloc((void **)&z, bytes) != hipSuccess)
+	uint32_t *pre, *out; float *z;
+	if(planes3_alloc(bytes, &pre, &out, &z) != PWN_OK)
 	{
-		(void)hipGetLastError();
-		(void)hipFree(pre); (void)hipFree(out); (void)hipFree(z);
 		snprintf(c->err, sizeof(c->err), "pwn_trace_views: no room for %d views of %d x %d", n, c->w, c->h);
 		return PWN_ENOMEM;
 	}
@@ -1743,14 +1802,12 @@ extern "C" int pwn_trace_views(pwn_ctx *c, int n, const float *cams, const float
 {
 	GRP_REFUSE(c, "pwn_trace_views");
 	if(c == NULL || cams == NULL || secs == NULL || sbuf == NULL || n < 1 || n > PWN_VIEWS_MAX) return PWN_EINVAL;
+	int rc = batch_refuse(c, n);
+	if(rc != PWN_OK) return rc;
 	const size_t plane = (size_t)c->w * (size_t)c->h;
-	if((size_t)n * plane > ((size_t)1 << 28)) return PWN_EINVAL;
-	if(c->blur_passes > 0 && (c->w & 3) != 0) return PWN_EINVAL;
-	if(c->tiled != NULL) return PWN_EBUSY;
-	if(!c->have_level) return PWN_ENOLEVEL;
 	(void)hipSetDevice(c->device);
 	hipStream_t s = c->stream;
-	int rc = wait_frames_in_flight(c, s);
+	rc = wait_frames_in_flight(c, s);
 	if(rc != PWN_OK) return rc;
 	rc = views_reserve(c, n, s);
 	if(rc != PWN_OK) return rc;
@@ -1759,14 +1816,11 @@ extern "C" int pwn_trace_views(pwn_ctx *c, int n, const float *cams, const float
 	for(int i = 0; i < n; i++)
 	{
 		const float *cam = cams + 16 * (size_t)i;
-		pwn_trace_params P;
-		frame_setup(c->w, c->h, cam, &P);
 		pwn_view_rec &r = c->h_vrec[i];
-		memcpy(r.rayb, P.rayb, sizeof(r.rayb)); memcpy(r.rdx, P.rdx, sizeof(r.rdx));
-		memcpy(r.rdy, P.rdy, sizeof(r.rdy)); memcpy(r.from, P.from, sizeof(r.from));
+		frame_setup(c->w, c->h, cam, &r);
 		r.sec_current = secs[i];
 		r.pad_[0] = r.pad_[1] = r.pad_[2] = 0.0f;
-		if(!(cam[3] == 0.0f && cam[7] == 0.0f && cam[11] == 0.0f && cam[15] == 1.0f)) has_w = true;
+		if(camera_has_w(cam)) has_w = true;
 	}
 	HIPCHK(c, hipEventRecord(c->ev[0], s));
 	// (the staging is free again: the call before this one ended with the stream drained)
@@ -1775,23 +1829,12 @@ extern "C" int pwn_trace_views(pwn_ctx *c, int n, const float *cams, const float
 	rc = pwn_i_launch_trace(c, &T);
 	if(rc != PWN_OK) return rc;
 	HIPCHK(c, hipEventRecord(c->ev[1], s));
-	uint32_t *cur = c->d_vpre, *other = c->d_vout;
-	for(int p = 0; p < c->blur_passes; p++)
-	{
-		const pwn_blur_launch B = { .y0 = 0, .y1 = c->h, .d_pre = cur, .d_z = c->d_vz, .d_out = other, .stream = s, .views = n };
-		rc = pwn_i_launch_blur(c, &B);
-		if(rc != PWN_OK) return rc;
-		uint32_t *t = cur; cur = other; other = t;
-	}
-	HIPCHK(c, hipEventRecord(c->ev[2], s));
-	HIPCHK(c, hipMemcpyAsync(sbuf, cur, (size_t)n * plane * 4, hipMemcpyDeviceToHost, s));
-	if(zbuf != NULL) HIPCHK(c, hipMemcpyAsync(zbuf, c->d_vz, (size_t)n * plane * 4, hipMemcpyDeviceToHost, s));
-	HIPCHK(c, hipEventRecord(c->ev[3], s));
-	HIPCHK(c, hipEventSynchronize(c->ev[3]));
-	(void)hipEventElapsedTime(&c->stats.trace_ms, c->ev[0], c->ev[1]);
-	(void)hipEventElapsedTime(&c->stats.blur_ms, c->ev[1], c->ev[2]);
-	(void)hipEventElapsedTime(&c->stats.total_ms, c->ev[0], c->ev[3]);
-	return PWN_OK;
+	uint32_t *cur = c->d_vpre;
+	rc = blur_passes_run(c, { .y0 = 0, .y1 = c->h, .d_z = c->d_vz, .stream = s, .views = n }, &cur, c->d_vout);
+	if(rc != PWN_OK) return rc;
+	rc = blocking_copies(c, s, sbuf, cur, zbuf, c->d_vz, (size_t)n * plane * 4);
+	if(rc != PWN_OK) return rc;
+	return blocking_wait(c, true);
 }
 
 // The device form: cameras and planes of the caller's in device memory, everything on the caller's stream, nothing waited for.
@@ -1803,20 +1846,20 @@ extern "C" int pwn_trace_views_device(pwn_ctx *c, int n, const void *d_cams, con
 	if(c == NULL || d_cams == NULL || d_secs == NULL || d_sbuf == NULL || d_zbuf == NULL || n < 1 || n > PWN_VIEWS_MAX ||
 	   (flags & ~PWN_VIEWS_HAS_W) != 0) return PWN_EINVAL;
 	const size_t plane = (size_t)c->w * (size_t)c->h;
-	if((size_t)n * plane > ((size_t)1 << 28)) return PWN_EINVAL;
-	if(c->blur_passes > 0 && ((c->w & 3) != 0 || d_work == NULL)) return PWN_EINVAL;
+	if(c->blur_passes > 0 && d_work == NULL) return PWN_EINVAL;
 	if((((uintptr_t)d_cams | (uintptr_t)d_secs | (uintptr_t)d_work | (uintptr_t)d_sbuf | (uintptr_t)d_zbuf) & 15u) != 0) return PWN_EINVAL;
 	{
 		const uintptr_t bytes = (uintptr_t)n * plane * 4, p[3] = { (uintptr_t)d_sbuf, (uintptr_t)d_zbuf, (uintptr_t)d_work };
 		for(int i = 0; i < 3; i++) for(int k = i + 1; k < 3; k++)
 			if(p[i] != 0 && p[k] != 0 && p[i] < p[k] + bytes && p[k] < p[i] + bytes) return PWN_EINVAL;
 	}
-	if(c->tiled != NULL) return PWN_EBUSY;
-	if(!c->have_level) return PWN_ENOLEVEL;
+	// (the rules above and the first two of batch_refuse all answer PWN_EINVAL: their order among themselves decides nothing)
+	int rc = batch_refuse(c, n);
+	if(rc != PWN_OK) return rc;
 	(void)hipSetDevice(c->device);
 	hipStream_t s = (hipStream_t)stream;
 	// (tables that cannot be packed refuse the call before anything is launched)
-	if(c->blob_dirty) { const int rc = pack_blob(c); if(rc != PWN_OK) return rc; }
+	if(c->blob_dirty) { rc = pack_blob(c); if(rc != PWN_OK) return rc; }
 	if(c->d_vrec_dev == NULL) HIPCHK(c, hipMalloc((void **)&c->d_vrec_dev, (size_t)PWN_TICKET_SETS * PWN_VIEWS_MAX * sizeof(pwn_view_rec)));
 	// The records of the ticket set the trace launch below counts in (pwn_i_launch_trace): the launch that read them last is the
 	// one 2R launches back, and launch n - R is behind it.  On one stream and in the rotation over R this stream is behind launch
@@ -1829,16 +1872,9 @@ extern "C" int pwn_trace_views_device(pwn_ctx *c, int n, const void *d_cams, con
 	uint32_t *cur = (c->blur_passes & 1) ? (uint32_t *)d_work : (uint32_t *)d_sbuf;
 	uint32_t *other = (c->blur_passes & 1) ? (uint32_t *)d_sbuf : (uint32_t *)d_work;
 	pwn_trace_launch T = { .y0 = 0, .y1 = c->h, .views = { recs, n, (flags & PWN_VIEWS_HAS_W) != 0, plane }, .d_sbuf = cur, .d_zbuf = (float *)d_zbuf, .stream = s };
-	int rc = pwn_i_launch_trace(c, &T);
+	rc = pwn_i_launch_trace(c, &T);
 	if(rc != PWN_OK) return rc;
-	for(int p = 0; p < c->blur_passes; p++)
-	{
-		const pwn_blur_launch B = { .y0 = 0, .y1 = c->h, .d_pre = cur, .d_z = (const float *)d_zbuf, .d_out = other, .stream = s, .views = n };
-		rc = pwn_i_launch_blur(c, &B);
-		if(rc != PWN_OK) return rc;
-		uint32_t *t = cur; cur = other; other = t;
-	}
-	return PWN_OK;
+	return blur_passes_run(c, { .y0 = 0, .y1 = c->h, .d_z = (const float *)d_zbuf, .stream = s, .views = n }, &cur, other);
 }
 
 // ---- views of their own sizes in one frame (pwn_trace_viewports) ----------------
@@ -1854,11 +1890,9 @@ static int viewports_reserve(pwn_ctx *c, hipStream_t s)
 	}
 	if(c->d_pz != NULL) return PWN_OK;
 	const size_t bytes = (size_t)c->w * (size_t)c->h * 4;
-	uint32_t *pre = NULL, *out = NULL; float *z = NULL;
-	if(hipMalloc((void **)&pre, bytes) != hipSuccess || hipMalloc((void **)&out, bytes) != hipSuccess || hipMalloc((void **)&z, bytes) != hipSuccess)
+	uint32_t *pre, *out; float *z;
+	if(planes3_alloc(bytes, &pre, &out, &z) != PWN_OK)
 	{
-		(void)hipGetLastError();
-		(void)hipFree(pre); (void)hipFree(out); (void)hipFree(z);
 		snprintf(c->err, sizeof(c->err), "pwn_trace_viewports: no room for three planes of %d x %d", c->w, c->h);
 		return PWN_ENOMEM;
 	}
@@ -1878,11 +1912,11 @@ extern "C" int pwn_trace_viewports(pwn_ctx *c, int n, const pwn_viewport *vp, co
 		snprintf(c->err, sizeof(c->err), "pwn_trace_viewports: %d rectangles of a %d x %d frame refused (the first offender: %llu)", n, c->w, c->h, plan[3]);
 		return PWN_EINVAL;
 	}
-	if(c->tiled != NULL) return PWN_EBUSY;
-	if(!c->have_level) return PWN_ENOLEVEL;
+	int rc = batch_refuse(c);
+	if(rc != PWN_OK) return rc;
 	(void)hipSetDevice(c->device);
 	hipStream_t s = c->stream;
-	int rc = wait_frames_in_flight(c, s);
+	rc = wait_frames_in_flight(c, s);
 	if(rc != PWN_OK) return rc;
 	rc = viewports_reserve(c, s);
 	if(rc != PWN_OK) return rc;
@@ -1899,11 +1933,8 @@ extern "C" int pwn_trace_viewports(pwn_ctx *c, int n, const pwn_viewport *vp, co
 	{
 		const int i = ord[j];
 		const float *cam = cams + 16 * (size_t)i;
-		pwn_trace_params P;
-		frame_setup(vp[i].w, vp[i].h, cam, &P);
 		pwn_viewport_rec &r = c->h_prec[j];
-		memcpy(r.rayb, P.rayb, sizeof(r.rayb)); memcpy(r.rdx, P.rdx, sizeof(r.rdx));
-		memcpy(r.rdy, P.rdy, sizeof(r.rdy)); memcpy(r.from, P.from, sizeof(r.from));
+		frame_setup(vp[i].w, vp[i].h, cam, &r);
 		r.sec_current = secs[i];
 		r.x = vp[i].x; r.y = vp[i].y; r.w = vp[i].w; r.h = vp[i].h;
 		r.units_x = (uint32_t)((vp[i].w + 15) / 16); r.rows_u = (uint32_t)((vp[i].h + 3) / 4); r.units = vu[i];
@@ -1914,7 +1945,7 @@ extern "C" int pwn_trace_viewports(pwn_ctx *c, int n, const pwn_viewport *vp, co
 		unit_div_magic((uint32_t)(n - j), &r.seg_magic, &sh); r.seg_shift = sh;
 		first += (uint32_t)(n - j) * (r.units - prev); prev = r.units;
 		r.pad_[0] = r.pad_[1] = 0u;
-		if(!(cam[3] == 0.0f && cam[7] == 0.0f && cam[11] == 0.0f && cam[15] == 1.0f)) has_w = true;
+		if(camera_has_w(cam)) has_w = true;
 	}
 	if((unsigned long long)first != plan[0]) { snprintf(c->err, sizeof(c->err), "pwn_trace_viewports: %u units in the records, %llu planned", first, plan[0]); return PWN_EINVAL; }
 	HIPCHK(c, hipEventRecord(c->ev[0], s));
@@ -1932,99 +1963,87 @@ extern "C" int pwn_trace_viewports(pwn_ctx *c, int n, const pwn_viewport *vp, co
 	rc = pwn_i_launch_trace(c, &T);
 	if(rc != PWN_OK) return rc;
 	HIPCHK(c, hipEventRecord(c->ev[1], s));
-	uint32_t *cur = c->d_ppre, *other = c->d_pout;
-	for(int p = 0; p < c->blur_passes; p++)
-	{
-		const pwn_blur_launch B = { .y0 = 0, .y1 = c->h, .d_pre = cur, .d_z = c->d_pz, .d_out = other, .stream = s, .vps = V };
-		rc = pwn_i_launch_blur(c, &B);
-		if(rc != PWN_OK) return rc;
-		uint32_t *t = cur; cur = other; other = t;
-	}
-	HIPCHK(c, hipEventRecord(c->ev[2], s));
-	HIPCHK(c, hipMemcpyAsync(sbuf, cur, plane * 4, hipMemcpyDeviceToHost, s));
-	if(zbuf != NULL) HIPCHK(c, hipMemcpyAsync(zbuf, c->d_pz, plane * 4, hipMemcpyDeviceToHost, s));
-	HIPCHK(c, hipEventRecord(c->ev[3], s));
-	HIPCHK(c, hipEventSynchronize(c->ev[3]));
-	(void)hipEventElapsedTime(&c->stats.trace_ms, c->ev[0], c->ev[1]);
-	(void)hipEventElapsedTime(&c->stats.blur_ms, c->ev[1], c->ev[2]);
-	(void)hipEventElapsedTime(&c->stats.total_ms, c->ev[0], c->ev[3]);
-	return PWN_OK;
+	uint32_t *cur = c->d_ppre;
+	rc = blur_passes_run(c, { .y0 = 0, .y1 = c->h, .d_z = c->d_pz, .stream = s, .vps = V }, &cur, c->d_pout);
+	if(rc != PWN_OK) return rc;
+	rc = blocking_copies(c, s, sbuf, cur, zbuf, c->d_pz, plane * 4);
+	if(rc != PWN_OK) return rc;
+	return blocking_wait(c, true);
 }
 
-// ---- a batch of rays (pwn_trace_rays) --------------------------------------------
+// ---- batches of rays (pwn_trace_rays, pwn_trace_hits) ----------------------------
 
-// Room for n rays of the host form, kept across calls: pinned staging and a device buffer of the same layout, for a call of n rays
-// the records at 0, the seeds at 32 n, the depths at 36 n and the colours at 40 n -- one copy up (records, seeds, depths) and one
-// down (depths, colours).  Grows to at least twice the old size; no kernel uses the old buffers (every call ends with its stream drained).
-static int rays_reserve(pwn_ctx *c, size_t n)
+// Room for n rays of a blocking ray call, kept across calls: pinned staging *h and a device buffer *d of the same layout, `per_ray`
+// bytes a ray.  Grows to at least twice the old size; no kernel uses the old buffers (every call ends with its stream drained).
+static int staging_reserve(pwn_ctx *c, size_t n, size_t per_ray, const char *who, unsigned char **h, unsigned char **d, size_t *cap_io)
 {
-	if(n <= c->rays_cap) return PWN_OK;
-	size_t cap = c->rays_cap * 2;
+	if(n <= *cap_io) return PWN_OK;
+	size_t cap = *cap_io * 2;
 	if(cap < 4096) cap = 4096;
 	if(cap > PWN_RAYS_MAX) cap = PWN_RAYS_MAX;
 	if(cap < n) cap = n;
-	const size_t bytes = cap * 44 + 16;            // (+16: the upload kernel copies whole 16-byte words)
-	unsigned char *h = NULL, *d = NULL;
-	if(hipHostMalloc((void **)&h, bytes, hipHostMallocDefault) != hipSuccess || hipMalloc((void **)&d, bytes) != hipSuccess)
+	const size_t bytes = cap * per_ray + 16;            // (+16: the upload kernel copies whole 16-byte words)
+	unsigned char *nh = NULL, *nd = NULL;
+	if(hipHostMalloc((void **)&nh, bytes, hipHostMallocDefault) != hipSuccess || hipMalloc((void **)&nd, bytes) != hipSuccess)
 	{
 		(void)hipGetLastError();
-		if(h != NULL) (void)hipHostFree(h);
-		(void)hipFree(d);
-		snprintf(c->err, sizeof(c->err), "pwn_trace_rays: no room for %zu rays", n);
+		if(nh != NULL) (void)hipHostFree(nh);
+		(void)hipFree(nd);
+		snprintf(c->err, sizeof(c->err), "%s: no room for %zu rays", who, n);
 		return PWN_ENOMEM;
 	}
-	if(c->h_rays != NULL) (void)hipHostFree(c->h_rays);
-	(void)hipFree(c->d_rays);
-	c->h_rays = h; c->d_rays = d; c->rays_cap = cap;
+	if(*h != NULL) (void)hipHostFree(*h);
+	(void)hipFree(*d);
+	*h = nh; *d = nd; *cap_io = cap;
 	return PWN_OK;
 }
 
-// the checks both forms share (include/pwnhip.h)
-static int rays_refuse(pwn_ctx *c)
+// What the two blocking ray calls do between filling their staging and reading it: N records into the staging's head, whether any
+// has the w lanes of anything but an ordinary camera's rays (camera_has_w's rule for rays: origin.w 1, direction.w 0), the first
+// `up` bytes of the staging to the device, the launch T of them, bytes [lo, hi) back, the wait and the times.
+static int rays_stage_and_launch(pwn_ctx *c, hipStream_t s, const float *rays, size_t N, unsigned char *h, unsigned char *d, size_t up,
+	pwn_trace_launch *T, size_t lo, size_t hi)
 {
-	if(c->tiled != NULL) return PWN_EBUSY;
-	if(!c->have_level) return PWN_ENOLEVEL;
-	return PWN_OK;
+	memcpy(h, rays, 32 * N);
+	bool has_w = false;
+	for(size_t i = 0; i < N && !has_w; i++) has_w = !(rays[8 * i + 3] == 1.0f && rays[8 * i + 7] == 0.0f);
+	T->rays.has_w = has_w;
+	HIPCHK(c, hipEventRecord(c->ev[0], s));
+	// (small batches by the upload kernel, as the view records: a DMA copy queues behind other copies of the device)
+	if(up <= 65536) HIPCHK(c, pwn_launch_upload(h, d, up, s));
+	else HIPCHK(c, hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, s));
+	const int rc = pwn_i_launch_trace(c, T);
+	if(rc != PWN_OK) return rc;
+	HIPCHK(c, hipEventRecord(c->ev[1], s));
+	HIPCHK(c, hipMemcpyAsync(h + lo, d + lo, hi - lo, hipMemcpyDeviceToHost, s));
+	HIPCHK(c, hipEventRecord(c->ev[3], s));
+	return blocking_wait(c, false);
 }
 
+// pwn_trace_rays' staging for a call of n rays: the records at 0, the seeds at 32 n, the depths at 36 n and the colours at 40 n --
+// one copy up (records, seeds, depths) and one down (depths, colours), 44 B a ray
 extern "C" int pwn_trace_rays(pwn_ctx *c, int n, const float *rays, const uint32_t *seeds, float sec, uint32_t *col, float *depth)
 {
 	GRP_REFUSE(c, "pwn_trace_rays");
 	if(c == NULL || n < 0 || n > PWN_RAYS_MAX || (n > 0 && rays == NULL) || (col == NULL && depth == NULL)) return PWN_EINVAL;
-	int rc = rays_refuse(c);
+	int rc = batch_refuse(c);
 	if(rc != PWN_OK || n == 0) return rc;
 	(void)hipSetDevice(c->device);
 	hipStream_t s = c->stream;
 	rc = wait_frames_in_flight(c, s);
 	if(rc != PWN_OK) return rc;
-	rc = rays_reserve(c, (size_t)n);
+	rc = staging_reserve(c, (size_t)n, 44, "pwn_trace_rays", &c->h_rays, &c->d_rays, &c->rays_cap);
 	if(rc != PWN_OK) return rc;
 	const size_t N = (size_t)n;
 	unsigned char *h = c->h_rays, *d = c->d_rays;
-	memcpy(h, rays, 32 * N);
 	if(seeds != NULL) memcpy(h + 32 * N, seeds, 4 * N); else memset(h + 32 * N, 0, 4 * N);
 	if(depth != NULL) memcpy(h + 36 * N, depth, 4 * N); else memset(h + 36 * N, 0, 4 * N);
-	// the 3-lane variants where every record has the w lanes of an ordinary camera's rays (pwn_i_launch_trace's rule for cameras)
-	bool has_w = false;
-	for(size_t i = 0; i < N && !has_w; i++) has_w = !(rays[8 * i + 3] == 1.0f && rays[8 * i + 7] == 0.0f);
-	HIPCHK(c, hipEventRecord(c->ev[0], s));
-	// (small batches by the upload kernel, as the view records: a DMA copy queues behind other copies of the device)
-	if(40 * N <= 65536) HIPCHK(c, pwn_launch_upload(h, d, 40 * N, s));
-	else HIPCHK(c, hipMemcpyAsync(d, h, 40 * N, hipMemcpyHostToDevice, s));
-	pwn_trace_launch T = { .sec = sec, .rays = { (const float *)d, (const uint32_t *)(d + 32 * N), (uint32_t)n, has_w },
+	pwn_trace_launch T = { .sec = sec, .rays = { (const float *)d, (const uint32_t *)(d + 32 * N), (uint32_t)n },
 		.d_sbuf = (uint32_t *)(d + 40 * N), .d_zbuf = (float *)(d + 36 * N), .stream = s };
-	rc = pwn_i_launch_trace(c, &T);
+	rc = rays_stage_and_launch(c, s, rays, N, h, d, 40 * N, &T, depth != NULL ? 36 * N : 40 * N, col != NULL ? 44 * N : 40 * N);
 	if(rc != PWN_OK) return rc;
-	HIPCHK(c, hipEventRecord(c->ev[1], s));
-	const size_t lo = depth != NULL ? 36 * N : 40 * N, hi = col != NULL ? 44 * N : 40 * N;
-	HIPCHK(c, hipMemcpyAsync(h + lo, d + lo, hi - lo, hipMemcpyDeviceToHost, s));
-	HIPCHK(c, hipEventRecord(c->ev[3], s));
-	HIPCHK(c, hipEventSynchronize(c->ev[3]));
 	if(depth != NULL) memcpy(depth, h + 36 * N, 4 * N);
 	if(col != NULL) memcpy(col, h + 40 * N, 4 * N);
-	(void)hipEventElapsedTime(&c->stats.trace_ms, c->ev[0], c->ev[1]);
-	c->stats.blur_ms = 0.0f;
-	(void)hipEventElapsedTime(&c->stats.total_ms, c->ev[0], c->ev[3]);
 	return PWN_OK;
 }
 
@@ -2036,7 +2055,7 @@ extern "C" int pwn_trace_rays_device(pwn_ctx *c, int n, const void *d_rays, cons
 	   (flags & ~PWN_RAYS_HAS_W) != 0) return PWN_EINVAL;
 	if(((uintptr_t)d_rays & 15u) != 0 || ((uintptr_t)d_seeds & 3u) != 0 || ((uintptr_t)d_col & 3u) != 0 || ((uintptr_t)d_depth & 3u) != 0)
 		return PWN_EINVAL;
-	const int rc = rays_refuse(c);
+	const int rc = batch_refuse(c);
 	if(rc != PWN_OK || n == 0) return rc;
 	(void)hipSetDevice(c->device);
 	pwn_trace_launch T = { .sec = sec, .rays = { (const float *)d_rays, (const uint32_t *)d_seeds, (uint32_t)n, (flags & PWN_RAYS_HAS_W) != 0 },
@@ -2044,66 +2063,28 @@ extern "C" int pwn_trace_rays_device(pwn_ctx *c, int n, const void *d_rays, cons
 	return pwn_i_launch_trace(c, &T);
 }
 
-// ---- first hits of a batch of rays (pwn_trace_hits) ------------------------------
-
-// Room for n rays of the host form, kept across calls as rays_reserve keeps pwn_trace_rays': the records at 0 (32 B a ray), the
-// hit records of a call of n rays behind them at 32 n (48 B a ray; 16-byte aligned) -- one copy up, one down.
-static int hits_reserve(pwn_ctx *c, size_t n)
-{
-	if(n <= c->hits_cap) return PWN_OK;
-	size_t cap = c->hits_cap * 2;
-	if(cap < 4096) cap = 4096;
-	if(cap > PWN_RAYS_MAX) cap = PWN_RAYS_MAX;
-	if(cap < n) cap = n;
-	const size_t bytes = cap * (32 + sizeof(pwn_hit)) + 16;            // (+16: the upload kernel copies whole 16-byte words)
-	unsigned char *h = NULL, *d = NULL;
-	if(hipHostMalloc((void **)&h, bytes, hipHostMallocDefault) != hipSuccess || hipMalloc((void **)&d, bytes) != hipSuccess)
-	{
-		(void)hipGetLastError();
-		if(h != NULL) (void)hipHostFree(h);
-		(void)hipFree(d);
-		snprintf(c->err, sizeof(c->err), "pwn_trace_hits: no room for %zu rays", n);
-		return PWN_ENOMEM;
-	}
-	if(c->h_hits != NULL) (void)hipHostFree(c->h_hits);
-	(void)hipFree(c->d_hits);
-	c->h_hits = h; c->d_hits = d; c->hits_cap = cap;
-	return PWN_OK;
-}
-
 static_assert(sizeof(pwn_hit) == PWN_HIT_REC_BYTES, "the kernel writes a pwn_hit as three 16-byte words (trace_kernel.hip trace_hit)");
 
+// pwn_trace_hits' staging for a call of n rays: the records at 0 (32 B a ray), the hit records behind them at 32 n (48 B a ray;
+// 16-byte aligned) -- one copy up, one down
 extern "C" int pwn_trace_hits(pwn_ctx *c, int n, const float *rays, pwn_hit *hits)
 {
 	GRP_REFUSE(c, "pwn_trace_hits");
 	if(c == NULL || n < 0 || n > PWN_RAYS_MAX || (n > 0 && (rays == NULL || hits == NULL))) return PWN_EINVAL;
-	int rc = rays_refuse(c);
+	int rc = batch_refuse(c);
 	if(rc != PWN_OK || n == 0) return rc;
 	(void)hipSetDevice(c->device);
 	hipStream_t s = c->stream;
 	rc = wait_frames_in_flight(c, s);
 	if(rc != PWN_OK) return rc;
-	rc = hits_reserve(c, (size_t)n);
+	rc = staging_reserve(c, (size_t)n, 32 + sizeof(pwn_hit), "pwn_trace_hits", &c->h_hits, &c->d_hits, &c->hits_cap);
 	if(rc != PWN_OK) return rc;
 	const size_t N = (size_t)n;
 	unsigned char *h = c->h_hits, *d = c->d_hits;
-	memcpy(h, rays, 32 * N);
-	bool has_w = false;          // (pwn_trace_rays' rule)
-	for(size_t i = 0; i < N && !has_w; i++) has_w = !(rays[8 * i + 3] == 1.0f && rays[8 * i + 7] == 0.0f);
-	HIPCHK(c, hipEventRecord(c->ev[0], s));
-	if(32 * N <= 65536) HIPCHK(c, pwn_launch_upload(h, d, 32 * N, s));
-	else HIPCHK(c, hipMemcpyAsync(d, h, 32 * N, hipMemcpyHostToDevice, s));
-	pwn_trace_launch T = { .rays = { (const float *)d, NULL, (uint32_t)n, has_w, d + 32 * N }, .stream = s };
-	rc = pwn_i_launch_trace(c, &T);
+	pwn_trace_launch T = { .rays = { (const float *)d, NULL, (uint32_t)n, false, d + 32 * N }, .stream = s };
+	rc = rays_stage_and_launch(c, s, rays, N, h, d, 32 * N, &T, 32 * N, (32 + sizeof(pwn_hit)) * N);
 	if(rc != PWN_OK) return rc;
-	HIPCHK(c, hipEventRecord(c->ev[1], s));
-	HIPCHK(c, hipMemcpyAsync(h + 32 * N, d + 32 * N, sizeof(pwn_hit) * N, hipMemcpyDeviceToHost, s));
-	HIPCHK(c, hipEventRecord(c->ev[3], s));
-	HIPCHK(c, hipEventSynchronize(c->ev[3]));
 	memcpy(hits, h + 32 * N, sizeof(pwn_hit) * N);
-	(void)hipEventElapsedTime(&c->stats.trace_ms, c->ev[0], c->ev[1]);
-	c->stats.blur_ms = 0.0f;
-	(void)hipEventElapsedTime(&c->stats.total_ms, c->ev[0], c->ev[3]);
 	return PWN_OK;
 }
 
@@ -2112,7 +2093,7 @@ extern "C" int pwn_trace_hits_device(pwn_ctx *c, int n, const void *d_rays, int 
 	GRP_REFUSE(c, "pwn_trace_hits_device");
 	if(c == NULL || n < 0 || n > PWN_RAYS_MAX || (n > 0 && (d_rays == NULL || d_hits == NULL)) || (flags & ~PWN_RAYS_HAS_W) != 0) return PWN_EINVAL;
 	if(((uintptr_t)d_rays & 15u) != 0 || ((uintptr_t)d_hits & 15u) != 0) return PWN_EINVAL;
-	const int rc = rays_refuse(c);
+	const int rc = batch_refuse(c);
 	if(rc != PWN_OK || n == 0) return rc;
 	(void)hipSetDevice(c->device);
 	pwn_trace_launch T = { .rays = { (const float *)d_rays, NULL, (uint32_t)n, (flags & PWN_RAYS_HAS_W) != 0, d_hits }, .stream = (hipStream_t)stream };
@@ -2246,14 +2227,9 @@ extern "C" int pwn_submit_frame(pwn_ctx *c, const float cam[16], float sec, int 
 	int rc = pwn_i_launch_trace(c, &T);
 	if(rc != PWN_OK) return rc;
 	if(timing) HIPCHK(c, hipEventRecord(sl.ev_k[1], s));
-	for(int p = 0; p < c->blur_passes; p++)
-	{
-		uint32_t *dst = (p == c->blur_passes - 1) ? sl.d_out : (cur == c->d_pre ? c->d_out : c->d_pre);      // (several passes: one stream)
-		const pwn_blur_launch B = { .y0 = 0, .y1 = c->h, .d_pre = cur, .d_z = sl.d_z, .d_out = dst, .stream = s };
-		rc = pwn_i_launch_blur(c, &B);
-		if(rc != PWN_OK) { (void)hipEventRecord(sl.ev_k[2], s); return rc; }     // (the trace launch counts on this event)
-		cur = dst;
-	}
+	// (several passes: one stream, so `pre` is d_pre and takes turns with d_out)
+	rc = blur_passes_run(c, { .y0 = 0, .y1 = c->h, .d_z = sl.d_z, .stream = s }, &cur, c->d_out, sl.d_out);
+	if(rc != PWN_OK) { (void)hipEventRecord(sl.ev_k[2], s); return rc; }     // (the trace launch counts on this event)
 	HIPCHK(c, hipEventRecord(sl.ev_k[2], s));
 	c->last_frame_done = sl.ev_k[2]; c->last_frame_stream = s;
 	hipEvent_t last = sl.ev_k[2];

@@ -1,5 +1,7 @@
 // pwn_internal.h -- the context behind include/pwnhip.h, shared by the translation
-// units of libpwnhip.so (pwn_api.cpp: frames, tables; pwn_tiled.cpp: row tiling over RCCL).
+// units of libpwnhip.so (pwn_api.cpp: context, options, tables, the trace and blur launches, the blocking call, the batches of
+// views, viewports, rays and hits, frames in flight, sink, probes; pwn_tiled.cpp: row tiling over RCCL; pwn_group.cpp: several
+// contexts behind one handle).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -260,7 +262,7 @@ struct pwn_ctx
 	// pwn_trace_views: per view slot a pre-blur, a colour and a depth plane (views_cap of each, view-major; the depth planes persist
 	// by slot and are kept when the count grows), the records of the call in pinned staging and on the device
 	uint32_t *d_vpre, *d_vout; float *d_vz; int views_cap;
-	pwn_view_rec *h_vrec, *d_vrec; int vrec_cap;
+	pwn_view_rec *h_vrec, *d_vrec;
 	// pwn_trace_views_device: PWN_VIEWS_MAX records per ticket set, written by the set-up kernel of the call whose trace launch
 	// counts in that set (so reuse is ordered as the sets' is); allocated by the first call
 	pwn_view_rec *d_vrec_dev;
@@ -268,9 +270,9 @@ struct pwn_ctx
 	// of the call in pinned staging and on the device (PWN_VIEWS_MAX of them)
 	uint32_t *d_ppre, *d_pout; float *d_pz;
 	pwn_viewport_rec *h_prec, *d_prec;
-	// pwn_trace_rays: room for rays_cap rays in pinned staging and on the device, 44 B each (record, seed, depth, colour; pwn_api.cpp rays_reserve)
+	// pwn_trace_rays: room for rays_cap rays in pinned staging and on the device, 44 B each (record, seed, depth, colour; pwn_api.cpp staging_reserve)
 	unsigned char *h_rays, *d_rays; size_t rays_cap;
-	// pwn_trace_hits: the same for hits_cap rays, 32 B in (record) and 48 B out (pwn_hit) each (pwn_api.cpp hits_reserve)
+	// pwn_trace_hits: the same for hits_cap rays, 32 B in (record) and 48 B out (pwn_hit) each
 	unsigned char *h_hits, *d_hits; size_t hits_cap;
 	uint32_t *d_tickets; unsigned ticket_set;  // PWN_TICKET_SETS sets of work-queue counters of the trace kernel, used in turn
 	uint32_t *d_scratch; size_t scratch_cap;   // upscale / probe staging
@@ -308,10 +310,13 @@ struct pwn_ctx
 	pwn_tiled *tiled;                // row tiling over RCCL, NULL until pwn_tiled_init
 	int tiled_init_ms, tiled_wait_ms;   // pwn_tiled_set_timeouts (0 = the default: environment, else 120 s / 60 s)
 
-	// The trace launch before the last one: the stream it went on and an event behind it.  Launch n clears the ticket set
-	// of launch n + 2 = the set launch n - 2 drew from, so it has to come after launch n - 2: true by itself on one
-	// stream and while frames alternate between two (n - 2 is then on n's stream), NOT when a launch leaves that pattern
-	// (a blocking call or a counted frame between alternating ones) -- pwn_i_launch_trace then waits for this event.
+	// The kernel's work queues are used in turn, 2R sets of them, R = launch_rot: launch n counts in set n mod 2R and clears set
+	// (n + R) mod 2R, the one of the launch R launches on = the set launch n - R drew from, so it has to come after launch n - R.
+	// Launches of a context are stream-ordered (include/pwnhip.h) -- on ONE stream, or rotating over the R = 2 compute streams of
+	// the frames in flight (pwn_submit_frame) or the R = 2 or 3 of a row tiling, where launch n + R is behind launch n on its
+	// stream and the launches between may run beside it with sets of their own.  So the order holds by itself on one stream and in
+	// the rotation, NOT when a launch leaves that pattern (a blocking call or a counted frame between alternating ones): the last
+	// launches' streams and an event behind each are kept here, and pwn_i_launch_trace then waits for the one R back.
 	hipStream_t launch_stream[3]; hipEvent_t launch_event[3];     // [0] the last launch, [1] the one before, [2] the one before that
 	unsigned long long launch_waits; // launches that left the rotation and were put behind the launch R before them (pwn_launch_order_waits)
 	int launch_rot;                  // streams that successive trace launches rotate over: 2 (one stream, or two alternating), 3 (pwn_i_set_launch_rotation)

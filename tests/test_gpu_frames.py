@@ -179,3 +179,60 @@ def test_a_launch_that_leaves_the_rotation_is_ordered_behind_the_launch_two_befo
         O.set_spheres(sph)
         assert oracle_lib.fnv64(fr["sbuf"]) == oracle_lib.fnv64(O.render(W, H, cam, sec=sec, blur=1)[0])
     r.close()
+
+
+_SEVERAL = {}
+
+
+def _several_passes_oracle(passes):
+    """the oracle's six small frames of `passes` blur passes, rendered once for both settings of the overlap"""
+    if passes not in _SEVERAL:
+        from oracle import Oracle
+        O = Oracle()
+        O.load_level(level_path("pwnfps_level"))
+        base = load_spheres("t0")
+        frames = []
+        for f in range(6):
+            cam, sec, sph = _scene(f, base)
+            O.set_spheres(sph)
+            frames.append(O.render(96, 64, cam, sec=sec, blur=passes))
+        _SEVERAL[passes] = frames
+    return _SEVERAL[passes]
+
+
+@pytest.mark.parametrize("overlap", [True, False])
+@pytest.mark.parametrize("passes", [2, 3])
+def test_frames_in_flight_with_several_blur_passes(passes, overlap, oracle_lib):
+    """Two and three blur passes under frames in flight: the passes take turns between the context's two planes and the LAST one
+    lands in the slot's own plane, whatever the parity.  Six 96 x 64 frames of different sec over three slots, with the frame
+    overlap asked for and not: every delivered colour and depth plane is the oracle's frame of the same passes, bit for bit, and
+    the blocking call's on the same context afterwards.  (At this size a last pass into the wrong plane shows in every pixel.)"""
+    import pwnfps_amd
+    w, h, slots = 96, 64, 3
+    base = load_spheres("t0")
+    want = _several_passes_oracle(passes)
+    r = pwnfps_amd.Renderer(w, h)
+    r.level_load(level_path("pwnfps_level"))
+    r.set_blur_passes(passes)
+    r.set_frame_overlap(overlap)
+    r.frames_config(slots, sbuf=True, zbuf=True)
+    got = {}
+    for f in range(6 + slots):
+        if f >= slots:
+            fr = r.wait_frame(f % slots)
+            assert fr["seq"] == f - slots + 1
+            got[f - slots] = (fr["sbuf"].copy(), fr["zbuf"].copy())
+        if f < 6:
+            cam, sec, sph = _scene(f, base)
+            r.set_objects(sph)
+            r.submit_frame(cam, sec, f % slots)
+    for k in range(6):
+        ob, oz = want[k]
+        assert (got[k][0] == ob).all(), "frame %d colour" % k
+        assert (got[k][1].view(np.uint32) == oz.view(np.uint32)).all(), "frame %d depth" % k
+        cam, sec, sph = _scene(k, base)
+        r.set_objects(sph)
+        sb, zb = r.trace_screen_centred(cam, sec)
+        assert (sb == got[k][0]).all(), "frame %d colour, the blocking call" % k
+        assert (zb.view(np.uint32) == got[k][1].view(np.uint32)).all(), "frame %d depth, the blocking call" % k
+    r.close()

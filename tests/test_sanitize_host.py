@@ -29,3 +29,23 @@ def test_host_logic_under_sanitizers(target, modes, tmp_path):
         assert "Sanitizer" not in out, out[-4000:]
         if m in ("late", "all"):
             assert "one call failed at the deadline" in out
+
+
+def test_host_calls_transcript(tmp_path):
+    """What every entry point of the host API sends to the device (tools/sanitize/calls_driver.cpp: runtime calls, launches with
+    their parameters, hashes of the outputs, the refusals, the out-of-memory paths) is what tests/golden/host_calls.txt recorded
+    before the batch calls' common code was folded, byte for byte, and the run is clean under AddressSanitizer + UBSan."""
+    out_dir = str(tmp_path)
+    _build("calls", out_dir)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1")
+    level = os.path.join(ROOT, "tests", "golden", "levels", "pwnfps_level.txt")
+    p = subprocess.run([os.path.join(out_dir, "calls_asan"), level], capture_output=True, timeout=600, env=env, cwd=out_dir)
+    assert p.returncode == 0, (p.stdout[-2000:] + p.stderr[-2000:]).decode(errors="replace")
+    assert b"Sanitizer" not in p.stdout + p.stderr, p.stderr[-4000:].decode(errors="replace")
+    with open(os.path.join(ROOT, "tests", "golden", "host_calls.txt"), "rb") as f:
+        want = f.read()
+    if p.stdout != want:
+        got, exp = p.stdout.split(b"\n"), want.split(b"\n")
+        first = next((i for i in range(min(len(got), len(exp))) if got[i] != exp[i]), min(len(got), len(exp)))
+        call = next((got[i] for i in range(min(first, len(got) - 1), -1, -1) if got[i].startswith(b"==")), b"")
+        raise AssertionError("line %d differs, in %r:\n  now      %r\n  recorded %r" % (first + 1, call, got[first:first + 1], exp[first:first + 1]))

@@ -9,15 +9,25 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
+#include <initializer_list>
 #include "pwn_internal.h"
 
 static uint32_t mix(uint32_t a, uint32_t b) { a ^= b + 0x9e3779b9u + (a << 6) + (a >> 2); return a * 2654435761u; }
 
-// (tables_driver.cpp looks at what a launch is handed: the tables as the kernels would read them)
-extern "C" { void (*pwn_fake_trace_hook)(const pwn_trace_params *P, size_t lds_bytes) = NULL; }
-extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int, size_t lds_bytes, bool count, hipStream_t)
+// (tables_driver.cpp looks at what a launch is handed: the tables as the kernels would read them; calls_driver.cpp writes every
+// launch down: the trace and blur launches with their parameters, the small ones with their name, source, destination and sizes)
+extern "C" {
+void (*pwn_fake_trace_hook)(const pwn_trace_params *P, int grid, size_t lds_bytes) = NULL;
+void (*pwn_fake_blur_hook)(const pwn_blur_params *B) = NULL;
+void (*pwn_fake_launch_hook)(const char *name, const void *src, const void *dst, int nsizes, const size_t *sizes) = NULL;
+}
+static void small_launch(const char *name, const void *src, const void *dst, std::initializer_list<size_t> sizes)
 {
-	if(pwn_fake_trace_hook != NULL) pwn_fake_trace_hook(P, lds_bytes);
+	if(pwn_fake_launch_hook != NULL) pwn_fake_launch_hook(name, src, dst, (int)sizes.size(), sizes.begin());
+}
+extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t)
+{
+	if(pwn_fake_trace_hook != NULL) pwn_fake_trace_hook(P, grid, lds_bytes);
 	uint32_t tab = 0;
 	for(uint32_t i = 0; i < P->blob_bytes / 4; i += 7) tab = mix(tab, P->blob[i]);
 	uint32_t secbits, cambits = 0;
@@ -49,6 +59,7 @@ extern "C" unsigned pwn_trace_lds_extra(void) { return 16u; }
 
 extern "C" hipError_t pwn_launch_blur(const pwn_blur_params *B, hipStream_t)
 {
+	if(pwn_fake_blur_hook != NULL) pwn_fake_blur_hook(B);
 	if(B->cost_acc != NULL) { *B->cost_out = (uint32_t)((unsigned long long)*B->cost_acc * B->cost_mul / B->cost_div); *B->cost_acc = 0u; }
 	unsigned missed = 0;
 	for(int y = B->y0; y < B->y1; y++)
@@ -65,18 +76,20 @@ extern "C" hipError_t pwn_launch_blur(const pwn_blur_params *B, hipStream_t)
 	if(B->miss != NULL && missed) *B->miss += missed;
 	return hipSuccess;
 }
-extern "C" hipError_t pwn_launch_order(const uint16_t *, uint32_t, uint32_t, uint32_t *, hipStream_t) { return hipSuccess; }
+extern "C" hipError_t pwn_launch_order(const uint16_t *cost, uint32_t units, uint32_t cap, uint32_t *perm, hipStream_t) { small_launch("order", cost, perm, { units, cap }); return hipSuccess; }
 extern "C" hipError_t pwn_launch_upscale(const uint32_t *src, uint32_t *dst, int w, int h, int scale, int pitch, hipStream_t)
 {
+	small_launch("upscale", src, dst, { (size_t)w, (size_t)h, (size_t)scale, (size_t)pitch });
 	const size_t rowadv = (size_t)w * scale + (size_t)pitch * (scale - 1);
 	for(int dy = 0; dy < h * scale; dy++) for(int dx = 0; dx < w * scale; dx++)
 		dst[(size_t)(dy / scale) * rowadv + (size_t)(dy % scale) * pitch + dx] = src[(size_t)(dy / scale) * w + dx / scale];
 	return hipSuccess;
 }
-extern "C" hipError_t pwn_launch_upload(const void *src, void *dst, size_t bytes, hipStream_t) { memcpy(dst, src, bytes); return hipSuccess; }
+extern "C" hipError_t pwn_launch_upload(const void *src, void *dst, size_t bytes, hipStream_t) { small_launch("upload", src, dst, { bytes }); memcpy(dst, src, bytes); return hipSuccess; }
 // (the camera set-up of pwn_trace_views_device: view_setup.hip's arithmetic, on "device" memory that is host memory here)
 extern "C" hipError_t pwn_launch_view_setup(const float *cams, const float *secs, pwn_view_rec *out, int n, int w, int h, hipStream_t)
 {
+	small_launch("view_setup", cams, out, { (size_t)n, (size_t)w, (size_t)h });
 	const pwn_setup_scalars S = pwn_frame_setup_scalars(w, h);
 	for(int v = 0; v < n; v++)
 	{

@@ -11,11 +11,11 @@
 #include <vector>
 #include "pwn_internal.h"
 
-extern "C" { extern void (*pwn_fake_trace_hook)(const pwn_trace_params *P, size_t lds_bytes); }
+extern "C" { extern void (*pwn_fake_trace_hook)(const pwn_trace_params *P, int grid, size_t lds_bytes); }
 static pwn_ctx *g_ctx;
 static int g_checked_global, g_checked_lds;
 #define REQ(x) do { if(!(x)) { fprintf(stderr, "CHECK FAILED %s line %d\n", #x, __LINE__); abort(); } } while(0)
-static void check_tables(const pwn_trace_params *P, size_t lds_bytes)
+static void check_tables(const pwn_trace_params *P, int, size_t lds_bytes)
 {
 	std::vector<uint16_t> counts(4096);
 	int n = pwn_get_bins(g_ctx, counts.data(), NULL, 0);
