@@ -87,6 +87,9 @@ extern "C" int pwn_init(pwn_ctx **out, int device, int width, int height)
 	if(const char *e = getenv("PWN_DBG_BLUR_TW")) c->dbg_blur_tw = atoi(e);
 	if(const char *e = getenv("PWN_DBG_BLUR_BATCH")) if(*e) c->dbg_blur_batch = atoi(e);
 	if(const char *e = getenv("PWN_DBG_BLOCKS_PER_CU")) { int v = atoi(e); if(v > 0) c->dbg_blocks_per_cu = v; }
+	// tile pairs (trace_kernel.hip): 0 never, 1 (default) in the launches that would draw their tickets two at a time, 2 always
+	c->tile_pairs = 1;
+	if(const char *e = getenv("PWN_TILE_PAIRS")) if(*e) { const int v = atoi(e); if(v >= 0 && v <= 2) c->tile_pairs = v; }
 	c->blob_cur = 0; c->blob_dirty = true; c->off_sph = 0; c->stage_next = 0; c->up_stream = NULL;
 	for(int i = 0; i < PWN_NBLOB; i++)
 	{
@@ -1144,12 +1147,41 @@ int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L)
 		if(reserve > 0 && grid > 2 * reserve) grid -= reserve;
 		L->cost_div = (uint32_t)grid;
 	}
-	// fewer units than resident waves (a 320 x 240 frame is 1200 units for 5120 waves): one unit per wave, a
-	// workgroup per four of them -- a workgroup whose waves find nothing still copies the tables into LDS
+	// (what the unit order needs: asked here, because a launch with an order keeps single units)
+	const bool want_cost = !refill && !batch && !glb && (c->unit_order || (c->wave_log_on && getenv("PWN_DBG_UNIT_COST") != NULL));
+	// Tile pairs (trace_kernel.hip): a frame's launch without an order hands out 32-pixel tiles, two units to a ticket -- where its
+	// tickets would go out two at a time (16 units or more per wave of the grid: the kernel's rule for draw_n), or always
+	// (PWN_TILE_PAIRS=2).  What the queues hold is then a row's tiles, ceil(tiles_x / 2), times the rows of units.
+	int items = P.tiles_total;
+	if(!refill && !batch && !want_cost && (c->tile_pairs == 2 || (c->tile_pairs == 1 && (long long)P.tiles_total >= 16ll * 4 * grid)))
+	{
+		const int tx = (P.tiles_x + 1) / 2;
+		P.tile_pairs = 1;
+		unit_div_magic((uint32_t)tx, &P.tx_magic, &P.tx_shift);
+		// The middle rows stay single units, in whole rows: the first round of the launch at least -- one item per wave of the grid, the
+		// static first tickets -- and a fifth of the rows.  That is where rays run longest (the middle-out order starts there for the
+		// same reason), and in a scene where single units are most of a launch the wave that holds one must not hold its neighbour too:
+		// synth256 at 4K has a column of such units down the middle of the frame, the dearest 1 744 wave steps, and a launch is as long
+		// as the dearest item: with tiles throughout, two neighbours of 1 295 + 1 069 steps (+37 % launch time); with the first round
+		// alone single, still those two (+22 %); outside the middle fifth the dearest tile has 577.  The tiles' saving is lost on that
+		// fifth.  PWN_TILE_PAIRS=2: tiles from the first ticket on.
+		const int rows = P.tiles_total / P.tiles_x;
+		int single = 0;
+		if(c->tile_pairs != 2)
+		{
+			single = (4 * grid + P.tiles_x - 1) / P.tiles_x;
+			if(single < (rows + 4) / 5) single = (rows + 4) / 5;
+		}
+		if(single > rows) single = rows;
+		P.pair_single_rows = single;
+		items = single * P.tiles_x + tx * (rows - single);
+	}
+	// fewer units (tiles, where they go out in pairs) than resident waves (a 320 x 240 frame is 1200 units for 5120 waves): one
+	// per wave, a workgroup per four of them -- a workgroup whose waves find nothing still copies the tables into LDS
 	{
 		const int wg_waves = 4;          // PWN_BLOCK / 64
-		if(!refill && grid > (P.tiles_total + wg_waves - 1) / wg_waves) grid = (P.tiles_total + wg_waves - 1) / wg_waves;
-		if(grid > P.tiles_total) grid = P.tiles_total;
+		if(!refill && grid > (items + wg_waves - 1) / wg_waves) grid = (items + wg_waves - 1) / wg_waves;
+		if(grid > items) grid = items;
 	}
 	// PWN_OPT_WAVE_LOG: every wave of this launch writes its start and end time; entry 0 is unused, entry
 	// 1 + 4 * workgroup + SIMD is a wave's (the buffer follows the grid of the launch)
@@ -1172,7 +1204,6 @@ int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L)
 	// and the wave log's span and residency are figures of the ordinary launch)
 	// (a batch of views or rays neither writes nor reads nor invalidates any of this)
 	// (nor do tables in the global form: their kernels have no ordered variant, PWN_OPT_UNIT_ORDER is ignored)
-	const bool want_cost = !refill && !batch && !glb && (c->unit_order || (c->wave_log_on && getenv("PWN_DBG_UNIT_COST") != NULL));
 	pwn_ctx::unit_order_state *uop = batch ? NULL : order_entry(c, stream, want_cost);
 	if(uop != NULL && want_cost)
 	{

@@ -121,7 +121,7 @@ static inline pwn_setup_scalars pwn_frame_setup_scalars(int w, int h)
                           // of frame f+1's tables had to wait for the end of frame f-1 and so ran right where trace f starts;
                           // with three or four it runs at once, somewhere beside the trace grid: 0.3823 -> 0.3790 ms per 4K frame
 #endif
-#define PWN_NCOUNTERS 48     // device counters of the counting kernel variants: 16 (pwn_stats) + 26 regions + waves + spare
+#define PWN_NCOUNTERS 48     // device counters of the counting kernel variants: 16 (pwn_stats) + 27 regions + waves + spare
 #define PWN_TILED_STREAMS_DEFAULT 2
 #define PWN_TICKET_SETS 6u  // launch n counts in set n mod 2R and clears set (n + R) mod 2R, R = pwn_ctx.launch_rot streams in rotation, 2 or 3 (pwn_i_launch_trace)
 #define PWN_NSTAGE 4      // pinned staging buffers for those uploads
@@ -257,6 +257,7 @@ struct pwn_ctx
 	int unit_order;                  // the option: 1 = units handed out by last launch's cost, 0 = arithmetic order
 	unsigned long long order_used, order_sorts;      // trace launches that ran in a sorted order; sorts launched (pwn_unit_order_state)
 	bool dbg_force_hasw; int dbg_blocks_per_cu;      // PWN_DBG_* hooks, read at pwn_init
+	int tile_pairs;                                  // PWN_TILE_PAIRS, read at pwn_init: 0 never, 1 where tickets would go out in pairs, 2 always (pwn_i_launch_trace)
 	int dbg_blur_th, dbg_blur_tw, dbg_blur_batch;                 // PWN_DBG_BLUR_TH: tile height of every blur launch (8 / 16 / 32), 0 = the launcher's choice
 	int grid_reserve;                // workgroups the persistent trace grid leaves free (row tiling over RCCL), else 0
 	// pwn_trace_views: per view slot a pre-blur, a colour and a depth plane (views_cap of each, view-major; the depth planes persist

@@ -223,6 +223,13 @@ struct pwn_trace_params
 	int nbounds;
 	uint32_t bound_ids[PWN_BOUNDS_MAX];
 	pwn_sphere_bound bounds[PWN_BOUNDS_MAX];
+	// Tile pairs (trace_kernel.hip, frames without an order; PWN_TILE_PAIRS): != 0: a ticket stands for a 32-pixel tile, whose two
+	// units the wave that draws it traces one after the other; tx_magic / tx_shift divide by the tiles per row, ceil(tiles_x / 2),
+	// as ux_magic / ux_shift divide by the units per row.  (Behind everything else: no other kernel's argument moves.)
+	// pair_single_rows: so many rows of units, the first in the launch's middle-out order, go out as single units in front of the tiles.
+	int tile_pairs;
+	uint32_t tx_magic; int tx_shift;
+	int pair_single_rows;
 };
 #define PWN_HIT_REC_BYTES 48u
 

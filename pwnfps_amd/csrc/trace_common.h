@@ -192,6 +192,7 @@ enum { RG_SEG = 0, RG_SETUP_SLOW, RG_EXHAUSTED, RG_WALL, RG_SPHERE, RG_FLOOR, RG
 	RG_COMP2, RG_COMP2_FOG, RG_HELP, RG_UNIT, RG_SPHTEST, RG_SPHUPD, RG_ELSE,
 	RG_UNIT_HALF, RG_HC_R2, RG_HC_OUT, RG_PORTAL_WALL, RG_PORTAL_GO, RG_PORTAL_ODD, RG_PORTAL_ROT2,
 	RG_SPHBOUND, RG_SPHSKIP,       // a list's ball is tested by the wave (trace_walk.inc, sphere_bound.h); ... and the list skipped
+	RG_UNIT_RIGHT,                 // tile pairs: a tile's right half is rebuilt from what its left half put aside (trace_kernel.hip)
 	RG_N };
 struct Counters { uint32_t rays, steps, portals, tests, exhausted, wsteps, wp[8], apasses, apass_lanes, rg[RG_N]; };
 // one count per wave64 that enters a code path with at least one lane (pwn_stats.wave_paths)

@@ -270,7 +270,7 @@ __device__ __forceinline__ void trace_hit(const Lds &L, Vec<HAS_W> from, Vec<HAS
 // v_add_f32 under a mask issues at full rate, the DPP form of the same systolic chain (v[j] = v[j-1] + rdx, round 2) at
 // half rate, and this is 45 of a unit's ~170 vector instructions.  All 64 lanes are active on entry (wave-uniform
 // control flow); rdx is wave-uniform (kernel argument).
-//@R k_unit
+//@R k_chain
 #define PWN_CHAIN_ROUND3(m) "s_mov_b32 exec_lo, " m "\n\ts_mov_b32 exec_hi, " m "\n\tv_add_f32 %0, %4, %0\n\tv_add_f32 %1, %5, %1\n\tv_add_f32 %2, %6, %2\n\t"
 #define PWN_CHAIN_ROUND4(m) "s_mov_b32 exec_lo, " m "\n\ts_mov_b32 exec_hi, " m "\n\tv_add_f32 %0, %5, %0\n\tv_add_f32 %1, %6, %1\n\tv_add_f32 %2, %7, %2\n\tv_add_f32 %3, %8, %3\n\t"
 #define PWN_CHAIN_ALL(R) R("0xfffefffe") R("0xfffcfffc") R("0xfff8fff8") R("0xfff0fff0") R("0xffe0ffe0") R("0xffc0ffc0") R("0xff80ff80") \
@@ -346,7 +346,25 @@ pwn_trace_kernel(pwn_trace_params P)
 	const uint32_t units_x = ((uint32_t)P.w + 15u) >> 4;
 	// (a batch of rays: 64 to a unit, P.nrays <= 2^28)
 	// (views of their own sizes: the host's sum over the views)
-	const uint32_t units = VPS ? (uint32_t)P.tiles_total : RAYS ? (P.nrays + 63u) >> 6 : units_x * (((uint32_t)(P.y1 - P.y0) + 3u) >> 2) * (VIEWS ? (uint32_t)P.nviews : 1u);
+	// Tile pairs (pwn_trace_params.tile_pairs; frames without an order only): the queues hand out whole 32-pixel TILES, and the wave
+	// that draws one traces its left half and then its right half (the unit loop).  `units` then counts tiles -- every queue
+	// length, QBASE, the help path's test and the host's grid rule with it -- and a draw takes one of them.
+	constexpr bool PAIRABLE = MODE == PWN_KM_FRAME && !ORDER;
+	const bool pairs = PAIRABLE && P.tile_pairs != 0;
+	const uint32_t tiles_x = (units_x + 1u) >> 1;
+	// (the setting as the unit loop reads it: 1 or 0, held in a scalar register -- left to itself the compiler keeps it as a lane
+	// value next to the unit's column, one register more than the 4-lane variants have)
+	uint32_t pair_shift = (uint32_t)__builtin_amdgcn_readfirstlane(pairs ? 1 : 0);
+	asm volatile("" : "+s"(pair_shift));
+	// The launch's FIRST items stay single units: the units of the first pair_single_rows rows of units in the middle-out order (the
+	// host makes that one item per wave of the grid or more).  Those are the static first tickets, started at the launch's first
+	// instant on the rows where rays run longest; where one unit is most of a launch (a hall of mirrors walked to the step limit),
+	// the wave that holds it must not hold its neighbour as well.  Items [0, pair_first) are those units, the rest are tiles.
+	const uint32_t rows_all = ((uint32_t)(P.y1 - P.y0) + 3u) >> 2;
+	// (both in scalar registers, as pair_shift below: as lane values they are kept in scratch memory across the unit loop)
+	const uint32_t single_rows = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pairs ? min((uint32_t)P.pair_single_rows, rows_all) : rows_all));
+	const uint32_t pair_first = (uint32_t)__builtin_amdgcn_readfirstlane((int)(single_rows * units_x));
+	const uint32_t units = VPS ? (uint32_t)P.tiles_total : RAYS ? (P.nrays + 63u) >> 6 : (pair_first + tiles_x * (rows_all - single_rows)) * (VIEWS ? (uint32_t)P.nviews : 1u);
 	if(blockIdx.x == 0 && threadIdx.x < PWN_QUEUES) P.tickets_next[threadIdx.x * PWN_QUEUE_STRIDE] = 0u;
 	if(blockIdx.x == 0 && threadIdx.x == PWN_QUEUES && P.clear_word != NULL) *P.clear_word = 0u;
 	uint32_t q = (blockIdx.x * (PWN_BLOCK / 64) + (uint32_t)wave) % PWN_QUEUES;
@@ -368,11 +386,12 @@ pwn_trace_kernel(pwn_trace_params P)
 #ifdef PWN_DRAW_PROBE
 	unsigned long long probe_ticks = 0ull, probe_n = 0ull;
 #endif
-	// Tickets are drawn two at a time when the launch is long (>= 16 units per wave): the returning atomic is a
+	// (Without tile pairs:) Tickets are drawn two at a time when the launch is long (>= 16 units per wave): the returning atomic is a
 	// 32-byte write at the memory side, 4 MB per 4K frame with one per unit, 2 MB with pairs.  Strips and small
 	// frames keep single tickets for the balance of their tail; three per draw measured 2.5 % slower at 4K (the
 	// tail) for another 0.6 MB.  `left` = tickets in hand after the current one (wave-uniform).
-	const uint32_t draw_n = units >= 16u * (PWN_BLOCK / 64u) * gridDim.x ? 2u : 1u;
+	// (a tile is two units in one ticket: the same commitment and as many returning atomics as a pair of tickets)
+	const uint32_t draw_n = !pairs && units >= 16u * (PWN_BLOCK / 64u) * gridDim.x ? 2u : 1u;
 	uint32_t left = 0u;
 	for(;;)
 	{
@@ -406,7 +425,6 @@ pwn_trace_kernel(pwn_trace_params P)
 			continue;
 		}
 		//@R k_unit
-		RG(RG_UNIT);
 		misses = 0;
 		// Which unit a ticket stands for: ticket * 64 + q in arithmetic order, or -- PWN_OPT_UNIT_ORDER, off by default -- what
 		// the table says: every queue's units sorted by what they cost in the last launch of this geometry, dearest first
@@ -535,6 +553,10 @@ pwn_trace_kernel(pwn_trace_params P)
 		int fw = P.w, fh = P.h, fy0 = P.y0, fy1 = P.y1;
 		uint32_t fux = units_x, fmagic = P.ux_magic;
 		int fshift = P.ux_shift;
+		// (tile pairs: behind the launch's single units the ticket stands for a tile, rows of tiles_x of them behind the single rows)
+		// (the unit number is the same for the whole wave: the choice is a scalar one)
+		uint32_t kbase = 0u, ush = 0u;
+		if(PAIRABLE && pair_shift != 0u && (uint32_t)__builtin_amdgcn_readfirstlane((int)unit) >= pair_first) { fu -= pair_first; fux = tiles_x; fmagic = P.tx_magic; fshift = P.tx_shift; kbase = single_rows; ush = 1u; }
 		uint32_t rows_u = ((uint32_t)(P.y1 - P.y0) + 3u) >> 2;
 		uint32_t org = 0u;
 		if constexpr(VPS)
@@ -579,7 +601,9 @@ pwn_trace_kernel(pwn_trace_params P)
 		// reciprocal hoisted to the top of the kernel and, in the 4-lane variant, parked in scratch memory)
 		if(fshift >= 0) k = __umulhi(fu, fmagic) >> fshift;
 		else k = fu;
-		const uint32_t ux = fu - k * fux;
+		// (tile pairs: the tile's left unit)
+		const uint32_t ux = (fu - k * fux) << (PAIRABLE ? ush : 0u);
+		if(PAIRABLE) k += kbase;
 		// ... of the FRAME: a strip of a row tiling starts at its rows nearest the frame's middle row (the strip of
 		// the whole frame at its own middle), not at its own middle
 		const int hrow = ((fh >> 1) - fy0) >> 2;
@@ -595,7 +619,7 @@ pwn_trace_kernel(pwn_trace_params P)
 		}
 		const int half = (int)(ux & 1u);                  // left / right half of the 32-wide tile
 		const int cx0 = (int)(ux >> 1) * 32;              // the 32-pixel tile of screen.h:6-7 this wave is in
-		const int x = (int)ux * 16 + (HAS_W ? (int)(ln & 15u) : l16), y = fy0 + (int)uy * 4 + (HAS_W ? (int)(ln >> 4) : (lane >> 4));
+		// (this unit's pixel: ux * 16 + lane & 15, fy0 + uy * 4 + lane >> 4 -- below, with what the tile's other half takes over)
 
 		// screen.h:12-18, in the order the reference build evaluates it:
 		// rayl = (cx*rdx + rayb) + y*rdy, then one "+= rdx" per pixel of the
@@ -605,7 +629,7 @@ pwn_trace_kernel(pwn_trace_params P)
 		//     v[j] = v[j-1] + rdx      (lane 0 of the row keeps its value)
 		// lanes 0..k hold their final value.  All 64 lanes take part (also those
 		// outside the frame), so this sits in front of the bounds test.
-		V rayl = vadd<HAS_W>(vadd<HAS_W>(vscale<HAS_W>((float)cx0, rdx), rayb), vscale<HAS_W>((float)y, rdy));
+		V rayl = vadd<HAS_W>(vadd<HAS_W>(vscale<HAS_W>((float)cx0, rdx), rayb), vscale<HAS_W>((float)(fy0 + (int)uy * 4 + (HAS_W ? (int)(ln >> 4) : (lane >> 4))), rdy));
 		if(half)
 		{
 			//@R k_unit_half
@@ -613,36 +637,84 @@ pwn_trace_kernel(pwn_trace_params P)
 #pragma unroll
 			for(int k = 0; k < 16; k++) rayl = vadd<HAS_W>(rayl, rdx);
 		}
-		//@R k_unit
-		rayl = vadd<HAS_W>(rayl, rdx);
-#ifndef PWN_CHAIN_DPP
-		chain_rounds<HAS_W>(rayl, rdx);
-#else
-		{
-			const bool first = (l16 == 0);
-			V add;
-			add.x = first ? rayl.x : rdx.x; add.y = first ? rayl.y : rdx.y; add.z = first ? rayl.z : rdx.z;
-			add.w = HAS_W ? (first ? rayl.w : rdx.w) : 0.0f;
-#pragma unroll
-			for(int k = 1; k < 16; k++)
-			{
-				rayl.x = dpp_row_shr1(rayl.x) + add.x;
-				rayl.y = dpp_row_shr1(rayl.y) + add.y;
-				rayl.z = dpp_row_shr1(rayl.z) + add.z;
-				if constexpr(HAS_W) rayl.w = dpp_row_shr1(rayl.w) + add.w;
-			}
-		}
-#endif
-
+		// Tile pairs: the tile's right half starts its chain where the left half's lane 15 of the same row ended -- base + 16 adds, the
+		// same fp32 additions from the same base that `if(half)` above makes -- and shares the tile's rows and columns.  What it needs is
+		// put aside behind the left half's chain in the lanes of ONE register (`carry`: lane 4c + r = component c of row r's lane 15;
+		// lane 16 and up = the tile's column and the unit's top row, 15 bits each), through the LDS crossbar (ds_bpermute: no LDS
+		// memory), because nothing else is free while a unit is traced: the kernel is at its register budget and the scalar registers
+		// already spill into lanes.  Both halves run the ONE text below (the chain, the bounds test, the trace, the stores).
+		float carry = 0.0f;
+		int x = (int)ux * 16 + (HAS_W ? (int)(ln & 15u) : l16), y = fy0 + (int)uy * 4 + (HAS_W ? (int)(ln >> 4) : (lane >> 4));
+		// (is there a right half: a frame with an odd number of units per row ends its rows with half a tile)
+		bool right_next = PAIRABLE && ush != 0u && (uint32_t)__builtin_amdgcn_readfirstlane((int)ux) + 1u < units_x;
 		unsigned long long u_begin = 0ull;
-		if(ORDER && P.unit_cost != NULL) u_begin = __builtin_amdgcn_s_memrealtime();
-		if(x < fw && y < fy1)
+#pragma unroll 1
+		for(;;)
 		{
-			const uint32_t seed = pixel_seed(x, y, fw);
-			float ox, oy, oz, ow;
-			const uint32_t o = __umul24((uint32_t)y, (uint32_t)P.w) + (uint32_t)x + org;      // w, h <= 32768 (pwn_init)
-			trace_pixel<COUNT, HAS_W, LISTS>(L, sec_current, seed, from, rayl, ox, oy, oz, ow, zbuf + o, cnt);
-			sbuf[o] = col_pack4(ox, oy, oz, ow);
+			//@R k_chain
+			RG(RG_UNIT);
+			rayl = vadd<HAS_W>(rayl, rdx);
+			chain_rounds<HAS_W>(rayl, rdx);
+			if(PAIRABLE && right_next)
+			{
+				//@R k_unit
+				uint32_t lp;
+				if constexpr(HAS_W)
+				{
+					lp = 0u;
+					asm volatile("" : "+v"(lp));
+					lp = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, lp));
+				}
+				else lp = (uint32_t)lane;
+				const int src = (int)(((lp & 3u) << 6) | 60u);            // byte address of lane 16 r + 15, r = lane & 3
+				const int px = __builtin_amdgcn_ds_bpermute(src, __float_as_int(rayl.x));
+				const int py = __builtin_amdgcn_ds_bpermute(src, __float_as_int(rayl.y));
+				const int pz = __builtin_amdgcn_ds_bpermute(src, __float_as_int(rayl.z));
+				int pc = lp < 4u ? px : lp < 8u ? py : pz;
+				if constexpr(HAS_W)
+				{
+					const int pw = __builtin_amdgcn_ds_bpermute(src, __float_as_int(rayl.w));
+					pc = lp < 12u ? pc : pw;
+				}
+				// (x and y are the left half's here: x - column in the half = the tile's first column, y - row in the unit = the top row)
+				const int xy = (x - (int)(lp & 15u)) | ((y - (int)(lp >> 4)) << 16);
+				carry = __int_as_float(lp < 16u ? pc : xy);
+			}
+			//@R k_chain
+			if(ORDER && P.unit_cost != NULL) u_begin = __builtin_amdgcn_s_memrealtime();
+			if(x < fw && y < fy1)
+			{
+				const uint32_t seed = pixel_seed(x, y, fw);
+				float ox, oy, oz, ow;
+				const uint32_t o = __umul24((uint32_t)y, (uint32_t)P.w) + (uint32_t)x + org;      // w, h <= 32768 (pwn_init)
+				trace_pixel<COUNT, HAS_W, LISTS>(L, sec_current, seed, from, rayl, ox, oy, oz, ow, zbuf + o, cnt);
+				sbuf[o] = col_pack4(ox, oy, oz, ow);
+			}
+			if(!(PAIRABLE && right_next)) break;
+			//@R k_unit_right
+			// The right half: its lanes' rows' rays from `carry`, its pixels 16 to the right of the left half's.  All 64 lanes are
+			// active again here, and the lanes of `carry` that are read were written by active lanes.
+			RG(RG_UNIT_RIGHT);
+			right_next = false;
+			{
+				uint32_t lp;
+				if constexpr(HAS_W)
+				{
+					lp = 0u;
+					asm volatile("" : "+v"(lp));
+					lp = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, lp));
+				}
+				else lp = (uint32_t)lane;
+				const int ci = __float_as_int(carry);
+				const int dst = (int)((lp >> 4) << 2);                    // byte address of lane r, r = the lane's row
+				rayl.x = __int_as_float(__builtin_amdgcn_ds_bpermute(dst, ci));
+				rayl.y = __int_as_float(__builtin_amdgcn_ds_bpermute(dst + 16, ci));
+				rayl.z = __int_as_float(__builtin_amdgcn_ds_bpermute(dst + 32, ci));
+				if constexpr(HAS_W) rayl.w = __int_as_float(__builtin_amdgcn_ds_bpermute(dst + 48, ci));
+				const int xy = __builtin_amdgcn_readlane(ci, 16);
+				x = (xy & 0xffff) + 16 + (int)(lp & 15u);
+				y = (xy >> 16) + (int)(lp >> 4);
+			}
 		}
 		// what this unit cost its wave (the add chain and the ticket arithmetic in front of it are the same for every unit)
 		if(ORDER && P.unit_cost != NULL && ln == 0u)

@@ -191,7 +191,7 @@ def parse(path, marks):
 
 
 COUNT_OF = {        # region -> key of the counts
-    "k_prologue": "waves", "k_epilogue": "waves", "k_unit": "units", "k_help": "help",
+    "k_prologue": "waves", "k_epilogue": "waves", "k_unit": "items", "k_help": "help",
     "p_setup": "segs", "p_setup_slow": "setup_slow", "p_walk_ctl": "wave_steps", "p_post": "segs", "p_exhausted": "exhausted_w",
     "p_wall": "wall", "p_sphere": "sphere", "p_floor": "floor", "p_sphrefl": "sphrefl", "p_jitter": "jitter",
     "p_comp": "units", "p_comp1": "comp1", "p_comp1_fog": "comp1_fog", "p_comp2": "comp2", "p_comp2_fog": "comp2_fog",
@@ -199,6 +199,9 @@ COUNT_OF = {        # region -> key of the counts
     "w_room": "wp1", "w_fog": "wp2", "w_height": "wp3", "w_height_r2": "hc_r2", "w_height_out": "hc_out", "w_else": "else", "w_ramp": "wp4",
     "w_portal": "wp5", "w_portal_wall": "portal_wall", "w_portal_go": "portal_go", "w_portal_odd": "portal_odd", "w_portal_rot2": "portal_rot2",
     "w_solid": "wp6", "k_unit_half": "unit_half",
+    # tile pairs: k_unit (ticket -> tile -> base ray, and what the right half needs put aside) runs once per ITEM -- a unit, or a
+    # tile of two -- k_chain (add chain, bounds test, seed, stores) once per unit, k_unit_right once per right half rebuilt
+    "k_chain": "units", "k_unit_right": "unit_right",
 }
 
 
@@ -254,6 +257,8 @@ def main():
     def totals(cnt):
         # a list's set-up (w_sphrun) runs in the visits that are not skipped: no counter of its own
         cnt = dict(cnt, sphrun=cnt.get("wp0", 0) - cnt.get("sphskip", 0))
+        # items handed out: every unit but the right halves that came with their tile
+        cnt["items"] = cnt.get("units", 0) - cnt.get("unit_right", 0)
         t = collections.Counter()
         by_region = {}
         for reg, c in per.items():

@@ -16,7 +16,7 @@ import pwnfps_amd  # noqa: E402
 gold = os.path.join(ROOT, "tests", "golden")
 out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "r4_region_counts.json")
 RG = ["segs", "setup_slow", "exhausted_w", "wall", "sphere", "floor", "sphrefl", "jitter", "comp1", "comp1_fog", "comp2", "comp2_fog",
-      "help", "units", "sphtest", "sphupd", "else", "unit_half", "hc_r2", "hc_out", "portal_wall", "portal_go", "portal_odd", "portal_rot2", "sphbound", "sphskip", "waves"]
+      "help", "units", "sphtest", "sphupd", "else", "unit_half", "hc_r2", "hc_out", "portal_wall", "portal_go", "portal_odd", "portal_rot2", "sphbound", "sphskip", "unit_right", "waves"]
 
 
 def pmc_4k():

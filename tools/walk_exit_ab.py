@@ -2,7 +2,7 @@
 """A/B of how the trace kernel's walk loop ends (trace_kernel.hip: the step limit carried in ev): per scene the trace launch by
 itself (frames on ONE compute stream, HIP events around every launch) and the frame on two streams.  One process per build -- the
 library is chosen by PWNHIP_LIB -- run alternately for the parent commit's library and this tree's.  -> profiles/walk_exit/ab.txt
-    PWNHIP_LIB=path python3 tools/walk_exit_ab.py LABEL [ROUNDS]"""
+    PWNHIP_LIB=path python3 tools/walk_exit_ab.py LABEL [ROUNDS [8k]]        (8k: level.txt at 7680 x 4320 as well)"""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -51,8 +51,11 @@ def measure(level, w, h, hasw):
     return out
 
 
-for level, w, h, hasw in (("pwnfps_level", 3840, 2160, False), ("pwnfps_level", 3840, 2160, True), ("pwnfps_level", 1280, 720, False),
-                          ("synth64", 1920, 1080, False), ("synth256", 3840, 2160, False)):
+CASES = [("pwnfps_level", 3840, 2160, False), ("pwnfps_level", 3840, 2160, True), ("pwnfps_level", 1280, 720, False),
+         ("synth64", 1920, 1080, False), ("synth256", 3840, 2160, False)]
+if "8k" in sys.argv[3:]:
+    CASES.append(("pwnfps_level", 7680, 4320, False))
+for level, w, h, hasw in CASES:
     for rep in range(rounds):
         o = measure(level, w, h, hasw)
         print("%-8s %-13s %4dx%-4d %s: trace launch alone %.4f ms (frame on one stream %.4f ms); frame on two streams %.4f ms" % (
