@@ -46,7 +46,7 @@ __device__ __forceinline__ float v4_dot(v4 a, v4 b)
 //   rsqrt: index = (e odd ? 1024 : 0) + mantissa bits 22..13 (i.e. bits 23..13
 //          of the input as they lie);     result = 2^(190-h+flag) * 1.m12,
 //          h = (e+1)>>1
-// An LDS entry is the 13 bits flag<<12 | m12 (u16, built by pack_blob() from
+// An LDS entry is the 13 bits flag<<12 | m12 (u16, built by pwn_i_pack_blob() from
 // approx_tables.inc); BASE + (entry << 11) is the result for e = 0 / h = 0 as an
 // fp32 bit pattern (BASE = 253<<23 resp. 190<<23), so a positive normal input
 // costs an index, one ds_read_u16, one shift-add and a subtract in the

@@ -10,7 +10,7 @@
  *
  *   pwn_sphere_bounds_build   a bounding ball for the longest per-cell lists (sphere_bound.h)
  *
- * All produce flat tables that pwn_api.cpp packs into the LDS blob.
+ * All produce flat tables that pwn_tables.cpp packs into the LDS blob.
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -275,7 +275,7 @@ int pwn_bin_spheres(const pwn_sphere *s, int n, int32_t *off, int32_t *idx, int 
 
 /* Bounding balls for the longest per-cell lists (sphere_bound.h has the predicate, the proof and the constants).
    off / idx: the lists as pwn_bin_spheres made them; form: PWN_LF_* of the tables they go into (tables.h: 0 indexed, 1 inline, 2 global), which decides what a list's id is
-   (bits 16..30 of its cell's word: tables.h, pack_blob).  The PWN_BOUNDS_MAX lists with the most records are taken, of equally long
+   (bits 16..30 of its cell's word: tables.h, pwn_i_pack_blob).  The PWN_BOUNDS_MAX lists with the most records are taken, of equally long
    ones the lower cell first, none shorter than PWN_BOUND_MIN_RECORDS; of those a list gets no ball (and no other list takes its
    place) when a member is not finite or far out, or its ball would be large.  Returns how many balls it wrote, longest list first. */
 int pwn_sphere_bounds_build(const pwn_sphere *s, const int32_t *off, const int32_t *idx, int form, pwn_sphere_bound *out)

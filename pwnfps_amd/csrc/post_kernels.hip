@@ -102,7 +102,7 @@ pwn_blur_kernel(pwn_blur_params P)
 // magnitude faster and the staging adds only (1 + 2*HALO/TW)(1 + 2*HALO/TH)
 // coalesced reads per output pixel.
 // The tile (BLUR_TW x BLUR_TH) and the form of the staging loop (BATCH) are template parameters; pwn_i_launch_blur
-// (pwn_api.cpp) picks them.  Rounds 1-2 ran 128 x 32 tiles (1024 threads, 42 KB of LDS: the least staging per output
+// (pwn_launch.cpp) picks them.  Rounds 1-2 ran 128 x 32 tiles (1024 threads, 42 KB of LDS: the least staging per output
 // pixel and the fastest launch BY ITSELF); judged by the frame rate with the next frame's trace grid on the chip
 // beside it, small workgroups win -- 32 x 32 (256 threads, 17 KB) on wide frames, 128 x 16 on narrow ones
 // (profiles/r3_blur_sweep.txt).

@@ -1,7 +1,12 @@
 // pwn_internal.h -- the context behind include/pwnhip.h, shared by the translation
-// units of libpwnhip.so (pwn_api.cpp: context, options, tables, the trace and blur launches, the blocking call, the batches of
-// views, viewports, rays and hits, frames in flight, sink, probes; pwn_tiled.cpp: row tiling over RCCL; pwn_group.cpp: several
-// contexts behind one handle).
+// units of libpwnhip.so:
+//   pwn_api.cpp     context, options, the room control, stats, sink, probes
+//   pwn_tables.cpp  level, objects, the sphere tables: their size rules, packing and upload
+//   pwn_launch.cpp  the trace and blur launchers (the launch geometry itself: launch_plan.h), the unit order, the *_rows_device calls
+//   pwn_calls.cpp   the blocking call and its strips, host registration, the batches of views, viewports, rays and hits
+//   pwn_frames.cpp  frames in flight
+//   pwn_tiled.cpp   row tiling over RCCL
+//   pwn_group.cpp   several contexts behind one handle
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -98,7 +103,7 @@ extern "C" hipError_t pwn_launch_words(const uint32_t *d_all, const uint32_t *d_
 extern "C" hipError_t pwn_launch_probe(int op, const uint32_t *in, uint32_t *out, int n, const uint16_t *tabs, hipStream_t stream);
 
 // The camera-independent scalars of the camera set-up (screen.h:43-57) of a w x h frame, in the reference build's operation
-// order: frame_setup (pwn_api.cpp) and the device's set-up (view_setup.hip) both take them from here, computed on the host.
+// order: frame_setup (below) and the device's set-up (view_setup.hip) both take them from here, computed on the host.
 struct pwn_setup_scalars { float yrat, xsrat, ysrat; };
 static inline pwn_setup_scalars pwn_frame_setup_scalars(int w, int h)
 {
@@ -109,6 +114,25 @@ static inline pwn_setup_scalars pwn_frame_setup_scalars(int w, int h)
 	s.ysrat = (s.yrat + s.yrat) / dimy;
 	return s;
 }
+// screen.h:43-57 in the reference build's operation order:
+// rayb = (cam.x + cam.z) + (-yrat)*cam.y
+// (into a launch's parameters, or into the head that a view's record shares with them: pwn_view_rec, pwn_viewport_rec)
+template<class T> static inline void frame_setup(int w, int h, const float cam[16], T *P)
+{
+	const pwn_setup_scalars S = pwn_frame_setup_scalars(w, h);
+	const float yrat = S.yrat, xsrat = S.xsrat, ysrat = S.ysrat;
+	for(int i = 0; i < 4; i++)
+	{
+		P->rayb[i] = (cam[0 + i] + cam[8 + i]) + (-yrat) * cam[4 + i];
+		P->rdx[i] = xsrat * cam[0 + i];
+		P->rdy[i] = ysrat * cam[4 + i];
+		P->from[i] = cam[12 + i];
+	}
+}
+// ordinary cameras (rows x,y,z with w = 0, position w = 1: mat4_iden + rotations,
+// main.c:61-64) never put anything but 0 / 1 into the w lanes; the kernel has a
+// 3-lane specialisation for them that is arithmetically identical
+static inline bool camera_has_w(const float cam[16]) { return !(cam[3] == 0.0f && cam[7] == 0.0f && cam[11] == 0.0f && cam[15] == 1.0f); }
 
 // LDS budget for the table blob: leave room so that at least two workgroups
 // fit per CU (160 KiB LDS per CU on gfx950)
@@ -195,7 +219,7 @@ struct pwn_ctx
 
 	uint8_t cells[4096];
 	uint32_t cell_base[65 * 65];      // the level's part of every cell word (class bits + the baked low byte, cell_bake.h; row / column 64 = the
-	bool cell_base_ok;               // clamp copies): built by pack_blob when the level OR its portal table changed, patched per upload with the cells' sphere lists
+	bool cell_base_ok;               // clamp copies): built by pwn_i_pack_blob when the level OR its portal table changed, patched per upload with the cells' sphere lists
 	uint32_t ep_recs[PWN_EP_MAX];    // ... and the portals' endpoint records that go with it
 	pwn_portal pmap[26];
 	int32_t spawn[2];
@@ -221,9 +245,9 @@ struct pwn_ctx
 	// The lists' global form (tables.h PWN_LF_GLOBAL): `blob` is then the LDS part alone and `big` the host image of the device-memory
 	// part, big_which / big_sph its sections.  Copy i of the tables has d_big[i] beside d_blob[i], under the same events; staging
 	// buffer i of the ring has h_big[i] beside h_stage[i].  All of them are allocated with the first tables that need them and
-	// grown to the largest so far (big_high); pack_blob says what growing waits for.
+	// grown to the largest so far (big_high); pwn_i_pack_blob says what growing waits for.
 	int lists_form;                  // PWN_LF_* of the tables in force
-	pwn_sphere_bound bounds[PWN_BOUNDS_MAX]; int nbounds;      // the balls of their longest lists (sphere_bound.h), made with them by pack_blob
+	pwn_sphere_bound bounds[PWN_BOUNDS_MAX]; int nbounds;      // the balls of their longest lists (sphere_bound.h), made with them by pwn_i_pack_blob
 	int dbg_sphere_bounds;           // PWN_SPHERE_BOUNDS of the environment: 0 = launches are sent no balls (tests, A/B in one process)
 	std::vector<uint8_t> big; uint64_t big_which, big_sph;
 	uint8_t *d_big[PWN_NBLOB]; size_t d_big_cap[PWN_NBLOB];
@@ -271,7 +295,7 @@ struct pwn_ctx
 	// of the call in pinned staging and on the device (PWN_VIEWS_MAX of them)
 	uint32_t *d_ppre, *d_pout; float *d_pz;
 	pwn_viewport_rec *h_prec, *d_prec;
-	// pwn_trace_rays: room for rays_cap rays in pinned staging and on the device, 44 B each (record, seed, depth, colour; pwn_api.cpp staging_reserve)
+	// pwn_trace_rays: room for rays_cap rays in pinned staging and on the device, 44 B each (record, seed, depth, colour; pwn_calls.cpp staging_reserve)
 	unsigned char *h_rays, *d_rays; size_t rays_cap;
 	// pwn_trace_hits: the same for hits_cap rays, 32 B in (record) and 48 B out (pwn_hit) each
 	unsigned char *h_hits, *d_hits; size_t hits_cap;
@@ -286,7 +310,7 @@ struct pwn_ctx
 	hipEvent_t last_frame_done; hipStream_t last_frame_stream;   // "kernels done" of the frame submitted last, and its stream
 	hipStream_t copy_stream;         // frames in flight: D2H of finished frames
 	hipEvent_t ev[4];
-	// The blocking call in row strips (PWN_OPT_CALL_STRIPS; pwn_api.cpp, call_in_strips): trace strip k, blur strip k - 1 from the
+	// The blocking call in row strips (PWN_OPT_CALL_STRIPS; pwn_calls.cpp, call_in_strips): trace strip k, blur strip k - 1 from the
 	// rows traced so far, strip k - 2 on its way to the caller's buffer -- the copy over PCIe is twice a 4K frame's kernels
 	int call_strips;                 // the option: -1 = by frame size (default), 0 = one launch per pass, n >= 2 = that many strips
 	hipStream_t copy_stream2;        // the blocking call in strips: chunks go out on one copy stream or on the two in turn
@@ -328,12 +352,25 @@ struct pwn_ctx
 #define HIPCHK(ctx, call) do { hipError_t e_ = (call); if(e_ != hipSuccess) { \
 	snprintf((ctx)->err, sizeof((ctx)->err), "%s: %s", #call, hipGetErrorString(e_)); return PWN_EHIP; } } while(0)
 
-// pwn_api.cpp internals used by pwn_tiled.cpp
+// pwn_init_multi's handle (pwn_group.cpp): the call goes to the group, or to its member 0 where it is about the one
+// level and object table, or is refused
+#define GRP_HEAD(c) ((c) != NULL && (c)->grp != NULL && (c)->grp_head)
+#define GRP_M0(c) pwn_group_member((c), 0)
+#define GRP_REFUSE(c, what) do { if(GRP_HEAD(c)) { snprintf((c)->err, sizeof((c)->err), "%s is not available on a group's handle", what); return PWN_ENOTSUP; } } while(0)
+
+// pwn_launch.cpp: the launchers, used by the calls, the frames in flight and pwn_tiled.cpp
 int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L);
 int pwn_i_launch_blur(pwn_ctx *c, const pwn_blur_launch *L);
 void pwn_launch_history_clear(pwn_ctx *c);      // the launch-order events are about to be destroyed (streams idle)
 int pwn_i_set_launch_rotation(pwn_ctx *c, int rot);
 int pwn_i_launch_order(pwn_ctx *c, hipStream_t stream);      // behind a frame's last kernel on `stream`: sort that stream's unit costs (no-op when there are none)
+// the blur passes behind a trace into *cur, the two planes taking turns, the last pass into `last` where one is given
+int pwn_i_blur_passes_run(pwn_ctx *c, pwn_blur_launch B, uint32_t **cur, uint32_t *other, uint32_t *last = NULL);
+// pwn_frames.cpp: every frame slot gone (no frame in flight); pwn_tables.cpp: the rcp / rsqrt tables as the kernels read them,
+// and the tables in force packed and uploaded into the next copy
+void pwn_i_frames_release(pwn_ctx *c);
+void pwn_i_expand_tables(uint16_t *rcp, uint16_t *rsq);
+int pwn_i_pack_blob(pwn_ctx *c);
 void pwn_tiled_destroy(pwn_ctx *c);
 bool pwn_tiled_busy(pwn_ctx *c);        // frames of the row tiling in flight
 // pwn_tiled.cpp internals used by pwn_group.cpp: a member's frame with the host buffers its strip is delivered into (NULL: the
@@ -342,7 +379,7 @@ int pwn_i_tiled_submit(pwn_ctx *c, const float cam[16], float sec, uint32_t *hos
 int pwn_i_tiled_surface(pwn_ctx *c, int scale, int pitch_bytes);
 int pwn_i_tiled_sink(pwn_ctx *c);
 int pwn_i_tiled_ready(pwn_ctx *c, int ahead);
-// pwn_api.cpp: level_prepare_render's binning of a compact list of live spheres (no context: PWN_ETOOBIG where the lists would not
+// pwn_tables.cpp: level_prepare_render's binning of a compact list of live spheres (no context: PWN_ETOOBIG where the lists would not
 // fit on chip), and its upload into one context; the object table of pwn_upload_spheres by itself
 struct pwn_binned { std::vector<pwn_sphere> s; std::vector<int32_t> off, idx; };
 // The size rules of the sphere tables, in one place: which form the per-cell lists of these bins take under this scheduler

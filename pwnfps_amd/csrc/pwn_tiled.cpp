@@ -764,8 +764,7 @@ struct pwn_tiled
 	bool prof; double p_trace, p_halo, p_blur, p_gather, p_events, p_meet, p_rest; unsigned long long p_frames;
 };
 
-#define GRP_HEAD(c) ((c) != NULL && (c)->grp != NULL && (c)->grp_head)
-#define GRP_REFUSE(c) do { if(GRP_HEAD(c)) { snprintf((c)->err, sizeof((c)->err), "a group's handle runs its own tiling (pwn_init_multi)"); return PWN_ENOTSUP; } } while(0)
+#define GRP_REFUSE_TILING(c) do { if(GRP_HEAD(c)) { snprintf((c)->err, sizeof((c)->err), "a group's handle runs its own tiling (pwn_init_multi)"); return PWN_ENOTSUP; } } while(0)
 #define TPCHK(c, call) do { int rc_ = (call); if(rc_ != PWN_OK) { snprintf((c)->err, sizeof((c)->err), "%s transport: %s", \
 	(c)->tiled->tp->name(), (c)->tiled->tp->err); return rc_; } } while(0)
 
@@ -980,7 +979,7 @@ bool pwn_tiled_busy(pwn_ctx *c) { return c->tiled != NULL && c->tiled->submitted
 
 extern "C" int pwn_tiled_init(pwn_ctx *c, int rank, int world, const void *id, int transport, int halo_rows)
 {
-	GRP_REFUSE(c);
+	GRP_REFUSE_TILING(c);
 	if(c == NULL || id == NULL || world < 1 || world > MAXW || rank < 0 || rank >= world) return PWN_EINVAL;
 	if(c->tiled != NULL) return PWN_EBUSY;
 	for(int i = 0; i < c->nslots; i++) if(c->slot[i].in_flight) return PWN_EBUSY;
@@ -1169,7 +1168,7 @@ extern "C" int pwn_tiled_init(pwn_ctx *c, int rank, int world, const void *id, i
 	// (the memsets above ran on the null stream, which the non-blocking streams of the frames do not wait for)
 	if(rc == PWN_OK && hipDeviceSynchronize() != hipSuccess) rc = PWN_EHIP;
 	if(rc != PWN_OK) { char keep[256]; memcpy(keep, c->err, sizeof(keep)); pwn_tiled_destroy(c); memcpy(c->err, keep, sizeof(keep)); return rc; }
-	// Room for RCCL's kernels beside the persistent trace grid (pwn_api.cpp): 16 workgroups of ~1280, i.e. one less
+	// Room for RCCL's kernels beside the persistent trace grid (pwn_launch.cpp, launch_plan.h): 16 workgroups of ~1280, i.e. one less
 	// on 16 CUs, 1.25 % of the grid.  Not measurable without several GPUs; PWN_TILED_RESERVE=n overrides it
 	// (0 = fill every CU), pwn_tiled_set_reserve() changes it between frames: bench.py --gpus N sweeps it.
 	c->grid_reserve = 0;
@@ -1193,7 +1192,7 @@ extern "C" int pwn_tiled_init(pwn_ctx *c, int rank, int world, const void *id, i
 
 extern "C" int pwn_tiled_balance(pwn_ctx *c, int every_frames)
 {
-	GRP_REFUSE(c);
+	GRP_REFUSE_TILING(c);
 	if(c == NULL || c->tiled == NULL || every_frames < 0) return PWN_EINVAL;
 	c->tiled->balance_every = every_frames;
 	return PWN_OK;
@@ -1201,7 +1200,7 @@ extern "C" int pwn_tiled_balance(pwn_ctx *c, int every_frames)
 
 extern "C" int pwn_tiled_set_reserve(pwn_ctx *c, int workgroups)
 {
-	GRP_REFUSE(c);
+	GRP_REFUSE_TILING(c);
 	if(c == NULL || c->tiled == NULL || workgroups < 0 || workgroups > 512) return PWN_EINVAL;
 	c->grid_reserve = workgroups;
 	c->tiled->info.grid_reserve = workgroups;
@@ -1210,7 +1209,7 @@ extern "C" int pwn_tiled_set_reserve(pwn_ctx *c, int workgroups)
 
 extern "C" int pwn_tiled_gather_root(pwn_ctx *c, int mode)
 {
-	GRP_REFUSE(c);
+	GRP_REFUSE_TILING(c);
 	if(c == NULL || c->tiled == NULL || (mode != PWN_TILED_ROOT_FIXED && mode != PWN_TILED_ROOT_ROTATE)) return PWN_EINVAL;
 	pwn_tiled *t = c->tiled;
 	if(t->submitted != t->delivered) return PWN_EBUSY;
@@ -1233,7 +1232,7 @@ extern "C" int pwn_tiled_gather_root(pwn_ctx *c, int mode)
 
 extern "C" int pwn_tiled_set_cuts(pwn_ctx *c, const int *cuts, int n)
 {
-	GRP_REFUSE(c);
+	GRP_REFUSE_TILING(c);
 	if(c == NULL || c->tiled == NULL || cuts == NULL) return PWN_EINVAL;
 	pwn_tiled *t = c->tiled;
 	if(n != t->world + 1) return PWN_EINVAL;
@@ -1251,7 +1250,7 @@ extern "C" int pwn_tiled_set_cuts(pwn_ctx *c, const int *cuts, int n)
 
 extern "C" int pwn_tiled_get_cuts(pwn_ctx *c, int *cuts, uint32_t *cost)
 {
-	GRP_REFUSE(c);
+	GRP_REFUSE_TILING(c);
 	if(c == NULL || c->tiled == NULL || cuts == NULL) return PWN_EINVAL;
 	pwn_tiled *t = c->tiled;
 	memcpy(cuts, t->cuts, sizeof(int) * (size_t)(t->world + 1));
@@ -1261,7 +1260,7 @@ extern "C" int pwn_tiled_get_cuts(pwn_ctx *c, int *cuts, uint32_t *cost)
 
 extern "C" int pwn_tiled_host_sink(pwn_ctx *c, void *base, size_t bytes)
 {
-	GRP_REFUSE(c);
+	GRP_REFUSE_TILING(c);
 	if(c == NULL || c->tiled == NULL || base == NULL) return PWN_EINVAL;
 	pwn_tiled *t = c->tiled;
 	if(t->submitted != 0 || t->host_base != NULL) return PWN_EBUSY;
@@ -1318,7 +1317,7 @@ int pwn_i_tiled_sink(pwn_ctx *c)
 
 extern "C" int pwn_tiled_get_info(pwn_ctx *c, pwn_tiled_info *out)
 {
-	GRP_REFUSE(c);
+	GRP_REFUSE_TILING(c);
 	if(c == NULL || out == NULL || c->tiled == NULL) return PWN_EINVAL;
 	pwn_tiled *t = c->tiled;
 	t->info.halo_rows = t->halo;
@@ -1569,7 +1568,7 @@ extern "C" int pwn_tiled_submit(pwn_ctx *c, const float cam[16], float sec) { re
 
 int pwn_i_tiled_submit(pwn_ctx *c, const float cam[16], float sec, uint32_t *host_sbuf, float *host_zbuf, int zplane, uint32_t *host_surface)
 {
-	GRP_REFUSE(c);
+	GRP_REFUSE_TILING(c);
 	if(c == NULL || cam == NULL || c->tiled == NULL) return PWN_EINVAL;
 	pwn_tiled *t = c->tiled;
 	if(t->sink && host_sbuf == NULL && t->host_base == NULL) return PWN_EINVAL;
@@ -1750,7 +1749,7 @@ int pwn_i_tiled_ready(pwn_ctx *c, int ahead)
 
 extern "C" int pwn_tiled_wait(pwn_ctx *c, int flags, pwn_tiled_frame *out)
 {
-	GRP_REFUSE(c);
+	GRP_REFUSE_TILING(c);
 	if(c == NULL || c->tiled == NULL) return PWN_EINVAL;
 	pwn_tiled *t = c->tiled;
 	if(t->delivered >= t->submitted) return PWN_EINVAL;          // nothing in flight

@@ -1,5 +1,5 @@
 // tables.h -- layout of the per-level table blob shared by the host packer
-// (pwn_api.cpp) and the kernels.  The blob is built once per level / sphere
+// (pwn_tables.cpp) and the kernels.  The blob is built once per level / sphere
 // upload, lives in HBM, and is copied verbatim into LDS by every workgroup.
 //
 //   [0      .. 4096)   rcp      u16 [2048]        RCPPS table     (trace.h:231), see dev_math.h
@@ -87,7 +87,7 @@ static inline uint32_t pwn_t_recsph_offset(uint32_t nrec) { return PWN_T_BINIDX 
 static inline uint32_t pwn_t_sph_offset_inl(uint32_t nrec) { return pwn_t_recsph_offset(nrec) + ((nrec * 2u + 15u) & ~15u); }
 static inline uint32_t pwn_t_total_inl(uint32_t nrec, uint32_t nsph) { return pwn_t_sph_offset_inl(nrec) + nsph * 32u; }
 
-// The per-cell lists in DEVICE MEMORY (sphere sets whose lists outgrow LDS, up to PWN_OBJ_MAX spheres: pwn_tables_plan, pwn_api.cpp).
+// The per-cell lists in DEVICE MEMORY (sphere sets whose lists outgrow LDS, up to PWN_OBJ_MAX spheres: pwn_tables_plan, pwn_tables.cpp).
 // LDS holds the blob up to and including eprec and, at PWN_T_BINIDX, `liststart`: one u32 per NON-EMPTY cell, the index of that
 // cell's first record.  The cell word keeps PWN_C_SPH; its bits 16..30 hold the non-empty cell's ordinal (at most 4096 cells,
 // however many records there are).  A buffer apart from the blob, in 16-byte aligned sections, nothing in it 16-bit:
@@ -113,7 +113,7 @@ static inline uint64_t pwn_g_total(uint64_t nrec, uint64_t nsph) { return pwn_g_
 	0x3feee89f995ad3ad, 0x3feeff76f2fb5e47, 0x3fef199bdd85529c, 0x3fef3720dcef9069, \
 	0x3fef5818dcfba487, 0x3fef7c97337b9b5f, 0x3fefa4afa2a490da, 0x3fefd0765b6e4540 }
 
-// the constant shading tables at PWN_T_FACES and PWN_T_EXP2 (host: pack_blob)
+// the constant shading tables at PWN_T_FACES and PWN_T_EXP2 (host: pwn_i_pack_blob)
 static inline void pwn_fill_faces(float *f)
 {
 	// wall class -> colour factors (BASE_CEIL, BASE_FLOOR, BASE_WALL, BASE_MAGENTA of trace_common.h)
@@ -266,7 +266,7 @@ struct pwn_blur_params
 // what a launch of the trace kernel traces (its MODE parameter, trace_kernel.hip)
 enum { PWN_KM_FRAME = 0, PWN_KM_VIEWS = 1, PWN_KM_RAYS = 2, PWN_KM_HITS = 3, PWN_KM_VIEWPORTS = 4 };
 
-// One view of a batch: the camera set-up of screen.h:43-57 for that view's camera (pwn_api.cpp frame_setup) and its
+// One view of a batch: the camera set-up of screen.h:43-57 for that view's camera (pwn_internal.h frame_setup) and its
 // sec_current.  80 bytes; the kernel reads a view's record with scalar loads.
 struct pwn_view_rec
 {
@@ -282,7 +282,7 @@ struct pwn_view_rec
 // has more than r units, so all views advance together, each from its middle row outwards, and a view drops out when it is done.
 // Views s .. nvp-1 take part in rounds [units of record s-1, units of record s): "segment" s, whose fields sit in record s --
 // seg_first = the launch's first ticket of the segment (rising with s; equal for an empty segment), seg_round = its first round,
-// seg_magic / seg_shift = the division by its nvp - s participants (unit_div_magic; shift < 0: one participant).
+// seg_magic / seg_shift = the division by its nvp - s participants (pwn_unit_div_magic; shift < 0: one participant).
 struct pwn_viewport_rec
 {
 	float rayb[4], rdx[4], rdy[4], from[4];

@@ -260,7 +260,7 @@ __device__ __forceinline__ void trace_hit(const Lds &L, Vec<HAS_W> from, Vec<HAS
 		r1 = make_uint4(__float_as_uint(dist), __float_as_uint(at.x), __float_as_uint(at.y), __float_as_uint(at.z));
 		r2 = make_uint4(__float_as_uint(ray.x), __float_as_uint(ray.y), __float_as_uint(ray.z), hit_cxz);
 	}
-	// three 16-byte stores (the record is 16-byte aligned: pwn_api.cpp checks the array)
+	// three 16-byte stores (the record is 16-byte aligned: pwn_calls.cpp checks the array)
 	out[0] = r0; out[1] = r1; out[2] = r2;
 }
 
@@ -471,7 +471,7 @@ pwn_trace_kernel(pwn_trace_params P)
 			//
 			// Any bit pattern in any lane (NaN, +-inf, 1e30, a zero direction, an origin far outside the grid) keeps every address in
 			// range.  Global: i < nrays <= 2^28 and 64-bit offsets, so rays + 32 i, seeds + 4 i, sbuf + 4 i and zbuf + 4 i lie in the
-			// caller's buffers of n entries (pwn_api.cpp checks n and the alignment).  LDS, in trace_pixel: the ray is never an index
+			// caller's buffers of n entries (pwn_calls.cpp checks n and the alignment).  LDS, in trace_pixel: the ray is never an index
 			// by itself.  The table reads take (bits >> 12 or 13) & 2047 of a float (dev_math.h: in range for every bit pattern).  The
 			// starting cell is (int)pos, which saturates (NaN converts to 0), pinned to [-16384, 16383] per axis (cxz_pack_start); a
 			// walk step moves it by one; the cell word is read at min(c, 64) per axis as unsigned 16-bit fields (cellword_pk: a negative
@@ -521,8 +521,8 @@ pwn_trace_kernel(pwn_trace_params P)
 		// from the wave number, which it derives from threadIdx.  Declaring q uniform and dividing by a multiply-high
 		// with a host-computed reciprocal moves ~35 VALU instructions per unit to the scalar unit: measured 0.8 %
 		// SLOWER at 4K, three runs -- a wave's scalar instructions issue one at a time and in order)
-		// unit / units_x by the host's reciprocal (pwn_trace_params.ux_magic: exact for every unit < 2^31, pwn_api.cpp
-		// unit_div_magic): two instructions where the compiler's division takes thirteen; frames one unit wide divide
+		// unit / units_x by the host's reciprocal (pwn_trace_params.ux_magic: exact for every unit < 2^31, launch_plan.h
+		// pwn_unit_div_magic): two instructions where the compiler's division takes thirteen; frames one unit wide divide
 		// A batch of views: the units are handed out INTERLEAVED, unit = (unit of the frame) * nviews + view, so that the first
 		// tickets of the launch cover every view's middle rows and each view's rows go out middle-out as one frame's do -- the
 		// expensive horizon bands of all views are started first and the cheap edges of all views make up the tail.  (View-major
@@ -597,7 +597,7 @@ pwn_trace_kernel(pwn_trace_params P)
 			org = ri[18] * (uint32_t)P.w + ri[17];
 		}
 		uint32_t k;
-		// (ux_shift < 0 only for units_x == 1, pwn_api.cpp unit_div_magic: then k = unit.  A real division here had its
+		// (ux_shift < 0 only for units_x == 1, launch_plan.h pwn_unit_div_magic: then k = unit.  A real division here had its
 		// reciprocal hoisted to the top of the kernel and, in the 4-lane variant, parked in scratch memory)
 		if(fshift >= 0) k = __umulhi(fu, fmagic) >> fshift;
 		else k = fu;
@@ -780,7 +780,7 @@ using Units = TraceKernels<pwn_trace_kernel<true, true, ORDER, LISTS, MODE>, pwn
 
 extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
 {
-	// (the blob says which form its per-cell lists have: pack_blob, pwn_api.cpp)
+	// (the blob says which form its per-cell lists have: pwn_i_pack_blob, pwn_tables.cpp)
 	// The global form: sixteen variants, MODE x COUNT x HAS_W, never ordered (pwn_i_launch_trace hands such a launch neither an
 	// order nor a cost array).
 	if(P->g_rec != NULL)

@@ -41,7 +41,7 @@ template<bool COUNT, bool HAS_W>
 __global__ void __launch_bounds__(PWN_BLOCK, PWN_MIN_WAVES)
 pwn_trace_refill_kernel(pwn_trace_params P)
 {
-	constexpr int LISTS = PWN_LF_INDEXED;          // (this scheduler reads the indexed lists: pack_blob packs those for it)
+	constexpr int LISTS = PWN_LF_INDEXED;          // (this scheduler reads the indexed lists: pwn_i_pack_blob packs those for it)
 	constexpr bool HITREC = false;       // (trace_walk.inc: nothing kept for hit records; the two names it would write, never touched)
 	[[maybe_unused]] uint32_t hit_cxz;
 	[[maybe_unused]] int hit_portals;

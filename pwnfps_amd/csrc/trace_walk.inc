@@ -87,7 +87,7 @@ if((int)cw < 0)
 		// LDS read.  The cell word names the non-empty cell, liststart (one LDS read per list) the index of its first record;
 		// aux_idx = the record's index.  The next record is asked for before this one is tested (behind the very last record lies
 		// one more that the host packed for this read).  Plain, cached loads: no copy of the tables is written while a launch
-		// reads it (pwn_api.cpp).  Every index here comes out of the tables the host packed -- the cell word, liststart, the end
+		// reads it (pwn_tables.cpp).  Every index here comes out of the tables the host packed -- the cell word, liststart, the end
 		// mark of a list -- and none out of a ray: no input bit pattern reaches an address (as argued at the ray modes' loads,
 		// trace_kernel.hip).
 		//@R w_sphrun

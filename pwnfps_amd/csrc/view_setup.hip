@@ -1,4 +1,4 @@
-// view_setup.hip -- the camera set-up of a batch of views on the device (pwn_trace_views_device): frame_setup of pwn_api.cpp,
+// view_setup.hip -- the camera set-up of a batch of views on the device (pwn_trace_views_device): frame_setup of pwn_internal.h,
 // one thread per view, from cameras that are already in device memory.
 //
 // This file is built with -fno-gpu-flush-denormals-to-zero (csrc/Makefile), alone of all the HIP files here: frame_setup runs

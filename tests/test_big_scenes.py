@@ -71,7 +71,7 @@ def test_swarm_all_first_hits_reach_objects_past_2048(oracle_lib):
 
 
 def test_plan_on_the_scenes_that_load_on_chip():
-    """t0, synth64, synth256: the form pack_blob picks for them (inline, inline, indexed by its comment) and that blob's bytes"""
+    """t0, synth64, synth256: the form pwn_i_pack_blob picks for them (inline, inline, indexed by its comment) and that blob's bytes"""
     import pwnfps_amd
     for key, form in (("t0", 1), ("synth64", 1), ("synth256", 0)):
         sph = load_spheres(key)

@@ -177,7 +177,7 @@ def test_ragged_large_frames_vs_oracle(oracle_lib):
 def test_extreme_aspect_frames_vs_oracle(oracle_lib):
     """The widest and the tallest frame pwn_init takes (32768), one unit high / one unit wide, and widths whose units per
     row are 1, a power of two, and neither: the kernel turns a unit number into (row, column) with a reciprocal the host
-    computes per launch (pwn_api.cpp unit_div_magic; frames one unit wide divide), the blur picks its tile shape by
+    computes per launch (launch_plan.h pwn_unit_div_magic; frames one unit wide divide), the blur picks its tile shape by
     the width, and the pixel index is 32-bit arithmetic.  Every pixel and depth against the oracle, blur included."""
     import pwnfps_amd
     from oracle import Oracle
@@ -478,7 +478,7 @@ def test_bounded_blur_reports_taps_outside_the_available_rows(oracle_lib, cases)
 def test_sphere_uploads_between_launches_in_flight(oracle_lib):
     """level_prepare_render every frame (main.c:95) with the strip forms: six frames with six
     different sphere sets are queued back to back on the caller's stream with no synchronisation
-    by the caller; an upload waits for the launch that still reads the tables (pwn_api.cpp).
+    by the caller; an upload waits for the launch that still reads the tables (pwn_launch.cpp, pwn_tables.cpp).
     (A fully asynchronous double-buffered upload was measured: the cross-stream event waits cost
     7 % of a 4K frame, the blocking form 0.3 %.)"""
     import torch

@@ -114,7 +114,7 @@ def _views(r, planes, sc, what, counters=False, cams=None, secs=None):
 # ---------------------------------------------------------------- the blocking call ----
 
 def _strips(h, k):
-    """PWN_OPT_CALL_STRIPS = k: strips of whole 32-row blur tiles (pwn_api.cpp strip_cuts); a frame of one strip runs in one piece"""
+    """PWN_OPT_CALL_STRIPS = k: strips of whole 32-row blur tiles (pwn_calls.cpp strip_cuts); a frame of one strip runs in one piece"""
     per = ((h + k - 1) // k + 31) // 32 * 32
     return (h + per - 1) // per
 

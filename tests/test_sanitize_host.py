@@ -1,4 +1,4 @@
-"""The host logic of the row tiling and of the group (pwn_tiled.cpp, pwn_group.cpp, pwn_api.cpp) on the CPU: compiled with g++
+"""The host logic of the row tiling and of the group (pwn_tiled.cpp, pwn_group.cpp and the host API's files they stand on) on the CPU: compiled with g++
 against a stand-in HIP runtime and stand-in kernels (tools/sanitize/), run under ThreadSanitizer and AddressSanitizer + UBSan.
 Every frame of 2..5 members -- blocking calls, frames in flight delivered and resident, moving cuts, a deep band that leaves the
 halo (repeat with whole strips), depth that carries over -- must equal the frame of one context; a member that is late past the
@@ -34,7 +34,8 @@ def test_host_logic_under_sanitizers(target, modes, tmp_path):
 def test_host_calls_transcript(tmp_path):
     """What every entry point of the host API sends to the device (tools/sanitize/calls_driver.cpp: runtime calls, launches with
     their parameters, hashes of the outputs, the refusals, the out-of-memory paths) is what tests/golden/host_calls.txt recorded
-    before the batch calls' common code was folded, byte for byte, and the run is clean under AddressSanitizer + UBSan."""
+    before the batch calls' common code was folded -- and, in its sections for the branches of the trace launcher, before the
+    launch geometry became a plan and pwn_api.cpp five files -- byte for byte, and the run is clean under AddressSanitizer + UBSan."""
     out_dir = str(tmp_path)
     _build("calls", out_dir)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1")

@@ -21,6 +21,7 @@ extern void (*pwn_fake_blur_hook)(const pwn_blur_params *B);
 extern void (*pwn_fake_launch_hook)(const char *name, const void *src, const void *dst, int nsizes, const size_t *sizes);
 extern void (*fakehip_call_hook)(const char *name, const void *a, const void *b, size_t bytes);
 extern long fakehip_alloc_fail_in;
+extern int fakehip_query_busy;
 }
 
 static uint64_t fnv(const void *p, size_t n, uint64_t h = 1469598103934665603ull)
@@ -57,6 +58,7 @@ static std::string nm(const void *p)
 		N(d_tickets, (size_t)PWN_TICKET_SETS * PWN_QUEUES * PWN_QUEUE_STRIDE * 4);
 		N(d_strip_miss, 64); N(h_strip_miss, 64);
 		N(stream, 1); N(stream2, 1); N(copy_stream, 1); N(copy_stream2, 1); N(up_stream, 1);
+		N(d_wave_log, c->wave_log_cap * 16);
 #undef N
 		for(int i = 0; i < PWN_NBLOB; i++)
 		{
@@ -141,6 +143,7 @@ static void on_trace(const pwn_trace_params *P, int grid, size_t lds_bytes)
 	f4("rayb", P->rayb); f4("rdx", P->rdx); f4("rdy", P->rdy); f4("from", P->from);
 	if(bits(P->sec_current)) emit(" sec %08x", bits(P->sec_current));
 	emit(" w %d h %d y %d %d tiles %d %d ux %u %d blob %u %u %u", P->w, P->h, P->y0, P->y1, P->tiles_x, P->tiles_total, P->ux_magic, P->ux_shift, P->blob_bytes, P->off_sph, P->off_recsph);
+	if(P->tile_pairs) emit(" pairs %d single %d tx %u %d", P->tile_pairs, P->pair_single_rows, P->tx_magic, P->tx_shift);
 	fp("sbuf", P->sbuf); fp("zbuf", P->zbuf); fp("blob", P->blob); fp("counters", P->counters); fp("wave_log", P->wave_log);
 	fu("has_w", (unsigned)P->has_w); fu("scheduler", (unsigned)P->scheduler); fu("refill_limit", (unsigned)P->refill_limit);
 	fp("tickets", P->tickets); fp("next", P->tickets_next); fp("cost_word", P->cost_word); fp("unit_cost", P->unit_cost); fp("perm", P->perm); fu("perm_cap", P->perm_cap);
@@ -232,6 +235,34 @@ static void out(const char *name, const void *p, size_t bytes) { printf(" | %s %
 static void opt(pwn_ctx *c, int o, int v) { REQ(pwn_set_option(c, o, v) == PWN_OK); }
 
 static unsigned rs = 2024; static float rnd() { rs = rs * 1664525u + 1013904223u; return (float)(rs >> 8) / 16777216.0f; }
+
+// ---- the trace launcher's branches (pwn_i_launch_trace): contexts of their own, whose pwn_init reads the settings given (name,
+// value, ...), with the level and these spheres; every launch is a pwn_trace_rows_device into planes of the caller's
+static std::vector<uint32_t> big_s(32768 * 16);
+static std::vector<float> big_z(32768 * 16);
+static pwn_ctx *ctx_env(int w, int h, const char *level, const std::vector<pwn_sphere> &sph, std::initializer_list<const char *> kv = {})
+{
+	for(const char *const *p = kv.begin(); p != kv.end(); p += 2) setenv(p[0], p[1], 1);
+	pwn_ctx *x = NULL;
+	REQ(pwn_init(&x, 0, w, h) == PWN_OK);
+	for(const char *const *p = kv.begin(); p != kv.end(); p += 2) unsetenv(p[0]);
+	REQ(pwn_level_load(x, level) == PWN_OK);
+	REQ(pwn_upload_spheres(x, sph.data(), (int)sph.size()) == PWN_OK);
+	return x;
+}
+static void section(const char *title) { close_line(); printf("---- launcher: %s\n", title); }
+static void rows(pwn_ctx *x, const float *cam, int y0, int y1, hipStream_t s = NULL)
+{
+	char b[96];
+	g_c = x;
+	snprintf(b, sizeof(b), "pwn_trace_rows_device %d x %d rows %d %d%s", x->w, x->h, y0, y1, s != NULL ? " on stream2" : "");
+	REQ(CALL(b, pwn_trace_rows_device(x, cam, 0.5f, y0, y1, big_s.data(), big_z.data(), s != NULL ? s : x->stream)) == PWN_OK);
+}
+static void blur_rows(pwn_ctx *x)
+{
+	g_c = x;
+	REQ(CALL("pwn_blur_rows_device", pwn_blur_rows_device(x, 0, x->h, big_s.data(), big_z.data(), big_z.data() + (size_t)x->w * x->h, x->stream)) == PWN_OK);
+}
 
 #define W 96
 #define H 64
@@ -607,6 +638,83 @@ int main(int argc, char **argv)
 	}
 	REQ(CALL("pwn_trace_rays n 5000 afterwards", pwn_trace_rays(m, 5000, rays, seeds, 0.0f, col, depth)) == PWN_OK);
 	REQ(CALL("pwn_trace_hits n 5000 afterwards", pwn_trace_hits(m, 5000, rays, hits)) == PWN_OK);
+
+
+	// ---- the branches of the trace launcher that 96 x 64 frames on four CUs do not reach
+	{
+		reg("big_s", big_s.data(), big_s.size() * 4); reg("big_z", big_z.data(), big_z.size() * 4);
+		const char *lv = argv[1];
+		pwn_ctx *x;
+		section("512 x 160, 1280 units = 16 * 4 * grid: tile pairs; a strip with y0 > 0");
+		x = ctx_env(512, 160, lv, sph);
+		rows(x, cams, 0, 160); rows(x, cams, 40, 120); rows(x, cams, 80, 80);
+		section("the same context: a number of PWN_OPT_TRACE_ROOM, one too large to take, the row tiling's reserve above it");
+		opt(x, PWN_OPT_TRACE_ROOM, 4); rows(x, cams, 0, 160);
+		opt(x, PWN_OPT_TRACE_ROOM, 10); rows(x, cams, 0, 160);
+		opt(x, PWN_OPT_TRACE_ROOM, 4); x->grid_reserve = 6; rows(x, cams, 0, 160);
+		x->grid_reserve = 0; opt(x, PWN_OPT_TRACE_ROOM, -1);
+		section("the same context: counters on");
+		opt(x, PWN_OPT_COUNTERS, 1); rows(x, cams, 0, 160); rows(x, cams + 48, 0, 160); opt(x, PWN_OPT_COUNTERS, 0);
+		section("the same context: the wave log follows the grid; with PWN_DBG_UNIT_COST the launch writes the units' costs");
+		opt(x, PWN_OPT_WAVE_LOG, 1); rows(x, cams, 0, 8); rows(x, cams, 0, 160);
+		REQ(CALL("pwn_trace_rays_device n 65 (a batch writes no wave log)", pwn_trace_rays_device(x, 65, rays, seeds, secs[2], 0, col, depth, x->stream)) == PWN_OK);
+		setenv("PWN_DBG_UNIT_COST", "/dev/null", 1); rows(x, cams, 0, 160); unsetenv("PWN_DBG_UNIT_COST");
+		opt(x, PWN_OPT_WAVE_LOG, 0);
+		section("the same context: a launch on the second stream waits for the launch two before it; tables whose upload is not through");
+		rows(x, cams, 0, 160); rows(x, cams, 0, 160, x->stream2);
+		printf(" | launch_waits %llu", x->launch_waits);
+		REQ(pwn_upload_spheres(x, sph.data(), 11) == PWN_OK);
+		fakehip_query_busy = 1; rows(x, cams, 0, 160); fakehip_query_busy = 0; rows(x, cams, 0, 160);
+		section("the same context: the refill scheduler (the tables are packed again)");
+		opt(x, PWN_OPT_SCHEDULER, PWN_SCHED_REFILL); rows(x, cams, 0, 160); rows(x, cams + 48, 0, 160);
+		REQ(CALL("pwn_trace_rays_device n 65 (a batch runs the units scheduler)", pwn_trace_rays_device(x, 65, rays, seeds, secs[2], 0, col, depth, x->stream)) == PWN_OK);
+		opt(x, PWN_OPT_SCHEDULER, PWN_SCHED_DEFAULT);
+		section("the same context: PWN_OPT_UNIT_ORDER keeps single units; the buffers grow, the sorted order is used for the same rows");
+		opt(x, PWN_OPT_UNIT_ORDER, 1);
+		rows(x, cams, 0, 40); rows(x, cams, 0, 160); blur_rows(x); rows(x, cams, 0, 160); rows(x, cams, 40, 120);
+		printf(" | order_used %llu order_sorts %llu", x->order_used, x->order_sorts);
+		// (the order of rows 0 .. 80: not for as many units of other rows)
+		rows(x, cams, 0, 80); blur_rows(x); rows(x, cams, 40, 120); rows(x, cams, 0, 78); rows(x, cams, 0, 80);
+		printf(" | order_used %llu order_sorts %llu", x->order_used, x->order_sorts);
+		opt(x, PWN_OPT_UNIT_ORDER, 0);
+		section("the same context: a frame slot's event guards a copy of the tables until the slot's next frame");
+		fakehip_call_hook = NULL;
+		REQ(pwn_frames_config(x, 1, 0, 0, 0) == PWN_OK);
+		fakehip_call_hook = on_call;
+		REQ(CALL("pwn_submit_frame slot 0", pwn_submit_frame(x, cams, 0.5f, 0)) == PWN_OK);
+		REQ(pwn_upload_spheres(x, sph.data(), 12) == PWN_OK);
+		REQ(CALL("pwn_wait_frame slot 0", pwn_wait_frame(x, 0, NULL)) == PWN_OK);
+		REQ(CALL("pwn_submit_frame slot 0, new tables", pwn_submit_frame(x, cams, 1.0f, 0)) == PWN_OK);
+		for(int i = 0; i < PWN_NBLOB; i++) printf(" | in_use[%d] %d", i, (int)x->tables_in_use[i]);
+		REQ(CALL("pwn_wait_frame slot 0", pwn_wait_frame(x, 0, NULL)) == PWN_OK);
+		g_c = NULL; pwn_destroy(x);
+		section("496 x 160, 1240 units: no pairs");
+		x = ctx_env(496, 160, lv, sph); rows(x, cams, 0, 160); g_c = NULL; pwn_destroy(x);
+		section("528 x 160, 33 units a row: pairs, the last tile of a row half empty");
+		x = ctx_env(528, 160, lv, sph); rows(x, cams, 0, 160); g_c = NULL; pwn_destroy(x);
+		section("32768 x 16: the first round's rows are the fifth of the rows");
+		x = ctx_env(32768, 16, lv, sph); rows(x, cams, 0, 16); g_c = NULL; pwn_destroy(x);
+		section("PWN_TILE_PAIRS=2 at 96 x 64 and at 16 x 64 (one unit a row)");
+		x = ctx_env(96, 64, lv, sph, { "PWN_TILE_PAIRS", "2" }); rows(x, cams, 0, 64); g_c = NULL; pwn_destroy(x);
+		x = ctx_env(16, 64, lv, sph, { "PWN_TILE_PAIRS", "2" }); rows(x, cams, 0, 64); g_c = NULL; pwn_destroy(x);
+		section("PWN_TILE_PAIRS=0 at 512 x 160");
+		x = ctx_env(512, 160, lv, sph, { "PWN_TILE_PAIRS", "0" }); rows(x, cams, 0, 160); g_c = NULL; pwn_destroy(x);
+		section("PWN_DBG_BLOCKS_PER_CU=2 at 512 x 160");
+		x = ctx_env(512, 160, lv, sph, { "PWN_DBG_BLOCKS_PER_CU", "2" }); rows(x, cams, 0, 160); g_c = NULL; pwn_destroy(x);
+		section("PWN_SCHEDULER=refill and PWN_DBG_FORCE_HASW at 96 x 64; more workgroups than units");
+		x = ctx_env(96, 64, lv, sph, { "PWN_SCHEDULER", "refill", "PWN_DBG_FORCE_HASW", "1" }); rows(x, cams, 0, 64); rows(x, cams, 0, 8); g_c = NULL; pwn_destroy(x);
+		section("PWN_SPHERE_LISTS=global at 512 x 160, also under the refill scheduler");
+		x = ctx_env(512, 160, lv, sph, { "PWN_SPHERE_LISTS", "global" }); rows(x, cams, 0, 160);
+		opt(x, PWN_OPT_SCHEDULER, PWN_SCHED_REFILL); opt(x, PWN_OPT_UNIT_ORDER, 1); rows(x, cams, 0, 160); g_c = NULL; pwn_destroy(x);
+		// 240 spheres, 40 of them in one cell: a blob of which four fit a CU's LDS where the occupancy query says five, and a list with a ball
+		std::vector<pwn_sphere> many;
+		for(int i = 0; i < 200; i++) many.push_back({ 0.1f + 0.3f * rnd(), rnd(), 2.0f + 20.0f * rnd(), rnd(), 2.0f + 20.0f * rnd(), rnd(), rnd(), rnd() });
+		for(int i = 0; i < 40; i++) many.push_back({ 0.05f, rnd(), 5.25f + 0.5f * rnd(), 0.5f, 5.25f + 0.5f * rnd(), rnd(), rnd(), rnd() });
+		section("240 spheres at 96 x 64: the LDS rule caps the workgroups per CU; the longest lists' balls, and PWN_SPHERE_BOUNDS=0");
+		x = ctx_env(96, 64, lv, many); rows(x, cams, 0, 64); g_c = NULL; pwn_destroy(x);
+		x = ctx_env(96, 64, lv, many, { "PWN_SPHERE_BOUNDS", "0" }); rows(x, cams, 0, 64); g_c = NULL; pwn_destroy(x);
+		g_c = c;
+	}
 
 	pwn_fake_trace_hook = NULL; pwn_fake_blur_hook = NULL; pwn_fake_launch_hook = NULL; fakehip_call_hook = NULL;
 	g_c = NULL;

@@ -13,8 +13,9 @@ static int g_devices = 8;
 
 // A driver may watch the calls that make up an entry point's choreography (calls_driver.cpp): the call's name, the two things it
 // is about (destination and source of a copy, event and stream of a record, the pointer of an allocation), for copies, memsets and
-// allocations the bytes.  And it may make the k-th allocation from now fail (hipMalloc and hipHostMalloc count together; 0: none does).
-extern "C" { void (*fakehip_call_hook)(const char *name, const void *a, const void *b, size_t bytes) = NULL; long fakehip_alloc_fail_in = 0; }
+// allocations the bytes.  And it may make the k-th allocation from now fail (hipMalloc and hipHostMalloc count together; 0: none does),
+// and every event look unfinished to hipEventQuery (fakehip_query_busy).
+extern "C" { void (*fakehip_call_hook)(const char *name, const void *a, const void *b, size_t bytes) = NULL; long fakehip_alloc_fail_in = 0; int fakehip_query_busy = 0; }
 #define HOOK(name, a, b, n) do { if(fakehip_call_hook != NULL) fakehip_call_hook(name, a, b, n); } while(0)
 static bool alloc_fails(void) { return fakehip_alloc_fail_in > 0 && --fakehip_alloc_fail_in == 0; }
 
@@ -77,6 +78,6 @@ hipError_t hipEventDestroy(hipEvent_t e) { delete e; return hipSuccess; }
 // (an event may be recorded by one member's thread and looked at by another's: the stand-in keeps that race-free with the lock)
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) { HOOK("hipEventRecord", e, s, 0); std::lock_guard<std::mutex> g(g_mu); e->t = now_ms(); e->recorded = true; return hipSuccess; }
 hipError_t hipEventSynchronize(hipEvent_t e) { HOOK("hipEventSynchronize", e, NULL, 0); return hipSuccess; }
-hipError_t hipEventQuery(hipEvent_t) { return hipSuccess; }
+hipError_t hipEventQuery(hipEvent_t) { return fakehip_query_busy ? hipErrorNotReady : hipSuccess; }
 hipError_t hipEventElapsedTime(float *ms, hipEvent_t a, hipEvent_t b) { std::lock_guard<std::mutex> g(g_mu); *ms = (float)(b->t - a->t); return hipSuccess; }
 }

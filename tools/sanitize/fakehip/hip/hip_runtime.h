@@ -1,5 +1,5 @@
-// A stand-in for the HIP runtime, for CPU sanitizer builds of libpwnhip's HOST logic only (tools/sanitize/README.txt): pwn_api.cpp,
-// pwn_tiled.cpp and pwn_group.cpp compiled with g++ -fsanitize=thread / address,undefined against this header, with CPU stand-ins for
+// A stand-in for the HIP runtime, for CPU sanitizer builds of libpwnhip's HOST logic only (tools/sanitize/README.txt): the host API's files
+// (pwn_internal.h has the map), pwn_tiled.cpp and pwn_group.cpp compiled with g++ -fsanitize=thread / address,undefined against this header, with CPU stand-ins for
 // the kernels (fake_kernels.cpp).  Test infrastructure: nothing under pwnfps_amd/ includes it, and nothing here computes a pixel of
 // the product.  Streams are synchronous: a launch or a copy has run when the call returns, an event has happened when it was
 // recorded -- what the sanitizers look at is what the host threads do to each other's memory, and the choreography's bookkeeping.

@@ -1,4 +1,4 @@
-// The host logic of the row tiling and of the group (pwn_tiled.cpp, pwn_group.cpp, pwn_api.cpp) under ThreadSanitizer and
+// The host logic of the row tiling and of the group (pwn_tiled.cpp, pwn_group.cpp and the host API's files they stand on) under ThreadSanitizer and
 // AddressSanitizer + UBSan, on the CPU: fake HIP runtime, stand-in kernels (fake_kernels.cpp).  Every frame of a group of N
 // members -- blocking calls, frames in flight delivered to the host, frames left on the devices -- must equal the frame of ONE
 // context, bit for bit, with moving cuts, with a band of deep pixels that leaves the halo (repeat with whole strips), with

@@ -1,4 +1,4 @@
-// The sphere tables' device-memory form (tables.h PWN_LF_GLOBAL) as pack_blob lays it out, read the way the kernels read it -- on the
+// The sphere tables' device-memory form (tables.h PWN_LF_GLOBAL) as pwn_i_pack_blob lays it out, read the way the kernels read it -- on the
 // CPU, under AddressSanitizer + UBSan, against the fake HIP runtime (README.txt).  A hook in the stand-in trace launch is handed
 // every launch's pwn_trace_params.  For tables in the global form it walks every cell as trace_walk.inc does -- cell word, ordinal,
 // liststart, records up to the end mark, the read-ahead behind the last one, which[], the sphere -- and holds each step to the
