@@ -1,7 +1,10 @@
 """PWN_OPT_UNIT_ORDER (an option, off by default): the trace kernel hands its units out by what they cost in the last launch of the same rows (every
 unit's cost written by the launch, sorted per queue behind the frame's last kernel).  Any order of the units gives the same
 frame: every frame of a sequence is the golden frame and has the golden counters, whichever order it was traced in; and the
-sorted order really is used (pwn_unit_order_state).  Replaces the static schedule of screen.h:63-64."""
+sorted order really is used (pwn_unit_order_state).  A launch that follows a sort must not find its frame in the planes already
+(a permutation that dropped units would leave it there): frames of a camera walk (tests/handout.py) stand between the golden
+frames, judged by the oracle, so every ordered launch renders what the planes do not hold.  Replaces the static schedule of
+screen.h:63-64."""
 import json
 import os
 
@@ -17,8 +20,16 @@ def case(cases, name):
     return [c for c in cases if c["name"] == name][0]
 
 
+def _oracle_of(c):
+    """the oracle on a case's level, which is one of the walk's, with the case's spheres"""
+    import handout as H
+    assert H.LEVELS[c["level"]] == c["spheres"]
+    return H.scene(c["level"])[0]
+
+
 @pytest.mark.parametrize("name", ["level_spawn_1280x720", "synth64_cam1_1920x1080", "synth256_cam0_1920x1080", "level_spawn_3840x2160"])
 def test_every_frame_of_a_sequence_is_the_golden_frame_in_any_order(name, cases, oracle_lib):
+    import handout as H
     import pwnfps_amd
     c = case(cases, name)
     w, h = c["w"], c["h"]
@@ -26,6 +37,10 @@ def test_every_frame_of_a_sequence_is_the_golden_frame_in_any_order(name, cases,
     r.level_load(level_path(c["level"]))
     r.set_objects(load_spheres(c["spheres"]))
     cam = np.array(c["cam"], np.float32).reshape(4, 4)
+    plane = H.Shown(_oracle_of(c), w, h)
+    # (a ray that runs out of steps keeps the depth it finds: where the golden frame has such rays it is the golden frame only on
+    # its own depth, and the walk's frames cannot stand between the golden ones -- they follow at the end)
+    between = c["exhausted"] == 0
     assert r.unit_order_state()["option"] == 0          # off by default: measured a loss on long launches (profiles/r4/unit_order_ab.txt)
     r.set_unit_order(True)
     for k in range(5):
@@ -38,19 +53,46 @@ def test_every_frame_of_a_sequence_is_the_golden_frame_in_any_order(name, cases,
             assert (st["rays"], st["steps"], st["portals"], st["sphere_tests"], st["exhausted"]) == (
                 c["rays"], c["steps"], c["portals"], c["sphere_tests"], c["exhausted"])
             r.set_counters(False)
+        # the oracle's side of the plane: the golden frame is what the planes hold now, no unit of the walk's frame keeps it ...
+        want = plane.show(cam, c["sec"], 1, again=k > 0 and not between)
+        assert oracle_lib.fnv64(want[0]) == c["post"] and oracle_lib.fnv64(want[1]) == c["z"], (name, k)
+        if between and k < 4:
+            # ... and the walk's frame k, in the order sorted from the golden frame's costs; the next golden frame follows in its order
+            wcam, wsec = H.walk(c["level"], k)
+            want = plane.show(wcam, wsec, 1)
+            sb, z = r.trace_screen_centred(wcam, wsec)
+            H.same((name, "walk", k), sb, z, *want)
     st = r.unit_order_state()
-    assert st["sorts"] == 5 and st["launches_in_sorted_order"] == 4 and st["units_ordered"] == ((w + 15) // 16) * ((h + 3) // 4), st
+    assert st["sorts"] == (9 if between else 5) and st["launches_in_sorted_order"] == (8 if between else 4), st
+    assert st["units_ordered"] == ((w + 15) // 16) * ((h + 3) // 4), st
     # ... and switched off: arithmetic order again, same frame
     r.set_unit_order(False)
     sb, z = r.trace_screen_centred(cam, c["sec"])
     assert oracle_lib.fnv64(sb) == c["post"]
-    assert r.unit_order_state()["launches_in_sorted_order"] == 4
+    assert r.unit_order_state()["launches_in_sorted_order"] == (8 if between else 4)
+    if not between:
+        # switched on again (which forgets the orders): the golden frame in arithmetic order, then two frames of the walk, each in
+        # the order sorted from the launch before it
+        plane.show(cam, c["sec"], 1, again=True)
+        r.set_unit_order(True)
+        sb, z = r.trace_screen_centred(cam, c["sec"])
+        assert oracle_lib.fnv64(sb) == c["post"] and oracle_lib.fnv64(z) == c["z"], name
+        H.same((name, "golden again"), sb, z, *plane.show(cam, c["sec"], 1, again=True))
+        for k in range(2):
+            wcam, wsec = H.walk(c["level"], k)
+            want = plane.show(wcam, wsec, 1)
+            sb, z = r.trace_screen_centred(wcam, wsec)
+            H.same((name, "walk", k), sb, z, *want)
+        st = r.unit_order_state()
+        assert st["sorts"] == 8 and st["launches_in_sorted_order"] == 6, st
     r.close()
 
 
 def test_order_follows_the_rows_it_was_made_for(cases, oracle_lib):
     """A strip launch (pwn_trace_rows_device) and frames of another camera in between: an order is only used for the rows it was
-    sorted from; frames in flight on two streams each keep their stream's own."""
+    sorted from; frames in flight on two streams each keep their stream's own.  Every second submit is a frame of the camera
+    walk, so each slot is shown the golden frame and a frame of the walk in turn and no launch finds its frame in its slot."""
+    import handout as H
     import pwnfps_amd
     c = case(cases, "level_spawn_1280x720")
     w, h = c["w"], c["h"]
@@ -59,15 +101,24 @@ def test_order_follows_the_rows_it_was_made_for(cases, oracle_lib):
     r.set_objects(load_spheres(c["spheres"]))
     cam = np.array(c["cam"], np.float32).reshape(4, 4)
     r.set_unit_order(True)
-    r.frames_config(3, sbuf=True)
+    r.frames_config(3, sbuf=True, zbuf=True)
+    planes = [H.Shown(_oracle_of(c), w, h) for _ in range(3)]
+    want = {}
+
+    def delivered(k):
+        # (k: the submit that is waited for)
+        f = r.wait_frame(k % 3)
+        if k % 2 == 0:
+            assert oracle_lib.fnv64(f["sbuf"]) == c["post"], k
+        H.same(("in flight", k), f["sbuf"], f["zbuf"], *want.pop(k))
     for k in range(9):
         if k >= 3:
-            f = r.wait_frame(k % 3)
-            assert oracle_lib.fnv64(f["sbuf"]) == c["post"], k
-        r.submit_frame(cam, c["sec"], k % 3)
+            delivered(k - 3)
+        fcam, fsec = (cam, c["sec"]) if k % 2 == 0 else H.walk(c["level"], k)
+        want[k] = planes[k % 3].show(fcam, fsec, 1)
+        r.submit_frame(fcam, fsec, k % 3)
     for k in range(9, 12):
-        f = r.wait_frame(k % 3)
-        assert oracle_lib.fnv64(f["sbuf"]) == c["post"], k
+        delivered(k - 3)
     st = r.unit_order_state()
     assert st["sorts"] == 9 and st["launches_in_sorted_order"] == 7, st          # each stream's first frame runs in arithmetic order
     r.frames_config(0)

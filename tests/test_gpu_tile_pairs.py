@@ -1,7 +1,9 @@
 """Tile pairs (trace_kernel.hip; PWN_TILE_PAIRS): a ticket of a frame's launch stands for a 32-pixel tile, and the wave that draws it
 traces the tile's left unit and then its right one, whose add chain starts from what the left one put aside.  Every frame here is
 rendered with pairs forced on (PWN_TILE_PAIRS=2) and off (0), twice through the same context -- the second launch runs on the
-ticket set the first one cleared -- with the blur off and on, and must equal the oracle bit for bit in colour and in depth.
+ticket set the first one cleared -- with the blur off and on, and must equal the oracle bit for bit in colour and in depth.  A
+second launch of the same camera finds its answer in the planes already, so two frames of a camera walk follow (tests/handout.py):
+no unit of those keeps what the planes held, and a launch that skipped one would show.
 The shapes are one way each for the pairing to go wrong (the table at SHAPES)."""
 import contextlib
 import os
@@ -74,6 +76,24 @@ def _want(w, h):
     return _cache[(w, h)]
 
 
+def _walked(w, h):
+    """the oracle's frames of the eight launches of _check_frames on one depth plane -- per blur setting the fixed camera twice, then
+    frames 1 and 2 of the walk -- as (colour, depth as uint32), computed once per shape"""
+    if ("walked", w, h) not in _cache:
+        import handout as H
+        O, _, _, cam = _scene()
+        plane = H.Shown(O, w, h)
+        out = []
+        for blur in (0, 1):
+            for k in range(4):
+                c, sec = (cam, SEC) if k < 2 else H.walk("pwnfps_level", k - 1)
+                sb, z = plane.show(c, sec, blur, again=k == 1)
+                sb.setflags(write=False)
+                out.append((sb, z.view(np.uint32).copy()))
+        _cache[("walked", w, h)] = out
+    return _cache[("walked", w, h)]
+
+
 def _renderer(w, h, pairs, **env):
     import pwnfps_amd
     _, level, sph, _ = _scene()
@@ -86,7 +106,9 @@ def _renderer(w, h, pairs, **env):
 
 
 def _check_frames(w, h, **env):
+    import handout as H
     pre, post, z = _want(w, h)
+    walked = _walked(w, h)
     cam = _scene()[3]
     for pairs in (2, 0):
         r = _renderer(w, h, pairs, **env)
@@ -100,6 +122,11 @@ def _check_frames(w, h, **env):
                 assert not bad.any(), (w, h, pairs, blur, k, int(bad.sum()), np.argwhere(bad)[:4].tolist())
                 badz = zb.view(np.uint32) != z
                 assert not badz.any(), (w, h, pairs, blur, k, int(badz.sum()), np.argwhere(badz)[:4].tolist())
+            # ... and two frames that the planes do not hold yet
+            for k in (2, 3):
+                wcam, wsec = H.walk("pwnfps_level", k - 1)
+                sb, zb = r.trace_screen_centred(wcam, wsec)
+                H.same((w, h, pairs, blur, k), sb, zb, *walked[4 * blur + k])
         r.close()
 
 
@@ -152,9 +179,10 @@ def test_strip_of_device_rows():
     for pairs in (2, 0):
         r = _renderer(w, h, pairs)
         for y0, y1 in ((5, 19), (37, 63)):
-            d_sb = torch.full((h, w), poison_s, dtype=torch.int32, device="cuda")
-            d_zb = torch.full((h, w), poison_z, dtype=torch.int32, device="cuda")
             for k in range(2):
+                # (fresh poison for every launch: the second one must not find the first one's rows in the planes)
+                d_sb = torch.full((h, w), poison_s, dtype=torch.int32, device="cuda")
+                d_zb = torch.full((h, w), poison_z, dtype=torch.int32, device="cuda")
                 torch.cuda.synchronize()
                 r.trace_rows_device(cam, SEC, y0, y1, d_sb.data_ptr(), d_zb.data_ptr())
                 torch.cuda.synchronize()

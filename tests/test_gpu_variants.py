@@ -239,7 +239,11 @@ def _order_size(sc):
 @pytest.mark.parametrize("sc", SCENES, ids=IDS)
 def test_sorted_unit_order(sc, oracle_lib):
     """PWN_OPT_UNIT_ORDER: the second frame of a camera is traced in the order the first one's costs sorted (the ORDER
-    variant); it is the oracle's frame on the depth the first frame left"""
+    variant); it is the oracle's frame on the depth the first frame left.  That second frame is the one the planes hold already,
+    so the frame follows twice as device rows into planes of poison (tests/handout.py), a moment later: the second of those
+    launches runs in the order sorted from the first, and a unit it did not trace keeps the poison"""
+    import torch
+    import handout as H
     w, h = _order_size(sc)
     O = HS.oracle(oracle_lib, sc)
     plane = HS.Plane(O, w, h)
@@ -251,6 +255,22 @@ def test_sorted_unit_order(sc, oracle_lib):
     _blocking(r, plane, sc, "order frame 2 at %dx%d" % (w, h))
     st = r.unit_order_state()
     assert st["launches_in_sorted_order"] >= 1 and st["sorts"] >= 1, (sc.name, st)
+    assert w % 4 == 0          # (the blur behind a strip's trace is what sorts its costs)
+    sec = np.float32(sc.sec + 0.5)
+    poison_z = np.full((h, w), H.POISON_Z, np.uint32).view(np.float32)
+    want_sb, want_z, _ = O.trace_rows(w, h, 0, h, sc.cam, sec=sec, sb=np.full((h, w), H.POISON_S, np.uint32), zb=poison_z)
+    assert not (want_sb == H.POISON_S).any(), sc.name
+    d_out = torch.zeros((h, w), dtype=torch.int32, device="cuda")
+    for k in range(2):
+        d_sb = torch.full((h, w), H.POISON_S, dtype=torch.int32, device="cuda")
+        d_zb = torch.full((h, w), H.POISON_Z, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        r.trace_rows_device(sc.cam, sec, 0, h, d_sb.data_ptr(), d_zb.data_ptr())
+        r.blur_rows_device(0, h, d_sb.data_ptr(), d_zb.data_ptr(), d_out.data_ptr())
+        torch.cuda.synchronize()
+        H.same((sc.name, "device rows", k), d_sb.cpu().numpy(), d_zb.cpu().numpy(), want_sb, want_z)
+        now = r.unit_order_state()
+        assert now["launches_in_sorted_order"] == st["launches_in_sorted_order"] + k and now["sorts"] == st["sorts"] + k + 1, (sc.name, k, st, now)
     r.close()
 
 
