@@ -555,6 +555,54 @@ int pwn_trace_hits_device(pwn_ctx *ctx, int n, const void *d_rays, int flags, vo
 int pwn_get_object_ids(pwn_ctx *ctx, int *ids, int cap);
 
 /*
+ * First-hit planes of a batch of views: what is under every pixel of n views of the context's w x h -- which object, which kind of
+ * surface, behind how many portals, in which cell, how far.  A label plane and a depth plane beside pwn_trace_views' colour for a
+ * network's observations, an object-id map for picking by look-up, the set of cells and spheres a camera sees.  Per pixel: the
+ * PRIMARY segment of trace_ray (trace.h:186) along the pixel's ray (screen.h:12-24) -- one set-up and one walk, as pwn_trace_hits,
+ * with the rays made on the device by the add chain of the frame kernel (screen.h:12-18) and 12 B a pixel stored.
+ *   cams                 n x 16 floats as for pwn_trace_views.  No secs: the primary segment reads no time and draws no random number.
+ *   planes               label, cell, dist: n x h x w 32-bit words each, view-major.  label is required; cell and dist may be NULL and
+ *                        are then not written.  EVERY pixel of every plane given is written: nothing is in / out, nothing persists
+ *                        between calls, and the call family owns no depth plane.
+ *   exactness            pixel (x, y) of view i holds the pwn_hit that pwn_trace_hits returns for pwn_pixel_rays(w, h, cams[i], (x, y)),
+ *                        every field that has a place bit for bit:
+ *                          label   kind | (face + 1) << 2 | (object + 1) << 5 | portals << 19   (PWN_LABEL_* take it apart)
+ *                          cell    cell_x in the low 16 bits, cell_z in the high 16, both int16 (the record's last word)
+ *                          dist    pwn_hit.dist
+ *                        PWN_HIT_NONE gives 0 in all three.  And so, through pwn_trace_hits' contract, to the reference's variables when
+ *                        trace_ray's primary walk returns; dist is what pwn_trace_views writes to that pixel of zbuf where the ray ends
+ *                        on something.  x y z and dx dy dz have no plane: pwn_trace_hits on pwn_pixel_rays serves the pixels that need them.
+ *   w lanes              as pwn_trace_views (the host form looks at the cameras) and pwn_trace_views_device (PWN_VIEWS_HAS_W).
+ *   ordering             the host form behind the frames in flight, as pwn_trace_views, and ends with its stream drained.
+ *   counters             with PWN_OPT_COUNTERS on: rays = n x w x h, and steps, portals, sphere_tests and exhausted of the primary
+ *                        segments, as pwn_trace_hits counts them.  The host form sets trace_ms (upload and trace) and total_ms, blur_ms 0.
+ *   not followed         as pwn_trace_views: always the units scheduler, never row strips, no unit order, no wave log; and no blur:
+ *                        PWN_OPT_BLUR_PASSES is ignored (w % 4 != 0 is no error).
+ *   left alone           the blocking call's planes, the view slots of pwn_trace_views, the planes of pwn_trace_viewports, the
+ *                        unit-order state, the trace-room measurement, the call-strips calibration window.
+ *   cost                 the host form keeps 12 B per pixel of pinned host memory and as much device memory between calls, grown to
+ *                        the largest call so far; pwn_destroy frees them.  They are pwn_trace_hits' buffers: the larger need counts.
+ *   errors               PWN_EINVAL for NULL ctx / cams / label, n < 1, n > PWN_VIEWS_MAX, n x w x h > 2^28; PWN_ENOLEVEL,
+ *                        PWN_ENOTSUP and PWN_EBUSY as pwn_trace_views; PWN_ENOMEM when the host form's buffers cannot grow.
+ */
+/* one word per pixel; 0 = the primary segment ran out of steps (PWN_HIT_NONE) */
+#define PWN_LABEL_KIND(l)     ((l) & 3u)                          /* PWN_HIT_* */
+#define PWN_LABEL_FACE(l)     ((int)(((l) >> 2) & 7u) - 1)        /* pwn_hit.face, -1 for a sphere / nothing */
+#define PWN_LABEL_OBJECT(l)   ((int)(((l) >> 5) & 0x3fffu) - 1)   /* pwn_hit.object, -1 = none */
+#define PWN_LABEL_PORTALS(l)  ((l) >> 19)                         /* pwn_hit.portals */
+/* Blocking, host memory. */
+int pwn_trace_view_hits(pwn_ctx *ctx, int n, const float *cams, uint32_t *label, uint32_t *cell, float *dist);
+/* The device form: cameras and planes in device memory, stream-ordered on `stream` (a hipStream_t, NULL = default stream) like
+   pwn_trace_views_device -- no synchronisation, no host copy.  d_cams n x 16 floats; d_label required, d_cell and d_dist or NULL;
+   all pointers 16-byte aligned.  flags: 0 or PWN_VIEWS_HAS_W, with pwn_trace_views_device's meaning.  One camera set-up launch and
+   one trace launch, both on `stream`; the trace launch falls under the rule for trace launches at the top of this file and uses
+   the view records of the counter set it counts in, as pwn_trace_views_device.  Sets no timings.  Beyond the host form's errors,
+   PWN_EINVAL for flags other than PWN_VIEWS_HAS_W, a pointer that is not 16-byte aligned, any two of the given plane ranges
+   overlapping.  A refused call launches nothing. */
+int pwn_trace_view_hits_device(pwn_ctx *ctx, int n, const void *d_cams, int flags,
+	void *d_label, void *d_cell, void *d_dist, void *stream);
+
+/*
  * Frames in flight.  The reference presents every frame on the host
  * (trace_screen_centred fills sbuf, screen_upscale fills screen->pixels, SDL_Flip:
  * main.c:107-109).  Over PCIe that hand-over takes longer than the kernels of a

@@ -133,6 +133,8 @@ ABI = [
     ("pwn_trace_hits", _i, [_vp, _i, _vp, _vp]),
     ("pwn_trace_hits_device", _i, [_vp, _i, _vp, _i, _vp, _vp]),
     ("pwn_get_object_ids", _i, [_vp, _vp, _i]),
+    ("pwn_trace_view_hits", _i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    ("pwn_trace_view_hits_device", _i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     ("pwn_frames_config", _i, [_vp, _i, _i, _i, _i]),
     ("pwn_submit_frame", _i, [_vp, _vp, _f, _i]),
     ("pwn_wait_frame", _i, [_vp, _i, C.POINTER(Frame)]),

@@ -1,5 +1,5 @@
 // pwn_calls.cpp -- the calls that return with their result on the host, and their device forms: the blocking call
-// (pwn_trace_screen_centred) in one piece and in row strips, host registration, the batches of views, viewports, rays and hits.
+// (pwn_trace_screen_centred) in one piece and in row strips, host registration, the batches of views, viewports, rays and hits, the first-hit planes of views.
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
@@ -21,11 +21,12 @@ static int wait_frames_in_flight(pwn_ctx *c, hipStream_t s)
 }
 
 // What refuses a batch call once its own arguments are in order (include/pwnhip.h), in the order that decides which code a caller
-// with two faults gets.  views > 0: a call that traces that many views of w x h and blurs them, with the two rules of those.
-static int batch_refuse(const pwn_ctx *c, int views = 0)
+// with two faults gets.  views > 0: a call that traces that many views of w x h and blurs them, with the two rules of those
+// (blurs = false: the first-hit planes of views, which are never blurred, with the first alone).
+static int batch_refuse(const pwn_ctx *c, int views = 0, bool blurs = true)
 {
 	if(views > 0 && (size_t)views * (size_t)c->w * (size_t)c->h > ((size_t)1 << 28)) return PWN_EINVAL;
-	if(views > 0 && c->blur_passes > 0 && (c->w & 3) != 0) return PWN_EINVAL;
+	if(views > 0 && blurs && c->blur_passes > 0 && (c->w & 3) != 0) return PWN_EINVAL;
 	if(c->tiled != NULL) return PWN_EBUSY;
 	if(!c->have_level) return PWN_ENOLEVEL;
 	return PWN_OK;
@@ -407,13 +408,18 @@ static int planes3_alloc(size_t bytes, uint32_t **pre, uint32_t **out, float **z
 // Room for n views: the records (PWN_VIEWS_MAX of them, with the first batch) and n planes of each kind.  A larger n moves the
 // depth planes of the slots so far into the new allocation and starts the new slots' planes at 0; the stream is idle behind
 // that before the old planes go (no kernel of an earlier batch reads them: every batch ends with its stream drained).
-static int views_reserve(pwn_ctx *c, int n, hipStream_t s)
+static int view_recs_reserve(pwn_ctx *c)
 {
 	if(c->h_vrec == NULL)
 	{
 		HIPCHK(c, hipHostMalloc((void **)&c->h_vrec, PWN_VIEWS_MAX * sizeof(pwn_view_rec), hipHostMallocDefault));
 		HIPCHK(c, hipMalloc((void **)&c->d_vrec, PWN_VIEWS_MAX * sizeof(pwn_view_rec)));
 	}
+	return PWN_OK;
+}
+static int views_reserve(pwn_ctx *c, int n, hipStream_t s)
+{
+	{ const int rc = view_recs_reserve(c); if(rc != PWN_OK) return rc; }
 	if(n <= c->views_cap) return PWN_OK;
 	const size_t plane = (size_t)c->w * (size_t)c->h, bytes = (size_t)n * plane * 4;
 	uint32_t *pre, *out; float *z;
@@ -730,5 +736,87 @@ extern "C" int pwn_trace_hits_device(pwn_ctx *c, int n, const void *d_rays, int 
 	if(rc != PWN_OK || n == 0) return rc;
 	(void)hipSetDevice(c->device);
 	pwn_trace_launch T = { .rays = { (const float *)d_rays, NULL, (uint32_t)n, (flags & PWN_RAYS_HAS_W) != 0, d_hits }, .stream = (hipStream_t)stream };
+	return pwn_i_launch_trace(c, &T);
+}
+
+// ---- first-hit planes of a batch of views (pwn_trace_view_hits) ------------------
+
+// The staging of a call of N = n x w x h pixels: the label plane at 0, the cell plane at 4 N, the distance plane at 8 N, on the
+// device and in pinned memory alike; the planes the caller wants come down, each in one copy, and go to the caller from there.
+// It is pwn_trace_hits' staging (80 B a ray there: 12 N bytes are ceil(12 N / 80) rays of it), which is free between calls.
+extern "C" int pwn_trace_view_hits(pwn_ctx *c, int n, const float *cams, uint32_t *label, uint32_t *cell, float *dist)
+{
+	GRP_REFUSE(c, "pwn_trace_view_hits");
+	if(c == NULL || cams == NULL || label == NULL || n < 1 || n > PWN_VIEWS_MAX) return PWN_EINVAL;
+	int rc = batch_refuse(c, n, false);
+	if(rc != PWN_OK) return rc;
+	const size_t plane = (size_t)c->w * (size_t)c->h, N = (size_t)n * plane;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = c->stream;
+	rc = wait_frames_in_flight(c, s);
+	if(rc != PWN_OK) return rc;
+	rc = view_recs_reserve(c);
+	if(rc != PWN_OK) return rc;
+	rc = staging_reserve(c, (12 * N + 79) / 80, 32 + sizeof(pwn_hit), "pwn_trace_view_hits", &c->h_hits, &c->d_hits, &c->hits_cap);
+	if(rc != PWN_OK) return rc;
+	// every view's record from the blocking call's own set-up, as pwn_trace_views; the primary segment reads no time
+	bool has_w = false;
+	for(int i = 0; i < n; i++)
+	{
+		const float *cam = cams + 16 * (size_t)i;
+		pwn_view_rec &r = c->h_vrec[i];
+		frame_setup(c->w, c->h, cam, &r);
+		r.sec_current = 0.0f;
+		r.pad_[0] = r.pad_[1] = r.pad_[2] = 0.0f;
+		if(camera_has_w(cam)) has_w = true;
+	}
+	HIPCHK(c, hipEventRecord(c->ev[0], s));
+	// (the staging is free again: the call before this one ended with the stream drained)
+	HIPCHK(c, pwn_launch_upload(c->h_vrec, c->d_vrec, (size_t)n * sizeof(pwn_view_rec), s));
+	unsigned char *h = c->h_hits, *d = c->d_hits;
+	pwn_trace_launch T = { .y0 = 0, .y1 = c->h, .views = { c->d_vrec, n, has_w, plane, (uint32_t *)d },
+		.d_sbuf = cell != NULL ? (uint32_t *)(d + 4 * N) : NULL, .d_zbuf = dist != NULL ? (float *)(d + 8 * N) : NULL, .stream = s };
+	rc = pwn_i_launch_trace(c, &T);
+	if(rc != PWN_OK) return rc;
+	HIPCHK(c, hipEventRecord(c->ev[1], s));
+	HIPCHK(c, hipMemcpyAsync(h, d, 4 * N, hipMemcpyDeviceToHost, s));
+	if(cell != NULL) HIPCHK(c, hipMemcpyAsync(h + 4 * N, d + 4 * N, 4 * N, hipMemcpyDeviceToHost, s));
+	if(dist != NULL) HIPCHK(c, hipMemcpyAsync(h + 8 * N, d + 8 * N, 4 * N, hipMemcpyDeviceToHost, s));
+	HIPCHK(c, hipEventRecord(c->ev[3], s));
+	rc = blocking_wait(c, false);
+	if(rc != PWN_OK) return rc;
+	memcpy(label, h, 4 * N);
+	if(cell != NULL) memcpy(cell, h + 4 * N, 4 * N);
+	if(dist != NULL) memcpy(dist, h + 8 * N, 4 * N);
+	return PWN_OK;
+}
+
+// The device form: cameras and planes of the caller's in device memory, the set-up kernel (no times) and the trace launch on the
+// caller's stream, nothing waited for -- pwn_trace_views_device without its blur
+extern "C" int pwn_trace_view_hits_device(pwn_ctx *c, int n, const void *d_cams, int flags, void *d_label, void *d_cell, void *d_dist, void *stream)
+{
+	GRP_REFUSE(c, "pwn_trace_view_hits_device");
+	if(c == NULL || d_cams == NULL || d_label == NULL || n < 1 || n > PWN_VIEWS_MAX || (flags & ~PWN_VIEWS_HAS_W) != 0) return PWN_EINVAL;
+	if((((uintptr_t)d_cams | (uintptr_t)d_label | (uintptr_t)d_cell | (uintptr_t)d_dist) & 15u) != 0) return PWN_EINVAL;
+	const size_t plane = (size_t)c->w * (size_t)c->h;
+	{
+		const uintptr_t bytes = (uintptr_t)n * plane * 4, p[3] = { (uintptr_t)d_label, (uintptr_t)d_cell, (uintptr_t)d_dist };
+		for(int i = 0; i < 3; i++) for(int k = i + 1; k < 3; k++)
+			if(p[i] != 0 && p[k] != 0 && p[i] < p[k] + bytes && p[k] < p[i] + bytes) return PWN_EINVAL;
+	}
+	int rc = batch_refuse(c, n, false);
+	if(rc != PWN_OK) return rc;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	// (tables that cannot be packed refuse the call before anything is launched)
+	if(c->blob_dirty) { rc = pwn_i_pack_blob(c); if(rc != PWN_OK) return rc; }
+	if(c->d_vrec_dev == NULL) HIPCHK(c, hipMalloc((void **)&c->d_vrec_dev, (size_t)PWN_TICKET_SETS * PWN_VIEWS_MAX * sizeof(pwn_view_rec)));
+	// (the records of the ticket set the trace launch counts in, and the wait of a call that leaves the rotation: pwn_trace_views_device)
+	const unsigned rot = (unsigned)c->launch_rot;
+	if(c->launch_event[rot - 1] != NULL && c->launch_stream[rot - 1] != s) HIPCHK(c, hipStreamWaitEvent(s, c->launch_event[rot - 1], 0));
+	pwn_view_rec *recs = c->d_vrec_dev + (size_t)(c->ticket_set % (2u * rot)) * PWN_VIEWS_MAX;
+	HIPCHK(c, pwn_launch_view_setup((const float *)d_cams, NULL, recs, n, c->w, c->h, s));
+	pwn_trace_launch T = { .y0 = 0, .y1 = c->h, .views = { recs, n, (flags & PWN_VIEWS_HAS_W) != 0, plane, (uint32_t *)d_label },
+		.d_sbuf = (uint32_t *)d_cell, .d_zbuf = (float *)d_dist, .stream = s };
 	return pwn_i_launch_trace(c, &T);
 }

@@ -19,12 +19,16 @@
 
 // A batch of views (pwn_trace_views) as what a trace launch traces: n views, their records (tables.h pwn_view_rec) already on
 // the device, into planes `plane` pixels apart; has_w: some view's camera has w components.  n = 0: none.
+// d_label (pwn_trace_view_hits / pwn_trace_view_hits_device): not NULL = the launch writes the views' first-hit planes instead, from the
+// primary segments alone: the label plane there, the cell plane to the launch's d_sbuf and the distance plane to its d_zbuf (each
+// unless NULL); the records' times are then not read.
 struct pwn_views_launch
 {
 	const pwn_view_rec *d_recs;
 	int n;
 	bool has_w;
 	unsigned long long plane;
+	uint32_t *d_label;
 };
 
 // Views of their own sizes in rectangles of one frame (pwn_trace_viewports) as what a launch traces or blurs: n records (tables.h
@@ -97,7 +101,7 @@ extern "C" hipError_t pwn_launch_blur(const pwn_blur_params *P, hipStream_t stre
 extern "C" hipError_t pwn_launch_order(const uint16_t *cost, uint32_t units, uint32_t cap, uint32_t *perm, hipStream_t stream);
 extern "C" hipError_t pwn_launch_upscale(const uint32_t *src, uint32_t *dst, int w, int h, int scale, int pitch, hipStream_t stream);
 extern "C" hipError_t pwn_launch_upload(const void *h_pinned_src, void *d_dst, size_t bytes, hipStream_t stream);
-// the camera set-up of n views from device memory (view_setup.hip): d_cams n x 16 floats and d_out 16-byte aligned
+// the camera set-up of n views from device memory (view_setup.hip): d_cams n x 16 floats and d_out 16-byte aligned; d_secs NULL: every time 0
 extern "C" hipError_t pwn_launch_view_setup(const float *d_cams, const float *d_secs, pwn_view_rec *d_out, int n, int w, int h, hipStream_t stream);
 extern "C" hipError_t pwn_launch_words(const uint32_t *d_all, const uint32_t *d_own, uint32_t *h_pinned_dst, int world, hipStream_t stream);
 extern "C" hipError_t pwn_launch_probe(int op, const uint32_t *in, uint32_t *out, int n, const uint16_t *tabs, hipStream_t stream);
@@ -297,7 +301,8 @@ struct pwn_ctx
 	pwn_viewport_rec *h_prec, *d_prec;
 	// pwn_trace_rays: room for rays_cap rays in pinned staging and on the device, 44 B each (record, seed, depth, colour; pwn_calls.cpp staging_reserve)
 	unsigned char *h_rays, *d_rays; size_t rays_cap;
-	// pwn_trace_hits: the same for hits_cap rays, 32 B in (record) and 48 B out (pwn_hit) each
+	// pwn_trace_hits: the same for hits_cap rays, 32 B in (record) and 48 B out (pwn_hit) each; pwn_trace_view_hits stages its planes
+	// here too, 12 B a pixel (a call's label plane, behind it its cell plane, then its distance plane): no call uses both at once
 	unsigned char *h_hits, *d_hits; size_t hits_cap;
 	uint32_t *d_tickets; unsigned ticket_set;  // PWN_TICKET_SETS sets of work-queue counters of the trace kernel, used in turn
 	uint32_t *d_scratch; size_t scratch_cap;   // upscale / probe staging

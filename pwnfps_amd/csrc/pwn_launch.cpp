@@ -254,7 +254,11 @@ int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L)
 	if(!batch) frame_setup(c->w, c->h, L->cam, &P);
 	P.sec_current = L->sec;
 	P.w = c->w; P.h = c->h; P.y0 = y0; P.y1 = y1;
-	if(views != NULL) { P.views = views->d_recs; P.nviews = views->n; P.plane = views->plane; }
+	if(views != NULL)
+	{
+		P.views = views->d_recs; P.nviews = views->n; P.plane = views->plane;
+		P.hits = views->d_label;        // (first-hit planes, pwn_trace_view_hits: the label plane; d_sbuf is then the cell plane, d_zbuf the distance plane)
+	}
 	if(vps != NULL) { P.vps = vps->d_recs; P.nvp = vps->n; }
 	if(rays != NULL)
 	{

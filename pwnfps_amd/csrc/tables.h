@@ -201,6 +201,11 @@ struct pwn_trace_params
 	int ray_w;
 	// First-hit records of a batch of rays (pwn_trace_hits): NULL, or nrays records of PWN_HIT_REC_BYTES (pwn_hit of pwnhip.h; 16-byte
 	// aligned) that ray i's primary segment is written to.  Then sbuf, zbuf, ray_seeds and sec_current are not read.
+	// With `views` (pwn_trace_view_hits): the first-hit planes of a batch of views.  The launch is one of `views` whose units trace the
+	// primary segment alone and write, per pixel, one packed word of what it ended on (pwnhip.h PWN_LABEL_*) to `hits`, the label
+	// plane (uint32), and -- each unless NULL -- the hit's cell word to sbuf and its distance to zbuf: nviews planes of `plane` words
+	// each, view v's at + v * plane.  The records' sec_current is not read.  (No field of its own: the struct, and with it every
+	// other kernel's argument block, stays as it was.)
 	void *hits;
 	// The lists' global form (above): NULL, or the three sections of the device-memory part of the tables.  Then blob_bytes is the LDS
 	// part alone, and off_sph / off_recsph are not read.
@@ -264,7 +269,7 @@ struct pwn_blur_params
 };
 
 // what a launch of the trace kernel traces (its MODE parameter, trace_kernel.hip)
-enum { PWN_KM_FRAME = 0, PWN_KM_VIEWS = 1, PWN_KM_RAYS = 2, PWN_KM_HITS = 3, PWN_KM_VIEWPORTS = 4 };
+enum { PWN_KM_FRAME = 0, PWN_KM_VIEWS = 1, PWN_KM_RAYS = 2, PWN_KM_HITS = 3, PWN_KM_VIEWPORTS = 4, PWN_KM_VIEW_HITS = 5 };
 
 // One view of a batch: the camera set-up of screen.h:43-57 for that view's camera (pwn_internal.h frame_setup) and its
 // sec_current.  80 bytes; the kernel reads a view's record with scalar loads.

@@ -27,6 +27,7 @@
 //   - no device function calls (dev_math.h) and no SLP packing (Makefile).
 #include <hip/hip_runtime.h>
 #include "trace_common.h"
+#include "pwnhip.h"      // PWN_OBJ_MAX (hit_store_planes)
 
 // The walk loops of this file count a segment's cell steps in ev itself (trace_pixel: "How the walk loop ends"): below zero while
 // the ray walks, and what a ray that made WALK_STEPS steps (trace.h:250) without an event leaves the loop with is this file's
@@ -186,14 +187,17 @@ __device__ __forceinline__ void trace_pixel(const Lds &L, float sec_current, uin
 	out_x = vx; out_y = vy; out_z = vz; out_w = vw + w_acc;
 }
 
-// One ray's PRIMARY segment for pwn_trace_hits: the set-up and the walk of trace_pixel's first pass through its loop -- the same
-// two texts -- and then, where trace_pixel shades, the walk's state written out as a 48-byte record (pwn_hit, pwnhip.h):
+// One ray's PRIMARY segment for pwn_trace_hits and pwn_trace_view_hits: the set-up and the walk of trace_pixel's first pass through
+// its loop -- the same two texts -- and then, where trace_pixel shades, the walk's state as the twelve words of a record (pwn_hit, pwnhip.h):
 //   word 0..3    kind (EV_WALL = PWN_HIT_WALL, EV_SPHERE = PWN_HIT_SPHERE, out of steps = PWN_HIT_NONE), face, object, portals
 //   word 4..7    dist (what the frame writes to zbuf), x, y, z (pos, or the sphere candidate's aux_pos)
 //   word 8..11   the walked ray x, y, z;  cell x | cell z << 16 (hit_cxz as the walk packs it: two int16)
 // No shading, bounce, jitter or composite, no composite stack, no random number, no sec_current.
+// trace_hit is the one body; what becomes of the words is its callers': hit_store_record (a batch of rays) writes all twelve,
+// hit_store_planes (a batch of views) packs the first four into one and keeps two more.
+struct HitWords { uint4 r0, r1, r2; };
 template<bool COUNT, bool HAS_W, int LISTS>
-__device__ __forceinline__ void trace_hit(const Lds &L, Vec<HAS_W> from, Vec<HAS_W> iray, uint4 *out, Counters &cnt)
+__device__ __forceinline__ HitWords trace_hit(const Lds &L, Vec<HAS_W> from, Vec<HAS_W> iray, Counters &cnt)
 {
 	typedef Vec<HAS_W> V;
 	constexpr bool HITREC = true;
@@ -260,8 +264,29 @@ __device__ __forceinline__ void trace_hit(const Lds &L, Vec<HAS_W> from, Vec<HAS
 		r1 = make_uint4(__float_as_uint(dist), __float_as_uint(at.x), __float_as_uint(at.y), __float_as_uint(at.z));
 		r2 = make_uint4(__float_as_uint(ray.x), __float_as_uint(ray.y), __float_as_uint(ray.z), hit_cxz);
 	}
-	// three 16-byte stores (the record is 16-byte aligned: pwn_calls.cpp checks the array)
-	out[0] = r0; out[1] = r1; out[2] = r2;
+	return HitWords{ r0, r1, r2 };
+}
+
+// pwn_trace_hits: the record as it is -- three 16-byte stores (the record is 16-byte aligned: pwn_calls.cpp checks the array)
+__device__ __forceinline__ void hit_store_record(const HitWords &h, uint4 *out)
+{
+	out[0] = h.r0; out[1] = h.r1; out[2] = h.r2;
+}
+
+// pwn_trace_view_hits: a pixel's word of each plane that was given (the tests are the same for the whole wave: launch parameters).
+//   label   kind | (face + 1) << 2 | (object + 1) << 5 | portals << 19   (pwnhip.h PWN_LABEL_*)
+//   cell    the record's word 11;   dist   its word 4
+// A segment that ran out of steps has face = object = -1 and every other word 0: all three planes get 0.
+// The fields do not run into each other: kind is 0..2, a face 0..5 (ldir of a wall; -1 otherwise), an object an index into the live
+// table of at most PWN_OBJ_MAX spheres, and a segment crosses at most one portal per step.
+static_assert(EV_SPHERE < 4 && FYN + 1 < 8, "kind in 2 bits, face + 1 in 3");
+static_assert(PWN_OBJ_MAX < (1 << 14) - 1, "object + 1 in 14 bits");
+static_assert(WALK_STEPS < (1 << 13), "portals in 13 bits");
+__device__ __forceinline__ void hit_store_planes(const HitWords &h, uint32_t *label, uint32_t *cell, float *dist)
+{
+	*label = h.r0.x | ((h.r0.y + 1u) << 2) | ((h.r0.z + 1u) << 5) | (h.r0.w << 19);
+	if(cell != NULL) *cell = h.r2.w;
+	if(dist != NULL) *dist = __uint_as_float(h.r1.x);
 }
 
 // Rounds 1..15 of the add chain of screen.h:12-18 (see the unit loop): in round k the lanes k..15 of every 16-lane row add
@@ -295,14 +320,16 @@ template<bool HAS_W> __device__ __forceinline__ void chain_rounds(Vec<HAS_W> &v,
 // same batch of rays (pwn_trace_hits), of which every lane traces the primary segment only and writes a first-hit record
 // (trace_hit) instead of a colour and a depth.  PWN_KM_VIEWPORTS: P.nvp views of their own sizes, each a frame of its own, into
 // rectangles of ONE pitch-P.w frame (pwn_trace_viewports): every unit finds its view and reads that view's set-up, size and
-// place from P.vps.  The last four are instantiated with ORDER = false only.
+// place from P.vps.  PWN_KM_VIEW_HITS: a batch of views handed out as PWN_KM_VIEWS' (pwn_trace_view_hits), of which every lane traces the
+// primary segment only (trace_hit) and writes packed first-hit words to the planes P.hits / sbuf / zbuf (label, cell, distance) instead
+// of a colour and a depth.  The last five are instantiated with ORDER = false only.
 // LISTS (tables.h PWN_LF_*): the form of the per-cell sphere lists -- indexed or inline records in LDS, or, for sphere sets whose
 // lists outgrow LDS, records in device memory (PWN_LF_GLOBAL: instantiated with ORDER = false only).
 template<bool COUNT, bool HAS_W, bool ORDER, int LISTS, int MODE>
 __global__ void __launch_bounds__(PWN_BLOCK, PWN_MIN_WAVES)
 pwn_trace_kernel(pwn_trace_params P)
 {
-	constexpr bool VIEWS = MODE == PWN_KM_VIEWS, HITS = MODE == PWN_KM_HITS, RAYS = MODE == PWN_KM_RAYS || HITS, VPS = MODE == PWN_KM_VIEWPORTS;
+	constexpr bool VHITS = MODE == PWN_KM_VIEW_HITS, VIEWS = MODE == PWN_KM_VIEWS || VHITS, HITS = MODE == PWN_KM_HITS, RAYS = MODE == PWN_KM_RAYS || HITS, VPS = MODE == PWN_KM_VIEWPORTS;
 	//@R k_prologue
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
 
@@ -502,7 +529,8 @@ pwn_trace_kernel(pwn_trace_params P)
 					// from the cell's liststart entry to the record with the end mark: inside the nrec records the host packed).
 					// Global: hits + 48 i for i < nrays <= 2^28 in 64-bit arithmetic lies in the
 					// caller's array of n records; a lane with i >= nrays stores nothing.  No seed, colour or depth is touched.
-					trace_hit<COUNT, HAS_W, LISTS>(L, org, dir, (uint4 *)((unsigned char *)P.hits + (size_t)i * PWN_HIT_REC_BYTES), cnt);
+					uint4 *const out = (uint4 *)((unsigned char *)P.hits + (size_t)i * PWN_HIT_REC_BYTES);
+					hit_store_record(trace_hit<COUNT, HAS_W, LISTS>(L, org, dir, cnt), out);
 				}
 				else
 				{
@@ -531,6 +559,7 @@ pwn_trace_kernel(pwn_trace_params P)
 		uint32_t fu = unit;
 		uint32_t *sbuf = P.sbuf;
 		float *zbuf = P.zbuf;
+		[[maybe_unused]] size_t vh_base = 0;              // (first-hit planes: where the view's planes begin, in words)
 		if constexpr(VIEWS)
 		{
 			fu = P.views_shift >= 0 ? __umulhi(unit, P.views_magic) >> P.views_shift : unit;
@@ -541,10 +570,14 @@ pwn_trace_kernel(pwn_trace_params P)
 			rdx.x = r[4]; rdx.y = r[5]; rdx.z = r[6]; rdx.w = HAS_W ? r[7] : 0.0f;
 			rdy.x = r[8]; rdy.y = r[9]; rdy.z = r[10]; rdy.w = HAS_W ? r[11] : 0.0f;
 			from.x = r[12]; from.y = r[13]; from.z = r[14]; from.w = HAS_W ? r[15] : 1.0f;
-			sec_current = r[16];
 			// (the view's planes: 64-bit offsets, a batch may hold 2^28 pixels per plane array)
-			sbuf += (size_t)view * (size_t)P.plane;
-			zbuf += (size_t)view * (size_t)P.plane;
+			if constexpr(VHITS) vh_base = (size_t)view * (size_t)P.plane;
+			else
+			{
+				sec_current = r[16];
+				sbuf += (size_t)view * (size_t)P.plane;
+				zbuf += (size_t)view * (size_t)P.plane;
+			}
 		}
 		// The frame this unit belongs to: the launch's -- or, views of their own sizes (pwn_trace_viewports), the view's own, from
 		// its record: width and height (bounds, pixel seed, middle row), units per row with their division constant, rows of
@@ -682,7 +715,22 @@ pwn_trace_kernel(pwn_trace_params P)
 			}
 			//@R k_chain
 			if(ORDER && P.unit_cost != NULL) u_begin = __builtin_amdgcn_s_memrealtime();
-			if(x < fw && y < fy1)
+			if constexpr(VHITS)
+			{
+				// First-hit planes (pwn_trace_view_hits): the pixel's ray as a frame's, through trace_hit in the place of trace_pixel.  Every
+				// LDS address: the argument of the hit mode above (trace_hit's set-up and walk are trace_pixel's, and the ray is a frame's,
+				// which the frame modes trace).  Global: only lanes with x < w and y < h store, one 4-byte word per plane given, at
+				// view * plane + y * w + x with view < nviews and plane = w * h: below nviews * w * h <= 2^28 words, in 64-bit arithmetic,
+				// inside planes of that many words (pwn_calls.cpp checks n and allocates the host form's own).  A plane whose pointer is
+				// NULL is skipped.  No seed, colour, depth or time is touched.
+				if(x < fw && y < fy1)
+				{
+					const size_t o = vh_base + (size_t)y * (size_t)P.w + (size_t)x;
+					// (tables.h: the label plane is P.hits, the cell plane P.sbuf, the distance plane P.zbuf)
+					hit_store_planes(trace_hit<COUNT, HAS_W, LISTS>(L, from, rayl, cnt), (uint32_t *)P.hits + o, P.sbuf != NULL ? P.sbuf + o : NULL, P.zbuf != NULL ? P.zbuf + o : NULL);
+				}
+			}
+			else if(x < fw && y < fy1)
 			{
 				const uint32_t seed = pixel_seed(x, y, fw);
 				float ox, oy, oz, ow;
@@ -781,10 +829,11 @@ using Units = TraceKernels<pwn_trace_kernel<true, true, ORDER, LISTS, MODE>, pwn
 extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
 {
 	// (the blob says which form its per-cell lists have: pwn_i_pack_blob, pwn_tables.cpp)
-	// The global form: sixteen variants, MODE x COUNT x HAS_W, never ordered (pwn_i_launch_trace hands such a launch neither an
+	// The global form: twenty-four variants, MODE x COUNT x HAS_W, never ordered (pwn_i_launch_trace hands such a launch neither an
 	// order nor a cost array).
 	if(P->g_rec != NULL)
 	{
+		if(P->views != NULL && P->hits != NULL) return Units<false, PWN_LF_GLOBAL, PWN_KM_VIEW_HITS>::launch(P, grid, lds_bytes, count, stream);
 		if(P->hits != NULL) return Units<false, PWN_LF_GLOBAL, PWN_KM_HITS>::launch(P, grid, lds_bytes, count, stream);
 		if(P->rays != NULL) return Units<false, PWN_LF_GLOBAL, PWN_KM_RAYS>::launch(P, grid, lds_bytes, count, stream);
 		if(P->views != NULL) return Units<false, PWN_LF_GLOBAL, PWN_KM_VIEWS>::launch(P, grid, lds_bytes, count, stream);
@@ -794,7 +843,8 @@ extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size
 	}
 	const bool inl = P->off_recsph != 0u;
 	// a batch of rays (pwn_trace_rays), of their first hits (pwn_trace_hits), of views (pwn_trace_views) or of views of their own sizes
-	// (pwn_trace_viewports): eight variants each, never ordered
+	// (pwn_trace_viewports), of views' first-hit planes (pwn_trace_view_hits): eight variants each, never ordered
+	if(P->views != NULL && P->hits != NULL) return inl ? Units<false, PWN_LF_INLINE, PWN_KM_VIEW_HITS>::launch(P, grid, lds_bytes, count, stream) : Units<false, PWN_LF_INDEXED, PWN_KM_VIEW_HITS>::launch(P, grid, lds_bytes, count, stream);
 	if(P->hits != NULL) return inl ? Units<false, PWN_LF_INLINE, PWN_KM_HITS>::launch(P, grid, lds_bytes, count, stream) : Units<false, PWN_LF_INDEXED, PWN_KM_HITS>::launch(P, grid, lds_bytes, count, stream);
 	if(P->rays != NULL) return inl ? Units<false, PWN_LF_INLINE, PWN_KM_RAYS>::launch(P, grid, lds_bytes, count, stream) : Units<false, PWN_LF_INDEXED, PWN_KM_RAYS>::launch(P, grid, lds_bytes, count, stream);
 	if(P->views != NULL) return inl ? Units<false, PWN_LF_INLINE, PWN_KM_VIEWS>::launch(P, grid, lds_bytes, count, stream) : Units<false, PWN_LF_INDEXED, PWN_KM_VIEWS>::launch(P, grid, lds_bytes, count, stream);

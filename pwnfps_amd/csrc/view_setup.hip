@@ -27,7 +27,7 @@ pwn_view_setup_kernel(const float4 *__restrict__ cams, const float *__restrict__
 	rdy.x = ysrat * cy.x; rdy.y = ysrat * cy.y; rdy.z = ysrat * cy.z; rdy.w = ysrat * cy.w;
 	float4 *r = out + 5 * (size_t)i;
 	r[0] = rayb; r[1] = rdx; r[2] = rdy; r[3] = cw;
-	r[4] = make_float4(secs[i], 0.0f, 0.0f, 0.0f);        // sec_current and the padding
+	r[4] = make_float4(secs != NULL ? secs[i] : 0.0f, 0.0f, 0.0f, 0.0f);        // sec_current (none: pwn_trace_view_hits_device) and the padding
 }
 
 // (d_cams and d_out 16-byte aligned: the kernel moves whole float4)

@@ -442,6 +442,66 @@ class Renderer:
             self._chk(lib.pwn_get_object_ids(self._ctx, ids.ctypes.data, n), "pwn_get_object_ids")
         return ids
 
+    # -- first-hit planes of a batch of views (pwn_trace_view_hits) -------------
+    def trace_view_hits(self, cams, want_cell=True, want_dist=True):
+        """pwn_trace_view_hits: what is under every pixel of n views of this context's size.  cams (n,4,4) or (n,16).  Returns
+        (label, cell, dist): label (n,h,w) uint32 packed words (unpack_labels takes them apart), cell (n,h,w,2) int16 cell x, z
+        and dist (n,h,w) float32 -- cell / dist None where not wanted.  Pixel (x, y) of view i is the record trace_hits returns
+        for pixel_rays(cams[i])'s ray of that pixel; a primary segment that ran out of steps gives 0 in all three."""
+        cams = np.asarray(cams)
+        if cams.ndim == 3 and cams.shape[1:] == (4, 4):
+            cams = cams.reshape(cams.shape[0], 16)
+        if cams.ndim != 2 or cams.shape[1] != 16 or cams.shape[0] < 1:
+            raise ValueError("trace_view_hits: cams must have shape (n,4,4) or (n,16) with n >= 1, not %s" % (cams.shape,))
+        n = cams.shape[0]
+        if n > _lib.PWN_VIEWS_MAX:
+            raise ValueError("trace_view_hits: %d views, at most %d" % (n, _lib.PWN_VIEWS_MAX))
+        cams = np.ascontiguousarray(cams, np.float32)
+        label = np.empty((n, self.h, self.w), np.uint32)
+        cell = np.empty((n, self.h, self.w, 2), np.int16) if want_cell else None
+        dist = np.empty((n, self.h, self.w), np.float32) if want_dist else None
+        self._chk(lib.pwn_trace_view_hits(self._ctx, n, cams.ctypes.data, label.ctypes.data, cell.ctypes.data if want_cell else None,
+                                          dist.ctypes.data if want_dist else None), "pwn_trace_view_hits")
+        return label, cell, dist
+
+    def trace_view_hits_device(self, cams, label, cell=None, dist=None, has_w=False, stream=None):
+        """pwn_trace_view_hits_device: the planes of trace_view_hits from cameras on the GPU into planes on the GPU, stream-ordered,
+        no synchronisation and no host copy.  All torch tensors on this context's GPU, contiguous and 16-byte aligned: cams (n,16)
+        or (n,4,4) float32, label (n,h,w) int32 or uint32, cell (n,h,w) int32 or uint32 -- or (n,h,w,2) int16 -- or None, dist
+        (n,h,w) float32 or None.  Every pixel of every plane given is written.  has_w and stream as trace_views_device takes them."""
+        import torch
+        who = "trace_view_hits_device"
+        words = (torch.int32, getattr(torch, "uint32", torch.int32))
+        if isinstance(cams, torch.Tensor) and cams.dim() == 3 and tuple(cams.shape[1:]) == (4, 4) and cams.is_contiguous():
+            cams = cams.view(cams.shape[0], 16)
+        n = _tensor_check(torch, cams, "cams", (torch.float32,), 2, who=who)
+        if cams.shape[1] != 16 or n < 1 or n > _lib.PWN_VIEWS_MAX:
+            raise ValueError("%s: cams must have shape (n,4,4) or (n,16) with 1 <= n <= %d, not %s" % (who, _lib.PWN_VIEWS_MAX, tuple(cams.shape)))
+        planes = [("label", label, words, 3)]
+        if cell is not None:
+            pairs = isinstance(cell, torch.Tensor) and cell.dtype == torch.int16
+            planes.append(("cell", cell, (torch.int16,), 4) if pairs else ("cell", cell, words, 3))
+        if dist is not None:
+            planes.append(("dist", dist, (torch.float32,), 3))
+        for name, t, dtypes, ndim in planes:
+            _tensor_check(torch, t, name, dtypes, ndim, n, who=who)
+            want = (n, self.h, self.w) + ((2,) if ndim == 4 else ())
+            if tuple(t.shape) != want:
+                raise ValueError("%s: %s must have shape %s, not %s" % (who, name, want, tuple(t.shape)))
+            if t.device != cams.device:
+                raise ValueError("%s: tensors on %s and %s" % (who, cams.device, t.device))
+        for name, t in [("cams", cams)] + [(name, t) for name, t, _, _ in planes]:
+            if t.data_ptr() % 16 != 0:
+                raise ValueError("%s: %s is not 16-byte aligned" % (who, name))
+        if stream is None:
+            stream = torch.cuda.current_stream(cams.device)
+        if not isinstance(stream, int):
+            stream = stream.cuda_stream
+        self._chk(lib.pwn_trace_view_hits_device(self._ctx, n, C.c_void_p(cams.data_ptr()), _lib.PWN_VIEWS_HAS_W if has_w else 0,
+                                                 C.c_void_p(label.data_ptr()), C.c_void_p(cell.data_ptr() if cell is not None else None),
+                                                 C.c_void_p(dist.data_ptr() if dist is not None else None), C.c_void_p(stream or 0)),
+                  "pwn_trace_view_hits_device")
+
     def set_call_strips(self, n):
         """PWN_OPT_CALL_STRIPS: -1 = by frame size (default), 0 = one launch per pass, 2..32 = that many row strips"""
         self._chk(lib.pwn_set_option(self._ctx, _lib.PWN_OPT_CALL_STRIPS, int(n)), "pwn_set_option(CALL_STRIPS)")
@@ -714,6 +774,24 @@ def _ray_records(rays, who):
     if rays.shape[0] > _lib.PWN_RAYS_MAX:
         raise ValueError("%s: %d rays, at most %d" % (who, rays.shape[0], _lib.PWN_RAYS_MAX))
     return np.ascontiguousarray(rays, np.float32)
+
+
+def unpack_labels(label):
+    """The fields of trace_view_hits' label words (PWN_LABEL_* of pwnhip.h): (kind, face, object, portals), int32 arrays of
+    label's shape.  0 = nothing hit: kind PWN_HIT_NONE, face and object -1, portals 0."""
+    l = np.asarray(label).astype(np.uint32)
+    return ((l & 3).astype(np.int32), ((l >> 2) & 7).astype(np.int32) - 1, ((l >> 5) & 0x3fff).astype(np.int32) - 1,
+            (l >> 19).astype(np.int32))
+
+
+def pack_labels(hits):
+    """unpack_labels' inverse, from HIT_DTYPE records (trace_hits): kind | (face + 1) << 2 | (object + 1) << 5 | portals << 19,
+    uint32 of hits' shape"""
+    hits = np.asarray(hits)
+    if hits.dtype != HIT_DTYPE:
+        raise ValueError("pack_labels: records of HIT_DTYPE, not %s" % (hits.dtype,))
+    u = lambda f, add=0: (hits[f].astype(np.int64) + add).astype(np.uint32)
+    return u("kind") | (u("face", 1) << np.uint32(2)) | (u("object", 1) << np.uint32(5)) | (u("portals") << np.uint32(19))
 
 
 def _tensor_check(torch, t, name, dtypes, ndim, n=None, who="trace_rays_device"):

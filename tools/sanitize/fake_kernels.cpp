@@ -28,6 +28,28 @@ static void small_launch(const char *name, const void *src, const void *dst, std
 extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t)
 {
 	if(pwn_fake_trace_hook != NULL) pwn_fake_trace_hook(P, grid, lds_bytes);
+	// first-hit planes of views (pwn_trace_view_hits; view_hits_driver.cpp): a word per pixel of every plane given that depends on the
+	// plane, the view's record and the pixel -- every word of n x h x w, and none beside them
+	if(P->views != NULL && P->hits != NULL)
+	{
+		for(int v = 0; v < P->nviews; v++)
+		{
+			uint32_t rec = 0;
+			for(int i = 0; i < 20; i++) { uint32_t u; memcpy(&u, (const float *)&P->views[v] + i, 4); rec = mix(rec, u); }
+			for(int y = P->y0; y < P->y1; y++)
+				for(int x = 0; x < P->w; x++)
+				{
+					const size_t o = (size_t)v * P->plane + (size_t)y * P->w + x;
+					const uint32_t k = mix(mix((uint32_t)x, (uint32_t)y), rec);
+					((uint32_t *)P->hits)[o] = k;
+					if(P->sbuf != NULL) P->sbuf[o] = k ^ 0x11111111u;
+					if(P->zbuf != NULL) P->zbuf[o] = (float)(k >> 8);
+				}
+		}
+		if(P->tickets_next) for(unsigned q = 0; q < PWN_QUEUES; q++) P->tickets_next[q * PWN_QUEUE_STRIDE] = 0u;
+		if(count && P->counters) P->counters[0] += (unsigned long long)P->nviews * P->plane;
+		return hipSuccess;
+	}
 	uint32_t tab = 0;
 	for(uint32_t i = 0; i < P->blob_bytes / 4; i += 7) tab = mix(tab, P->blob[i]);
 	uint32_t secbits, cambits = 0;
@@ -103,7 +125,7 @@ extern "C" hipError_t pwn_launch_view_setup(const float *cams, const float *secs
 			r.rdy[i] = S.ysrat * cam[4 + i];
 			r.from[i] = cam[12 + i];
 		}
-		r.sec_current = secs[v];
+		r.sec_current = secs != NULL ? secs[v] : 0.0f;
 		out[v] = r;
 	}
 	return hipSuccess;
