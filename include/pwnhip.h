@@ -628,6 +628,17 @@ int pwn_trace_view_hits_device(pwn_ctx *ctx, int n, const void *d_cams, int flag
  *   pwn_wait_frame     block until the slot's frame is on the host; the pointers in
  *                      *out stay valid until the next submit on that slot.
  *   pwn_frame_ready    1 / 0 without blocking.
+ *   depth per slot     every slot has a colour and a depth plane of its own (pwn_frame.d_sbuf / d_zbuf), apart from the
+ *                      blocking call's planes, the view slots of pwn_trace_views and the planes of pwn_trace_viewports.  A
+ *                      slot's depth plane is zero when allocated and keeps its previous value -- the slot's previous frame --
+ *                      where the primary ray runs out of steps (trace.h:677).  EVERY pwn_frames_config allocates the slots
+ *                      afresh: their depth planes start from zero again, also when the number of slots stays the same, and
+ *                      nothing counts as submitted (pwn_wait_frame: PWN_EINVAL); pwn_frame.seq goes on counting.
+ *   shared             the pre-blur plane and, under two or more blur passes, the blocking call's colour plane: the passes of
+ *                      a frame in flight take turns on the two and the last lands in the slot's own plane, so behind such a
+ *                      frame pwn_screen_upscale(NULL, ...) reads that frame's FIRST pass, not the last blocking frame, until the
+ *                      next pwn_trace_screen_centred.  With 0 or 1 passes the blocking call's colour is left alone; its depth
+ *                      plane always is.
  * Frames complete in submission order.  The blocking pwn_trace_screen_centred may be
  * mixed in; it is ordered behind the submitted frames.
  */
@@ -831,8 +842,10 @@ int pwn_tiled_recut(const int *cuts, const uint32_t *cost, int world, int height
 
 /* screen_upscale (screen.h:126-149): replicate every pixel scale x scale into
    a surface of `pitch_bytes` per row (SDL_Surface->pitch / ->pixels).
-   Host form (uploads sbuf... uses the last frame on the device if src is NULL)
-   and device form. */
+   Host form (uploads sbuf... uses the last frame on the device if src is NULL:
+   the last pwn_trace_screen_centred's, zeros before the first; a frame in flight
+   submitted since under two or more blur passes has left its first pass there,
+   see "shared" at pwn_frames_config) and device form. */
 int pwn_screen_upscale(pwn_ctx *ctx, const uint32_t *sbuf, int scale, int pitch_bytes,
 	uint32_t *pixels);
 int pwn_upscale_device(pwn_ctx *ctx, const void *d_src, int scale, int pitch_bytes,
