@@ -603,6 +603,61 @@ int pwn_trace_view_hits_device(pwn_ctx *ctx, int n, const void *d_cams, int flag
 	void *d_label, void *d_cell, void *d_dist, void *stream);
 
 /*
+ * The players' step: what produces the cameras of pwn_trace_views[_device].  The motion of the reference's loop (main.c:188-379:
+ * turning, walking with push-back out of solid cells, gravity, the step between the floors of a two-high room, walking through a
+ * portal with its turn) for a batch of n players at once, on the device, on the level in force -- so that step -> observe -> step
+ * of many agents runs on one stream with no host round trip.
+ *   a tick               one pwn_player_step(p, k, tdiff, cells, pmap) of host/player.c.  `ticks` of them run with the same keys and
+ *                        the same tdiff.
+ *   cams                 n x 16 floats, rows x, y, z, w: exactly the cams of pwn_trace_views[_device].  In / out.  Row y (floats
+ *                        4..7) is never read or written by the step.
+ *   gravity              n x 4 floats, in / out (main.c:48,59).
+ *   traversals           n int32, in / out: portals walked through so far (pwn_player.traversals).  May be NULL; it is then neither
+ *                        read nor written.
+ *   keys                 n bytes: bit i is field i of pwn_keys (host/player.h) = PWN_KEY_* i = main.c:72-79, the PWN_MOVE_* below.
+ *   exactness            every float and every counter is bit-identical to `ticks` successive pwn_player_step calls on the level
+ *                        pwn_get_level returns, for every state in the domain: all 20 floats finite, |pos.x| and |pos.z| <= 2^20,
+ *                        tdiff finite.  Denormals are kept, as on the host; all four lanes of the velocity, the position and the
+ *                        gravity take part, the w lane included; sinf / cosf are glibc 2.35's.
+ *   outside the domain   (NaN, infinities, positions beyond 2^20, where the host's (int) is undefined) the values of that player are
+ *                        unspecified.  The call is PWN_OK all the same and reads nothing outside its tables: every cell index goes
+ *                        through get_cell's clamp (util.h:151-158) as an integer, the portal index is c - 'A' of a tested letter.
+ *                        The other players of the batch are exact.
+ *   the level            the one in force when the call is made; the device form waits on `stream` for its upload if that is still
+ *                        pending, as a trace launch does.  A level uploaded after the call does not reach it.
+ *   ordering             the device form is ONE launch on `stream` (a hipStream_t, NULL = default stream) with no synchronisation.
+ *                        It uses no work-queue counters: the rule for trace launches at the top of this file does not apply to it.
+ *                        The host form (blocking) is ordered behind the frames in flight, as pwn_trace_rays, and ends with its
+ *                        stream drained.
+ *   left alone           everything pwn_trace_view_hits leaves alone, and pwn_stats (no counters, no timings, in either form),
+ *                        pwn_launch_order_waits and the sphere tables.
+ *   cost                 the host form keeps 85 B per player of pinned host memory and as much device memory between calls, grown to
+ *                        the largest batch so far (at least 4096 players); pwn_destroy frees them.
+ *   device pointers      d_cams and d_gravity 16-byte aligned, d_traversals 4-byte aligned, d_keys any.
+ *   errors               PWN_EINVAL for NULL ctx, NULL keys / cams / gravity with n > 0, n < 0, n > PWN_PLAYERS_MAX, ticks < 1,
+ *                        ticks > PWN_TICKS_MAX, a tdiff that is not finite, a misaligned device pointer, any two of the device
+ *                        ranges overlapping; PWN_ENOLEVEL before a level; PWN_ENOTSUP on a pwn_init_multi handle; PWN_EBUSY while
+ *                        the context runs a row tiling (pwn_tiled_init); PWN_ENOMEM when the host form's buffers cannot grow.
+ *                        n == 0 is PWN_OK once the other checks pass, and launches nothing.  A refused call launches nothing.
+ */
+#define PWN_PLAYERS_MAX (1 << 20)
+#define PWN_TICKS_MAX   1024
+#define PWN_MOVE_TURN_LEFT 1
+#define PWN_MOVE_TURN_RIGHT 2
+#define PWN_MOVE_TURN_UP 4       /* read and unused, as main.c:188 */
+#define PWN_MOVE_TURN_DOWN 8     /* read and unused */
+#define PWN_MOVE_FORWARD 16
+#define PWN_MOVE_BACK 32
+#define PWN_MOVE_LEFT 64
+#define PWN_MOVE_RIGHT 128
+/* Blocking, host memory, in / out. */
+int pwn_players_step(pwn_ctx *ctx, int n, const uint8_t *keys, float tdiff, int ticks,
+	float *cams, float *gravity, int32_t *traversals);
+/* Device memory, stream-ordered. */
+int pwn_players_step_device(pwn_ctx *ctx, int n, const void *d_keys, float tdiff, int ticks,
+	void *d_cams, void *d_gravity, void *d_traversals, void *stream);
+
+/*
  * Frames in flight.  The reference presents every frame on the host
  * (trace_screen_centred fills sbuf, screen_upscale fills screen->pixels, SDL_Flip:
  * main.c:107-109).  Over PCIe that hand-over takes longer than the kernels of a

@@ -30,6 +30,11 @@ PWN_RAYS_HAS_W = 1
 PWN_VIEWS_HAS_W = 1
 PWN_RAYS_MAX = 1 << 28
 PWN_HIT_NONE, PWN_HIT_WALL, PWN_HIT_SPHERE = 0, 1, 2
+PWN_PLAYERS_MAX = 1 << 20
+PWN_TICKS_MAX = 1024
+# one key byte per player of pwn_players_step: bit i is field i of pwn_keys (host/player.h)
+(PWN_MOVE_TURN_LEFT, PWN_MOVE_TURN_RIGHT, PWN_MOVE_TURN_UP, PWN_MOVE_TURN_DOWN,
+ PWN_MOVE_FORWARD, PWN_MOVE_BACK, PWN_MOVE_LEFT, PWN_MOVE_RIGHT) = (1 << i for i in range(8))
 (PROBE_RCP, PROBE_RSQRT, PROBE_SINF, PROBE_COSF, PROBE_EXPF, PROBE_SQRT, PROBE_DIV,
  PROBE_FTOINT, PROBE_RANDFS, PROBE_SIN_OF_PAIR, PROBE_COS_OF_PAIR) = range(11)
 
@@ -135,6 +140,8 @@ ABI = [
     ("pwn_get_object_ids", _i, [_vp, _vp, _i]),
     ("pwn_trace_view_hits", _i, [_vp, _i, _vp, _vp, _vp, _vp]),
     ("pwn_trace_view_hits_device", _i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    ("pwn_players_step", _i, [_vp, _i, _vp, _f, _i, _vp, _vp, _vp]),
+    ("pwn_players_step_device", _i, [_vp, _i, _vp, _f, _i, _vp, _vp, _vp, _vp]),
     ("pwn_frames_config", _i, [_vp, _i, _i, _i, _i]),
     ("pwn_submit_frame", _i, [_vp, _vp, _f, _i]),
     ("pwn_wait_frame", _i, [_vp, _i, C.POINTER(Frame)]),

@@ -87,6 +87,11 @@ extern "C" int pwn_init(pwn_ctx **out, int device, int width, int height)
 	c->d_ppre = c->d_pout = NULL; c->d_pz = NULL; c->h_prec = c->d_prec = NULL;
 	c->h_rays = c->d_rays = NULL; c->rays_cap = 0;
 	c->h_hits = c->d_hits = NULL; c->hits_cap = 0;
+	c->h_players = c->d_players = NULL; c->players_cap = 0; c->dbg_players_stage = -1;
+	if(const char *e = getenv("PWN_PLAYERS_STAGE")) if(*e) c->dbg_players_stage = atoi(e) != 0;      // (A/B of the step's LDS staging: tools/players_bench.py)
+	for(int i = 0; i < PWN_NBLOB; i++) { c->d_walk[i] = NULL; c->walk_of[i] = i; c->ev_walk[i] = NULL; c->walk_in_use[i] = false; c->walk_stream[i] = NULL; }
+	for(int i = 0; i < PWN_NSTAGE; i++) c->h_walk[i] = NULL;
+	c->walk_dirty = false;
 	memset(&c->room, 0, sizeof(c->room)); c->room.mode = -1;
 	if(const char *e = getenv("PWN_TRACE_ROOM")) if(*e) c->room.mode = atoi(e) < 0 ? -1 : atoi(e);      // (the option's default for every context of a process)
 	c->d_scratch = NULL; c->scratch_cap = 0;
@@ -143,6 +148,11 @@ extern "C" int pwn_init(pwn_ctx **out, int device, int width, int height)
 			if(hipMalloc((void **)&c->d_blob[i], PWN_BLOB_MAX) != hipSuccess) rc = PWN_ENOMEM;
 		for(int i = 0; i < PWN_NSTAGE && rc == PWN_OK; i++)
 			if(hipHostMalloc((void **)&c->h_stage[i], PWN_BLOB_MAX, hipHostMallocDefault) != hipSuccess) rc = PWN_ENOMEM;
+		// the walk tables of the players' step beside them (pwn_internal.h d_walk)
+		for(int i = 0; i < PWN_NBLOB && rc == PWN_OK; i++)
+			if(hipMalloc((void **)&c->d_walk[i], sizeof(pwn_walk_table)) != hipSuccess) rc = PWN_ENOMEM;
+		for(int i = 0; i < PWN_NSTAGE && rc == PWN_OK; i++)
+			if(hipHostMalloc((void **)&c->h_walk[i], sizeof(pwn_walk_table), hipHostMallocDefault) != hipSuccess) rc = PWN_ENOMEM;
 		if(rc != PWN_OK) break;
 		if(hipMemset(c->d_z, 0, n * 4) != hipSuccess || hipMemset(c->d_pre, 0, n * 4) != hipSuccess ||
 		   hipMemset(c->d_out, 0, n * 4) != hipSuccess) { rc = PWN_EHIP; break; }
@@ -171,7 +181,8 @@ extern "C" int pwn_init(pwn_ctx **out, int device, int width, int height)
 		for(int i = 0; i < 4; i++) if(hipEventCreate(&c->ev[i]) != hipSuccess) { rc = PWN_EHIP; break; }
 		for(int i = 0; i < PWN_NBLOB && rc == PWN_OK; i++)
 			if(hipEventCreateWithFlags(&c->ev_tables[i], hipEventDisableTiming) != hipSuccess ||
-			   hipEventCreateWithFlags(&c->ev_upload[i], hipEventDisableTiming) != hipSuccess) rc = PWN_EHIP;
+			   hipEventCreateWithFlags(&c->ev_upload[i], hipEventDisableTiming) != hipSuccess ||
+			   hipEventCreateWithFlags(&c->ev_walk[i], hipEventDisableTiming) != hipSuccess) rc = PWN_EHIP;
 		for(int i = 0; i < PWN_NSTAGE && rc == PWN_OK; i++)
 			if(hipEventCreateWithFlags(&c->ev_stage[i], hipEventDisableTiming) != hipSuccess) rc = PWN_EHIP;
 		if(rc != PWN_OK) break;
@@ -216,6 +227,8 @@ extern "C" void pwn_destroy(pwn_ctx *c)
 	{
 		if(c->ev_tables[i]) (void)hipEventDestroy(c->ev_tables[i]);
 		if(c->ev_upload[i]) (void)hipEventDestroy(c->ev_upload[i]);
+		if(c->ev_walk[i]) (void)hipEventDestroy(c->ev_walk[i]);
+		(void)hipFree(c->d_walk[i]);
 		(void)hipFree(c->d_blob[i]);
 		(void)hipFree(c->d_big[i]);
 	}
@@ -224,6 +237,7 @@ extern "C" void pwn_destroy(pwn_ctx *c)
 		if(c->ev_stage[i]) (void)hipEventDestroy(c->ev_stage[i]);
 		if(c->h_stage[i]) (void)hipHostFree(c->h_stage[i]);
 		if(c->h_big[i]) (void)hipHostFree(c->h_big[i]);
+		if(c->h_walk[i]) (void)hipHostFree(c->h_walk[i]);
 	}
 	if(c->stream) (void)hipStreamDestroy(c->stream);
 	if(c->stream2) (void)hipStreamDestroy(c->stream2);
@@ -240,6 +254,8 @@ extern "C" void pwn_destroy(pwn_ctx *c)
 	if(c->h_rays) (void)hipHostFree(c->h_rays);
 	(void)hipFree(c->d_hits);
 	if(c->h_hits) (void)hipHostFree(c->h_hits);
+	(void)hipFree(c->d_players);
+	if(c->h_players) (void)hipHostFree(c->h_players);
 	for(int i = 0; i < 4; i++) { (void)hipFree(c->order[i].d_cost); (void)hipFree(c->order[i].d_perm); }
 	(void)hipFree(c->d_skip); (void)hipFree(c->d_counters); (void)hipFree(c->d_tickets); (void)hipFree(c->d_scratch);
 	delete c;

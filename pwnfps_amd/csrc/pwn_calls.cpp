@@ -12,7 +12,7 @@
 
 // The blocking calls (pwn_trace_screen_centred, pwn_trace_views) on compute stream s: behind the frames in flight, whichever
 // compute stream their kernels are on
-static int wait_frames_in_flight(pwn_ctx *c, hipStream_t s)
+int pwn_i_wait_frames_in_flight(pwn_ctx *c, hipStream_t s)
 {
 	if(c->last_frame_done != NULL && c->last_frame_stream != s) HIPCHK(c, hipStreamWaitEvent(s, c->last_frame_done, 0));
 	if(c->last_frame_done != NULL && c->stream2 != NULL && c->last_frame_stream != c->stream2) HIPCHK(c, hipStreamWaitEvent(c->stream2, c->last_frame_done, 0));      // (strips use both)
@@ -23,7 +23,7 @@ static int wait_frames_in_flight(pwn_ctx *c, hipStream_t s)
 // What refuses a batch call once its own arguments are in order (include/pwnhip.h), in the order that decides which code a caller
 // with two faults gets.  views > 0: a call that traces that many views of w x h and blurs them, with the two rules of those
 // (blurs = false: the first-hit planes of views, which are never blurred, with the first alone).
-static int batch_refuse(const pwn_ctx *c, int views = 0, bool blurs = true)
+int pwn_i_batch_refuse(const pwn_ctx *c, int views, bool blurs)
 {
 	if(views > 0 && (size_t)views * (size_t)c->w * (size_t)c->h > ((size_t)1 << 28)) return PWN_EINVAL;
 	if(views > 0 && blurs && c->blur_passes > 0 && (c->w & 3) != 0) return PWN_EINVAL;
@@ -337,7 +337,7 @@ extern "C" int pwn_trace_screen_centred(pwn_ctx *c, const float cam[16], float s
 	(void)hipSetDevice(c->device);
 	size_t n = (size_t)c->w * (size_t)c->h;
 	hipStream_t s = c->stream;
-	{ const int rc = wait_frames_in_flight(c, s); if(rc != PWN_OK) return rc; }
+	{ const int rc = pwn_i_wait_frames_in_flight(c, s); if(rc != PWN_OK) return rc; }
 	// ---- in row strips, the copies beside the kernels (PWN_OPT_CALL_STRIPS)
 	{
 		int cuts[PWN_CALL_STRIPS_MAX + 1], K = 1;
@@ -441,12 +441,12 @@ extern "C" int pwn_trace_views(pwn_ctx *c, int n, const float *cams, const float
 {
 	GRP_REFUSE(c, "pwn_trace_views");
 	if(c == NULL || cams == NULL || secs == NULL || sbuf == NULL || n < 1 || n > PWN_VIEWS_MAX) return PWN_EINVAL;
-	int rc = batch_refuse(c, n);
+	int rc = pwn_i_batch_refuse(c, n);
 	if(rc != PWN_OK) return rc;
 	const size_t plane = (size_t)c->w * (size_t)c->h;
 	(void)hipSetDevice(c->device);
 	hipStream_t s = c->stream;
-	rc = wait_frames_in_flight(c, s);
+	rc = pwn_i_wait_frames_in_flight(c, s);
 	if(rc != PWN_OK) return rc;
 	rc = views_reserve(c, n, s);
 	if(rc != PWN_OK) return rc;
@@ -492,8 +492,8 @@ extern "C" int pwn_trace_views_device(pwn_ctx *c, int n, const void *d_cams, con
 		for(int i = 0; i < 3; i++) for(int k = i + 1; k < 3; k++)
 			if(p[i] != 0 && p[k] != 0 && p[i] < p[k] + bytes && p[k] < p[i] + bytes) return PWN_EINVAL;
 	}
-	// (the rules above and the first two of batch_refuse all answer PWN_EINVAL: their order among themselves decides nothing)
-	int rc = batch_refuse(c, n);
+	// (the rules above and the first two of pwn_i_batch_refuse all answer PWN_EINVAL: their order among themselves decides nothing)
+	int rc = pwn_i_batch_refuse(c, n);
 	if(rc != PWN_OK) return rc;
 	(void)hipSetDevice(c->device);
 	hipStream_t s = (hipStream_t)stream;
@@ -551,11 +551,11 @@ extern "C" int pwn_trace_viewports(pwn_ctx *c, int n, const pwn_viewport *vp, co
 		snprintf(c->err, sizeof(c->err), "pwn_trace_viewports: %d rectangles of a %d x %d frame refused (the first offender: %llu)", n, c->w, c->h, plan[3]);
 		return PWN_EINVAL;
 	}
-	int rc = batch_refuse(c);
+	int rc = pwn_i_batch_refuse(c);
 	if(rc != PWN_OK) return rc;
 	(void)hipSetDevice(c->device);
 	hipStream_t s = c->stream;
-	rc = wait_frames_in_flight(c, s);
+	rc = pwn_i_wait_frames_in_flight(c, s);
 	if(rc != PWN_OK) return rc;
 	rc = viewports_reserve(c, s);
 	if(rc != PWN_OK) return rc;
@@ -614,12 +614,12 @@ extern "C" int pwn_trace_viewports(pwn_ctx *c, int n, const pwn_viewport *vp, co
 
 // Room for n rays of a blocking ray call, kept across calls: pinned staging *h and a device buffer *d of the same layout, `per_ray`
 // bytes a ray.  Grows to at least twice the old size; no kernel uses the old buffers (every call ends with its stream drained).
-static int staging_reserve(pwn_ctx *c, size_t n, size_t per_ray, const char *who, unsigned char **h, unsigned char **d, size_t *cap_io)
+int pwn_i_staging_reserve(pwn_ctx *c, size_t n, size_t per_ray, const char *who, unsigned char **h, unsigned char **d, size_t *cap_io, size_t cap_max, const char *unit)
 {
 	if(n <= *cap_io) return PWN_OK;
 	size_t cap = *cap_io * 2;
 	if(cap < 4096) cap = 4096;
-	if(cap > PWN_RAYS_MAX) cap = PWN_RAYS_MAX;
+	if(cap > cap_max) cap = cap_max;
 	if(cap < n) cap = n;
 	const size_t bytes = cap * per_ray + 16;            // (+16: the upload kernel copies whole 16-byte words)
 	unsigned char *nh = NULL, *nd = NULL;
@@ -628,7 +628,7 @@ static int staging_reserve(pwn_ctx *c, size_t n, size_t per_ray, const char *who
 		(void)hipGetLastError();
 		if(nh != NULL) (void)hipHostFree(nh);
 		(void)hipFree(nd);
-		snprintf(c->err, sizeof(c->err), "%s: no room for %zu rays", who, n);
+		snprintf(c->err, sizeof(c->err), "%s: no room for %zu %s", who, n, unit);
 		return PWN_ENOMEM;
 	}
 	if(*h != NULL) (void)hipHostFree(*h);
@@ -665,13 +665,13 @@ extern "C" int pwn_trace_rays(pwn_ctx *c, int n, const float *rays, const uint32
 {
 	GRP_REFUSE(c, "pwn_trace_rays");
 	if(c == NULL || n < 0 || n > PWN_RAYS_MAX || (n > 0 && rays == NULL) || (col == NULL && depth == NULL)) return PWN_EINVAL;
-	int rc = batch_refuse(c);
+	int rc = pwn_i_batch_refuse(c);
 	if(rc != PWN_OK || n == 0) return rc;
 	(void)hipSetDevice(c->device);
 	hipStream_t s = c->stream;
-	rc = wait_frames_in_flight(c, s);
+	rc = pwn_i_wait_frames_in_flight(c, s);
 	if(rc != PWN_OK) return rc;
-	rc = staging_reserve(c, (size_t)n, 44, "pwn_trace_rays", &c->h_rays, &c->d_rays, &c->rays_cap);
+	rc = pwn_i_staging_reserve(c, (size_t)n, 44, "pwn_trace_rays", &c->h_rays, &c->d_rays, &c->rays_cap);
 	if(rc != PWN_OK) return rc;
 	const size_t N = (size_t)n;
 	unsigned char *h = c->h_rays, *d = c->d_rays;
@@ -694,7 +694,7 @@ extern "C" int pwn_trace_rays_device(pwn_ctx *c, int n, const void *d_rays, cons
 	   (flags & ~PWN_RAYS_HAS_W) != 0) return PWN_EINVAL;
 	if(((uintptr_t)d_rays & 15u) != 0 || ((uintptr_t)d_seeds & 3u) != 0 || ((uintptr_t)d_col & 3u) != 0 || ((uintptr_t)d_depth & 3u) != 0)
 		return PWN_EINVAL;
-	const int rc = batch_refuse(c);
+	const int rc = pwn_i_batch_refuse(c);
 	if(rc != PWN_OK || n == 0) return rc;
 	(void)hipSetDevice(c->device);
 	pwn_trace_launch T = { .sec = sec, .rays = { (const float *)d_rays, (const uint32_t *)d_seeds, (uint32_t)n, (flags & PWN_RAYS_HAS_W) != 0 },
@@ -710,13 +710,13 @@ extern "C" int pwn_trace_hits(pwn_ctx *c, int n, const float *rays, pwn_hit *hit
 {
 	GRP_REFUSE(c, "pwn_trace_hits");
 	if(c == NULL || n < 0 || n > PWN_RAYS_MAX || (n > 0 && (rays == NULL || hits == NULL))) return PWN_EINVAL;
-	int rc = batch_refuse(c);
+	int rc = pwn_i_batch_refuse(c);
 	if(rc != PWN_OK || n == 0) return rc;
 	(void)hipSetDevice(c->device);
 	hipStream_t s = c->stream;
-	rc = wait_frames_in_flight(c, s);
+	rc = pwn_i_wait_frames_in_flight(c, s);
 	if(rc != PWN_OK) return rc;
-	rc = staging_reserve(c, (size_t)n, 32 + sizeof(pwn_hit), "pwn_trace_hits", &c->h_hits, &c->d_hits, &c->hits_cap);
+	rc = pwn_i_staging_reserve(c, (size_t)n, 32 + sizeof(pwn_hit), "pwn_trace_hits", &c->h_hits, &c->d_hits, &c->hits_cap);
 	if(rc != PWN_OK) return rc;
 	const size_t N = (size_t)n;
 	unsigned char *h = c->h_hits, *d = c->d_hits;
@@ -732,7 +732,7 @@ extern "C" int pwn_trace_hits_device(pwn_ctx *c, int n, const void *d_rays, int 
 	GRP_REFUSE(c, "pwn_trace_hits_device");
 	if(c == NULL || n < 0 || n > PWN_RAYS_MAX || (n > 0 && (d_rays == NULL || d_hits == NULL)) || (flags & ~PWN_RAYS_HAS_W) != 0) return PWN_EINVAL;
 	if(((uintptr_t)d_rays & 15u) != 0 || ((uintptr_t)d_hits & 15u) != 0) return PWN_EINVAL;
-	const int rc = batch_refuse(c);
+	const int rc = pwn_i_batch_refuse(c);
 	if(rc != PWN_OK || n == 0) return rc;
 	(void)hipSetDevice(c->device);
 	pwn_trace_launch T = { .rays = { (const float *)d_rays, NULL, (uint32_t)n, (flags & PWN_RAYS_HAS_W) != 0, d_hits }, .stream = (hipStream_t)stream };
@@ -748,16 +748,16 @@ extern "C" int pwn_trace_view_hits(pwn_ctx *c, int n, const float *cams, uint32_
 {
 	GRP_REFUSE(c, "pwn_trace_view_hits");
 	if(c == NULL || cams == NULL || label == NULL || n < 1 || n > PWN_VIEWS_MAX) return PWN_EINVAL;
-	int rc = batch_refuse(c, n, false);
+	int rc = pwn_i_batch_refuse(c, n, false);
 	if(rc != PWN_OK) return rc;
 	const size_t plane = (size_t)c->w * (size_t)c->h, N = (size_t)n * plane;
 	(void)hipSetDevice(c->device);
 	hipStream_t s = c->stream;
-	rc = wait_frames_in_flight(c, s);
+	rc = pwn_i_wait_frames_in_flight(c, s);
 	if(rc != PWN_OK) return rc;
 	rc = view_recs_reserve(c);
 	if(rc != PWN_OK) return rc;
-	rc = staging_reserve(c, (12 * N + 79) / 80, 32 + sizeof(pwn_hit), "pwn_trace_view_hits", &c->h_hits, &c->d_hits, &c->hits_cap);
+	rc = pwn_i_staging_reserve(c, (12 * N + 79) / 80, 32 + sizeof(pwn_hit), "pwn_trace_view_hits", &c->h_hits, &c->d_hits, &c->hits_cap);
 	if(rc != PWN_OK) return rc;
 	// every view's record from the blocking call's own set-up, as pwn_trace_views; the primary segment reads no time
 	bool has_w = false;
@@ -804,7 +804,7 @@ extern "C" int pwn_trace_view_hits_device(pwn_ctx *c, int n, const void *d_cams,
 		for(int i = 0; i < 3; i++) for(int k = i + 1; k < 3; k++)
 			if(p[i] != 0 && p[k] != 0 && p[i] < p[k] + bytes && p[k] < p[i] + bytes) return PWN_EINVAL;
 	}
-	int rc = batch_refuse(c, n, false);
+	int rc = pwn_i_batch_refuse(c, n, false);
 	if(rc != PWN_OK) return rc;
 	(void)hipSetDevice(c->device);
 	hipStream_t s = (hipStream_t)stream;

@@ -4,6 +4,7 @@
 //   pwn_tables.cpp  level, objects, the sphere tables: their size rules, packing and upload
 //   pwn_launch.cpp  the trace and blur launchers (the launch geometry itself: launch_plan.h), the unit order, the *_rows_device calls
 //   pwn_calls.cpp   the blocking call and its strips, host registration, the batches of views, viewports, rays and hits
+//   pwn_players.cpp the players' step: a batch of cameras walked through the level (host and device form)
 //   pwn_frames.cpp  frames in flight
 //   pwn_tiled.cpp   row tiling over RCCL
 //   pwn_group.cpp   several contexts behind one handle
@@ -103,6 +104,10 @@ extern "C" hipError_t pwn_launch_upscale(const uint32_t *src, uint32_t *dst, int
 extern "C" hipError_t pwn_launch_upload(const void *h_pinned_src, void *d_dst, size_t bytes, hipStream_t stream);
 // the camera set-up of n views from device memory (view_setup.hip): d_cams n x 16 floats and d_out 16-byte aligned; d_secs NULL: every time 0
 extern "C" hipError_t pwn_launch_view_setup(const float *d_cams, const float *d_secs, pwn_view_rec *d_out, int n, int w, int h, hipStream_t stream);
+// ticks of host/player.c's pwn_player_step for n players (player_step.hip): d_cams n x 16 floats and d_gravity n x 4 floats, 16-byte aligned,
+// d_traversals n int32 or NULL, d_keys n bytes; stage != 0: every workgroup copies the walk table into LDS first
+extern "C" hipError_t pwn_launch_players_step(float *d_cams, float *d_gravity, int32_t *d_traversals, const uint8_t *d_keys, int n,
+	float tdiff, int ticks, const pwn_walk_table *d_walk, int stage, hipStream_t stream);
 extern "C" hipError_t pwn_launch_words(const uint32_t *d_all, const uint32_t *d_own, uint32_t *h_pinned_dst, int world, hipStream_t stream);
 extern "C" hipError_t pwn_launch_probe(int op, const uint32_t *in, uint32_t *out, int n, const uint16_t *tabs, hipStream_t stream);
 
@@ -258,6 +263,16 @@ struct pwn_ctx
 	uint8_t *h_big[PWN_NSTAGE]; size_t h_big_cap[PWN_NSTAGE];
 	size_t big_high;
 	bool blob_dirty;
+	// The walk tables of the players' step (tables.h pwn_walk_table): as many buffers as copies of the tables.  Copy i of the tables
+	// reads buffer walk_of[i].  A level upload fills a buffer no other copy refers to, from pinned h_walk[staging slot], on the upload
+	// stream under the copy's ev_upload; an upload of spheres alone hands the current copy's buffer on to the copy it makes current
+	// and sends nothing.  A step that reads copy i records ev_walk[i] behind itself, and the next upload into copy i waits for it.
+	// An event holds one record: a step on another stream than the last one that read copy i (walk_stream[i]) first puts the upload
+	// stream behind the record that is there, so that no upload gets ahead of a step on any stream.
+	pwn_walk_table *d_walk[PWN_NBLOB], *h_walk[PWN_NSTAGE];
+	int walk_of[PWN_NBLOB];
+	bool walk_dirty;                 // the level changed and no walk table of it has been sent yet
+	hipEvent_t ev_walk[PWN_NBLOB]; bool walk_in_use[PWN_NBLOB]; hipStream_t walk_stream[PWN_NBLOB];
 	size_t occ_lds[12]; int occ_blocks[12];    // cached occupancy query per kernel variant
 
 	uint32_t *d_pre, *d_out;         // pre-blur ("tsbuf") and final ("sbuf") frames
@@ -299,11 +314,13 @@ struct pwn_ctx
 	// of the call in pinned staging and on the device (PWN_VIEWS_MAX of them)
 	uint32_t *d_ppre, *d_pout; float *d_pz;
 	pwn_viewport_rec *h_prec, *d_prec;
-	// pwn_trace_rays: room for rays_cap rays in pinned staging and on the device, 44 B each (record, seed, depth, colour; pwn_calls.cpp staging_reserve)
+	// pwn_trace_rays: room for rays_cap rays in pinned staging and on the device, 44 B each (record, seed, depth, colour; pwn_calls.cpp pwn_i_staging_reserve)
 	unsigned char *h_rays, *d_rays; size_t rays_cap;
 	// pwn_trace_hits: the same for hits_cap rays, 32 B in (record) and 48 B out (pwn_hit) each; pwn_trace_view_hits stages its planes
 	// here too, 12 B a pixel (a call's label plane, behind it its cell plane, then its distance plane): no call uses both at once
 	unsigned char *h_hits, *d_hits; size_t hits_cap;
+	// pwn_players_step: room for players_cap players in pinned staging and on the device, 85 B each (camera, gravity, traversals, key byte)
+	unsigned char *h_players, *d_players; size_t players_cap; int dbg_players_stage;      // (PWN_PLAYERS_STAGE=0 of the environment: the walk table read from device memory, not staged in LDS)
 	uint32_t *d_tickets; unsigned ticket_set;  // PWN_TICKET_SETS sets of work-queue counters of the trace kernel, used in turn
 	uint32_t *d_scratch; size_t scratch_cap;   // upscale / probe staging
 
@@ -366,6 +383,12 @@ struct pwn_ctx
 // pwn_launch.cpp: the launchers, used by the calls, the frames in flight and pwn_tiled.cpp
 int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L);
 int pwn_i_launch_blur(pwn_ctx *c, const pwn_blur_launch *L);
+int pwn_i_tables_uploaded(pwn_ctx *c, int cur, hipStream_t stream);      // a launch on `stream` that reads copy `cur` of the tables comes after their upload
+// pwn_calls.cpp, shared with pwn_players.cpp: what refuses a batch call once its own arguments are in order; a blocking call on
+// stream s put behind the frames in flight; the pinned staging and device buffer of a blocking batch call grown to n records
+int pwn_i_batch_refuse(const pwn_ctx *c, int views = 0, bool blurs = true);
+int pwn_i_wait_frames_in_flight(pwn_ctx *c, hipStream_t s);
+int pwn_i_staging_reserve(pwn_ctx *c, size_t n, size_t per_ray, const char *who, unsigned char **h, unsigned char **d, size_t *cap_io, size_t cap_max = PWN_RAYS_MAX, const char *unit = "rays");
 void pwn_launch_history_clear(pwn_ctx *c);      // the launch-order events are about to be destroyed (streams idle)
 int pwn_i_set_launch_rotation(pwn_ctx *c, int rot);
 int pwn_i_launch_order(pwn_ctx *c, hipStream_t stream);      // behind a frame's last kernel on `stream`: sort that stream's unit costs (no-op when there are none)

@@ -132,7 +132,7 @@ static int resident_per_cu(pwn_ctx *c, bool glb, bool refill, bool has_w, size_t
 }
 
 // the upload of the tables (copy `cur`) runs on its own stream: a launch on `stream` comes after it
-static int tables_uploaded(pwn_ctx *c, int cur, hipStream_t stream)
+int pwn_i_tables_uploaded(pwn_ctx *c, int cur, hipStream_t stream)
 {
 	if(!c->upload_pending[cur]) return PWN_OK;
 	if(hipEventQuery(c->ev_upload[cur]) == hipSuccess) c->upload_pending[cur] = false;
@@ -310,7 +310,7 @@ int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L)
 	P.tile_pairs = plan.tile_pairs; P.pair_single_rows = plan.pair_single_rows; P.tx_magic = plan.tx_magic; P.tx_shift = plan.tx_shift;
 
 	// from here on the runtime is talked to, in the order tests/golden/host_calls.txt records
-	int rc = tables_uploaded(c, cur, stream);
+	int rc = pwn_i_tables_uploaded(c, cur, stream);
 	if(rc != PWN_OK) return rc;
 	if(c->counters_on) HIPCHK(c, hipMemsetAsync(c->d_counters, 0, PWN_NCOUNTERS * sizeof(unsigned long long), stream));
 	L->cost_mul = plan.cost_mul; L->cost_div = plan.cost_div;

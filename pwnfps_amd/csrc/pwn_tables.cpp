@@ -236,9 +236,41 @@ int pwn_i_pack_blob(pwn_ctx *c)
 	}
 	// launches still reading that copy (two uploads ago) finish first -- a wait between streams
 	if(c->tables_in_use[nb]) HIPCHK(c, hipStreamWaitEvent(c->up_stream, c->tables_wait[nb], 0));
+	if(c->walk_in_use[nb]) { HIPCHK(c, hipStreamWaitEvent(c->up_stream, c->ev_walk[nb], 0)); c->walk_in_use[nb] = false; }      // ... and the players' steps that read it
 	// (a kernel that reads the pinned buffer, not a DMA copy: see pwn_upload_kernel; total and from are multiples of 16)
 	HIPCHK(c, pwn_launch_upload(c->h_stage[st], c->d_blob[nb] + from, total - from, c->up_stream));
 	if(glb) HIPCHK(c, pwn_launch_upload(c->h_big[st], c->d_big[nb], c->big.size(), c->up_stream));
+	// The walk table of the players' step (tables.h pwn_walk_table; pwn_internal.h d_walk).  A new level: into a buffer that no
+	// other copy of the tables refers to (of four buffers the other three copies leave one free; what read it did so through a copy
+	// whose later upload, earlier on this stream, waited for it, or through copy nb).  Spheres alone: the copy made current takes
+	// the current copy's buffer over, and nothing travels.
+	if(c->walk_dirty)
+	{
+		// INVARIANT: a buffer no OTHER copy refers to is safe to fill behind what this upload has waited for.  Its readers read it
+		// through copy nb (waited for above: ev_walk[nb]), or through a copy j whose reference has since changed -- by an upload into
+		// j, which waited for ev_walk[j] earlier on this same stream -- and a step on a second stream put this stream behind the
+		// record it replaced (pwn_players.cpp step_launch).  So everything that read the buffer is in front of us on up_stream.
+		int wb = 0;
+		for(; wb < PWN_NBLOB - 1; wb++)
+		{
+			bool taken = false;
+			for(int i = 0; i < PWN_NBLOB; i++) if(i != nb && c->walk_of[i] == wb) taken = true;
+			if(!taken) break;
+		}
+		pwn_walk_table *hw = c->h_walk[st];
+		memset(hw, 0, sizeof(*hw));
+		memcpy(hw->cells, c->cells, 4096);
+		for(int i = 0; i < 26; i++)
+		{
+			const pwn_portal &q = c->pmap[i];
+			const int32_t v[7] = { q.x1, q.z1, q.x2, q.z2, q.rot12, q.c1, q.c2 };
+			memcpy(hw->pmap + 7 * i, v, sizeof(v));
+		}
+		HIPCHK(c, pwn_launch_upload(hw, c->d_walk[wb], sizeof(*hw), c->up_stream));
+		c->walk_of[nb] = wb;
+		c->walk_dirty = false;
+	}
+	else c->walk_of[nb] = c->walk_of[c->blob_cur];
 	HIPCHK(c, hipEventRecord(c->ev_stage[st], c->up_stream));
 	HIPCHK(c, hipEventRecord(c->ev_upload[nb], c->up_stream));
 	c->stage_used[st] = true;
@@ -258,6 +290,7 @@ extern "C" int pwn_upload_level(pwn_ctx *c, const uint8_t data[4096], const pwn_
 	memcpy(c->pmap, pmap, sizeof(c->pmap));
 	c->have_level = true;
 	c->cell_base_ok = false;
+	c->walk_dirty = true;
 	c->blob_dirty = true;
 	return pwn_i_pack_blob(c);
 }
@@ -270,6 +303,7 @@ extern "C" int pwn_level_load_mem(pwn_ctx *c, const char *text, int len)
 	if(pwn_parse_level(text, len, c->cells, c->pmap, c->spawn) != 0) return PWN_EINVAL;
 	c->have_level = true;
 	c->cell_base_ok = false;
+	c->walk_dirty = true;
 	c->blob_dirty = true;
 	return pwn_i_pack_blob(c);
 }

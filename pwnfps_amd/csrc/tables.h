@@ -301,6 +301,17 @@ struct pwn_viewport_rec
 };
 #define PWN_VP_REC_BYTES 128u
 
+// What the players' step (player_step.hip) reads of a level: the raw cell characters (lv->data, defs.h:103) and the portal table
+// (lv->pmap, seven int32 a letter: pwn_portal), neither of which the baked cell words hold.  4096 + 728 bytes, padded to whole
+// 16-byte words (the upload kernel and the step's LDS staging move those).
+struct pwn_walk_table
+{
+	uint8_t cells[4096];
+	int32_t pmap[26 * 7];
+	uint32_t pad_[2];
+};
+#define PWN_WALK_BYTES 4832u
+
 #ifndef PWN_QUEUES
 #define PWN_QUEUES 64u                       /* a power of two <= 64: one lane of a wave looks at each */
 #endif

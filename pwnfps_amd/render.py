@@ -502,6 +502,71 @@ class Renderer:
                                                  C.c_void_p(dist.data_ptr() if dist is not None else None), C.c_void_p(stream or 0)),
                   "pwn_trace_view_hits_device")
 
+    # -- the players' step (pwn_players_step) ---------------------------------
+    def players_step(self, keys, cams, gravity, traversals=None, tdiff=1 / 60, ticks=1):
+        """pwn_players_step: `ticks` ticks of the reference's player motion (main.c:188-379, host/player.c) for n players on the level
+        in force.  keys (n,) uint8 of PWN_MOVE_* bits, cams (n,16) or (n,4,4) float32, gravity (n,4) float32, traversals (n,) int32 or
+        None.  Returns new arrays (cams, gravity, traversals) -- traversals None where none was given; the arguments are not changed."""
+        who = "players_step"
+        keys = np.asarray(keys)
+        cams_in = np.asarray(cams)
+        shape = cams_in.shape
+        if cams_in.ndim == 3 and shape[1:] == (4, 4):
+            cams_in = cams_in.reshape(shape[0], 16)
+        if cams_in.ndim != 2 or cams_in.shape[1] != 16:
+            raise ValueError("%s: cams must have shape (n,4,4) or (n,16), not %s" % (who, shape))
+        n = cams_in.shape[0]
+        gravity = np.asarray(gravity)
+        if keys.shape != (n,) or keys.dtype != np.uint8:
+            raise ValueError("%s: keys must be (%d,) uint8, not %s %s" % (who, n, keys.dtype, keys.shape))
+        if gravity.shape != (n, 4):
+            raise ValueError("%s: gravity must have shape (%d,4), not %s" % (who, n, gravity.shape))
+        if traversals is not None and np.asarray(traversals).shape != (n,):
+            raise ValueError("%s: traversals must have shape (%d,), not %s" % (who, n, np.asarray(traversals).shape))
+        _players_numbers(who, n, tdiff, ticks)
+        keys = np.ascontiguousarray(keys)
+        out_c = np.array(cams_in, np.float32, order="C")
+        out_g = np.array(gravity, np.float32, order="C")
+        out_t = np.array(traversals, np.int32, order="C") if traversals is not None else None
+        self._chk(lib.pwn_players_step(self._ctx, n, keys.ctypes.data if n else None, float(tdiff), int(ticks), out_c.ctypes.data if n else None,
+                                       out_g.ctypes.data if n else None, out_t.ctypes.data if out_t is not None and n else None), "pwn_players_step")
+        return out_c.reshape(shape), out_g, out_t
+
+    def players_step_device(self, keys, cams, gravity, traversals=None, tdiff=1 / 60, ticks=1, stream=None):
+        """pwn_players_step_device: the same on the GPU, in place, one launch on `stream` (a torch stream or a raw hipStream_t; None =
+        torch's current stream), no synchronisation.  Torch tensors on this context's GPU, contiguous: keys (n,) uint8, cams (n,16) or
+        (n,4,4) float32 and gravity (n,4) float32, both 16-byte aligned, traversals (n,) int32 or None.  cams is the tensor
+        trace_views_device takes: step, then observe, on one stream."""
+        import torch
+        who = "players_step_device"
+        if isinstance(cams, torch.Tensor) and cams.dim() == 3 and tuple(cams.shape[1:]) == (4, 4) and cams.is_contiguous():
+            cams = cams.view(cams.shape[0], 16)
+        n = _tensor_check(torch, cams, "cams", (torch.float32,), 2, who=who)
+        if cams.shape[1] != 16:
+            raise ValueError("%s: cams must have shape (n,4,4) or (n,16), not %s" % (who, tuple(cams.shape)))
+        _players_numbers(who, n, tdiff, ticks)
+        if not isinstance(keys, torch.Tensor) or keys.device.type != "cuda" or keys.dtype != torch.uint8 or keys.dim() != 1 or keys.shape[0] != n or not keys.is_contiguous():
+            raise ValueError("%s: keys must be a contiguous uint8 GPU tensor of shape (%d,)" % (who, n))
+        _tensor_check(torch, gravity, "gravity", (torch.float32,), 2, n, who=who)
+        if gravity.shape[1] != 4:
+            raise ValueError("%s: gravity must have shape (%d,4), not %s" % (who, n, tuple(gravity.shape)))
+        if traversals is not None:
+            _tensor_check(torch, traversals, "traversals", (torch.int32,), 1, n, who=who)
+        for name, t in (("keys", keys), ("gravity", gravity), ("traversals", traversals)):
+            if t is not None and t.device != cams.device:
+                raise ValueError("%s: tensors on %s and %s" % (who, cams.device, t.device))
+        for name, t in (("cams", cams), ("gravity", gravity)):
+            if t.data_ptr() % 16 != 0:
+                raise ValueError("%s: %s is not 16-byte aligned" % (who, name))
+        if stream is None:
+            stream = torch.cuda.current_stream(cams.device)
+        if not isinstance(stream, int):
+            stream = stream.cuda_stream
+        self._chk(lib.pwn_players_step_device(self._ctx, n, C.c_void_p(keys.data_ptr() if n else None), float(tdiff), int(ticks),
+                                              C.c_void_p(cams.data_ptr() if n else None), C.c_void_p(gravity.data_ptr() if n else None),
+                                              C.c_void_p(traversals.data_ptr() if traversals is not None and n else None), C.c_void_p(stream or 0)),
+                  "pwn_players_step_device")
+
     def set_call_strips(self, n):
         """PWN_OPT_CALL_STRIPS: -1 = by frame size (default), 0 = one launch per pass, 2..32 = that many row strips"""
         self._chk(lib.pwn_set_option(self._ctx, _lib.PWN_OPT_CALL_STRIPS, int(n)), "pwn_set_option(CALL_STRIPS)")
@@ -792,6 +857,28 @@ def pack_labels(hits):
         raise ValueError("pack_labels: records of HIT_DTYPE, not %s" % (hits.dtype,))
     u = lambda f, add=0: (hits[f].astype(np.int64) + add).astype(np.uint32)
     return u("kind") | (u("face", 1) << np.uint32(2)) | (u("object", 1) << np.uint32(5)) | (u("portals") << np.uint32(19))
+
+
+def _players_numbers(who, n, tdiff, ticks):
+    if n > _lib.PWN_PLAYERS_MAX:
+        raise ValueError("%s: %d players, at most %d" % (who, n, _lib.PWN_PLAYERS_MAX))
+    if int(ticks) != ticks or not 1 <= ticks <= _lib.PWN_TICKS_MAX:
+        raise ValueError("%s: ticks must be 1..%d, not %r" % (who, _lib.PWN_TICKS_MAX, ticks))
+    with np.errstate(over="ignore"):
+        tdiff32 = np.float32(tdiff)
+    if not np.isfinite(tdiff32):
+        raise ValueError("%s: tdiff must be finite, not %r" % (who, tdiff))
+
+
+def players_spawn(spawn, n):
+    """pwn_player_init's state (main.c:59-64) for n players: (cams (n,16) float32, gravity (n,4) float32, traversals (n,) int32) --
+    the identity camera at the centre of the spawn cell, height 0.5, no gravity, no portal walked through."""
+    cams = np.zeros((int(n), 16), np.float32)
+    cams[:, 0] = cams[:, 5] = cams[:, 10] = cams[:, 15] = 1.0
+    cams[:, 12] = np.float32(0.5) + np.float32(int(spawn[0]))
+    cams[:, 13] = 0.5
+    cams[:, 14] = np.float32(0.5) + np.float32(int(spawn[1]))
+    return cams, np.zeros((int(n), 4), np.float32), np.zeros(int(n), np.int32)
 
 
 def _tensor_check(torch, t, name, dtypes, ndim, n=None, who="trace_rays_device"):

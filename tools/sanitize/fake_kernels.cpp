@@ -15,11 +15,13 @@
 static uint32_t mix(uint32_t a, uint32_t b) { a ^= b + 0x9e3779b9u + (a << 6) + (a >> 2); return a * 2654435761u; }
 
 // (tables_driver.cpp looks at what a launch is handed: the tables as the kernels would read them; calls_driver.cpp writes every
-// launch down: the trace and blur launches with their parameters, the small ones with their name, source, destination and sizes)
+// launch down: the trace and blur launches with their parameters, the small ones with their name, source, destination and sizes;
+// players_driver.cpp looks at the walk table a step is handed)
 extern "C" {
 void (*pwn_fake_trace_hook)(const pwn_trace_params *P, int grid, size_t lds_bytes) = NULL;
 void (*pwn_fake_blur_hook)(const pwn_blur_params *B) = NULL;
 void (*pwn_fake_launch_hook)(const char *name, const void *src, const void *dst, int nsizes, const size_t *sizes) = NULL;
+void (*pwn_fake_players_hook)(const pwn_walk_table *walk, int n, int ticks, int stage) = NULL;
 }
 static void small_launch(const char *name, const void *src, const void *dst, std::initializer_list<size_t> sizes)
 {
@@ -127,6 +129,23 @@ extern "C" hipError_t pwn_launch_view_setup(const float *cams, const float *secs
 		}
 		r.sec_current = secs != NULL ? secs[v] : 0.0f;
 		out[v] = r;
+	}
+	return hipSuccess;
+}
+// (the players' step: every player's position moves by a number that depends on its key byte, the ticks and the walk table -- which
+// player, which keys and which level a call was given shows; host/player.c is the arithmetic's model, not this)
+extern "C" hipError_t pwn_launch_players_step(float *cams, float *gravity, int32_t *traversals, const uint8_t *keys, int n, float tdiff, int ticks,
+	const pwn_walk_table *walk, int stage, hipStream_t)
+{
+	small_launch("players_step", keys, cams, { (size_t)n, (size_t)ticks, (size_t)stage });
+	if(pwn_fake_players_hook != NULL) pwn_fake_players_hook(walk, n, ticks, stage);
+	uint32_t tab = 0;
+	for(int i = 0; i < 4096; i += 5) tab = mix(tab, walk->cells[i]);
+	for(int i = 0; i < n; i++)
+	{
+		cams[16 * (size_t)i + 12] += tdiff * (float)ticks * (float)(keys[i] + 1) + (float)(tab & 7u);
+		gravity[4 * (size_t)i + 1] -= tdiff;
+		if(traversals != NULL) traversals[i] += ticks;
 	}
 	return hipSuccess;
 }
