@@ -196,8 +196,28 @@ void pwn_destroy(pwn_ctx *ctx);
  *                   in-process under the bring-up deadline) when the ordinals are distinct and librccl loads, else -- and
  *                   with PWN_GROUP_TRANSPORT=local in the environment -- PWN_TRANSPORT_LOCAL: peer-to-peer copies behind
  *                   events.  pwn_group_info says which.
- *   errors          a member's error is the call's (pwn_last_error names the member); a member that stops answering ends the
- *                   call with PWN_ETIMEDOUT after pwn_tiled_set_timeouts' limits, which the handle takes too.
+ *   errors          1. A refusal is not a failure.  A call that a pwn_init handle refuses with the same arguments in the same state
+ *                   (PWN_EINVAL, PWN_EBUSY, PWN_ENOLEVEL, PWN_ENOTSUP, PWN_EIO, PWN_ETOOBIG) returns the same code here and leaves the
+ *                   handle as it was: the next call of any kind returns what it would have returned without it, frames in flight are
+ *                   delivered, the tiling in force stays in force (pwn_group_info's transport, note, cuts, halo_rows, host_sink,
+ *                   frames are what they were).  pwn_last_error after a later successful call may be anything.  A group's own
+ *                   refusals are of the same kind: PWN_OPT_BLUR_PASSES above 1 and pwn_screen_upscale(NULL, ...) before a blocking
+ *                   call has delivered a frame (PWN_EINVAL), pwn_trace_screen_centred and the options a tiling fixes
+ *                   (PWN_OPT_BLUR_PASSES, _FRAME_OVERLAP, _TILED_*) with frames in flight (PWN_EBUSY), pwn_tiled_* and the strip
+ *                   forms (PWN_ENOTSUP).
+ *                   2. A real failure breaks the group and is mended.  A member past its deadline (PWN_ETIMEDOUT after
+ *                   pwn_tiled_set_timeouts' limits, which the handle takes too), a transport error, PWN_EHIP / PWN_ENOMEM, and
+ *                   whatever leaves the members in different states (a sphere upload that one member could not allocate for, a
+ *                   frame that failed on one member after others had enqueued it, a table call refused by one member only): the
+ *                   first call that waits for the members reports it, pwn_last_error naming the member; the tiling goes down, and
+ *                   the next frame call brings it up again (its depth planes start from zero, as after pwn_frames_config).  After
+ *                   a failed table upload the host uploads again; from then on the frames are one device's.
+ *                   3. A lost frame is reported per slot.  After a real failure with frames in flight, pwn_wait_frame returns that
+ *                   failure's code once for every slot whose frame was lost (a frame that had reached the host's frames before
+ *                   is delivered); *out is not written, and the slot is then free -- a further wait without a submit is
+ *                   PWN_EINVAL, as for a slot never submitted.  pwn_frame_ready of a lost slot returns the code, never 1.  It is
+ *                   never PWN_OK with NULL planes.
+ *                   Not covered: a member's thread that never returns from a HIP or RCCL call holds the call that waits for it.
  * pwn_tiled_* (other than set_timeouts) and the strip forms are refused on such a handle (PWN_ENOTSUP): it runs its own tiling.
  */
 typedef struct pwn_group_info
@@ -715,6 +735,10 @@ typedef struct pwn_frame
 } pwn_frame;
 int pwn_frames_config(pwn_ctx *ctx, int nslots, int flags, int scale, int pitch_bytes);
 int pwn_submit_frame(pwn_ctx *ctx, const float cam[16], float sec_current, int slot);
+/* pwn_wait_frame: PWN_EINVAL for a slot nothing was submitted to (since pwn_frames_config).  On a pwn_init_multi handle, after a failure
+   of the group that took frames in flight with it: that failure's code, once per lost slot, *out not written, the slot then free (a
+   further wait: PWN_EINVAL) -- never PWN_OK with NULL planes.  pwn_frame_ready: 1 ready (or nothing in flight), 0 not yet; of a lost
+   slot the failure's code, until its pwn_wait_frame or the next submit. */
 int pwn_wait_frame(pwn_ctx *ctx, int slot, pwn_frame *out);
 int pwn_frame_ready(pwn_ctx *ctx, int slot);
 /* blocking copy of a device plane of a waited-for frame (pwn_frame.d_*) to host memory, for hosts

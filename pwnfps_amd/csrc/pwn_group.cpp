@@ -32,6 +32,11 @@
 #define MAXM PWN_TILED_MAX_WORLD
 #define GROUP_RING 32u
 enum { MODE_NONE = 0, MODE_SINK = 1, MODE_RESIDENT = 2 };
+// What a job's non-OK return means (pwn_init_multi's `errors`, include/pwnhip.h).  JOB_STRICT: a failure of the group, whatever the code
+// and whichever member -- the frame and transport jobs, which leave the members half way, and the jobs nobody waits for.  JOB_ALL: the
+// same call on every member -- a refusal (refusal()) that every member gives alike is the call's return code and nothing else; members
+// that disagree are in different states, which is a failure.  JOB_ONE: member 0's call -- its refusal is the call's.
+enum { JOB_STRICT = 0, JOB_ALL = 1, JOB_ONE = 2 };
 
 struct pwn_group
 {
@@ -45,9 +50,10 @@ struct pwn_group
 	// either goes on (the tables of the next frame, a frame's submission: the members run ahead of the host loop like the ranks
 	// of a process-per-GPU run do) or waits for it (a frame's delivery, everything rare).  Jobs run in the order they were
 	// posted, on every member.  The first failure marks the group broken: the members skip what is queued behind it, and the
-	// next call that waits reports it.
+	// next call that waits reports it.  A refusal is no failure: the member that is last through a job writes it to the job's
+	// `result`, where run_all finds it.
 	std::thread th[MAXM];
-	struct job_t { std::function<int(int)> fn; bool always; } jobs[GROUP_RING];
+	struct job_t { std::function<int(int)> fn; bool always; int kind; int rc[MAXM]; std::atomic<int> through; int result; } jobs[GROUP_RING];
 	std::atomic<unsigned long long> posted;                 // jobs 1..posted exist (job k in jobs[k % GROUP_RING])
 	std::atomic<unsigned long long> done[MAXM];             // ... and member i is through jobs 1..done[i]
 	std::atomic<bool> quit, broken;
@@ -64,12 +70,13 @@ struct pwn_group
 	int surf_scale, surf_pitch;                  // PWN_FRAME_SURFACE as configured; the tiling in force upscales with these (tiling_surf_*)
 	int tiling_surf_scale, tiling_surf_pitch;
 	bool in_flight[PWN_MAX_SLOTS], delivered[PWN_MAX_SLOTS];
+	int lost[PWN_MAX_SLOTS]; char lost_text[256];           // a failure took the slot's frame with it: its code until pwn_wait_frame has reported it, and what pwn_last_error said
 	pwn_frame fdone[PWN_MAX_SLOTS];
 	float sec[PWN_MAX_SLOTS];
 	int fifo[PWN_MAX_SLOTS + 1], fifo_n;        // slots in submission order, oldest first
 	uint64_t frame_seq;
 	const uint32_t *last_sbuf;                   // where the last blocking call delivered (pwn_screen_upscale(NULL, ...), main.c:108)
-	unsigned long long calls; int stall_member, stall_ms; unsigned long long stall_call;      // PWN_DBG_GROUP_STALL (pwn_group_trace_screen_centred)
+	unsigned long long calls, submits; int stall_member, stall_ms; unsigned long long stall_call; bool stall_submit;      // PWN_DBG_GROUP_STALL (stall())
 	pwn_tiled_frame tf[MAXM];
 };
 
@@ -105,6 +112,21 @@ int pwn_hub_meet(pwn_hub *h, int wait_ms)
 }
 
 // ---- jobs
+// what a one-device handle answers to arguments or to a state it does not take, leaving itself as it was
+static bool refusal(int rc) { return rc == PWN_EINVAL || rc == PWN_EBUSY || rc == PWN_ENOLEVEL || rc == PWN_ENOTSUP || rc == PWN_EIO || rc == PWN_ETOOBIG; }
+
+static void failed(pwn_group *g, int i, int rc)
+{
+	std::lock_guard<std::mutex> lk(g->err_mu);
+	if(g->err_rc == PWN_OK)
+	{
+		g->err_rc = rc; g->err_member = i;
+		snprintf(g->err_text, sizeof(g->err_text), "%.190s", g->m[i]->err[0] ? g->m[i]->err : pwn_strerror(rc));
+	}
+	g->broken.store(true, std::memory_order_release);
+	g->hub.failed.store(1);             // (nobody waits for this member any longer)
+}
+
 static void worker(pwn_group *g, int i)
 {
 	(void)hipSetDevice(g->devices[i]);
@@ -127,20 +149,18 @@ static void worker(pwn_group *g, int i)
 		{
 			pwn_group::job_t &j = g->jobs[(seen + 1) % GROUP_RING];
 			const double t0 = g->prof ? now_ms() : 0.0;
-			if(j.always || !g->broken.load(std::memory_order_acquire))
+			int rc = PWN_OK;
+			if(j.always || !g->broken.load(std::memory_order_acquire)) rc = j.fn(i);
+			j.rc[i] = rc;
+			if(rc != PWN_OK && (j.kind == JOB_STRICT || !refusal(rc))) failed(g, i, rc);
+			// the member that is last through the job: a refusal is the call's answer where every member gave it (JOB_ALL) or member 0
+			// did (JOB_ONE); members that disagree have parted ways
+			if(j.through.fetch_add(1, std::memory_order_acq_rel) + 1 == g->n && j.kind != JOB_STRICT)
 			{
-				const int rc = j.fn(i);
-				if(rc != PWN_OK)
-				{
-					std::lock_guard<std::mutex> lk(g->err_mu);
-					if(g->err_rc == PWN_OK)
-					{
-						g->err_rc = rc; g->err_member = i;
-						snprintf(g->err_text, sizeof(g->err_text), "%.190s", g->m[i]->err[0] ? g->m[i]->err : pwn_strerror(rc));
-					}
-					g->broken.store(true, std::memory_order_release);
-					g->hub.failed.store(1);             // (nobody waits for this member any longer)
-				}
+				int odd = -1;
+				for(int k = 1; k < g->n && j.kind == JOB_ALL && odd < 0; k++) if(j.rc[k] != j.rc[0]) odd = j.rc[k] != PWN_OK ? k : 0;
+				if(odd < 0) j.result = j.rc[0];
+				else if(refusal(j.rc[odd])) failed(g, odd, j.rc[odd]);
 			}
 			if(g->prof) g->p_job[i] += now_ms() - t0;
 			seen++;
@@ -150,7 +170,7 @@ static void worker(pwn_group *g, int i)
 }
 
 // post `fn` for every member -- member i runs fn(i) on its own thread, behind everything posted before -- and go on
-static unsigned long long post(pwn_group *g, std::function<int(int)> fn, bool always = false)
+static unsigned long long post(pwn_group *g, std::function<int(int)> fn, bool always = false, int kind = JOB_STRICT)
 {
 	const unsigned long long id = g->posted.load(std::memory_order_relaxed) + 1;
 	// (the slot's last job, GROUP_RING jobs back, has to be through on every member)
@@ -159,7 +179,8 @@ static unsigned long long post(pwn_group *g, std::function<int(int)> fn, bool al
 			for(unsigned long long spins = 0; g->done[i].load(std::memory_order_acquire) + GROUP_RING < id; spins++)
 				if(spins > 100000) { struct timespec ts = { 0, 20 * 1000 }; nanosleep(&ts, NULL); }
 	g->jobs[id % GROUP_RING].fn = std::move(fn);
-	g->jobs[id % GROUP_RING].always = always;
+	g->jobs[id % GROUP_RING].always = always; g->jobs[id % GROUP_RING].kind = kind;
+	g->jobs[id % GROUP_RING].through.store(0, std::memory_order_relaxed); g->jobs[id % GROUP_RING].result = PWN_OK;
 	g->posted.store(id, std::memory_order_release);
 	if(g->prof) g->p_jobs++;
 	return id;
@@ -182,14 +203,25 @@ static int join(pwn_group *g, unsigned long long id)
 	return PWN_OK;
 }
 
-static int run_all(pwn_group *g, std::function<int(int)> fn, bool always = false) { return join(g, post(g, std::move(fn), always)); }
+// ... a failure of the group, else what the job's members answered: PWN_OK or their refusal (pwn_last_error: member 0's)
+static int run_all(pwn_group *g, std::function<int(int)> fn, bool always = false, int kind = JOB_STRICT)
+{
+	const unsigned long long id = post(g, std::move(fn), always, kind);
+	int rc = join(g, id);
+	if(rc == PWN_OK && (rc = g->jobs[id % GROUP_RING].result) != PWN_OK) snprintf(g->head->err, sizeof(g->head->err), "%s", g->m[0]->err[0] ? g->m[0]->err : pwn_strerror(rc));
+	return rc;
+}
 
-// the group is in order again (the caller has dealt with the failure: the tiling is down)
+// the group is in order again (the caller has dealt with the failure: the tiling is down, no member's thread is inside a job): nothing
+// of the failure stays behind, in the group or at the members' meeting point
 static void mend(pwn_group *g)
 {
 	std::lock_guard<std::mutex> lk(g->err_mu);
 	g->err_rc = PWN_OK; g->err_member = 0; g->err_text[0] = 0;
 	g->broken.store(false, std::memory_order_release);
+	g->hub.failed.store(0);
+	g->hub.bar_count.store(0);
+	for(int i = 0; i < g->n * g->n; i++) { g->hub.boxes[i].posted.store(0); g->hub.boxes[i].copied.store(0); g->hub.boxes[i].consumed.store(0); }
 }
 
 pwn_ctx *pwn_group_member(pwn_ctx *h, int i) { return (h != NULL && h->grp != NULL && i >= 0 && i < h->grp->n) ? h->grp->m[i] : NULL; }
@@ -201,30 +233,42 @@ static void frames_free(pwn_group *g)
 		if(g->h_sbuf[i]) (void)hipHostFree(g->h_sbuf[i]);
 		if(g->h_zbuf[i]) (void)hipHostFree(g->h_zbuf[i]);
 		if(g->h_surface[i]) (void)hipHostFree(g->h_surface[i]);
-		g->h_sbuf[i] = NULL; g->h_zbuf[i] = NULL; g->h_surface[i] = NULL; g->in_flight[i] = g->delivered[i] = false;
+		g->h_sbuf[i] = NULL; g->h_zbuf[i] = NULL; g->h_surface[i] = NULL; g->in_flight[i] = g->delivered[i] = false; g->lost[i] = PWN_OK;
+		g->fdone[i].seq = 0;             // (nothing counts as submitted to slots that are made afresh)
 	}
 	g->nslots = 0; g->flags = 0; g->fifo_n = 0;
 }
 
-// the tiling of the members, in the mode the next frame needs: delivered to the host by every member, or gathered on member 0
+// the tiling of the members, in the mode the next frame needs: delivered to the host by every member, or gathered on member 0.
+// Down: every member is through what was posted, and the group is in order again.  A failure among what was posted, which no call
+// has reported yet (a sphere upload that one member could not make), is what comes back, pwn_last_error set
 static int tiling_down(pwn_group *g)
 {
-	if(g->mode == MODE_NONE) return PWN_OK;
-	(void)run_all(g, [g](int i) { pwn_tiled_shutdown(g->m[i]); return PWN_OK; }, true);
+	const int rc = run_all(g, [g](int i) { pwn_tiled_shutdown(g->m[i]); return PWN_OK; }, true);
 	g->mode = MODE_NONE;
 	g->tiling_surf_scale = g->tiling_surf_pitch = 0;
 	mend(g);
-	g->hub.failed.store(0);
-	g->hub.bar_count.store(0);
-	for(int i = 0; i < g->n * g->n; i++) { g->hub.boxes[i].posted.store(0); g->hub.boxes[i].copied.store(0); g->hub.boxes[i].consumed.store(0); }
-	return PWN_OK;
+	return rc;
+}
+
+// a failure took the frames in flight with it: every such slot's pwn_wait_frame says so, once (a frame that every member had
+// delivered to the host before is the host's)
+static void frames_lost(pwn_group *g, int rc)
+{
+	for(int i = 0; i < PWN_MAX_SLOTS; i++)
+	{
+		if(g->in_flight[i] && g->delivered[i] && g->flags != 0) continue;
+		if(g->in_flight[i]) { g->lost[i] = rc; memcpy(g->lost_text, g->head->err, sizeof(g->lost_text)); }
+		g->in_flight[i] = g->delivered[i] = false;
+	}
+	g->fifo_n = 0;
 }
 
 static int tiling_up(pwn_group *g, int mode)
 {
 	const int sscale = (mode == MODE_SINK && (g->flags & PWN_FRAME_SURFACE)) ? g->surf_scale : 0, spitch = sscale ? g->surf_pitch : 0;
 	if(g->mode == mode && (sscale == 0 || (sscale == g->tiling_surf_scale && spitch == g->tiling_surf_pitch))) return PWN_OK;
-	tiling_down(g);
+	{ const int rc = tiling_down(g); if(rc != PWN_OK) { frames_lost(g, rc); return rc; } }
 	unsigned char id[PWN_TILED_ID_BYTES];
 	memset(id, 0, sizeof(id));
 	if(g->transport == PWN_TRANSPORT_RCCL)
@@ -247,8 +291,7 @@ static int tiling_up(pwn_group *g, int mode)
 	{
 		char keep[256];
 		memcpy(keep, g->head->err, sizeof(keep));
-		g->mode = mode;               // (whatever came up goes down again)
-		tiling_down(g);
+		(void)tiling_down(g);         // (whatever came up goes down again)
 		memcpy(g->head->err, keep, sizeof(keep));
 		// RCCL did not come up between the members (it has never had to, on this pool): the rows can travel as copies between the
 		// members' planes instead -- in one process nothing else is needed.  Once, and said in pwn_group_info.note; a host that
@@ -272,11 +315,27 @@ static int frame_failed(pwn_group *g, int rc)
 {
 	char keep[256];
 	memcpy(keep, g->head->err, sizeof(keep));
-	tiling_down(g);
-	for(int i = 0; i < PWN_MAX_SLOTS; i++) g->in_flight[i] = g->delivered[i] = false;
-	g->fifo_n = 0;
+	(void)tiling_down(g);
 	memcpy(g->head->err, keep, sizeof(keep));
+	frames_lost(g, rc);
 	return rc;
+}
+
+// a call that waits for the members: their refusal comes back as it is; a failure takes the tiling down
+static int call_all(pwn_group *g, std::function<int(int)> fn, int kind, bool always = false)
+{
+	const int rc = run_all(g, std::move(fn), always, kind);
+	return (rc != PWN_OK && g->broken.load(std::memory_order_acquire)) ? frame_failed(g, rc) : rc;
+}
+
+// test hook (tests/test_gpu_group.py, tools/sanitize/group_driver.cpp): PWN_DBG_GROUP_STALL=member:call:milliseconds[:submit] -- that
+// member's thread is late to that blocking call (with the fourth field: to that pwn_submit_frame) by so long (a device that stops
+// answering): the others must come back with PWN_ETIMEDOUT at the deadline
+static void stall(pwn_group *g, int i, unsigned long long call, bool submit)
+{
+	if(g->stall_member != i || g->stall_call != call || g->stall_submit != submit) return;
+	struct timespec ts = { g->stall_ms / 1000, (long)(g->stall_ms % 1000) * 1000000L };
+	nanosleep(&ts, NULL);
 }
 
 extern "C" int pwn_init_multi(pwn_ctx **out, const int *devices, int ndev, int width, int height)
@@ -289,12 +348,17 @@ extern "C" int pwn_init_multi(pwn_ctx **out, const int *devices, int ndev, int w
 	if(g == NULL || h == NULL) { delete g; delete h; return PWN_ENOMEM; }
 	g->n = ndev; g->head = h; g->mode = MODE_NONE; g->posted.store(0); g->quit.store(false); g->broken.store(false);
 	g->err_rc = PWN_OK; g->err_member = 0; g->err_text[0] = 0;
-	g->calls = 0; g->stall_member = -1; g->stall_ms = 0; g->stall_call = 0;
-	if(const char *e = getenv("PWN_DBG_GROUP_STALL")) { int a = -1, c = 0; unsigned long long b = 0; if(sscanf(e, "%d:%llu:%d", &a, &b, &c) == 3) { g->stall_member = a; g->stall_call = b; g->stall_ms = c; } }
+	g->calls = g->submits = 0; g->stall_member = -1; g->stall_ms = 0; g->stall_call = 0; g->stall_submit = false;
+	if(const char *e = getenv("PWN_DBG_GROUP_STALL"))
+	{
+		int a = -1, c = 0; unsigned long long b = 0; char what[8] = "";
+		if(sscanf(e, "%d:%llu:%d:%7s", &a, &b, &c, what) >= 3) { g->stall_member = a; g->stall_call = b; g->stall_ms = c; g->stall_submit = strcmp(what, "submit") == 0; }
+	}
 	g->prof = getenv("PWN_DBG_GROUP_PROF") != NULL; g->p_join = 0.0; g->p_jobs = g->p_joins = 0;
 	for(int i = 0; i < MAXM; i++) { g->p_job[i] = 0.0; g->done[i].store(0); }
 	g->init_ms = g->wait_ms = 0; g->nslots = 0; g->flags = 0; g->fifo_n = 0; g->frame_seq = 0; g->last_sbuf = NULL;
-	for(int i = 0; i < PWN_MAX_SLOTS; i++) { g->h_sbuf[i] = NULL; g->h_zbuf[i] = NULL; g->h_surface[i] = NULL; g->in_flight[i] = g->delivered[i] = false; }
+	for(int i = 0; i < PWN_MAX_SLOTS; i++) { g->h_sbuf[i] = NULL; g->h_zbuf[i] = NULL; g->h_surface[i] = NULL; g->in_flight[i] = g->delivered[i] = false; g->lost[i] = PWN_OK; }
+	g->lost_text[0] = 0;
 	g->surf_scale = g->surf_pitch = g->tiling_surf_scale = g->tiling_surf_pitch = 0;
 	for(int i = 0; i < MAXM; i++) { g->m[i] = NULL; g->devices[i] = -1; g->hub.member[i] = NULL; }
 	g->hub.world = ndev; g->hub.failed.store(0); g->hub.bar_count.store(0); g->hub.bar_gen.store(0); g->hub.boxes = NULL;
@@ -356,8 +420,7 @@ extern "C" int pwn_init_multi(pwn_ctx **out, const int *devices, int ndev, int w
 void pwn_group_destroy(pwn_ctx *h)
 {
 	pwn_group *g = h->grp;
-	tiling_down(g);
-	(void)join(g, g->posted.load());
+	(void)tiling_down(g);
 	g->quit.store(true);
 	for(int i = 0; i < g->n; i++) if(g->th[i].joinable()) g->th[i].join();
 	frames_free(g);
@@ -397,13 +460,23 @@ extern "C" int pwn_group_info_get(pwn_ctx *h, pwn_group_info *out)
 int pwn_group_set_option(pwn_ctx *h, int option, int value)
 {
 	pwn_group *g = h->grp;
-	for(int i = 0; i < PWN_MAX_SLOTS; i++) if(g->in_flight[i]) return PWN_EBUSY;
-	// (what a tiling fixes when it is set up: it goes down and comes up again with the next frame)
+	// what a tiling fixes when it is set up: it goes down and comes up again with the next frame -- once the option is one the members
+	// will take (pwn_set_option's own rules for these five, and a group's: no second blur pass, none of them with frames in flight)
 	if(option == PWN_OPT_BLUR_PASSES || option == PWN_OPT_FRAME_OVERLAP || option == PWN_OPT_TILED_CHOREO || option == PWN_OPT_TILED_COMMS ||
-	   option == PWN_OPT_TILED_STREAMS) tiling_down(g);
-	if(option == PWN_OPT_BLUR_PASSES && value > 1) { snprintf(h->err, sizeof(h->err), "a group renders with POSTPROC_BLUR 0 or 1"); return PWN_EINVAL; }
-	const int rc = run_all(g, [g, option, value](int i) { return pwn_set_option(g->m[i], option, value); }, true);
-	if(rc != PWN_OK) { mend(g); return rc; }        // (a refused option is no failure of the group)
+	   option == PWN_OPT_TILED_STREAMS)
+	{
+		if(option == PWN_OPT_BLUR_PASSES && (value < 0 || value > 16)) return PWN_EINVAL;
+		if(option == PWN_OPT_TILED_CHOREO && value != PWN_TILED_CHOREO_INSTREAM && value != PWN_TILED_CHOREO_SPLIT) return PWN_EINVAL;
+		if(option == PWN_OPT_TILED_COMMS && value != PWN_TILED_COMMS_ONE && value != PWN_TILED_COMMS_PER_STREAM) return PWN_EINVAL;
+		if(option == PWN_OPT_TILED_STREAMS && value != 2 && value != 3) return PWN_EINVAL;
+		if(option == PWN_OPT_BLUR_PASSES && value > 1) { snprintf(h->err, sizeof(h->err), "a group renders with POSTPROC_BLUR 0 or 1"); return PWN_EINVAL; }
+		for(int i = 0; i < PWN_MAX_SLOTS; i++) if(g->in_flight[i]) return PWN_EBUSY;
+		const int rc = tiling_down(g);
+		if(rc != PWN_OK) return rc;
+	}
+	// (every other option: the members take or refuse it as one context does, the tiling left alone)
+	const int rc = call_all(g, [g, option, value](int i) { return pwn_set_option(g->m[i], option, value); }, JOB_ALL, true);
+	if(rc != PWN_OK) return rc;
 	if(option == PWN_OPT_BLUR_PASSES) h->blur_passes = value;
 	return PWN_OK;
 }
@@ -417,7 +490,7 @@ int pwn_group_level_mem(pwn_ctx *h, const char *text, int len)
 int pwn_group_upload_level(pwn_ctx *h, const uint8_t *data, const pwn_portal *pmap)
 {
 	pwn_group *g = h->grp;
-	return run_all(g, [g, data, pmap](int i) { return pwn_upload_level(g->m[i], data, pmap); });
+	return call_all(g, [g, data, pmap](int i) { return pwn_upload_level(g->m[i], data, pmap); }, JOB_ALL);
 }
 
 // level_prepare_render (level.h:64-81) for every device: the handle's ONE object table (member 0's, touched by the caller's thread
@@ -458,22 +531,16 @@ int pwn_group_sync(pwn_ctx *h) { return join(h->grp, h->grp->posted.load()); }
 int pwn_group_on_member0(pwn_ctx *h, const std::function<int(pwn_ctx *)> &fn)
 {
 	pwn_group *g = h->grp;
-	const int rc = run_all(g, [g, &fn](int i) { return i == 0 ? fn(g->m[0]) : PWN_OK; }, true);
-	if(rc != PWN_OK && !g->broken.load()) snprintf(h->err, sizeof(h->err), "%s", g->m[0]->err);
-	return rc;
+	return call_all(g, [g, &fn](int i) { return i == 0 ? fn(g->m[0]) : PWN_OK; }, JOB_ONE, true);
 }
 
 int pwn_group_host_register(pwn_ctx *h, void *base, size_t bytes)
 {
-	const int rc = pwn_group_on_member0(h, [base, bytes](pwn_ctx *m0) { return pwn_host_register(m0, base, bytes); });
-	if(rc != PWN_OK) mend(h->grp);
-	return rc;
+	return pwn_group_on_member0(h, [base, bytes](pwn_ctx *m0) { return pwn_host_register(m0, base, bytes); });
 }
 int pwn_group_host_unregister(pwn_ctx *h, void *base)
 {
-	const int rc = pwn_group_on_member0(h, [base](pwn_ctx *m0) { return pwn_host_unregister(m0, base); });
-	if(rc != PWN_OK) mend(h->grp);
-	return rc;
+	return pwn_group_on_member0(h, [base](pwn_ctx *m0) { return pwn_host_unregister(m0, base); });
 }
 
 int pwn_group_set_timeouts(pwn_ctx *h, int init_ms, int wait_ms)
@@ -481,7 +548,7 @@ int pwn_group_set_timeouts(pwn_ctx *h, int init_ms, int wait_ms)
 	pwn_group *g = h->grp;
 	if(init_ms != 0) g->init_ms = init_ms > 0 ? init_ms : 0;
 	if(wait_ms != 0) g->wait_ms = wait_ms > 0 ? wait_ms : 0;
-	(void)run_all(g, [g, init_ms, wait_ms](int i) { return pwn_tiled_set_timeouts(g->m[i], init_ms, wait_ms); }, true);
+	(void)run_all(g, [g, init_ms, wait_ms](int i) { return pwn_tiled_set_timeouts(g->m[i], init_ms, wait_ms); }, true, JOB_ALL);
 	return PWN_OK;
 }
 
@@ -507,6 +574,7 @@ int pwn_group_trace_screen_centred(pwn_ctx *h, const float cam[16], float sec, u
 	if(cam == NULL || sbuf == NULL) return PWN_EINVAL;
 	if(h->blur_passes > 0 && (h->w & 3) != 0) return PWN_EINVAL;
 	for(int i = 0; i < PWN_MAX_SLOTS; i++) if(g->in_flight[i]) { snprintf(h->err, sizeof(h->err), "a group's blocking call needs its frames in flight waited for first"); return PWN_EBUSY; }
+	if(!g->m[0]->have_level) return PWN_ENOLEVEL;          // (the level calls wait for the members: member 0's answer is every member's)
 	const double t0 = now_ms();
 	int rc = tiling_up(g, MODE_SINK);
 	if(rc != PWN_OK) return rc;
@@ -515,9 +583,7 @@ int pwn_group_trace_screen_centred(pwn_ctx *h, const float cam[16], float sec, u
 	const unsigned long long call = ++g->calls;
 	rc = run_all(g, [g, cm, sec, sbuf, zbuf, call](int i)
 	{
-		// test hook (tests/test_gpu_group.py): PWN_DBG_GROUP_STALL=member:call:milliseconds -- that member's thread is late to that
-		// blocking call by so long (a device that stops answering): the others must come back with PWN_ETIMEDOUT at the deadline
-		if(g->stall_member == i && g->stall_call == call) { struct timespec ts = { g->stall_ms / 1000, (long)(g->stall_ms % 1000) * 1000000L }; nanosleep(&ts, NULL); }
+		stall(g, i, call, false);
 		// (depth plane PWN_MAX_SLOTS: the blocking calls' own -- every call's depth lives in the same plane, so that a pixel whose
 		// primary ray runs out of steps keeps the previous call's value, trace.h:677, as the context's plane does on one device)
 		int r = pwn_i_tiled_submit(g->m[i], cm.data(), sec, sbuf, zbuf, PWN_MAX_SLOTS, NULL);
@@ -570,6 +636,7 @@ int pwn_group_submit_frame(pwn_ctx *h, const float cam[16], float sec, int slot)
 	if(cam == NULL || slot < 0 || slot >= g->nslots) return PWN_EINVAL;
 	if(h->blur_passes > 0 && (h->w & 3) != 0) return PWN_EINVAL;
 	if(g->in_flight[slot]) return PWN_EBUSY;
+	if(!g->m[0]->have_level) return PWN_ENOLEVEL;
 	const bool sink = g->flags != 0;
 	int rc = tiling_up(g, sink ? MODE_SINK : MODE_RESIDENT);
 	if(rc != PWN_OK) return rc;
@@ -580,8 +647,9 @@ int pwn_group_submit_frame(pwn_ctx *h, const float cam[16], float sec, int slot)
 	std::array<float, 16> cm;
 	memcpy(cm.data(), cam, sizeof(float) * 16);
 	// (depth plane `slot`: a frame slot's depth carries from the slot's previous frame, as a one-device context's slot planes do)
-	(void)post(g, [g, cm, sec, hs, hz, slot, hsurf](int i) { return pwn_i_tiled_submit(g->m[i], cm.data(), sec, hs, hz, slot, hsurf); });
-	g->in_flight[slot] = true; g->delivered[slot] = false; g->sec[slot] = sec;
+	const unsigned long long call = ++g->submits;
+	(void)post(g, [g, cm, sec, hs, hz, slot, hsurf, call](int i) { stall(g, i, call, true); return pwn_i_tiled_submit(g->m[i], cm.data(), sec, hs, hz, slot, hsurf); });
+	g->in_flight[slot] = true; g->delivered[slot] = false; g->sec[slot] = sec; g->lost[slot] = PWN_OK;
 	g->fifo[g->fifo_n++] = slot;
 	memset(&g->fdone[slot], 0, sizeof(pwn_frame));
 	g->fdone[slot].seq = ++g->frame_seq;
@@ -613,9 +681,14 @@ int pwn_group_wait_frame(pwn_ctx *h, int slot, pwn_frame *out)
 	pwn_group *g = h->grp;
 	if(slot < 0 || slot >= g->nslots || g->fdone[slot].seq == 0) return PWN_EINVAL;
 	while(g->in_flight[slot] && !g->delivered[slot])
+		if(deliver_oldest(g) != PWN_OK) break;            // (the slot's frame is lost with the others in flight)
+	// a failure took the slot's frame: its code, once -- nothing is written, and the slot is as if never submitted
+	if(g->lost[slot] != PWN_OK)
 	{
-		const int rc = deliver_oldest(g);
-		if(rc != PWN_OK) return rc;
+		const int rc = g->lost[slot];
+		g->lost[slot] = PWN_OK; g->fdone[slot].seq = 0;
+		memcpy(h->err, g->lost_text, sizeof(g->lost_text));
+		return rc;
 	}
 	g->in_flight[slot] = false;
 	if(out != NULL) *out = g->fdone[slot];
@@ -626,6 +699,7 @@ int pwn_group_frame_ready(pwn_ctx *h, int slot)
 {
 	pwn_group *g = h->grp;
 	if(slot < 0 || slot >= g->nslots) return PWN_EINVAL;
+	if(g->lost[slot] != PWN_OK) { memcpy(h->err, g->lost_text, sizeof(g->lost_text)); return g->lost[slot]; }
 	if(!g->in_flight[slot] || g->delivered[slot]) return 1;
 	// every member's share of the slot's frame -- the k-th oldest in flight -- is through on its device (a job on the members'
 	// threads, behind the submissions that were posted: it waits for those to be ENQUEUED, not for the GPUs)

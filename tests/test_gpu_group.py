@@ -339,3 +339,171 @@ def test_two_devices_over_rccl(oracle_lib, cases):
         assert oracle_lib.fnv64(r.read_plane(r.wait_frame(i)["d_sbuf"])) == c["post"]
     r.frames_config(0)
     r.close()
+
+
+# ---- a refused call leaves a group as it was; a real failure is every lost slot's (include/pwnhip.h, pwn_init_multi: errors) ----
+def _info(r):
+    gi = r.group_info()
+    return {k: gi[k] for k in ("transport", "note", "cuts", "halo_rows", "host_sink", "frames")}
+
+
+def _refusals(r, cam, c):
+    """(name, the call, the code one device gives) -- the scripted list of tools/sanitize/group_driver.cpp's `refusals` as far as
+    Python reaches it; raw calls where the wrapper would check first"""
+    from pwnfps_amd import _lib
+    from pwnfps_amd.render import lib
+    data, pmap, _ = r.get_level()
+    bad_pmap = pmap.copy()
+    bad_pmap[7, :] = 0x7f7f7f7f
+    many = np.zeros(_lib.PWN_OBJ_MAX + 1, load_spheres(c["spheres"]).dtype)
+    one_cell = np.zeros(4097, many.dtype)                   # one cell's list beyond PWN_LIST_MAX
+    one_cell["r"], one_cell["x"], one_cell["y"], one_cell["z"] = 0.1, 2.5, 0.4, 2.5
+    sb = np.zeros((c["h"], c["w"]), np.uint32)
+    px = np.zeros((c["h"] * 2, c["w"] * 2), np.uint32)
+    w4 = np.zeros(4, np.uint32)
+    chk = r._chk
+    return [
+        ("upload_level, bad portal map", lambda: r.upload_level(data, bad_pmap), _lib.PWN_EINVAL),
+        ("level_load_mem(NULL)", lambda: chk(lib.pwn_level_load_mem(r._ctx, None, 10), "pwn_level_load_mem"), _lib.PWN_EINVAL),
+        ("level_load, missing path", lambda: r.level_load("/nonexistent/level.txt"), _lib.PWN_EIO),
+        ("set_objects, PWN_OBJ_MAX + 1", lambda: r.set_objects(many), _lib.PWN_EINVAL),
+        ("set_objects, tables too big", lambda: r.set_objects(one_cell), _lib.PWN_ETOOBIG),
+        ("screen_upscale, scale 0", lambda: chk(lib.pwn_screen_upscale(r._ctx, sb.ctypes.data, 0, c["w"] * 8, px.ctypes.data), "pwn_screen_upscale"), _lib.PWN_EINVAL),
+        ("screen_upscale, small pitch", lambda: r.screen_upscale(sb, 2, c["w"] * 8 - 4, px), _lib.PWN_EINVAL),
+        ("probe, unknown op", lambda: r.probe(9999, w4), _lib.PWN_EINVAL),
+        ("read_plane(NULL)", lambda: chk(lib.pwn_read_plane(r._ctx, None, px.ctypes.data, 64), "pwn_read_plane"), _lib.PWN_EINVAL),
+        ("set_option, unknown", lambda: chk(lib.pwn_set_option(r._ctx, 9999, 1), "pwn_set_option"), _lib.PWN_EINVAL),
+        ("set_option, BLUR_PASSES 2", lambda: r.set_blur_passes(2), _lib.PWN_EINVAL),
+        ("host_register(NULL)", lambda: chk(lib.pwn_host_register(r._ctx, None, 4096), "pwn_host_register"), _lib.PWN_EINVAL),
+        ("frames_config, bad flags", lambda: chk(lib.pwn_frames_config(r._ctx, 3, 64, 1, 0), "pwn_frames_config"), _lib.PWN_EINVAL),
+        ("submit_frame, bad slot", lambda: r.submit_frame(cam, c["sec"], _lib.PWN_MAX_SLOTS), _lib.PWN_EINVAL),
+        ("wait_frame, never submitted", lambda: r.wait_frame(0), _lib.PWN_EINVAL),
+        ("trace_screen_centred(NULL cam)", lambda: chk(lib.pwn_trace_screen_centred(r._ctx, None, 0.5, sb.ctypes.data, None), "pwn_trace_screen_centred"), _lib.PWN_EINVAL),
+        ("tiled_submit", lambda: r.tiled_submit(cam, 0.0), _lib.PWN_ENOTSUP),
+    ]
+
+
+@pytest.mark.parametrize("members", [2, 3])
+def test_a_refused_call_leaves_the_group_as_it_was(oracle_lib, cases, members):
+    """every refusal gives the code one device gives, the next blocking call the golden frame and depth, and the group's info is what it was"""
+    import pwnfps_amd
+    c = _case(cases, "level_spawn_320x240")
+    r = _group(c["w"], c["h"], members)
+    cam = _load(r, c)
+    sb, zb = r.trace_screen_centred(cam, c["sec"])
+    assert oracle_lib.fnv64(sb) == c["post"] and oracle_lib.fnv64(zb) == c["z"]
+    frames = 1
+    for name, call, code in _refusals(r, cam, c):
+        before = _info(r)
+        with pytest.raises(pwnfps_amd.PwnError) as e:
+            call()
+        assert e.value.code == code, (name, str(e.value))
+        assert _info(r) == before, name
+        sb, zb = r.trace_screen_centred(cam, c["sec"])
+        frames += 1
+        assert oracle_lib.fnv64(sb) == c["post"] and oracle_lib.fnv64(zb) == c["z"], name
+        assert r.group_info()["frames"] == frames, name              # (the tiling stayed in force: it counts on)
+    r.close()
+
+
+@pytest.mark.parametrize("members", [2, 3])
+def test_a_refusal_before_the_first_frame_and_a_refused_level_then_the_good_one(oracle_lib, cases, members):
+    import pwnfps_amd
+    from pwnfps_amd import _lib
+    c = _case(cases, "level_spawn_320x240")
+    r = _group(c["w"], c["h"], members)
+    cam = np.array(c["cam"], np.float32)
+    with pytest.raises(pwnfps_amd.PwnError) as e:
+        r.trace_screen_centred(cam, c["sec"])
+    assert e.value.code == _lib.PWN_ENOLEVEL
+    with pytest.raises(pwnfps_amd.PwnError) as e:
+        r.screen_upscale(None, 2)                       # (no frame was delivered yet: a group's own refusal)
+    assert e.value.code == _lib.PWN_EINVAL
+    r.level_load(level_path(c["level"]))
+    data, pmap, _ = r.get_level()
+    bad = pmap.copy()
+    bad[7, :] = 0x7f7f7f7f
+    with pytest.raises(pwnfps_amd.PwnError) as e:
+        r.upload_level(data, bad)
+    assert e.value.code == _lib.PWN_EINVAL
+    r.upload_level(data, pmap)                          # the same call with the good portal map
+    with open(level_path(c["level"]), "rb") as f:
+        r.level_load_text(f.read())                     # ... and the host's fallback level (level.h:110-115)
+    r.set_objects(load_spheres(c["spheres"]))
+    with pytest.raises(pwnfps_amd.PwnError):
+        r.probe(9999, np.zeros(4, np.uint32))
+    sb, zb = r.trace_screen_centred(cam, c["sec"])      # the first frame of the handle, behind three refusals
+    assert oracle_lib.fnv64(sb) == c["post"] and oracle_lib.fnv64(zb) == c["z"]
+    r.close()
+
+
+@pytest.mark.parametrize("members", [2, 3])
+def test_a_refusal_between_submits_loses_no_frame(oracle_lib, cases, members):
+    import pwnfps_amd
+    from pwnfps_amd import _lib
+    c = _case(cases, "level_spawn_320x240")
+    r = _group(c["w"], c["h"], members)
+    cam = _load(r, c)
+    r.frames_config(3, sbuf=True, zbuf=True)
+    r.submit_frame(cam, c["sec"], 0)
+    with pytest.raises(pwnfps_amd.PwnError) as e:
+        r.probe(9999, np.zeros(4, np.uint32))
+    assert e.value.code == _lib.PWN_EINVAL
+    r.submit_frame(cam, c["sec"], 1)
+    with pytest.raises(pwnfps_amd.PwnError) as e:
+        r.submit_frame(cam, c["sec"], 1)                # busy
+    assert e.value.code == _lib.PWN_EBUSY
+    with pytest.raises(pwnfps_amd.PwnError) as e:
+        r.trace_screen_centred(cam, c["sec"])           # a group's own rule: frames in flight first
+    assert e.value.code == _lib.PWN_EBUSY
+    r.submit_frame(cam, c["sec"], 2)
+    for slot in (1, 0, 2):
+        assert pwnfps_amd.render.lib.pwn_frame_ready(r._ctx, slot) >= 0, slot
+    for slot in range(3):
+        f = r.wait_frame(slot)
+        assert f["seq"] == slot + 1
+        assert oracle_lib.fnv64(f["sbuf"]) == c["post"] and oracle_lib.fnv64(f["zbuf"]) == c["z"], slot
+    r.frames_config(0)
+    r.close()
+
+
+def test_a_member_late_to_a_submit_loses_the_frames_in_flight_and_says_so(oracle_lib, cases, monkeypatch):
+    """the late member of test_a_member_that_stops_answering_is_an_error_not_a_hang, late to a pwn_submit_frame: every slot whose frame
+    was lost says so at its wait, once, naming a member -- never PWN_OK with nothing rendered -- and three fresh frames are golden"""
+    import time
+    import pwnfps_amd
+    from pwnfps_amd import _lib
+    from pwnfps_amd.render import lib
+    monkeypatch.setenv("PWN_DBG_GROUP_STALL", "2:2:2500:submit")   # member 2 is 2.5 s late to the second submit
+    c = _case(cases, "level_spawn_320x240")
+    r = _group(c["w"], c["h"], 3)
+    cam = _load(r, c)
+    r.tiled_set_timeouts(20.0, 0.5)
+    r.frames_config(3, sbuf=True, zbuf=True)
+    for slot in range(3):
+        r.submit_frame(cam, c["sec"], slot)
+    t0 = time.perf_counter()
+    lost = 0
+    for slot in range(3):
+        try:
+            f = r.wait_frame(slot)
+        except pwnfps_amd.PwnError as e:
+            lost += 1
+            assert e.code in (_lib.PWN_ETIMEDOUT, _lib.PWN_EHIP) and "member" in str(e), str(e)
+            for behind in range(slot + 1, 3):
+                assert lib.pwn_frame_ready(r._ctx, behind) < 0, behind
+            with pytest.raises(pwnfps_amd.PwnError) as again:
+                r.wait_frame(slot)
+            assert again.value.code == _lib.PWN_EINVAL
+        else:
+            assert oracle_lib.fnv64(f["sbuf"]) == c["post"], slot      # (a frame that is delivered is the frame)
+    dt = time.perf_counter() - t0
+    assert lost == 3, lost                      # (the first frame's wait is queued behind the submit the late member holds up)
+    assert dt < 4.0, dt
+    for slot in range(3):
+        r.submit_frame(cam, c["sec"], slot)
+    for slot in range(3):
+        f = r.wait_frame(slot)
+        assert oracle_lib.fnv64(f["sbuf"]) == c["post"] and oracle_lib.fnv64(f["zbuf"]) == c["z"], slot
+    r.frames_config(0)
+    r.close()

@@ -2,8 +2,10 @@
 against a stand-in HIP runtime and stand-in kernels (tools/sanitize/), run under ThreadSanitizer and AddressSanitizer + UBSan.
 Every frame of 2..5 members -- blocking calls, frames in flight delivered and resident, moving cuts, a deep band that leaves the
 halo (repeat with whole strips), depth that carries over -- must equal the frame of one context; a member that is late past the
-deadline comes back as PWN_ETIMEDOUT and the handle recovers; processes over the shared-memory transport.  No GPU needed: the
-N > 1 host paths run in the CPU suite."""
+deadline comes back as PWN_ETIMEDOUT and the handle recovers; processes over the shared-memory transport; a call that one
+context refuses is refused by a group with the same code and leaves it as it was (`refusals`: the same scripts on one context
+and on groups, transcripts equal); a real failure with frames in flight is reported once per lost slot and mended (`lost`).
+No GPU needed: the N > 1 host paths run in the CPU suite."""
 import os
 import subprocess
 
@@ -17,7 +19,7 @@ def _build(target, out):
     assert p.returncode == 0, p.stderr[-3000:]
 
 
-@pytest.mark.parametrize("target,modes", [("tsan", ("group", "late", "shm")), ("asan", ("all",))])
+@pytest.mark.parametrize("target,modes", [("tsan", ("group", "late", "shm", "refusals", "lost")), ("asan", ("all",))])
 def test_host_logic_under_sanitizers(target, modes, tmp_path):
     out_dir = str(tmp_path)
     _build(target, out_dir)
@@ -29,6 +31,10 @@ def test_host_logic_under_sanitizers(target, modes, tmp_path):
         assert "Sanitizer" not in out, out[-4000:]
         if m in ("late", "all"):
             assert "one call failed at the deadline" in out
+        if m in ("refusals", "all"):
+            assert "a group's info unchanged over every refused call" in out
+        if m in ("lost", "all"):
+            assert "every lost slot's wait failed once, naming a member" in out and out.count("reported once, naming the member") == 3 and "refused by one member only is a failure naming it" in out
 
 
 def test_host_calls_transcript(tmp_path):

@@ -17,7 +17,8 @@ static int g_devices = 8;
 // and every event look unfinished to hipEventQuery (fakehip_query_busy).
 extern "C" { void (*fakehip_call_hook)(const char *name, const void *a, const void *b, size_t bytes) = NULL; long fakehip_alloc_fail_in = 0; int fakehip_query_busy = 0; }
 #define HOOK(name, a, b, n) do { if(fakehip_call_hook != NULL) fakehip_call_hook(name, a, b, n); } while(0)
-static bool alloc_fails(void) { return fakehip_alloc_fail_in > 0 && --fakehip_alloc_fail_in == 0; }
+// (a group's members allocate on threads of their own, group_driver.cpp's `lost` mode: the count goes down atomically)
+static bool alloc_fails(void) { return __atomic_load_n(&fakehip_alloc_fail_in, __ATOMIC_RELAXED) > 0 && __atomic_sub_fetch(&fakehip_alloc_fail_in, 1, __ATOMIC_ACQ_REL) == 0; }
 
 static double now_ms(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; }
 
