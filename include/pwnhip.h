@@ -521,6 +521,46 @@ int pwn_trace_viewports(pwn_ctx *ctx, int n, const pwn_viewport *vp, const float
    Tracing them reproduces that frame's pre-blur colour and depth at those pixels.  PWN_EINVAL: cam NULL, xy or rays NULL with
    n > 0, n < 0, n > PWN_RAYS_MAX, a pixel outside the frame, width or height outside pwn_init's 1..32768. */
 int pwn_pixel_rays(int width, int height, const float cam[16], int n, const int32_t *xy, float *rays, uint32_t *seeds);
+/*
+ * pwn_pixel_rays on the device: the ray records and seeds of m pixels of each of n cameras that are already in device memory, written
+ * to device memory on the caller's stream -- so that step -> aim -> pwn_trace_hits_device (which object does every player's
+ * crosshair rest on), picking under a cursor, or a sparse or foveated subset of a view's pixels need no host round trip.
+ *   what            for camera i and its pixel j the record and the seed that pwn_pixel_rays(width, height, cam_i, ...) writes for that pixel.
+ *   rays            ray i * m + j is camera i's pixel j.  A record is 8 floats, origin then direction, as pwn_trace_rays takes them.
+ *   width, height   1..32768: the frame the pixels belong to, which need not be the context's.
+ *   d_cams          n x 16 floats, rows x, y, z, w: the array pwn_players_step_device steps and pwn_trace_views_device reads.
+ *   d_xy            int32 pairs (x, y): m of them with PWN_PIXELS_SHARED, which every camera then uses; otherwise n x m, camera-major.
+ *                   May be NULL with PWN_PIXELS_SHARED and m == width * height: the pixels are then the whole frame, row-major
+ *                   (x = j % width, y = j / width).
+ *   d_work          n x PWN_PIXEL_WORK_BYTES of the caller's scratch (as pwn_trace_views_device's d_work: the call owns no buffer,
+ *                   allocates nothing and never synchronises).  What it holds afterwards is unspecified.
+ *   d_rays          n x m records of 32 B.
+ *   d_seeds         n x m uint32, or NULL: none is written.
+ *   alignment       d_cams, d_work and d_rays 16 bytes, d_xy 8 bytes, d_seeds 4 bytes.
+ *   exactness       record and seed are bit-identical to pwn_pixel_rays' for every finite camera, cameras with denormal entries and
+ *                   with w components included: the camera set-up runs with denormals kept and the add chain flushed, as on the host.
+ *                   The origin is the camera's row w bit for bit (a copy, not arithmetic).  All four lanes of the direction are
+ *                   written (there is no HAS_W flag here: the caller tells the trace call about w lanes).  Through pwn_pixel_rays'
+ *                   own contract the rays reproduce a frame's pre-blur colour and depth.
+ *   outside the frame   the device cannot refuse a pixel.  The record is the formula's value for that (x, y) -- the ray through that
+ *                   point of the image plane -- and the seed the uint32 formula's, defined for -32768 <= x, y < 65536; beyond
+ *                   that the values are unspecified.  Whatever d_xy holds, the call reads and writes nothing outside its ranges,
+ *                   and the add chain is (x & 31) + 1 long, never more.
+ *   ordering        at most two launches on `stream` (a hipStream_t, NULL = default stream): no synchronisation, no events, no wait
+ *                   for table uploads.  It uses no work-queue counters and does not enter the launch rotation: the rule for trace
+ *                   launches at the top of this file does not apply to it.
+ *   no level        it reads no tables: PWN_OK before a level is loaded.
+ *   left alone      everything pwn_players_step leaves alone, pwn_stats and pwn_launch_order_waits included.
+ *   errors          PWN_EINVAL for a NULL ctx, width or height out of range, n < 0, n > PWN_PLAYERS_MAX, m < 0, n x m > PWN_RAYS_MAX
+ *                   (in 64 bits), flags other than PWN_PIXELS_SHARED, a NULL d_cams, d_work or d_rays with n x m > 0, a NULL d_xy
+ *                   outside the whole-frame case, a misaligned pointer, any two of the five ranges overlapping; PWN_ENOTSUP on a
+ *                   pwn_init_multi handle; PWN_EBUSY while the context runs a row tiling (pwn_tiled_init).
+ *                   n x m == 0 is PWN_OK once the checks pass.  A refused or empty call launches nothing.
+ */
+#define PWN_PIXELS_SHARED   1    /* flags: d_xy holds m pixels that every camera uses; without it n x m, camera-major */
+#define PWN_PIXEL_WORK_BYTES 80  /* bytes of d_work per camera (= a view record) */
+int pwn_pixel_rays_device(pwn_ctx *ctx, int width, int height, int n, const void *d_cams,
+	int m, const void *d_xy, int flags, void *d_work, void *d_rays, void *d_seeds, void *stream);
 /* Blocking, host memory.  seeds NULL: every seed 0.  col or depth may be NULL (not both); depth NULL: every ray starts at 0. */
 int pwn_trace_rays(pwn_ctx *ctx, int n, const float *rays, const uint32_t *seeds, float sec_current,
 	uint32_t *col, float *depth);

@@ -7,4 +7,5 @@ from .render import (Renderer, PwnError, SPHERE_DTYPE, PORTAL_DTYPE, HIT_DTYPE, 
                      mat4_iden, mat4_roty, mat4_rotx, spawn_camera, pixel_rays, unit_order_xy, sphere_tables_plan, sphere_bounds_plan,
                      viewports_plan, pack_labels, unpack_labels, players_spawn)
 from ._lib import (PWN_MOVE_TURN_LEFT, PWN_MOVE_TURN_RIGHT, PWN_MOVE_TURN_UP, PWN_MOVE_TURN_DOWN,  # noqa: F401
-                   PWN_MOVE_FORWARD, PWN_MOVE_BACK, PWN_MOVE_LEFT, PWN_MOVE_RIGHT, PWN_PLAYERS_MAX, PWN_TICKS_MAX)
+                   PWN_MOVE_FORWARD, PWN_MOVE_BACK, PWN_MOVE_LEFT, PWN_MOVE_RIGHT, PWN_PLAYERS_MAX, PWN_TICKS_MAX,
+                   PWN_PIXELS_SHARED, PWN_PIXEL_WORK_BYTES)

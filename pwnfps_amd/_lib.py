@@ -32,6 +32,8 @@ PWN_RAYS_MAX = 1 << 28
 PWN_HIT_NONE, PWN_HIT_WALL, PWN_HIT_SPHERE = 0, 1, 2
 PWN_PLAYERS_MAX = 1 << 20
 PWN_TICKS_MAX = 1024
+PWN_PIXELS_SHARED = 1
+PWN_PIXEL_WORK_BYTES = 80
 # one key byte per player of pwn_players_step: bit i is field i of pwn_keys (host/player.h)
 (PWN_MOVE_TURN_LEFT, PWN_MOVE_TURN_RIGHT, PWN_MOVE_TURN_UP, PWN_MOVE_TURN_DOWN,
  PWN_MOVE_FORWARD, PWN_MOVE_BACK, PWN_MOVE_LEFT, PWN_MOVE_RIGHT) = (1 << i for i in range(8))
@@ -133,6 +135,7 @@ ABI = [
     ("pwn_viewports_plan", _i, [_i, _i, _i, _i, _vp, _vp]),
     ("pwn_trace_viewports", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     ("pwn_pixel_rays", _i, [_i, _i, _vp, _i, _vp, _vp, _vp]),
+    ("pwn_pixel_rays_device", _i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     ("pwn_trace_rays", _i, [_vp, _i, _vp, _vp, _f, _vp, _vp]),
     ("pwn_trace_rays_device", _i, [_vp, _i, _vp, _vp, _f, _i, _vp, _vp, _vp]),
     ("pwn_trace_hits", _i, [_vp, _i, _vp, _vp]),

@@ -5,6 +5,7 @@
 //   pwn_launch.cpp  the trace and blur launchers (the launch geometry itself: launch_plan.h), the unit order, the *_rows_device calls
 //   pwn_calls.cpp   the blocking call and its strips, host registration, the batches of views, viewports, rays and hits
 //   pwn_players.cpp the players' step: a batch of cameras walked through the level (host and device form)
+//   pwn_pixel_rays.cpp  pixel rays from cameras on the device (pwn_pixel_rays_device)
 //   pwn_frames.cpp  frames in flight
 //   pwn_tiled.cpp   row tiling over RCCL
 //   pwn_group.cpp   several contexts behind one handle
@@ -108,6 +109,11 @@ extern "C" hipError_t pwn_launch_view_setup(const float *d_cams, const float *d_
 // d_traversals n int32 or NULL, d_keys n bytes; stage != 0: every workgroup copies the walk table into LDS first
 extern "C" hipError_t pwn_launch_players_step(float *d_cams, float *d_gravity, int32_t *d_traversals, const uint8_t *d_keys, int n,
 	float tdiff, int ticks, const pwn_walk_table *d_walk, int stage, hipStream_t stream);
+// the ray records and seeds of pwn_pixel_rays_device (pixel_rays.hip) from the view records d_recs: total = n x m rays, ray i * m + j camera
+// i's pixel j; d_xy m pairs (shared != 0) or total pairs, or NULL = the whole frame (m == width x height); d_seeds or NULL; the magic
+// numbers of the divisions by m and by width (launch_plan.h pwn_unit_div_magic)
+extern "C" hipError_t pwn_launch_pixel_rays(const pwn_view_rec *d_recs, const int32_t *d_xy, float *d_rays, uint32_t *d_seeds, uint32_t total,
+	uint32_t m, uint32_t m_magic, int m_shift, int shared, int width, uint32_t w_magic, int w_shift, hipStream_t stream);
 extern "C" hipError_t pwn_launch_words(const uint32_t *d_all, const uint32_t *d_own, uint32_t *h_pinned_dst, int world, hipStream_t stream);
 extern "C" hipError_t pwn_launch_probe(int op, const uint32_t *in, uint32_t *out, int n, const uint16_t *tabs, hipStream_t stream);
 

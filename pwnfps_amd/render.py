@@ -567,6 +567,89 @@ class Renderer:
                                               C.c_void_p(traversals.data_ptr() if traversals is not None and n else None), C.c_void_p(stream or 0)),
                   "pwn_players_step_device")
 
+    # -- pixel rays from cameras on the GPU (pwn_pixel_rays_device) ------------
+    def pixel_rays_device(self, cams, xy=None, *, width=None, height=None, shared=None, rays=None, seeds=None, work=None, stream=None):
+        """pwn_pixel_rays_device: pixel_rays for n cameras on the GPU, at most two launches on `stream` (a torch stream or a raw
+        hipStream_t; None = torch's current stream), no synchronisation.  Torch tensors on this context's GPU, contiguous: cams (n,16)
+        or (n,4,4) float32 -- the tensor players_step_device steps; xy (m,2) int32, pixels that every camera uses, or (n,m,2), each
+        camera's own, or None: the whole width x height frame, row-major.  width / height: the frame the pixels belong to (default:
+        the renderer's).  shared: None = what xy's shape says; given, it has to agree with it.  rays (n*m,8) or (n,m,8) float32,
+        seeds (n*m,) or (n,m) int32 / uint32 -- or False: none is written -- and work (n,20) float32 scratch are made when not given.
+        cams, work and rays 16-byte aligned, xy 8-byte aligned.  Returns (rays, seeds); ray i * m + j is camera i's pixel j, and
+        trace_rays_device / trace_hits_device take them as they are (has_w for cameras with w components)."""
+        import torch
+        who = "pixel_rays_device"
+        words = (torch.int32, getattr(torch, "uint32", torch.int32))
+        if isinstance(cams, torch.Tensor) and cams.dim() == 3 and tuple(cams.shape[1:]) == (4, 4) and cams.is_contiguous():
+            cams = cams.view(cams.shape[0], 16)
+        n = _tensor_check(torch, cams, "cams", (torch.float32,), 2, who=who)
+        if cams.shape[1] != 16 or n > _lib.PWN_PLAYERS_MAX:
+            raise ValueError("%s: cams must have shape (n,4,4) or (n,16) with n <= %d, not %s" % (who, _lib.PWN_PLAYERS_MAX, tuple(cams.shape)))
+        width, height = self.w if width is None else width, self.h if height is None else height
+        for name, v in (("width", width), ("height", height)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1 or v > 32768:
+                raise ValueError("%s: %s must be an integer 1 ... 32768, not %r" % (who, name, v))
+        width, height = int(width), int(height)
+        if shared is not None and not isinstance(shared, (bool, np.bool_)):
+            raise ValueError("%s: shared must be None, True or False, not %r" % (who, shared))
+        if xy is None:
+            if shared is not None and not shared:
+                raise ValueError("%s: the whole frame (xy=None) is shared by every camera" % who)
+            shared, m = True, width * height
+        else:
+            if not isinstance(xy, torch.Tensor) or xy.dim() not in (2, 3):
+                raise ValueError("%s: xy must be a GPU tensor of shape (m,2) or (n,m,2), or None" % who)
+            _tensor_check(torch, xy, "xy", (torch.int32,), xy.dim(), n if xy.dim() == 3 else None, who=who)
+            if xy.shape[-1] != 2:
+                raise ValueError("%s: xy must have shape (m,2) or (n,m,2), not %s" % (who, tuple(xy.shape)))
+            if shared is not None and bool(shared) != (xy.dim() == 2):
+                raise ValueError("%s: shared=%s does not go with xy of shape %s" % (who, bool(shared), tuple(xy.shape)))
+            shared, m = xy.dim() == 2, int(xy.shape[-2])
+            if xy.data_ptr() % 8 != 0:
+                raise ValueError("%s: xy is not 8-byte aligned" % who)
+        total = n * m
+        if total > _lib.PWN_RAYS_MAX:
+            raise ValueError("%s: %d x %d rays, at most %d" % (who, n, m, _lib.PWN_RAYS_MAX))
+        dev = cams.device
+        if rays is None:
+            rays = torch.empty((total, 8), dtype=torch.float32, device=dev)
+        else:
+            _tensor_check(torch, rays, "rays", (torch.float32,), rays.dim() if isinstance(rays, torch.Tensor) and rays.dim() in (2, 3) else 2, who=who)
+            if tuple(rays.shape) not in ((total, 8), (n, m, 8)):
+                raise ValueError("%s: rays must have shape (%d,8) or (%d,%d,8), not %s" % (who, total, n, m, tuple(rays.shape)))
+        if seeds is None:
+            seeds = torch.empty(total, dtype=torch.int32, device=dev)
+        elif seeds is False:
+            seeds = None
+        else:
+            _tensor_check(torch, seeds, "seeds", words, seeds.dim() if isinstance(seeds, torch.Tensor) and seeds.dim() in (1, 2) else 1, who=who)
+            if tuple(seeds.shape) not in ((total,), (n, m)):
+                raise ValueError("%s: seeds must have shape (%d,) or (%d,%d), not %s" % (who, total, n, m, tuple(seeds.shape)))
+        if work is None:
+            work = torch.empty((n, _lib.PWN_PIXEL_WORK_BYTES // 4), dtype=torch.float32, device=dev)
+        else:
+            _tensor_check(torch, work, "work", (torch.float32,), 2, n, who=who)
+            if work.shape[1] != _lib.PWN_PIXEL_WORK_BYTES // 4:
+                raise ValueError("%s: work must have shape (%d,%d), not %s" % (who, n, _lib.PWN_PIXEL_WORK_BYTES // 4, tuple(work.shape)))
+        for name, t in (("xy", xy), ("rays", rays), ("seeds", seeds), ("work", work)):
+            if t is not None and t.device != dev:
+                raise ValueError("%s: tensors on %s and %s" % (who, dev, t.device))
+        for name, t in (("cams", cams), ("rays", rays), ("work", work)):
+            if t.data_ptr() % 16 != 0:
+                raise ValueError("%s: %s is not 16-byte aligned" % (who, name))
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        if not isinstance(stream, int):
+            stream = stream.cuda_stream
+        live = total > 0
+        self._chk(lib.pwn_pixel_rays_device(self._ctx, width, height, n, C.c_void_p(cams.data_ptr() if n else None), m,
+                                            C.c_void_p(xy.data_ptr() if xy is not None and xy.numel() else None),
+                                            _lib.PWN_PIXELS_SHARED if shared else 0, C.c_void_p(work.data_ptr() if n else None),
+                                            C.c_void_p(rays.data_ptr() if live else None),
+                                            C.c_void_p(seeds.data_ptr() if seeds is not None and live else None), C.c_void_p(stream or 0)),
+                  "pwn_pixel_rays_device")
+        return rays, seeds
+
     def set_call_strips(self, n):
         """PWN_OPT_CALL_STRIPS: -1 = by frame size (default), 0 = one launch per pass, 2..32 = that many row strips"""
         self._chk(lib.pwn_set_option(self._ctx, _lib.PWN_OPT_CALL_STRIPS, int(n)), "pwn_set_option(CALL_STRIPS)")

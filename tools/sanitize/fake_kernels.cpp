@@ -149,6 +149,27 @@ extern "C" hipError_t pwn_launch_players_step(float *cams, float *gravity, int32
 	}
 	return hipSuccess;
 }
+// (the rays of pwn_pixel_rays_device; pixel_rays_driver.cpp: every byte of the two output ranges and none beside them, each word
+// made of the ray's number, its camera's record and its pixel -- every record and every pixel pair of the ranges given is read, and
+// which camera, which pixel and which layout a call was given shows; pwn_pixel_rays is the arithmetic's model, not this)
+extern "C" hipError_t pwn_launch_pixel_rays(const pwn_view_rec *recs, const int32_t *xy, float *rays, uint32_t *seeds, uint32_t total,
+	uint32_t m, uint32_t m_magic, int m_shift, int shared, int width, uint32_t w_magic, int w_shift, hipStream_t)
+{
+	small_launch("pixel_rays", recs, rays, { (size_t)total, (size_t)m, (size_t)shared, (size_t)width });
+	for(uint32_t i = 0; i < total; i++)
+	{
+		const uint32_t cam = m_shift >= 0 ? (uint32_t)(((unsigned long long)i * m_magic) >> 32) >> m_shift : i, j = i - cam * m;
+		int32_t x, y;
+		if(xy != NULL) { x = xy[2 * (size_t)(shared ? j : i)]; y = xy[2 * (size_t)(shared ? j : i) + 1]; }
+		else { const uint32_t row = w_shift >= 0 ? (uint32_t)(((unsigned long long)j * w_magic) >> 32) >> w_shift : j; x = (int32_t)(j - row * (uint32_t)width); y = (int32_t)row; }
+		uint32_t rec = 0;
+		for(int k = 0; k < 20; k++) { uint32_t u; memcpy(&u, (const float *)&recs[cam] + k, 4); rec = mix(rec, u); }
+		const uint32_t key = mix(mix(rec, (uint32_t)x), mix((uint32_t)y, i));
+		for(int k = 0; k < 8; k++) { const uint32_t u = mix(key, (uint32_t)k) & 0x3fffffffu; memcpy(&rays[8 * (size_t)i + k], &u, 4); }
+		if(seeds != NULL) seeds[i] = key;
+	}
+	return hipSuccess;
+}
 extern "C" hipError_t pwn_launch_words(const uint32_t *all, const uint32_t *own, uint32_t *h, int world, hipStream_t)
 {
 	for(int i = 0; i < 2 * world + 2; i++) h[i] = i < 2 * world ? all[i] : own[i - 2 * world];
