@@ -308,6 +308,76 @@ int pwn_sphere_bounds_plan(const pwn_sphere *spheres, int n, double out[PWN_BOUN
 int pwn_sphere_tables_state(pwn_ctx *ctx, unsigned long long out[6]);
 
 /*
+ * The sphere tables built on the device: pwn_upload_spheres for spheres that are already in device memory, on the caller's
+ * stream, with no host round trip -- the other players of an arena drawn as spheres, a projectile, anything a policy moves.
+ *   what                 d_spheres holds n records of pwn_sphere (8 floats, 32 B: r, refl, x, y, z, cb, cg, cr), 16-byte aligned, in
+ *                        device memory.  The call bins them as level_prepare_render does (level.h:64-81: object order inside a
+ *                        cell, cells outside the grid skipped), builds a full copy of the tables in the lists' device-memory form
+ *                        (pwn_sphere_tables_state: form 2) and makes that copy the tables in force.  pwn_hit.object and the label
+ *                        planes' object field index d_spheres' order.  d_spheres is read by the call's own launches only: in stream
+ *                        order the caller may overwrite it afterwards.
+ *   capacity             the host cannot know the lists' sizes, so the caller declares them: max_pairs is the most (cell, sphere)
+ *                        pairs the tables may hold.  The on-chip part is then laid out for min(4096, max_pairs) non-empty cells and
+ *                        the device-memory part for max_pairs records and n spheres (16 B a pair and 16 more, 4 B a pair, 32 B a
+ *                        sphere, each section rounded up to 16).  Tables with max_pairs >= 4096 take 42 KB of LDS per workgroup
+ *                        (three workgroups per CU), whatever the spheres are.
+ *   overflow             the device cannot refuse.  Spheres that make more than max_pairs pairs, or one cell's list longer than
+ *                        PWN_LIST_MAX, put tables WITHOUT ANY sphere into force -- exactly the tables of n = 0 -- and
+ *                        pwn_spheres_device_state says why.  Nothing is truncated, nothing is read or written out of range.
+ *   exactness            with these tables every call family -- frames, frames in flight, strips, views, viewports, rays, hits, view
+ *                        hits, their device forms, the five counters -- returns bit for bit what it returns after pwn_upload_spheres of
+ *                        the same n spheres.  Such tables carry no bounding balls (pwn_sphere_bounds_plan); results and counters never
+ *                        depend on those.  This holds for every bit pattern in the records: NaN, infinities, coordinates and radii
+ *                        beyond int, negative and denormal radii, r * r below FLT_MIN stored as 0.  The box is (int)(x - r) etc. as
+ *                        the x86 build computes it (INT_MIN for NaN and anything outside int), then clamped; positions, refl and
+ *                        colours are moved, not computed with.  Every address comes from counted values and the clamped box: no
+ *                        input bit pattern reaches one.
+ *   ordering             at most FIVE launches on `stream` (a hipStream_t, NULL = the default stream): four of the build, and in the
+ *                        first call after a level change one more that brings the level's part of the tables (static head, baked
+ *                        cell words, portal records) into a device-resident base copy from one pinned slot.  No host wait, no
+ *                        synchronisation and, from the second call of a level on, no copy from host memory.  Trace launches and
+ *                        players' steps made after the call returns read the new tables, on any stream: they are put behind the
+ *                        build as they are put behind an upload.  Launches made before it keep the copy they were given.  The build
+ *                        takes the next of the four copies of the tables and waits ON `stream` for the launches and steps that
+ *                        still read that copy.  The walk table of the players' step is handed on as an upload of spheres alone
+ *                        hands it on.  Builds of one context on different streams are put behind each other.  No work-queue
+ *                        counters are used and the launch rotation is not entered.
+ *   memory               the context's: the copies' device-memory parts grow to the largest need so far.  A call that needs more
+ *                        than any before allocates and may synchronise the device once, as pwn_upload_spheres does; a call that
+ *                        fits allocates nothing.  The first call of a context allocates the builder's scratch (74 KB) and the base
+ *                        copy (25 KB on the device and pinned).  pwn_destroy frees them.
+ *   in force until       the next call that builds tables from the host's object table: pwn_upload_spheres, pwn_prepare_render,
+ *                        pwn_level_load, pwn_level_load_mem, pwn_upload_level, which behave exactly as they always did.
+ *                        pwn_set_option never replaces them: under PWN_SCHED_REFILL they run the units kernel, as form 2 always
+ *                        does, and a change of scheduler repacks nothing.  pwn_get_objects, pwn_get_object_ids and pwn_get_bins go
+ *                        on describing the host's table.  pwn_sphere_tables_state reports out[0] = 2, out[1] and out[2] as laid out
+ *                        above, out[3..5] the capacity's bounds: max_pairs, min(4096, max_pairs), min(PWN_LIST_MAX, max_pairs).
+ *   left alone           everything pwn_players_step leaves alone, pwn_stats and pwn_launch_order_waits included.
+ *   cost                 measured on an MI355X (profiles/spheres_device/bench.txt): the call 35 us for up to 64
+ *                        spheres, 43 us for 1024, 99 us for 10000, against 53 to 325 us for copying the records down,
+ *                        pwn_upload_spheres and the wait for its upload.  The trace pays for the device-memory form (one 16-byte
+ *                        global load per sphere test where the on-chip forms make an LDS read) and for its LDS: the blocking
+ *                        call's trace time at 3840x2160 was +2.4 % on level.txt's 14 spheres and -0.1 % on synth64's 64 with
+ *                        max_pairs = 4096, differences the measurement does not resolve below a few per cent.
+ *   errors               PWN_EINVAL for a NULL ctx, n < 0, n > PWN_OBJ_MAX, max_pairs < 0, a NULL or misaligned d_spheres with
+ *                        n > 0; PWN_ETOOBIG when the device-memory part as laid out above exceeds PWN_TABLES_MAX; PWN_ENOLEVEL before
+ *                        a level; PWN_ENOTSUP on a pwn_init_multi handle; PWN_EBUSY while the context runs a row tiling; PWN_ENOMEM
+ *                        when a buffer cannot grow.  n == 0 is PWN_OK and puts empty tables into force (it still takes the next
+ *                        copy).  A refused call launches nothing and leaves the tables in force as they were.
+ *   pwn_spheres_device_state   BLOCKS: waits for the last build.  For tests and for hosts that size max_pairs.
+ *                        out[0]  1 if device-built tables are in force, else 0
+ *                        out[1]  n of the last build            out[2]  max_pairs of the last build
+ *                        out[3]  the pairs the spheres made (the full count also when over capacity)
+ *                        out[4]  non-empty cells                out[5]  the longest list
+ *                        out[6]  0 = built, 1 = more pairs than max_pairs, 2 = a list longer than PWN_LIST_MAX
+ *                        out[7]  device uploads so far
+ *                        All eight are 0 before any device upload.  PWN_EINVAL for a NULL ctx or out, PWN_ENOTSUP on a
+ *                        pwn_init_multi handle, PWN_EBUSY under a row tiling.
+ */
+int pwn_upload_spheres_device(pwn_ctx *ctx, int n, const void *d_spheres, int max_pairs, void *stream);
+int pwn_spheres_device_state(pwn_ctx *ctx, unsigned long long out[8]);
+
+/*
  * The object table behind those lists, driven the way game.lua drives the
  * reference (script.h:1-64): lv->objs[OBJ_MAX] (defs.h:4,98-99).
  *   pwn_obj_new        level_obj_new (level.h:41-62): first freed slot, else

@@ -120,6 +120,8 @@ ABI = [
     ("pwn_sphere_tables_plan", _i, [_vp, _i, _vp]),
     ("pwn_sphere_bounds_plan", _i, [_vp, _i, _vp]),
     ("pwn_sphere_tables_state", _i, [_vp, _vp]),
+    ("pwn_upload_spheres_device", _i, [_vp, _i, _vp, _i, _vp]),
+    ("pwn_spheres_device_state", _i, [_vp, _vp]),
     ("pwn_obj_new", _i, [_vp]),
     ("pwn_obj_set_sphere", _i, [_vp, _i, _d, _d, _d, _d, _d, _d, _d, _d]),
     ("pwn_obj_free", _i, [_vp, _i]),

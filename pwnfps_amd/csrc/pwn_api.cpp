@@ -92,6 +92,7 @@ extern "C" int pwn_init(pwn_ctx **out, int device, int width, int height)
 	for(int i = 0; i < PWN_NBLOB; i++) { c->d_walk[i] = NULL; c->walk_of[i] = i; c->ev_walk[i] = NULL; c->walk_in_use[i] = false; c->walk_stream[i] = NULL; }
 	for(int i = 0; i < PWN_NSTAGE; i++) c->h_walk[i] = NULL;
 	c->walk_dirty = false;
+	memset(&c->sd, 0, sizeof(c->sd));
 	memset(&c->room, 0, sizeof(c->room)); c->room.mode = -1;
 	if(const char *e = getenv("PWN_TRACE_ROOM")) if(*e) c->room.mode = atoi(e) < 0 ? -1 : atoi(e);      // (the option's default for every context of a process)
 	c->d_scratch = NULL; c->scratch_cap = 0;
@@ -232,6 +233,7 @@ extern "C" void pwn_destroy(pwn_ctx *c)
 		(void)hipFree(c->d_blob[i]);
 		(void)hipFree(c->d_big[i]);
 	}
+	pwn_i_spheres_device_release(c);
 	for(int i = 0; i < PWN_NSTAGE; i++)
 	{
 		if(c->ev_stage[i]) (void)hipEventDestroy(c->ev_stage[i]);
@@ -320,7 +322,9 @@ extern "C" int pwn_set_option(pwn_ctx *c, int option, int value)
 		case PWN_OPT_COUNTERS: c->counters_on = value ? 1 : 0; return PWN_OK;
 		case PWN_OPT_SCHEDULER:
 			if(value < 0 || value > PWN_SCHED_REFILL) return PWN_EINVAL;
-			if(value != c->scheduler) c->blob_dirty = true;          // (the form of the per-cell sphere lists goes with the scheduler: pwn_i_pack_blob)
+			// (the form of the per-cell sphere lists goes with the scheduler: pwn_i_pack_blob -- but tables built on the device stay in
+			// force and in their form, which runs the units kernel under any scheduler: nothing is repacked from the host's spheres)
+			if(value != c->scheduler && !c->sd.in_force) c->blob_dirty = true;
 			c->scheduler = value; return PWN_OK;
 		case PWN_OPT_WAVE_LOG: c->wave_log_on = value ? 1 : 0; return PWN_OK;
 		case PWN_OPT_FRAME_TIMING: if(value < 0) return PWN_EINVAL; c->frame_timing = value; return PWN_OK;

@@ -6,6 +6,7 @@
 //   pwn_calls.cpp   the blocking call and its strips, host registration, the batches of views, viewports, rays and hits
 //   pwn_players.cpp the players' step: a batch of cameras walked through the level (host and device form)
 //   pwn_pixel_rays.cpp  pixel rays from cameras on the device (pwn_pixel_rays_device)
+//   pwn_spheres_device.cpp  the sphere tables built on the device (pwn_upload_spheres_device)
 //   pwn_frames.cpp  frames in flight
 //   pwn_tiled.cpp   row tiling over RCCL
 //   pwn_group.cpp   several contexts behind one handle
@@ -114,6 +115,16 @@ extern "C" hipError_t pwn_launch_players_step(float *d_cams, float *d_gravity, i
 // numbers of the divisions by m and by width (launch_plan.h pwn_unit_div_magic)
 extern "C" hipError_t pwn_launch_pixel_rays(const pwn_view_rec *d_recs, const int32_t *d_xy, float *d_rays, uint32_t *d_seeds, uint32_t total,
 	uint32_t m, uint32_t m_magic, int m_shift, int shared, int width, uint32_t w_magic, int w_shift, hipStream_t stream);
+// the sphere tables in the lists' device-memory form built from n sphere records in device memory (sphere_bins.hip): four launches on
+// `stream`.  d_scratch: PWN_SD_SCRATCH_BYTES; d_base: the level's part of the blob, PWN_T_BINIDX bytes; d_blob: the copy's LDS part;
+// d_big: its device-memory part, laid out for max_pairs records and n spheres, sections at which_off / sph_off
+extern "C" hipError_t pwn_launch_sphere_bins(const void *d_spheres, uint32_t n, uint32_t max_pairs, void *d_scratch, const void *d_base,
+	void *d_blob, void *d_big, uint64_t which_off, uint64_t sph_off, hipStream_t stream);
+// ... its scratch: a box word per sphere, 4096 counts, 4096 list starts, the status words of the last build
+#define PWN_SD_BOX_WORDS 10240u
+#define PWN_SD_STATUS_WORD (PWN_SD_BOX_WORDS + 8192u)
+#define PWN_SD_SCRATCH_BYTES ((PWN_SD_STATUS_WORD + 8u) * 4u)
+enum { PWN_SD_ST_PAIRS = 0, PWN_SD_ST_NCELL = 1, PWN_SD_ST_LONGEST = 2, PWN_SD_ST_REASON = 3, PWN_SD_ST_N = 4, PWN_SD_ST_MAX_PAIRS = 5 };
 extern "C" hipError_t pwn_launch_words(const uint32_t *d_all, const uint32_t *d_own, uint32_t *h_pinned_dst, int world, hipStream_t stream);
 extern "C" hipError_t pwn_launch_probe(int op, const uint32_t *in, uint32_t *out, int n, const uint16_t *tabs, hipStream_t stream);
 
@@ -280,6 +291,20 @@ struct pwn_ctx
 	bool walk_dirty;                 // the level changed and no walk table of it has been sent yet
 	hipEvent_t ev_walk[PWN_NBLOB]; bool walk_in_use[PWN_NBLOB]; hipStream_t walk_stream[PWN_NBLOB];
 	size_t occ_lds[12]; int occ_blocks[12];    // cached occupancy query per kernel variant
+	// pwn_upload_spheres_device (pwn_spheres_device.cpp): tables built on the device from spheres in device memory, into the next copy
+	// of the ring above, in the lists' device-memory form laid out for a declared capacity.  in_force: the tables in force are such
+	// tables -- pwn_i_pack_blob clears it, and while it is set nothing repacks from the host's spheres (pwn_set_option).  d_base: the
+	// level's part of the blob on the device (static head, cell words without sphere bits, eprec), made from pinned h_base by the
+	// first build after a level change (base_ok; pwn_i_pack_blob clears that with cell_base_ok), under ev_base.  Builds share
+	// d_scratch and d_base, so each is put behind the one before it (ev_build, build_stream) where the stream differs.
+	struct spheres_device_state
+	{
+		bool in_force, base_ok, base_used, built;
+		int n, max_pairs;                         // of the last build
+		unsigned long long uploads;
+		uint8_t *d_base, *h_base, *d_scratch;
+		hipEvent_t ev_base, ev_build; hipStream_t build_stream;
+	} sd;
 
 	uint32_t *d_pre, *d_out;         // pre-blur ("tsbuf") and final ("sbuf") frames
 	float *d_z;
@@ -405,6 +430,7 @@ int pwn_i_blur_passes_run(pwn_ctx *c, pwn_blur_launch B, uint32_t **cur, uint32_
 void pwn_i_frames_release(pwn_ctx *c);
 void pwn_i_expand_tables(uint16_t *rcp, uint16_t *rsq);
 int pwn_i_pack_blob(pwn_ctx *c);
+void pwn_i_spheres_device_release(pwn_ctx *c);      // pwn_spheres_device.cpp: the device builder's buffers and events gone (pwn_destroy)
 void pwn_tiled_destroy(pwn_ctx *c);
 bool pwn_tiled_busy(pwn_ctx *c);        // frames of the row tiling in flight
 // pwn_tiled.cpp internals used by pwn_group.cpp: a member's frame with the host buffers its strip is delivered into (NULL: the

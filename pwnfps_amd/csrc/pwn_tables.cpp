@@ -127,6 +127,7 @@ int pwn_i_pack_blob(pwn_ctx *c)
 		for(int x = 0; x <= 64; x++)
 			c->cell_base[z * PWN_GRID_PITCH + x] = (uint32_t)bits[z * PWN_GRID_PITCH + x] | pwn_cell_class(c->cells[(z & 63) * 64 + (x & 63)]);
 		c->cell_base_ok = true;
+		c->sd.base_ok = false;       // (the device builder's copy of these words is the previous level's: pwn_spheres_device.cpp)
 	}
 	memcpy(ci, c->cell_base, sizeof(c->cell_base));
 	uint32_t at = 0;
@@ -278,6 +279,7 @@ int pwn_i_pack_blob(pwn_ctx *c)
 	c->blob_has_static[nb] = true;
 	c->blob_cur = nb;
 	c->blob_dirty = false;
+	c->sd.in_force = false;          // the tables in force are the host's again (pwn_upload_spheres_device)
 	return PWN_OK;
 }
 
@@ -581,6 +583,16 @@ extern "C" int pwn_sphere_tables_state(pwn_ctx *c, unsigned long long out[6])
 {
 	if(GRP_HEAD(c)) { const int rc = pwn_group_sync(c); return rc != PWN_OK ? rc : pwn_sphere_tables_state(GRP_M0(c), out); }      // (as pwn_get_bins)
 	if(c == NULL || out == NULL) return PWN_EINVAL;
+	// tables built on the device (pwn_upload_spheres_device): the host knows their capacity, not their lists
+	if(c->sd.in_force)
+	{
+		const uint64_t mp = (uint64_t)c->sd.max_pairs;
+		out[0] = PWN_LF_GLOBAL;
+		out[1] = (unsigned long long)c->blob.size() + pwn_trace_lds_extra();
+		out[2] = pwn_g_total(mp, (uint64_t)c->sd.n);
+		out[3] = mp; out[4] = mp < 4096u ? mp : 4096u; out[5] = mp < (uint64_t)PWN_LIST_MAX ? mp : (uint64_t)PWN_LIST_MAX;
+		return PWN_OK;
+	}
 	// (the lists in force are the context's bins: a refused upload has put the previous ones back)
 	pwn_tables_plan p;
 	const int rc = pwn_i_tables_plan(c->bin_off.data(), (uint32_t)c->spheres.size(), c->scheduler, c->dbg_sphere_lists, &p);

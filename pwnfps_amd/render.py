@@ -227,6 +227,40 @@ class Renderer:
         self._chk(lib.pwn_sphere_tables_state(self._ctx, out), "pwn_sphere_tables_state")
         return _tables_dict(out)
 
+    # -- sphere tables built on the GPU (pwn_upload_spheres_device) ------------
+    def upload_spheres_device(self, spheres, max_pairs, stream=None):
+        """pwn_upload_spheres_device: upload_spheres for spheres that are on the GPU already, at most five launches on `stream` (a
+        torch stream or a raw hipStream_t; None = torch's current stream), no synchronisation.  spheres: a contiguous float32 GPU
+        tensor (n,8) on this context's GPU, 16-byte aligned, rows r, refl, x, y, z, cb, cg, cr (SPHERE_DTYPE's order); max_pairs: the
+        most (cell, sphere) pairs the tables may hold -- spheres that make more put tables without any sphere into force
+        (spheres_device_state says so).  The tensor may be overwritten, in stream order, once the call has returned."""
+        import torch
+        who = "upload_spheres_device"
+        n = _tensor_check(torch, spheres, "spheres", (torch.float32,), 2, who=who)
+        if spheres.shape[1] != 8:
+            raise ValueError("%s: spheres must have shape (n,8), not %s" % (who, tuple(spheres.shape)))
+        if n > _lib.PWN_OBJ_MAX:
+            raise ValueError("%s: %d spheres are more than PWN_OBJ_MAX (%d)" % (who, n, _lib.PWN_OBJ_MAX))
+        if spheres.device.index != self.device:
+            raise ValueError("%s: spheres are on %s, the context is on GPU %d" % (who, spheres.device, self.device))
+        if n and spheres.data_ptr() % 16 != 0:
+            raise ValueError("%s: spheres is not 16-byte aligned" % who)
+        if isinstance(max_pairs, bool) or not isinstance(max_pairs, (int, np.integer)) or not 0 <= int(max_pairs) < 2 ** 31:
+            raise ValueError("%s: max_pairs must be an integer 0 .. 2^31 - 1, not %r" % (who, max_pairs))
+        if stream is None:
+            stream = torch.cuda.current_stream(spheres.device)
+        if not isinstance(stream, int):
+            stream = stream.cuda_stream
+        self._chk(lib.pwn_upload_spheres_device(self._ctx, n, C.c_void_p(spheres.data_ptr() if n else None), int(max_pairs), C.c_void_p(stream or 0)),
+                  "pwn_upload_spheres_device")
+
+    def spheres_device_state(self):
+        """pwn_spheres_device_state (blocks: waits for the last build): dict(in_force, n, max_pairs, pairs, cells, longest, reason,
+        uploads); reason 0 = built, 1 = more pairs than max_pairs, 2 = a list longer than PWN_LIST_MAX"""
+        out = (C.c_uint64 * 8)()
+        self._chk(lib.pwn_spheres_device_state(self._ctx, out), "pwn_spheres_device_state")
+        return dict(zip(("in_force", "n", "max_pairs", "pairs", "cells", "longest", "reason", "uploads"), (int(v) for v in out)))
+
     # -- frame (screen.h:31-124) ---------------------------------------------
     def trace_screen_centred(self, cam, sec_current=0.0, want_z=True, sbuf=None, zbuf=None):
         cam = np.ascontiguousarray(cam, np.float32).reshape(16)

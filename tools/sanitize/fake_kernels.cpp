@@ -22,6 +22,7 @@ void (*pwn_fake_trace_hook)(const pwn_trace_params *P, int grid, size_t lds_byte
 void (*pwn_fake_blur_hook)(const pwn_blur_params *B) = NULL;
 void (*pwn_fake_launch_hook)(const char *name, const void *src, const void *dst, int nsizes, const size_t *sizes) = NULL;
 void (*pwn_fake_players_hook)(const pwn_walk_table *walk, int n, int ticks, int stage) = NULL;
+void (*pwn_fake_sphere_bins_hook)(const void *d_scratch, const void *d_base, const void *d_blob) = NULL;
 }
 static void small_launch(const char *name, const void *src, const void *dst, std::initializer_list<size_t> sizes)
 {
@@ -168,6 +169,63 @@ extern "C" hipError_t pwn_launch_pixel_rays(const pwn_view_rec *recs, const int3
 		for(int k = 0; k < 8; k++) { const uint32_t u = mix(key, (uint32_t)k) & 0x3fffffffu; memcpy(&rays[8 * (size_t)i + k], &u, 4); }
 		if(seeds != NULL) seeds[i] = key;
 	}
+	return hipSuccess;
+}
+// (the tables of pwn_upload_spheres_device; spheres_device_driver.cpp: sphere_bins.hip's four launches as one sequential pass that reads
+// and writes exactly what they do -- the n records, the whole base copy, the scratch's words, the blob's level part and liststart
+// below the non-empty cells, the device-memory part's records up to and including the read-ahead one, which[] and the spheres --
+// through sphere_box.h, the arithmetic the kernels share with the host.  Here the stand-in IS the model: the tables it leaves
+// are held against pwn_i_pack_blob's by the driver.)
+#include "sphere_box.h"
+extern "C" hipError_t pwn_launch_sphere_bins(const void *d_spheres, uint32_t n, uint32_t max_pairs, void *d_scratch, const void *d_base,
+	void *d_blob, void *d_big, uint64_t which_off, uint64_t sph_off, hipStream_t)
+{
+	small_launch("sphere_bins", d_spheres, d_big, { (size_t)n, (size_t)max_pairs, (size_t)which_off, (size_t)sph_off });
+	if(pwn_fake_sphere_bins_hook != NULL) pwn_fake_sphere_bins_hook(d_scratch, d_base, d_blob);
+	uint32_t *box = (uint32_t *)d_scratch, *count = box + PWN_SD_BOX_WORDS, *start = count + 4096, *status = box + PWN_SD_STATUS_WORD;
+	uint32_t *rec = (uint32_t *)d_big, *which = (uint32_t *)((uint8_t *)d_big + which_off), *sph = (uint32_t *)((uint8_t *)d_big + sph_off);
+	const uint32_t *in = (const uint32_t *)d_spheres;
+	memcpy(d_blob, d_base, PWN_T_BINIDX);
+	for(uint32_t i = 0; i < n; i++)
+	{
+		const uint32_t *q = in + 8 * (size_t)i;
+		float r, x, z;
+		memcpy(&r, q + 0, 4); memcpy(&x, q + 2, 4); memcpy(&z, q + 4, 4);
+		box[i] = pwn_box_pack(x, z, r);
+		const float r2 = pwn_box_r2(r);
+		uint32_t *o = sph + 8 * (size_t)i;
+		o[0] = q[2]; o[1] = q[3]; o[2] = q[4]; memcpy(o + 3, &r2, 4);
+		o[4] = q[1]; o[5] = q[5]; o[6] = q[6]; o[7] = q[7];
+	}
+	uint32_t pairs = 0, ncell = 0, longest = 0;
+	for(uint32_t cell = 0; cell < 4096; cell++)
+	{
+		uint32_t k = 0;
+		for(uint32_t i = 0; i < n; i++) k += pwn_box_covers(box[i], cell & 63u, cell >> 6) != 0;
+		count[cell] = k; start[cell] = pairs;
+		pairs += k; ncell += k != 0; if(k > longest) longest = k;
+	}
+	const uint32_t reason = pairs > max_pairs ? 1u : (longest > (uint32_t)PWN_LIST_MAX ? 2u : 0u);
+	status[PWN_SD_ST_PAIRS] = pairs; status[PWN_SD_ST_NCELL] = ncell; status[PWN_SD_ST_LONGEST] = longest; status[PWN_SD_ST_REASON] = reason;
+	status[PWN_SD_ST_N] = n; status[PWN_SD_ST_MAX_PAIRS] = max_pairs;
+	if(reason != 0u) return hipSuccess;
+	uint32_t *cells = (uint32_t *)d_blob + PWN_T_CELLINFO / 4u, *liststart = (uint32_t *)d_blob + PWN_T_BINIDX / 4u, ord = 0;
+	for(uint32_t cell = 0; cell < 4096; cell++)
+	{
+		if(count[cell] == 0u) continue;
+		liststart[ord] = start[cell];
+		cells[(cell >> 6) * PWN_GRID_PITCH + (cell & 63u)] |= PWN_C_SPH | (ord << 16);
+		ord++;
+		uint32_t k = start[cell];
+		for(uint32_t i = 0; i < n; i++)
+		{
+			if(!pwn_box_covers(box[i], cell & 63u, cell >> 6)) continue;
+			memcpy(rec + 4 * (size_t)k, sph + 8 * (size_t)i, 16);
+			if(k + 1u == start[cell] + count[cell]) rec[4 * (size_t)k + 3] |= 0x80000000u;
+			which[k++] = i;
+		}
+	}
+	memset(rec + 4 * (size_t)pairs, 0, 16);
 	return hipSuccess;
 }
 extern "C" hipError_t pwn_launch_words(const uint32_t *all, const uint32_t *own, uint32_t *h, int world, hipStream_t)
