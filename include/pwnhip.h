@@ -546,6 +546,68 @@ typedef struct pwn_viewport { int32_t x, y, w, h; } pwn_viewport;   /* a rectang
 int pwn_viewports_plan(int W, int H, int blur_passes, int n, const pwn_viewport *vp, unsigned long long out[4]);
 int pwn_trace_viewports(pwn_ctx *ctx, int n, const pwn_viewport *vp, const float *cams, const float *secs,
 	uint32_t *sbuf, float *zbuf);
+/*
+ * The device form: views of their own sizes from cameras in device memory into planes of the CALLER's in device memory, of a frame
+ * size the caller chooses -- stream-ordered on `stream` (a hipStream_t, NULL = default stream) like pwn_trace_views_device, no
+ * synchronisation, no host copy.  Observations of many agents at their own resolutions in one tensor (an atlas), a 4K spectator
+ * frame or a split screen from the cameras pwn_players_step_device moves, on the context that holds the level and the tables of
+ * pwn_upload_spheres_device -- whatever that context's own size is: it plays no part in any pixel.
+ *
+ * A LAYOUT is the part of a call the host knows beforehand and that does not change: the frame size W x H (1..32768 each, an
+ * argument, not the context's) and n rectangles of it.  pwn_viewports_layout makes one -- it may block, allocate and copy, and needs
+ * no level -- and any number of calls use it: the typical host has one per screen arrangement or atlas and moves only cameras.
+ *   rules                pwn_viewports_plan's for blur 0, by calling that very function: n in 1..PWN_VIEWS_MAX, every rectangle
+ *                        inside W x H, no two overlapping (touching is fine).  Whether the blur rules hold as well (W % 4 == 0,
+ *                        every x_i % 4 == 0 and w_i % 4 == 0) is recorded: a call with blur on needs such a layout.
+ *   pwn_viewports_layout_info   out[0..5] = W, H, n, the 16 x 4-pixel units of a launch, the pixels covered, 1 if usable with blur on.
+ *   pwn_viewports_layout_free   waits on the host for the last launches that read the layout (an event recorded behind every use,
+ *                        per stream it was used on), then frees it.  PWN_EINVAL for a layout of another context or one already
+ *                        freed.  pwn_destroy frees what is left.
+ *   cost                 on the device 148 B a rectangle and 8 B per 4 pixels of the widest view (the blur's skip-ahead table, which
+ *                        the context has only for views up to its own width), 128 B a rectangle on the host.
+ *   errors               PWN_EINVAL for what pwn_viewports_plan refuses with blur 0 and for a NULL ctx or out; PWN_ENOMEM;
+ *                        PWN_ENOTSUP on a pwn_init_multi handle.  *out is NULL unless the call returns PWN_OK.
+ *
+ * pwn_trace_viewports_device:
+ *   d_cams, d_secs       n x 16 floats (rows x,y,z,w), camera i for rectangle i of the layout -- the array pwn_players_step_device
+ *                        steps -- and n floats.
+ *   d_sbuf, d_zbuf, d_work   ONE plane of W x H words each, pitch W, all the caller's.  d_zbuf is required and in / out: a primary ray
+ *                        that runs out of steps keeps what the plane holds at its destination pixel (trace.h:677).  d_work is
+ *                        required when PWN_OPT_BLUR_PASSES > 0; the trace writes whichever of d_work / d_sbuf makes the last blur
+ *                        pass land in d_sbuf (d_work for an odd number of passes), as pwn_trace_views_device.
+ *                        All five pointers are 16-byte aligned.
+ *   flags                0 or PWN_VIEWS_HAS_W, with pwn_trace_views_device's meaning.
+ *   launches             one set-up launch (a thread per record: its geometry from the layout, its head from the view's camera), one
+ *                        trace launch, one blur launch per pass, all on `stream`.  After the context's first such call, which
+ *                        allocates the records below, a call makes no allocation, no copy from host memory, no event wait on the
+ *                        host and no synchronisation.  The trace launch falls under the rule for trace launches at the top of this
+ *                        file; a call that leaves the rotation is put behind launch n - R on `stream` before its set-up kernel writes.
+ *   records              the library's, as pwn_trace_views_device's: PWN_VIEWS_MAX records of 128 B per set of work-queue counters
+ *                        (768 KB in all), allocated by the first call, freed by pwn_destroy; a launch uses the records of the set it
+ *                        counts in.
+ *   exactness            rectangle i is bit-identical, colour and depth, to rectangle i of pwn_trace_viewports on a context of size
+ *                        W x H with the same rectangles, cameras, times, level, objects and PWN_OPT_BLUR_PASSES, provided d_zbuf on
+ *                        entry holds what that context's viewport depth plane held (zero for a fresh one) -- and so, through that
+ *                        call's contract, to pwn_trace_screen_centred on a context of w_i x h_i.  The set-up runs on the device with
+ *                        the host's arithmetic, operation for operation, denormals kept.
+ *   outside the rectangles   nothing of d_sbuf or d_zbuf is written (the host form clears; this form leaves alone): several calls,
+ *                        with other layouts of the same W x H or from other contexts, may fill one atlas.  What d_work holds
+ *                        afterwards is unspecified.
+ *   counters, not followed, left alone
+ *                        as pwn_trace_views_device; the planes and the depth plane of pwn_trace_viewports are left alone too.  The
+ *                        call sets no timings.
+ *   errors               PWN_EINVAL for a NULL ctx / layout / d_cams / d_secs / d_sbuf / d_zbuf, a NULL d_work with blur on, a
+ *                        layout of another context (or a freed one), flags other than PWN_VIEWS_HAS_W, a pointer that is not 16-byte
+ *                        aligned, any two of the three plane ranges (W x H x 4 bytes each) overlapping, blur on with a layout that
+ *                        is not usable with blur; PWN_ENOLEVEL, PWN_ENOTSUP and PWN_EBUSY as pwn_trace_views.  A refused call
+ *                        launches nothing and changes nothing.
+ */
+typedef struct pwn_vp_layout pwn_vp_layout;
+int pwn_viewports_layout(pwn_ctx *ctx, int W, int H, int n, const pwn_viewport *vp, pwn_vp_layout **out);
+int pwn_viewports_layout_free(pwn_ctx *ctx, pwn_vp_layout *layout);
+int pwn_viewports_layout_info(const pwn_vp_layout *layout, unsigned long long out[6]);
+int pwn_trace_viewports_device(pwn_ctx *ctx, const pwn_vp_layout *layout, const void *d_cams, const void *d_secs, int flags,
+	void *d_work, void *d_sbuf, void *d_zbuf, void *stream);
 
 /*
  * Caller-supplied rays: trace_ray(0, &seed_i, lv, &depth_i, &origin_i, &dir_i, {1,1,1,1}) (trace.h:186, called as at

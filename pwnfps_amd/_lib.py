@@ -136,6 +136,10 @@ ABI = [
     ("pwn_trace_views_device", _i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     ("pwn_viewports_plan", _i, [_i, _i, _i, _i, _vp, _vp]),
     ("pwn_trace_viewports", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    ("pwn_viewports_layout", _i, [_vp, _i, _i, _i, _vp, C.POINTER(_vp)]),
+    ("pwn_viewports_layout_free", _i, [_vp, _vp]),
+    ("pwn_viewports_layout_info", _i, [_vp, _vp]),
+    ("pwn_trace_viewports_device", _i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     ("pwn_pixel_rays", _i, [_i, _i, _vp, _i, _vp, _vp, _vp]),
     ("pwn_pixel_rays_device", _i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     ("pwn_trace_rays", _i, [_vp, _i, _vp, _vp, _f, _vp, _vp]),

@@ -84,7 +84,7 @@ extern "C" int pwn_init(pwn_ctx **out, int device, int width, int height)
 	c->d_pre = c->d_out = NULL; c->d_z = NULL; c->d_skip = NULL; c->d_counters = NULL; c->d_tickets = NULL; c->ticket_set = 0; c->launch_rot = 2; c->launch_waits = 0;
 	c->grid_reserve = 0;
 	c->d_vpre = c->d_vout = NULL; c->d_vz = NULL; c->views_cap = 0; c->h_vrec = c->d_vrec = NULL; c->d_vrec_dev = NULL;
-	c->d_ppre = c->d_pout = NULL; c->d_pz = NULL; c->h_prec = c->d_prec = NULL;
+	c->d_ppre = c->d_pout = NULL; c->d_pz = NULL; c->h_prec = c->d_prec = NULL; c->d_prec_dev = NULL;
 	c->h_rays = c->d_rays = NULL; c->rays_cap = 0;
 	c->h_hits = c->d_hits = NULL; c->hits_cap = 0;
 	c->h_players = c->d_players = NULL; c->players_cap = 0; c->dbg_players_stage = -1;
@@ -234,6 +234,7 @@ extern "C" void pwn_destroy(pwn_ctx *c)
 		(void)hipFree(c->d_big[i]);
 	}
 	pwn_i_spheres_device_release(c);
+	pwn_i_viewports_device_release(c);
 	for(int i = 0; i < PWN_NSTAGE; i++)
 	{
 		if(c->ev_stage[i]) (void)hipEventDestroy(c->ev_stage[i]);

@@ -540,6 +540,31 @@ static int viewports_reserve(pwn_ctx *c, hipStream_t s)
 	return PWN_OK;
 }
 
+// The order of the records and their geometry words (pwn_internal.h): what the host form makes per call and a layout of the device
+// form bakes once.  Rising units (tables.h pwn_viewport_rec: the kernel's rounds), ties in the given order.
+uint32_t pwn_i_viewport_recs_bake(int n, const pwn_viewport *vp, pwn_viewport_rec *recs, int *ord)
+{
+	uint32_t vu[PWN_VIEWS_MAX];
+	for(int i = 0; i < n; i++) { ord[i] = i; vu[i] = (uint32_t)((vp[i].w + 15) / 16) * (uint32_t)((vp[i].h + 3) / 4); }
+	std::stable_sort(ord, ord + n, [&vu](int a, int b) { return vu[a] < vu[b]; });
+	uint32_t first = 0u, prev = 0u;
+	for(int j = 0; j < n; j++)
+	{
+		const int i = ord[j];
+		pwn_viewport_rec &r = recs[j];
+		r.x = vp[i].x; r.y = vp[i].y; r.w = vp[i].w; r.h = vp[i].h;
+		r.units_x = (uint32_t)((vp[i].w + 15) / 16); r.rows_u = (uint32_t)((vp[i].h + 3) / 4); r.units = vu[i];
+		int sh;
+		pwn_unit_div_magic(r.units_x, &r.ux_magic, &sh); r.ux_shift = sh;
+		// segment j: rounds [prev, units) of the views j .. n-1
+		r.seg_first = first; r.seg_round = prev;
+		pwn_unit_div_magic((uint32_t)(n - j), &r.seg_magic, &sh); r.seg_shift = sh;
+		first += (uint32_t)(n - j) * (r.units - prev); prev = r.units;
+		r.pad_[0] = r.pad_[1] = 0u;
+	}
+	return first;
+}
+
 extern "C" int pwn_trace_viewports(pwn_ctx *c, int n, const pwn_viewport *vp, const float *cams, const float *secs, uint32_t *sbuf, float *zbuf)
 {
 	GRP_REFUSE(c, "pwn_trace_viewports");
@@ -563,11 +588,8 @@ extern "C" int pwn_trace_viewports(pwn_ctx *c, int n, const pwn_viewport *vp, co
 	// call's own frame_setup for a frame of the VIEW's size (this file's operation order is part of the bit-exact path).
 	// (the staging is free: the call before this one ended with the stream drained)
 	int ord[PWN_VIEWS_MAX];
-	uint32_t vu[PWN_VIEWS_MAX];
-	for(int i = 0; i < n; i++) { ord[i] = i; vu[i] = (uint32_t)((vp[i].w + 15) / 16) * (uint32_t)((vp[i].h + 3) / 4); }
-	std::stable_sort(ord, ord + n, [&vu](int a, int b) { return vu[a] < vu[b]; });
+	const uint32_t first = pwn_i_viewport_recs_bake(n, vp, c->h_prec, ord);
 	bool has_w = false;
-	uint32_t first = 0u, prev = 0u;
 	for(int j = 0; j < n; j++)
 	{
 		const int i = ord[j];
@@ -575,15 +597,6 @@ extern "C" int pwn_trace_viewports(pwn_ctx *c, int n, const pwn_viewport *vp, co
 		pwn_viewport_rec &r = c->h_prec[j];
 		frame_setup(vp[i].w, vp[i].h, cam, &r);
 		r.sec_current = secs[i];
-		r.x = vp[i].x; r.y = vp[i].y; r.w = vp[i].w; r.h = vp[i].h;
-		r.units_x = (uint32_t)((vp[i].w + 15) / 16); r.rows_u = (uint32_t)((vp[i].h + 3) / 4); r.units = vu[i];
-		int sh;
-		pwn_unit_div_magic(r.units_x, &r.ux_magic, &sh); r.ux_shift = sh;
-		// segment j: rounds [prev, units) of the views j .. n-1
-		r.seg_first = first; r.seg_round = prev;
-		pwn_unit_div_magic((uint32_t)(n - j), &r.seg_magic, &sh); r.seg_shift = sh;
-		first += (uint32_t)(n - j) * (r.units - prev); prev = r.units;
-		r.pad_[0] = r.pad_[1] = 0u;
 		if(camera_has_w(cam)) has_w = true;
 	}
 	if((unsigned long long)first != plan[0]) { snprintf(c->err, sizeof(c->err), "pwn_trace_viewports: %u units in the records, %llu planned", first, plan[0]); return PWN_EINVAL; }
@@ -597,7 +610,7 @@ extern "C" int pwn_trace_viewports(pwn_ctx *c, int n, const pwn_viewport *vp, co
 		HIPCHK(c, hipMemsetAsync(c->d_ppre, 0, plane * 4, s));
 		if(c->blur_passes > 0) HIPCHK(c, hipMemsetAsync(c->d_pout, 0, plane * 4, s));
 	}
-	const pwn_vps_launch V = { c->d_prec, c->h_prec, n, has_w, first };
+	const pwn_vps_launch V = { c->d_prec, c->h_prec, n, has_w, first, 0, 0, NULL };
 	pwn_trace_launch T = { .y0 = 0, .y1 = c->h, .vps = V, .d_sbuf = c->d_ppre, .d_zbuf = c->d_pz, .stream = s };
 	rc = pwn_i_launch_trace(c, &T);
 	if(rc != PWN_OK) return rc;

@@ -7,6 +7,7 @@
 //   pwn_players.cpp the players' step: a batch of cameras walked through the level (host and device form)
 //   pwn_pixel_rays.cpp  pixel rays from cameras on the device (pwn_pixel_rays_device)
 //   pwn_spheres_device.cpp  the sphere tables built on the device (pwn_upload_spheres_device)
+//   pwn_viewports_device.cpp  views of their own sizes from device cameras (pwn_viewports_layout, pwn_trace_viewports_device)
 //   pwn_frames.cpp  frames in flight
 //   pwn_tiled.cpp   row tiling over RCCL
 //   pwn_group.cpp   several contexts behind one handle
@@ -37,12 +38,16 @@ struct pwn_views_launch
 // Views of their own sizes in rectangles of one frame (pwn_trace_viewports) as what a launch traces or blurs: n records (tables.h
 // pwn_viewport_rec) on the device, in the order the trace kernel expects, and the same records on the host (the blur launcher
 // counts the tiles of the shape it picks); units = the launch's 16 x 4 units over all views.  n = 0: none.
+// fw x fh: the size of the planes the rectangles lie in (fw is their pitch), 0 = the context's (pwn_trace_viewports); d_skip: the
+// blur's skip-ahead table where the context's may be too short for the widest view (pwn_trace_viewports_device), NULL = the context's.
 struct pwn_vps_launch
 {
 	const pwn_viewport_rec *d_recs, *h_recs;
 	int n;
 	bool has_w;
 	uint32_t units;
+	int fw, fh;
+	const uint2 *d_skip;
 };
 
 // A batch of caller-supplied rays (pwn_trace_rays / pwn_trace_rays_device; tables.h pwn_trace_params.rays): n rays into
@@ -106,6 +111,11 @@ extern "C" hipError_t pwn_launch_upscale(const uint32_t *src, uint32_t *dst, int
 extern "C" hipError_t pwn_launch_upload(const void *h_pinned_src, void *d_dst, size_t bytes, hipStream_t stream);
 // the camera set-up of n views from device memory (view_setup.hip): d_cams n x 16 floats and d_out 16-byte aligned; d_secs NULL: every time 0
 extern "C" hipError_t pwn_launch_view_setup(const float *d_cams, const float *d_secs, pwn_view_rec *d_out, int n, int w, int h, hipStream_t stream);
+// the records of pwn_trace_viewports_device (viewport_setup.hip): record j's geometry words from the layout's master copy d_master, its
+// head from camera d_perm[j] and time d_secs[d_perm[j]] with the view's own scalars d_scal[j] = (-yrat, xsrat, ysrat, 0); all but
+// d_secs and d_perm 16-byte aligned, every d_perm[j] < n
+extern "C" hipError_t pwn_launch_viewport_setup(const pwn_viewport_rec *d_master, const float *d_scal, const uint32_t *d_perm,
+	const float *d_cams, const float *d_secs, pwn_viewport_rec *d_out, int n, hipStream_t stream);
 // ticks of host/player.c's pwn_player_step for n players (player_step.hip): d_cams n x 16 floats and d_gravity n x 4 floats, 16-byte aligned,
 // d_traversals n int32 or NULL, d_keys n bytes; stage != 0: every workgroup copies the walk table into LDS first
 extern "C" hipError_t pwn_launch_players_step(float *d_cams, float *d_gravity, int32_t *d_traversals, const uint8_t *d_keys, int n,
@@ -345,6 +355,10 @@ struct pwn_ctx
 	// of the call in pinned staging and on the device (PWN_VIEWS_MAX of them)
 	uint32_t *d_ppre, *d_pout; float *d_pz;
 	pwn_viewport_rec *h_prec, *d_prec;
+	// pwn_trace_viewports_device (pwn_viewports_device.cpp): PWN_VIEWS_MAX records per ticket set, as d_vrec_dev, allocated by the first
+	// call; the layouts alive (pwn_viewports_layout), which pwn_destroy frees
+	pwn_viewport_rec *d_prec_dev;
+	std::vector<struct pwn_vp_layout *> vp_layouts;
 	// pwn_trace_rays: room for rays_cap rays in pinned staging and on the device, 44 B each (record, seed, depth, colour; pwn_calls.cpp pwn_i_staging_reserve)
 	unsigned char *h_rays, *d_rays; size_t rays_cap;
 	// pwn_trace_hits: the same for hits_cap rays, 32 B in (record) and 48 B out (pwn_hit) each; pwn_trace_view_hits stages its planes
@@ -431,6 +445,11 @@ void pwn_i_frames_release(pwn_ctx *c);
 void pwn_i_expand_tables(uint16_t *rcp, uint16_t *rsq);
 int pwn_i_pack_blob(pwn_ctx *c);
 void pwn_i_spheres_device_release(pwn_ctx *c);      // pwn_spheres_device.cpp: the device builder's buffers and events gone (pwn_destroy)
+void pwn_i_viewports_device_release(pwn_ctx *c);    // pwn_viewports_device.cpp: every layout and the records gone (pwn_destroy, streams idle)
+// pwn_calls.cpp, shared with pwn_viewports_device.cpp: the records of n rectangles in order of rising units, ties in the given order --
+// recs[j] stands for rectangle ord[j]; its geometry words (rectangle, units, division constants, segment) are filled in, its head
+// (rayb .. sec_current) is left alone.  Returns the units of all views.
+uint32_t pwn_i_viewport_recs_bake(int n, const pwn_viewport *vp, pwn_viewport_rec *recs, int *ord);
 void pwn_tiled_destroy(pwn_ctx *c);
 bool pwn_tiled_busy(pwn_ctx *c);        // frames of the row tiling in flight
 // pwn_tiled.cpp internals used by pwn_group.cpp: a member's frame with the host buffers its strip is delivered into (NULL: the

@@ -253,7 +253,9 @@ int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L)
 	// (a batch has every view's camera set-up and time in its record, every ray's origin and direction in its own)
 	if(!batch) frame_setup(c->w, c->h, L->cam, &P);
 	P.sec_current = L->sec;
-	P.w = c->w; P.h = c->h; P.y0 = y0; P.y1 = y1;
+	// (views of their own sizes in planes of the caller's, pwn_trace_viewports_device: the planes' size, not the context's)
+	const int fw = vps != NULL && vps->fw > 0 ? vps->fw : c->w, fh = vps != NULL && vps->fh > 0 ? vps->fh : c->h;
+	P.w = fw; P.h = fh; P.y0 = y0; P.y1 = y1;
 	if(views != NULL)
 	{
 		P.views = views->d_recs; P.nviews = views->n; P.plane = views->plane;
@@ -292,7 +294,7 @@ int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L)
 	P.refill_limit = c->refill_limit;
 
 	// the geometry (launch_plan.h): the units, how they are handed out, the grid
-	pwn_launch_shape S = { .w = c->w, .y0 = y0, .y1 = y1, .tile_w = pwn_trace_tile_w(), .tile_h = pwn_trace_tile_h() };
+	pwn_launch_shape S = { .w = fw, .y0 = y0, .y1 = y1, .tile_w = pwn_trace_tile_w(), .tile_h = pwn_trace_tile_h() };
 	if(views != NULL) { S.kind = PWN_LAUNCH_VIEWS; S.n = (uint32_t)views->n; }
 	if(vps != NULL) { S.kind = PWN_LAUNCH_VIEWPORTS; S.n = (uint32_t)vps->n; S.vp_units = vps->units; }
 	if(rays != NULL) { S.kind = PWN_LAUNCH_RAYS; S.n = rays->n; }
@@ -378,14 +380,16 @@ extern "C" int pwn_unit_order_state(pwn_ctx *c, unsigned long long out[4])
 
 int pwn_i_launch_blur(pwn_ctx *c, const pwn_blur_launch *L)
 {
-	if((c->w & 3) != 0) return PWN_EINVAL; // screen.h:88,117: aligned 16-B store per group
+	const pwn_vps_launch *vps = L->vps.n > 0 ? &L->vps : NULL;
+	// (views of their own sizes in planes of the caller's, pwn_trace_viewports_device: the planes' size and the layout's skip-ahead table)
+	const int fw = vps != NULL && vps->fw > 0 ? vps->fw : c->w, fh = vps != NULL && vps->fh > 0 ? vps->fh : c->h;
+	if((fw & 3) != 0) return PWN_EINVAL; // screen.h:88,117: aligned 16-B store per group
 	pwn_blur_params B;
 	B.views = L->views; B.plane = (unsigned long long)c->w * (unsigned long long)c->h;
-	const pwn_vps_launch *vps = L->vps.n > 0 ? &L->vps : NULL;
 	B.vps = vps != NULL ? vps->d_recs : NULL; B.nvp = vps != NULL ? vps->n : 0; B.vp_tiles = 0;
-	B.w = c->w; B.h = c->h; B.y0 = L->y0; B.y1 = L->y1;
-	B.groups = c->w / 4;
-	B.pre = L->d_pre; B.zbuf = L->d_z; B.out = L->d_out; B.skip = c->d_skip;
+	B.w = fw; B.h = fh; B.y0 = L->y0; B.y1 = L->y1;
+	B.groups = fw / 4;
+	B.pre = L->d_pre; B.zbuf = L->d_z; B.out = L->d_out; B.skip = vps != NULL && vps->d_skip != NULL ? vps->d_skip : c->d_skip;
 	B.avail_y0 = L->avail_y0; B.avail_y1 = L->avail_y1; B.miss = L->d_miss;
 	B.cost_acc = L->d_cost_acc; B.cost_out = L->d_cost_out;
 	B.cost_mul = L->cost_mul ? L->cost_mul : 1u; B.cost_div = L->cost_div ? L->cost_div : 1u;

@@ -66,6 +66,9 @@ class Renderer:
         if getattr(self, "_ctx", None) is not None and self._ctx.value:
             lib.pwn_destroy(self._ctx)
             self._ctx = C.c_void_p()
+            for lay in getattr(self, "_layouts", None) or []:       # (pwn_destroy freed them)
+                lay._ptr = None
+            self._layouts = []
 
     def __del__(self):
         try:
@@ -354,6 +357,56 @@ class Renderer:
         self._chk(lib.pwn_trace_viewports(self._ctx, n, rects.ctypes.data, cams.ctypes.data, secs.ctypes.data, sbuf.ctypes.data,
                                           zbuf.ctypes.data if want_z else None), "pwn_trace_viewports")
         return sbuf, zbuf
+
+    def viewports_layout(self, W, H, rects):
+        """pwn_viewports_layout: the part of trace_viewports_device that is known beforehand -- a frame of W x H (any size, not
+        this context's) and rects (n,4) int (x, y, w, h) inside it, no two overlapping.  Made once (blocks, allocates), used by any
+        number of calls.  Returns a ViewportsLayout with .info() and .free(); closing the renderer frees what is left."""
+        rects = _rect_records(rects, "viewports_layout")
+        ptr = C.c_void_p()
+        self._chk(lib.pwn_viewports_layout(self._ctx, int(W), int(H), rects.shape[0], rects.ctypes.data, C.byref(ptr)), "pwn_viewports_layout")
+        lay = ViewportsLayout(self, ptr, int(W), int(H), rects.shape[0])
+        if getattr(self, "_layouts", None) is None:
+            self._layouts = []
+        self._layouts.append(lay)
+        return lay
+
+    def trace_viewports_device(self, layout, cams, secs, sbuf, zbuf, work=None, has_w=False, stream=None):
+        """pwn_trace_viewports_device: the views of a viewports_layout from cameras on the GPU into ONE frame of the layout's W x H on
+        the GPU, stream-ordered, no synchronisation and no host copy.  All torch tensors on this context's GPU, contiguous and
+        16-byte aligned: cams (n,16) or (n,4,4) float32, camera i for rectangle i; secs (n,) float32; sbuf (H,W) int32 or uint32
+        (rectangle i as trace_screen_centred renders it on a context of w_i x h_i; nothing outside the rectangles is written);
+        zbuf (H,W) float32 (in / out: a primary ray that runs out of steps keeps what it holds); work (H,W) int32 or uint32 scratch,
+        needed with blur on.  has_w and stream as trace_views_device takes them."""
+        import torch
+        who = "trace_viewports_device"
+        if not isinstance(layout, ViewportsLayout) or layout._ptr is None or layout._renderer is not self:
+            raise ValueError("%s: layout must be a live ViewportsLayout of this renderer" % who)
+        words = (torch.int32, getattr(torch, "uint32", torch.int32))
+        if isinstance(cams, torch.Tensor) and cams.dim() == 3 and tuple(cams.shape[1:]) == (4, 4) and cams.is_contiguous():
+            cams = cams.view(cams.shape[0], 16)
+        n = _tensor_check(torch, cams, "cams", (torch.float32,), 2, layout.n, who=who)
+        if cams.shape[1] != 16:
+            raise ValueError("%s: cams must have shape (%d,4,4) or (%d,16), not %s" % (who, layout.n, layout.n, tuple(cams.shape)))
+        _tensor_check(torch, secs, "secs", (torch.float32,), 1, n, who=who)
+        planes = [("sbuf", sbuf, words), ("zbuf", zbuf, (torch.float32,))] + ([("work", work, words)] if work is not None else [])
+        for name, t, dtypes in planes:
+            _tensor_check(torch, t, name, dtypes, 2, who=who)
+            if tuple(t.shape) != (layout.H, layout.W):
+                raise ValueError("%s: %s must have shape (%d,%d), not %s" % (who, name, layout.H, layout.W, tuple(t.shape)))
+        for name, t in [("cams", cams), ("secs", secs)] + [(name, t) for name, t, _ in planes]:
+            if t.device != cams.device:
+                raise ValueError("%s: tensors on %s and %s" % (who, cams.device, t.device))
+            if t.data_ptr() % 16 != 0:
+                raise ValueError("%s: %s is not 16-byte aligned" % (who, name))
+        if stream is None:
+            stream = torch.cuda.current_stream(cams.device)
+        if not isinstance(stream, int):
+            stream = stream.cuda_stream
+        self._chk(lib.pwn_trace_viewports_device(self._ctx, layout._ptr, C.c_void_p(cams.data_ptr()), C.c_void_p(secs.data_ptr()),
+                                                 _lib.PWN_VIEWS_HAS_W if has_w else 0,
+                                                 C.c_void_p(work.data_ptr() if work is not None else None), C.c_void_p(sbuf.data_ptr()),
+                                                 C.c_void_p(zbuf.data_ptr()), C.c_void_p(stream or 0)), "pwn_trace_viewports_device")
 
     # -- caller-supplied rays (pwn_trace_rays) --------------------------------
     def pixel_rays(self, cam, xy=None, order="rows"):
@@ -915,6 +968,35 @@ def sphere_bounds_plan(spheres):
         raise PwnError(rc, "pwn_sphere_bounds_plan")
     return [{"cell": int(o[0]), "records": int(o[1]), "id": int(o[2]), "centre": (float(o[3]), float(o[4]), float(o[5])),
              "r_eff": float(o[6]), "rr": float(o[7])} for o in out[:rc]]
+
+
+class ViewportsLayout:
+    """A layout of Renderer.viewports_layout (pwn_vp_layout): frame size W x H and n rectangles, for trace_viewports_device."""
+
+    def __init__(self, renderer, ptr, W, H, n):
+        self._renderer, self._ptr, self.W, self.H, self.n = renderer, ptr, W, H, n
+
+    def info(self):
+        """pwn_viewports_layout_info: dict(W, H, n, units, pixels, blur_ok)"""
+        if self._ptr is None:
+            raise ValueError("ViewportsLayout.info: the layout was freed")
+        out = (C.c_uint64 * 6)()
+        rc = lib.pwn_viewports_layout_info(self._ptr, out)
+        if rc != 0:
+            raise PwnError(rc, "pwn_viewports_layout_info")
+        d = dict(zip(("W", "H", "n", "units", "pixels"), (int(v) for v in out)))
+        d["blur_ok"] = bool(out[5])
+        return d
+
+    def free(self):
+        """pwn_viewports_layout_free: waits for the last launches that read the layout, then frees it (once; later calls do nothing)"""
+        if self._ptr is None:
+            return
+        ptr, self._ptr = self._ptr, None
+        r = self._renderer
+        if self in (getattr(r, "_layouts", None) or []):
+            r._layouts.remove(self)
+        r._chk(lib.pwn_viewports_layout_free(r._ctx, ptr), "pwn_viewports_layout_free")
 
 
 def _rect_records(rects, who):

@@ -23,6 +23,7 @@ void (*pwn_fake_blur_hook)(const pwn_blur_params *B) = NULL;
 void (*pwn_fake_launch_hook)(const char *name, const void *src, const void *dst, int nsizes, const size_t *sizes) = NULL;
 void (*pwn_fake_players_hook)(const pwn_walk_table *walk, int n, int ticks, int stage) = NULL;
 void (*pwn_fake_sphere_bins_hook)(const void *d_scratch, const void *d_base, const void *d_blob) = NULL;
+void (*pwn_fake_viewport_setup_hook)(const pwn_viewport_rec *master, const float *scal, const uint32_t *perm, const pwn_viewport_rec *out, int n) = NULL;
 }
 static void small_launch(const char *name, const void *src, const void *dst, std::initializer_list<size_t> sizes)
 {
@@ -131,6 +132,32 @@ extern "C" hipError_t pwn_launch_view_setup(const float *cams, const float *secs
 		r.sec_current = secs != NULL ? secs[v] : 0.0f;
 		out[v] = r;
 	}
+	return hipSuccess;
+}
+// (the records of pwn_trace_viewports_device; viewports_device_driver.cpp: viewport_setup.hip's algorithm, one record after the other --
+// the geometry words from the master copy, the head from camera perm[j] with the view's own scalars, every product and sum rounded
+// by itself.  Reads exactly n master records, n scalar words, n perm entries, n cameras and n times, writes n records.)
+extern "C" hipError_t pwn_launch_viewport_setup(const pwn_viewport_rec *master, const float *scal, const uint32_t *perm,
+	const float *cams, const float *secs, pwn_viewport_rec *out, int n, hipStream_t)
+{
+	small_launch("viewport_setup", cams, out, { (size_t)n });
+	for(int j = 0; j < n; j++)
+	{
+		const uint32_t i = perm[j];
+		if(i >= (uint32_t)n) continue;
+		const float *cam = cams + 16 * (size_t)i, yrat_neg = scal[4 * (size_t)j], xsrat = scal[4 * (size_t)j + 1], ysrat = scal[4 * (size_t)j + 2];
+		pwn_viewport_rec r = master[j];
+		for(int k = 0; k < 4; k++)
+		{
+			r.rayb[k] = (cam[0 + k] + cam[8 + k]) + yrat_neg * cam[4 + k];
+			r.rdx[k] = xsrat * cam[0 + k];
+			r.rdy[k] = ysrat * cam[4 + k];
+		}
+		memcpy(r.from, cam + 12, 16);
+		memcpy(&r.sec_current, secs + i, 4);
+		out[j] = r;
+	}
+	if(pwn_fake_viewport_setup_hook != NULL) pwn_fake_viewport_setup_hook(master, scal, perm, out, n);
 	return hipSuccess;
 }
 // (the players' step: every player's position moves by a number that depends on its key byte, the ticks and the walk table -- which

@@ -13,6 +13,15 @@ Every figure is the median of --reps calls, and every layout is measured --repea
 Colour only (no depth plane to the host); the frame buffers are registered with the device (pwn_host_register) unless --no-register.
 
     python tools/viewports_bench.py [--reps 20] [--repeats 3] [--layouts grid16,grid64,split,mixed] [--out profiles/viewports/bench.jsonl]
+
+--device-form measures pwn_trace_viewports_device instead (stream time between two events around the call, trace and blur; the two
+sides of each comparison alternate call by call in one run, medians of --reps, --repeats lines each) and writes text:
+  atlas   64 views of 160x120 into a 1280x960 atlas on a 3840x2160 context, against the same pixels through pwn_trace_views_device
+          on a 160x120 context -- what the library could do before this call existed
+  host    layout L1 of tests/test_gpu_viewports.py (eight views that tile 336x208) on a 3840x2160 context: the device form's stream
+          time against the host form pwn_trace_viewports' total_ms on a 336x208 context (which includes its copy to the host)
+
+    python tools/viewports_bench.py --device-form [--out profiles/viewports/device_form.txt]
 """
 import argparse
 import json
@@ -52,6 +61,106 @@ def cameras(spawn, n, seed):
     return cams, np.zeros(n, np.float32)
 
 
+def device_form(args):
+    import torch
+    import pwnfps_amd
+    level = os.path.join(GOLD, "levels", "pwnfps_level.txt")
+    sph = np.load(os.path.join(GOLD, "spheres_t0.npy"))
+    dev = torch.device("cuda", 0)
+    out = open(args.out, "w")
+
+    def say(line):
+        print(line, flush=True)
+        out.write(line + "\n"); out.flush()
+
+    def renderer(w, h):
+        r = pwnfps_amd.Renderer(w, h)
+        r.level_load(level)
+        r.set_objects(sph)
+        r.set_blur_passes(args.blur)
+        return r
+
+    def timed(fn, stream):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        fn()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    med = lambda v: float(np.median(v))       # noqa: E731
+    say("# tools/viewports_bench.py --device-form: blur %d, medians of %d calls, the two sides alternating call by call, %d repeats" % (args.blur, args.reps, args.repeats))
+    big = renderer(3840, 2160)
+    _, _, spawn = big.get_level()
+    stream = torch.cuda.Stream(dev)
+    with torch.cuda.stream(stream):
+        # (a) the atlas against the parent's route
+        n, vw, vh = 64, 160, 120
+        W, H = 8 * vw, 8 * vh
+        rects = [(vw * (i % 8), vh * (i // 8), vw, vh) for i in range(n)]
+        cams, secs = cameras(spawn, n, args.seed + n)
+        t_cams = torch.from_numpy(cams.reshape(n, 16).copy()).to(dev)
+        t_secs = torch.from_numpy(secs.copy()).to(dev)
+        lay = big.viewports_layout(W, H, rects)
+        a_sb, a_work = (torch.zeros((H, W), dtype=torch.int32, device=dev) for _ in range(2))
+        a_z = torch.zeros((H, W), dtype=torch.float32, device=dev)
+        small = renderer(vw, vh)
+        v_sb, v_work = (torch.zeros((n, vh, vw), dtype=torch.int32, device=dev) for _ in range(2))
+        v_z = torch.zeros((n, vh, vw), dtype=torch.float32, device=dev)
+        f_atlas = lambda: big.trace_viewports_device(lay, t_cams, t_secs, a_sb, a_z, work=a_work)      # noqa: E731
+        f_views = lambda: small.trace_views_device(t_cams, t_secs, v_sb, v_z, work=v_work)             # noqa: E731
+        f_atlas(); f_views()
+        stream.synchronize()
+        same = all(bool((a_sb[y:y + h, x:x + w] == v_sb[i]).all()) for i, (x, y, w, h) in enumerate(rects))
+        say("(a) atlas: %d views of %d x %d into %d x %d on a 3840 x 2160 context (new) / pwn_trace_views_device on a %d x %d context (parent's route); same pixels: %s"
+            % (n, vw, vh, W, H, vw, vh, same))
+        for rep_no in range(args.repeats):
+            ta, tv = [], []
+            for rep in range(args.warmup + args.reps):
+                x, y = timed(f_atlas, stream), timed(f_views, stream)
+                if rep >= args.warmup:
+                    ta.append(x); tv.append(y)
+            say("    repeat %d: atlas %.4f ms (min %.4f max %.4f)   views %.4f ms (min %.4f max %.4f)   atlas / views %.3f"
+                % (rep_no, med(ta), min(ta), max(ta), med(tv), min(tv), max(tv), med(ta) / med(tv)))
+        lay.free()
+        small.close()
+        # (b) the device form against the host form
+        # (layout L1 of tests/test_gpu_viewports.py: eight views that tile 336 x 208, from 4 x 4 pixels to 196 x 108)
+        W, H, rects = 336, 208, [(0, 0, 160, 100), (160, 0, 176, 100), (0, 100, 100, 108), (100, 100, 36, 38), (136, 100, 4, 4), (136, 104, 4, 104),
+                                 (100, 138, 36, 70), (140, 100, 196, 108)]
+        n = len(rects)
+        cams, secs = cameras(spawn, n, args.seed + n)
+        t_cams = torch.from_numpy(cams.reshape(n, 16).copy()).to(dev)
+        t_secs = torch.from_numpy(secs.copy()).to(dev)
+        lay = big.viewports_layout(W, H, rects)
+        d_sb, d_work = (torch.zeros((H, W), dtype=torch.int32, device=dev) for _ in range(2))
+        d_z = torch.zeros((H, W), dtype=torch.float32, device=dev)
+        host = renderer(W, H)
+        frame = np.empty((H, W), np.uint32)
+        host.host_register(frame)
+        f_dev = lambda: big.trace_viewports_device(lay, t_cams, t_secs, d_sb, d_z, work=d_work)        # noqa: E731
+        f_dev()
+        host.trace_viewports(rects, cams, secs, want_z=False, sbuf=frame)
+        stream.synchronize()
+        same = bool((d_sb.cpu().numpy().view(np.uint32) == frame).all())
+        say("(b) L1: %d views of their own sizes into %d x %d: the device form on a 3840 x 2160 context (stream time) / pwn_trace_viewports on a %d x %d context (its trace + blur, its total_ms with the copy to the host); same pixels: %s"
+            % (n, W, H, W, H, same))
+        for rep_no in range(args.repeats):
+            td, tk, tt = [], [], []
+            for rep in range(args.warmup + args.reps):
+                x = timed(f_dev, stream)
+                host.trace_viewports(rects, cams, secs, want_z=False, sbuf=frame)
+                st = host.stats()
+                if rep >= args.warmup:
+                    td.append(x); tk.append(st["trace_ms"] + st["blur_ms"]); tt.append(st["total_ms"])
+            say("    repeat %d: device form %.4f ms (min %.4f max %.4f)   host form kernels %.4f ms, total %.4f ms (min %.4f max %.4f)   device / host total %.3f, device / host kernels %.3f"
+                % (rep_no, med(td), min(td), max(td), med(tk), med(tt), min(tt), max(tt), med(td) / med(tt), med(td) / med(tk)))
+        lay.free()
+        host.close()
+    big.close()
+    out.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -61,8 +170,13 @@ def main():
     ap.add_argument("--blur", type=int, default=1)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--no-register", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "viewports", "bench.jsonl"))
+    ap.add_argument("--device-form", action="store_true")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "viewports", "device_form.txt" if args.device_form else "bench.jsonl")
+    if args.device_form:
+        return device_form(args)
     import pwnfps_amd
     level = os.path.join(GOLD, "levels", "pwnfps_level.txt")
     sph = np.load(os.path.join(GOLD, "spheres_t0.npy"))
