@@ -795,6 +795,60 @@ int pwn_trace_view_hits_device(pwn_ctx *ctx, int n, const void *d_cams, int flag
 	void *d_label, void *d_cell, void *d_dist, void *stream);
 
 /*
+ * First-hit planes of views of their OWN sizes: pwn_trace_view_hits' three planes for the rectangles of pwn_trace_viewports -- label and
+ * depth observations of agents at their own resolutions in one atlas beside a 4K spectator frame, from the ONE context that holds the
+ * level and the tables of pwn_upload_spheres_device; picking by look-up under a split screen or a picture-in-picture frame at 12 B a
+ * pixel.  n views, view i a frame of its own of w_i x h_i in rectangle vp[i] of a frame of W x H.
+ *   cams                 n x 16 floats, camera i for rectangle i.  No secs, no seed, no blur: the primary segment reads no time and
+ *                        draws no random number.
+ *   planes               label, cell, dist: ONE plane of W x H 32-bit words each, pitch W (the host form: the context's w x h).  label is
+ *                        required; cell and dist may be NULL and are then not written.  EVERY pixel of every rectangle is written in
+ *                        every plane given: nothing is in / out, nothing persists between calls.
+ *   exactness            pixel (x, y) of rectangle i, local to the rectangle, holds what pwn_trace_view_hits writes for pixel (x, y) of a
+ *                        one-view batch of cams[i] on a context of size w_i x h_i with the same level and objects -- and so, through
+ *                        that call's contract, the pwn_hit that pwn_trace_hits returns for pwn_pixel_rays(w_i, h_i, cams[i], (x, y)),
+ *                        bit for bit: label with the PWN_LABEL_* packing, cell = the record's last word, dist = pwn_hit.dist;
+ *                        PWN_HIT_NONE gives 0 in all three.  The view is a frame of its own: the camera set-up of a w_i x h_i frame
+ *                        and the 32-pixel add chain from the view's local column 0.
+ *   outside the rectangles   the host form gives 0 in every plane given (it owns its staging, as pwn_trace_viewports clears its
+ *                        planes); the device form writes nothing there: several calls and several layouts may fill one atlas, as
+ *                        with pwn_trace_viewports_device.
+ *   rectangles           pwn_viewports_plan(W, H, 0, ...)'s rules, by calling that function: any rectangle inside W x H that overlaps
+ *                        no other.  No % 4 rule: PWN_OPT_BLUR_PASSES is ignored.
+ *   w lanes              the host form looks at the cameras; the device form takes PWN_VIEWS_HAS_W, as pwn_trace_views_device.
+ *   ordering             the host form behind the frames in flight, and ends with its stream drained, as pwn_trace_view_hits.
+ *   counters             with PWN_OPT_COUNTERS on: rays = the pixels covered, and steps, portals, sphere_tests and exhausted of the
+ *                        primary segments, as pwn_trace_hits counts them, summed over the views.  The host form sets trace_ms (upload
+ *                        and trace) and total_ms, blur_ms 0; the device form sets no timings.
+ *   not followed         as pwn_trace_view_hits[_device]: always the units scheduler, never row strips, no unit order, no wave log, no blur.
+ *   left alone           what pwn_trace_view_hits[_device] leaves alone, and the planes and the depth plane of pwn_trace_viewports, the
+ *                        view slots, the blocking call's planes, the unit-order state, the trace-room measurement, the call-strips window.
+ *   cost                 the host form keeps 12 B per pixel of W x H in pinned host memory and as much device memory between calls:
+ *                        they are pwn_trace_hits' buffers, and the larger need counts.  Its records are pwn_trace_viewports' (128 B a
+ *                        view for PWN_VIEWS_MAX views, pinned and on the device, with the first call of either).  The device form's
+ *                        records are pwn_trace_viewports_device's.  pwn_destroy frees them.
+ *   errors               PWN_EINVAL for a NULL ctx / vp / cams / label and for what pwn_viewports_plan refuses; PWN_ENOLEVEL,
+ *                        PWN_ENOTSUP on a pwn_init_multi handle and PWN_EBUSY under a row tiling, as pwn_trace_viewports;
+ *                        PWN_ENOMEM when the staging cannot grow.
+ */
+/* Blocking, host memory: planes of the context's W x H, pitch W. */
+int pwn_trace_viewport_hits(pwn_ctx *ctx, int n, const pwn_viewport *vp, const float *cams,
+	uint32_t *label, uint32_t *cell, float *dist);
+/* Device form: a layout (pwn_viewports_layout), cameras and planes of the CALLER's in device memory, stream-ordered.  Any layout of
+   this context: whether it is usable with blur plays no part.  d_cams n x 16 floats, camera i for rectangle i (the array
+   pwn_players_step_device steps); the planes W x H words of the layout's frame size, pitch W; all pointers 16-byte aligned.  flags: 0
+   or PWN_VIEWS_HAS_W.  One set-up launch and one trace launch on `stream`, nothing else; after the context's first such call (or
+   first pwn_trace_viewports_device, whose records these are) no allocation, no copy from host memory, no host wait and no
+   synchronisation.  The trace launch falls under the rule for trace launches at the top of this file and uses the viewport records
+   of the counter set it counts in; a call that leaves the rotation is put behind launch n - R on `stream` before its set-up kernel
+   writes.  A use of the layout records the event pwn_viewports_layout_free waits for.  PWN_EINVAL for a NULL ctx / layout / d_cams /
+   d_label, a layout of another context (or a freed one), flags other than PWN_VIEWS_HAS_W, a pointer that is not 16-byte aligned,
+   any two of the given plane ranges (W x H x 4 bytes each) overlapping; PWN_ENOLEVEL, PWN_ENOTSUP and PWN_EBUSY as the host form.
+   A refused call launches nothing and changes nothing. */
+int pwn_trace_viewport_hits_device(pwn_ctx *ctx, const pwn_vp_layout *layout, const void *d_cams, int flags,
+	void *d_label, void *d_cell, void *d_dist, void *stream);
+
+/*
  * The players' step: what produces the cameras of pwn_trace_views[_device].  The motion of the reference's loop (main.c:188-379:
  * turning, walking with push-back out of solid cells, gravity, the step between the floors of a two-high room, walking through a
  * portal with its turn) for a batch of n players at once, on the device, on the level in force -- so that step -> observe -> step

@@ -149,6 +149,8 @@ ABI = [
     ("pwn_get_object_ids", _i, [_vp, _vp, _i]),
     ("pwn_trace_view_hits", _i, [_vp, _i, _vp, _vp, _vp, _vp]),
     ("pwn_trace_view_hits_device", _i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    ("pwn_trace_viewport_hits", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    ("pwn_trace_viewport_hits_device", _i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     ("pwn_players_step", _i, [_vp, _i, _vp, _f, _i, _vp, _vp, _vp]),
     ("pwn_players_step_device", _i, [_vp, _i, _vp, _f, _i, _vp, _vp, _vp, _vp]),
     ("pwn_frames_config", _i, [_vp, _i, _i, _i, _i]),

@@ -1,5 +1,6 @@
 // pwn_calls.cpp -- the calls that return with their result on the host, and their device forms: the blocking call
-// (pwn_trace_screen_centred) in one piece and in row strips, host registration, the batches of views, viewports, rays and hits, the first-hit planes of views.
+// (pwn_trace_screen_centred) in one piece and in row strips, host registration, the batches of views, viewports, rays and hits, the first-hit planes of views
+// and of views of their own sizes.
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
@@ -520,13 +521,18 @@ extern "C" int pwn_trace_views_device(pwn_ctx *c, int n, const void *d_cams, con
 
 // The records (PWN_VIEWS_MAX of them) and the three planes of w x h, with the first call.  The depth plane starts at zero and
 // is never cleared again: it persists by destination pixel.
-static int viewports_reserve(pwn_ctx *c, hipStream_t s)
+static int viewport_recs_reserve(pwn_ctx *c)
 {
 	if(c->h_prec == NULL)
 	{
 		HIPCHK(c, hipHostMalloc((void **)&c->h_prec, PWN_VIEWS_MAX * sizeof(pwn_viewport_rec), hipHostMallocDefault));
 		HIPCHK(c, hipMalloc((void **)&c->d_prec, PWN_VIEWS_MAX * sizeof(pwn_viewport_rec)));
 	}
+	return PWN_OK;
+}
+static int viewports_reserve(pwn_ctx *c, hipStream_t s)
+{
+	{ const int rc = viewport_recs_reserve(c); if(rc != PWN_OK) return rc; }
 	if(c->d_pz != NULL) return PWN_OK;
 	const size_t bytes = (size_t)c->w * (size_t)c->h * 4;
 	uint32_t *pre, *out; float *z;
@@ -832,4 +838,74 @@ extern "C" int pwn_trace_view_hits_device(pwn_ctx *c, int n, const void *d_cams,
 	pwn_trace_launch T = { .y0 = 0, .y1 = c->h, .views = { recs, n, (flags & PWN_VIEWS_HAS_W) != 0, plane, (uint32_t *)d_label },
 		.d_sbuf = (uint32_t *)d_cell, .d_zbuf = (float *)d_dist, .stream = s };
 	return pwn_i_launch_trace(c, &T);
+}
+
+// ---- first-hit planes of views of their own sizes (pwn_trace_viewport_hits) -------
+
+// pwn_trace_viewports' records (their times 0: the primary segment reads none) and launch geometry, pwn_trace_view_hits' planes and
+// staging: N = w x h pixels, the label plane at 0, the cell plane at 4 N, the distance plane at 8 N of pwn_trace_hits' buffers.
+// Where the rectangles leave some of the frame uncovered, the staging of every plane given is cleared on the device first: the
+// planes come back 0 there.  The context grows by the records (pwn_trace_viewports' own, with the first call of either) and the
+// staging; the planes and the depth plane of pwn_trace_viewports are neither made nor touched.
+extern "C" int pwn_trace_viewport_hits(pwn_ctx *c, int n, const pwn_viewport *vp, const float *cams, uint32_t *label, uint32_t *cell, float *dist)
+{
+	GRP_REFUSE(c, "pwn_trace_viewport_hits");
+	if(c == NULL || vp == NULL || cams == NULL || label == NULL) return PWN_EINVAL;
+	// (the rules of pwn_trace_viewports with blur off, by the function a host can ask beforehand: these planes are never blurred)
+	unsigned long long plan[4];
+	if(pwn_viewports_plan(c->w, c->h, 0, n, vp, plan) != PWN_OK)
+	{
+		snprintf(c->err, sizeof(c->err), "pwn_trace_viewport_hits: %d rectangles of a %d x %d frame refused (the first offender: %llu)", n, c->w, c->h, plan[3]);
+		return PWN_EINVAL;
+	}
+	int rc = pwn_i_batch_refuse(c, 0, false);
+	if(rc != PWN_OK) return rc;
+	const size_t N = (size_t)c->w * (size_t)c->h;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = c->stream;
+	rc = pwn_i_wait_frames_in_flight(c, s);
+	if(rc != PWN_OK) return rc;
+	rc = viewport_recs_reserve(c);
+	if(rc != PWN_OK) return rc;
+	rc = pwn_i_staging_reserve(c, (12 * N + 79) / 80, 32 + sizeof(pwn_hit), "pwn_trace_viewport_hits", &c->h_hits, &c->d_hits, &c->hits_cap);
+	if(rc != PWN_OK) return rc;
+	// (the staging and the records are free: the call before this one ended with the stream drained)
+	int ord[PWN_VIEWS_MAX];
+	const uint32_t first = pwn_i_viewport_recs_bake(n, vp, c->h_prec, ord);
+	bool has_w = false;
+	for(int j = 0; j < n; j++)
+	{
+		const int i = ord[j];
+		const float *cam = cams + 16 * (size_t)i;
+		pwn_viewport_rec &r = c->h_prec[j];
+		frame_setup(vp[i].w, vp[i].h, cam, &r);
+		r.sec_current = 0.0f;
+		if(camera_has_w(cam)) has_w = true;
+	}
+	if((unsigned long long)first != plan[0]) { snprintf(c->err, sizeof(c->err), "pwn_trace_viewport_hits: %u units in the records, %llu planned", first, plan[0]); return PWN_EINVAL; }
+	HIPCHK(c, hipEventRecord(c->ev[0], s));
+	HIPCHK(c, pwn_launch_upload(c->h_prec, c->d_prec, (size_t)n * sizeof(pwn_viewport_rec), s));
+	unsigned char *h = c->h_hits, *d = c->d_hits;
+	if(plan[1] < (unsigned long long)N)
+	{
+		HIPCHK(c, hipMemsetAsync(d, 0, 4 * N, s));
+		if(cell != NULL) HIPCHK(c, hipMemsetAsync(d + 4 * N, 0, 4 * N, s));
+		if(dist != NULL) HIPCHK(c, hipMemsetAsync(d + 8 * N, 0, 4 * N, s));
+	}
+	const pwn_vps_launch V = { c->d_prec, c->h_prec, n, has_w, first, 0, 0, NULL, (uint32_t *)d };
+	pwn_trace_launch T = { .y0 = 0, .y1 = c->h, .vps = V,
+		.d_sbuf = cell != NULL ? (uint32_t *)(d + 4 * N) : NULL, .d_zbuf = dist != NULL ? (float *)(d + 8 * N) : NULL, .stream = s };
+	rc = pwn_i_launch_trace(c, &T);
+	if(rc != PWN_OK) return rc;
+	HIPCHK(c, hipEventRecord(c->ev[1], s));
+	HIPCHK(c, hipMemcpyAsync(h, d, 4 * N, hipMemcpyDeviceToHost, s));
+	if(cell != NULL) HIPCHK(c, hipMemcpyAsync(h + 4 * N, d + 4 * N, 4 * N, hipMemcpyDeviceToHost, s));
+	if(dist != NULL) HIPCHK(c, hipMemcpyAsync(h + 8 * N, d + 8 * N, 4 * N, hipMemcpyDeviceToHost, s));
+	HIPCHK(c, hipEventRecord(c->ev[3], s));
+	rc = blocking_wait(c, false);
+	if(rc != PWN_OK) return rc;
+	memcpy(label, h, 4 * N);
+	if(cell != NULL) memcpy(cell, h + 4 * N, 4 * N);
+	if(dist != NULL) memcpy(dist, h + 8 * N, 4 * N);
+	return PWN_OK;
 }

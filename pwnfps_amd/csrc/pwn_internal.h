@@ -40,6 +40,9 @@ struct pwn_views_launch
 // counts the tiles of the shape it picks); units = the launch's 16 x 4 units over all views.  n = 0: none.
 // fw x fh: the size of the planes the rectangles lie in (fw is their pitch), 0 = the context's (pwn_trace_viewports); d_skip: the
 // blur's skip-ahead table where the context's may be too short for the widest view (pwn_trace_viewports_device), NULL = the context's.
+// d_label (pwn_trace_viewport_hits / pwn_trace_viewport_hits_device): not NULL = the launch writes the views' first-hit planes instead,
+// from the primary segments alone: the label plane there, the cell plane to the launch's d_sbuf and the distance plane to its d_zbuf
+// (each unless NULL), one plane of fw x fh words each; the records' times are then not read.
 struct pwn_vps_launch
 {
 	const pwn_viewport_rec *d_recs, *h_recs;
@@ -48,6 +51,7 @@ struct pwn_vps_launch
 	uint32_t units;
 	int fw, fh;
 	const uint2 *d_skip;
+	uint32_t *d_label;
 };
 
 // A batch of caller-supplied rays (pwn_trace_rays / pwn_trace_rays_device; tables.h pwn_trace_params.rays): n rays into
@@ -113,7 +117,7 @@ extern "C" hipError_t pwn_launch_upload(const void *h_pinned_src, void *d_dst, s
 extern "C" hipError_t pwn_launch_view_setup(const float *d_cams, const float *d_secs, pwn_view_rec *d_out, int n, int w, int h, hipStream_t stream);
 // the records of pwn_trace_viewports_device (viewport_setup.hip): record j's geometry words from the layout's master copy d_master, its
 // head from camera d_perm[j] and time d_secs[d_perm[j]] with the view's own scalars d_scal[j] = (-yrat, xsrat, ysrat, 0); all but
-// d_secs and d_perm 16-byte aligned, every d_perm[j] < n
+// d_secs and d_perm 16-byte aligned, every d_perm[j] < n; d_secs NULL: every time 0 (pwn_trace_viewport_hits_device)
 extern "C" hipError_t pwn_launch_viewport_setup(const pwn_viewport_rec *d_master, const float *d_scal, const uint32_t *d_perm,
 	const float *d_cams, const float *d_secs, pwn_viewport_rec *d_out, int n, hipStream_t stream);
 // ticks of host/player.c's pwn_player_step for n players (player_step.hip): d_cams n x 16 floats and d_gravity n x 4 floats, 16-byte aligned,

@@ -261,7 +261,11 @@ int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L)
 		P.views = views->d_recs; P.nviews = views->n; P.plane = views->plane;
 		P.hits = views->d_label;        // (first-hit planes, pwn_trace_view_hits: the label plane; d_sbuf is then the cell plane, d_zbuf the distance plane)
 	}
-	if(vps != NULL) { P.vps = vps->d_recs; P.nvp = vps->n; }
+	if(vps != NULL)
+	{
+		P.vps = vps->d_recs; P.nvp = vps->n;
+		P.hits = vps->d_label;          // (first-hit planes, pwn_trace_viewport_hits: the label plane; d_sbuf is then the cell plane, d_zbuf the distance plane)
+	}
 	if(rays != NULL)
 	{
 		P.rays = rays->d_rays; P.ray_seeds = rays->d_seeds; P.nrays = rays->n; P.ray_w = rays->has_w ? 1 : 0;

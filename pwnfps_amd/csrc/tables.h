@@ -206,6 +206,9 @@ struct pwn_trace_params
 	// plane (uint32), and -- each unless NULL -- the hit's cell word to sbuf and its distance to zbuf: nviews planes of `plane` words
 	// each, view v's at + v * plane.  The records' sec_current is not read.  (No field of its own: the struct, and with it every
 	// other kernel's argument block, stays as it was.)
+	// With `vps` (pwn_trace_viewport_hits): the same three planes for views of their own sizes -- ONE plane of w x h words each, pitch w,
+	// in which view i's pixel (x, y) lies at (rec.y + y) * w + rec.x + x; the launch is one of `vps` otherwise, and the records'
+	// sec_current is not read.
 	void *hits;
 	// The lists' global form (above): NULL, or the three sections of the device-memory part of the tables.  Then blob_bytes is the LDS
 	// part alone, and off_sph / off_recsph are not read.
@@ -269,7 +272,7 @@ struct pwn_blur_params
 };
 
 // what a launch of the trace kernel traces (its MODE parameter, trace_kernel.hip)
-enum { PWN_KM_FRAME = 0, PWN_KM_VIEWS = 1, PWN_KM_RAYS = 2, PWN_KM_HITS = 3, PWN_KM_VIEWPORTS = 4, PWN_KM_VIEW_HITS = 5 };
+enum { PWN_KM_FRAME = 0, PWN_KM_VIEWS = 1, PWN_KM_RAYS = 2, PWN_KM_HITS = 3, PWN_KM_VIEWPORTS = 4, PWN_KM_VIEW_HITS = 5, PWN_KM_VIEWPORT_HITS = 6 };
 
 // One view of a batch: the camera set-up of screen.h:43-57 for that view's camera (pwn_internal.h frame_setup) and its
 // sec_current.  80 bytes; the kernel reads a view's record with scalar loads.

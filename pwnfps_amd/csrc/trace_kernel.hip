@@ -322,14 +322,17 @@ template<bool HAS_W> __device__ __forceinline__ void chain_rounds(Vec<HAS_W> &v,
 // rectangles of ONE pitch-P.w frame (pwn_trace_viewports): every unit finds its view and reads that view's set-up, size and
 // place from P.vps.  PWN_KM_VIEW_HITS: a batch of views handed out as PWN_KM_VIEWS' (pwn_trace_view_hits), of which every lane traces the
 // primary segment only (trace_hit) and writes packed first-hit words to the planes P.hits / sbuf / zbuf (label, cell, distance) instead
-// of a colour and a depth.  The last five are instantiated with ORDER = false only.
+// of a colour and a depth.  PWN_KM_VIEWPORT_HITS: views of their own sizes handed out and placed as PWN_KM_VIEWPORTS'
+// (pwn_trace_viewport_hits), of which every lane traces the primary segment only and writes the same packed words into ONE plane each
+// of the pitch-P.w frame, P.hits / sbuf / zbuf.  The last six are instantiated with ORDER = false only.
 // LISTS (tables.h PWN_LF_*): the form of the per-cell sphere lists -- indexed or inline records in LDS, or, for sphere sets whose
 // lists outgrow LDS, records in device memory (PWN_LF_GLOBAL: instantiated with ORDER = false only).
 template<bool COUNT, bool HAS_W, bool ORDER, int LISTS, int MODE>
 __global__ void __launch_bounds__(PWN_BLOCK, PWN_MIN_WAVES)
 pwn_trace_kernel(pwn_trace_params P)
 {
-	constexpr bool VHITS = MODE == PWN_KM_VIEW_HITS, VIEWS = MODE == PWN_KM_VIEWS || VHITS, HITS = MODE == PWN_KM_HITS, RAYS = MODE == PWN_KM_RAYS || HITS, VPS = MODE == PWN_KM_VIEWPORTS;
+	constexpr bool VHITS = MODE == PWN_KM_VIEW_HITS, VIEWS = MODE == PWN_KM_VIEWS || VHITS, HITS = MODE == PWN_KM_HITS, RAYS = MODE == PWN_KM_RAYS || HITS;
+	constexpr bool VPHITS = MODE == PWN_KM_VIEWPORT_HITS, VPS = MODE == PWN_KM_VIEWPORTS || VPHITS;
 	//@R k_prologue
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
 
@@ -623,7 +626,7 @@ pwn_trace_kernel(pwn_trace_params P)
 			rdx.x = r[4]; rdx.y = r[5]; rdx.z = r[6]; rdx.w = HAS_W ? r[7] : 0.0f;
 			rdy.x = r[8]; rdy.y = r[9]; rdy.z = r[10]; rdy.w = HAS_W ? r[11] : 0.0f;
 			from.x = r[12]; from.y = r[13]; from.z = r[14]; from.w = HAS_W ? r[15] : 1.0f;
-			sec_current = r[16];
+			if constexpr(!VPHITS) sec_current = r[16];        // (first-hit planes read no time)
 			fw = (int)ri[19]; fh = (int)ri[20]; fy0 = 0; fy1 = fh;
 			fux = ri[21]; fmagic = ri[22]; fshift = (int)ri[23]; rows_u = ri[24];
 			// (the rectangle lies inside the w x h <= 2^30 pixels of the planes: pwn_viewports_plan)
@@ -730,6 +733,22 @@ pwn_trace_kernel(pwn_trace_params P)
 					hit_store_planes(trace_hit<COUNT, HAS_W, LISTS>(L, from, rayl, cnt), (uint32_t *)P.hits + o, P.sbuf != NULL ? P.sbuf + o : NULL, P.zbuf != NULL ? P.zbuf + o : NULL);
 				}
 			}
+			else if constexpr(VPHITS)
+			{
+				// First-hit planes of views of their own sizes (pwn_trace_viewport_hits): the viewports mode up to here -- the view's record,
+				// its frame, x and y LOCAL to the view -- then trace_hit in the place of trace_pixel, as the mode above.  Every LDS address
+				// comes from trace_hit: the argument of the hit mode (its set-up and walk are trace_pixel's, and the ray is a frame's).
+				// Global: only lanes with x < fw and y < fh store (fy1 = fh here), one 4-byte word per plane given, at org + y * P.w + x
+				// with org = rec.y * P.w + rec.x; the rectangle lies inside the P.w x P.h <= 2^30 words of a plane (pwn_viewports_plan, by
+				// which every record was admitted), so (rec.y + y) * P.w + rec.x + x < P.w * P.h fits 32 bits and lies inside a plane of
+				// P.w x P.h words.  A plane whose pointer is NULL is skipped.  No seed, colour, depth or time is touched.
+				if(x < fw && y < fy1)
+				{
+					const uint32_t o = __umul24((uint32_t)y, (uint32_t)P.w) + (uint32_t)x + org;      // w, h <= 32768
+					// (tables.h: the label plane is P.hits, the cell plane P.sbuf, the distance plane P.zbuf)
+					hit_store_planes(trace_hit<COUNT, HAS_W, LISTS>(L, from, rayl, cnt), (uint32_t *)P.hits + o, P.sbuf != NULL ? P.sbuf + o : NULL, P.zbuf != NULL ? P.zbuf + o : NULL);
+				}
+			}
 			else if(x < fw && y < fy1)
 			{
 				const uint32_t seed = pixel_seed(x, y, fw);
@@ -829,10 +848,11 @@ using Units = TraceKernels<pwn_trace_kernel<true, true, ORDER, LISTS, MODE>, pwn
 extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
 {
 	// (the blob says which form its per-cell lists have: pwn_i_pack_blob, pwn_tables.cpp)
-	// The global form: twenty-four variants, MODE x COUNT x HAS_W, never ordered (pwn_i_launch_trace hands such a launch neither an
+	// The global form: twenty-eight variants, MODE x COUNT x HAS_W, never ordered (pwn_i_launch_trace hands such a launch neither an
 	// order nor a cost array).
 	if(P->g_rec != NULL)
 	{
+		if(P->vps != NULL && P->hits != NULL) return Units<false, PWN_LF_GLOBAL, PWN_KM_VIEWPORT_HITS>::launch(P, grid, lds_bytes, count, stream);
 		if(P->views != NULL && P->hits != NULL) return Units<false, PWN_LF_GLOBAL, PWN_KM_VIEW_HITS>::launch(P, grid, lds_bytes, count, stream);
 		if(P->hits != NULL) return Units<false, PWN_LF_GLOBAL, PWN_KM_HITS>::launch(P, grid, lds_bytes, count, stream);
 		if(P->rays != NULL) return Units<false, PWN_LF_GLOBAL, PWN_KM_RAYS>::launch(P, grid, lds_bytes, count, stream);
@@ -843,7 +863,8 @@ extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size
 	}
 	const bool inl = P->off_recsph != 0u;
 	// a batch of rays (pwn_trace_rays), of their first hits (pwn_trace_hits), of views (pwn_trace_views) or of views of their own sizes
-	// (pwn_trace_viewports), of views' first-hit planes (pwn_trace_view_hits): eight variants each, never ordered
+	// (pwn_trace_viewports), of views' first-hit planes (pwn_trace_view_hits, pwn_trace_viewport_hits): eight variants each, never ordered
+	if(P->vps != NULL && P->hits != NULL) return inl ? Units<false, PWN_LF_INLINE, PWN_KM_VIEWPORT_HITS>::launch(P, grid, lds_bytes, count, stream) : Units<false, PWN_LF_INDEXED, PWN_KM_VIEWPORT_HITS>::launch(P, grid, lds_bytes, count, stream);
 	if(P->views != NULL && P->hits != NULL) return inl ? Units<false, PWN_LF_INLINE, PWN_KM_VIEW_HITS>::launch(P, grid, lds_bytes, count, stream) : Units<false, PWN_LF_INDEXED, PWN_KM_VIEW_HITS>::launch(P, grid, lds_bytes, count, stream);
 	if(P->hits != NULL) return inl ? Units<false, PWN_LF_INLINE, PWN_KM_HITS>::launch(P, grid, lds_bytes, count, stream) : Units<false, PWN_LF_INDEXED, PWN_KM_HITS>::launch(P, grid, lds_bytes, count, stream);
 	if(P->rays != NULL) return inl ? Units<false, PWN_LF_INLINE, PWN_KM_RAYS>::launch(P, grid, lds_bytes, count, stream) : Units<false, PWN_LF_INDEXED, PWN_KM_RAYS>::launch(P, grid, lds_bytes, count, stream);

@@ -35,7 +35,7 @@ pwn_viewport_setup_kernel(const uint4 *__restrict__ master, const float4 *__rest
 	rdy.x = ysrat * cy.x; rdy.y = ysrat * cy.y; rdy.z = ysrat * cy.z; rdy.w = ysrat * cy.w;
 	const uint4 *m = master + 8 * (size_t)j;
 	uint4 g4 = m[4];                 // sec_current (the master's is 0), x, y, w
-	g4.x = secs[i];
+	g4.x = secs != NULL ? secs[i] : 0u;        // (no times: pwn_trace_viewport_hits_device, whose launch reads none)
 	uint4 *r = out + 8 * (size_t)j;
 	r[0] = make_uint4(__float_as_uint(rayb.x), __float_as_uint(rayb.y), __float_as_uint(rayb.z), __float_as_uint(rayb.w));
 	r[1] = make_uint4(__float_as_uint(rdx.x), __float_as_uint(rdx.y), __float_as_uint(rdx.z), __float_as_uint(rdx.w));

@@ -737,6 +737,71 @@ class Renderer:
                   "pwn_pixel_rays_device")
         return rays, seeds
 
+    # -- first-hit planes of views of their own sizes (pwn_trace_viewport_hits) --
+    def trace_viewport_hits(self, rects, cams, want_cell=True, want_dist=True):
+        """pwn_trace_viewport_hits: what is under every pixel of n views of their own sizes, in ONE frame of this context's size.
+        rects (n,4) int (x, y, w, h), cams (n,4,4) or (n,16).  Returns (label, cell, dist): label (h,w) uint32 packed words
+        (unpack_labels takes them apart), cell (h,w,2) int16 cell x, z and dist (h,w) float32 -- cell / dist None where not wanted.
+        Pixel (x, y) of rectangle i is the record trace_hits returns for pixel_rays(w_i, h_i, cams[i])'s ray of that pixel; 0 in
+        all three where the primary segment ran out of steps, and outside the rectangles."""
+        rects = _rect_records(rects, "trace_viewport_hits")
+        n = rects.shape[0]
+        cams = np.asarray(cams)
+        if cams.ndim == 3 and cams.shape[1:] == (4, 4):
+            cams = cams.reshape(cams.shape[0], 16)
+        if cams.shape != (n, 16):
+            raise ValueError("trace_viewport_hits: cams must have shape (%d,4,4) or (%d,16), not %s" % (n, n, cams.shape))
+        cams = np.ascontiguousarray(cams, np.float32)
+        label = np.empty((self.h, self.w), np.uint32)
+        cell = np.empty((self.h, self.w, 2), np.int16) if want_cell else None
+        dist = np.empty((self.h, self.w), np.float32) if want_dist else None
+        self._chk(lib.pwn_trace_viewport_hits(self._ctx, n, rects.ctypes.data, cams.ctypes.data, label.ctypes.data,
+                                              cell.ctypes.data if want_cell else None, dist.ctypes.data if want_dist else None),
+                  "pwn_trace_viewport_hits")
+        return label, cell, dist
+
+    def trace_viewport_hits_device(self, layout, cams, label, cell=None, dist=None, has_w=False, stream=None):
+        """pwn_trace_viewport_hits_device: the planes of trace_viewport_hits for the views of a viewports_layout, from cameras on the
+        GPU into ONE frame of the layout's W x H on the GPU, stream-ordered, no synchronisation and no host copy.  All torch tensors
+        on this context's GPU, contiguous and 16-byte aligned: cams (n,16) or (n,4,4) float32, camera i for rectangle i; label (H,W)
+        int32 or uint32; cell (H,W) int32 or uint32 -- or (H,W,2) int16 -- or None; dist (H,W) float32 or None.  Every pixel of
+        every rectangle is written in every plane given, nothing outside them.  has_w and stream as trace_views_device takes them."""
+        import torch
+        who = "trace_viewport_hits_device"
+        if not isinstance(layout, ViewportsLayout) or layout._ptr is None or layout._renderer is not self:
+            raise ValueError("%s: layout must be a live ViewportsLayout of this renderer" % who)
+        words = (torch.int32, getattr(torch, "uint32", torch.int32))
+        if isinstance(cams, torch.Tensor) and cams.dim() == 3 and tuple(cams.shape[1:]) == (4, 4) and cams.is_contiguous():
+            cams = cams.view(cams.shape[0], 16)
+        _tensor_check(torch, cams, "cams", (torch.float32,), 2, layout.n, who=who)
+        if cams.shape[1] != 16:
+            raise ValueError("%s: cams must have shape (%d,4,4) or (%d,16), not %s" % (who, layout.n, layout.n, tuple(cams.shape)))
+        planes = [("label", label, words, 2)]
+        if cell is not None:
+            pairs = isinstance(cell, torch.Tensor) and cell.dtype == torch.int16
+            planes.append(("cell", cell, (torch.int16,), 3) if pairs else ("cell", cell, words, 2))
+        if dist is not None:
+            planes.append(("dist", dist, (torch.float32,), 2))
+        for name, t, dtypes, ndim in planes:
+            _tensor_check(torch, t, name, dtypes, ndim, who=who)
+            want = (layout.H, layout.W) + ((2,) if ndim == 3 else ())
+            if tuple(t.shape) != want:
+                raise ValueError("%s: %s must have shape %s, not %s" % (who, name, want, tuple(t.shape)))
+        for name, t in [("cams", cams)] + [(name, t) for name, t, _, _ in planes]:
+            if t.device != cams.device:
+                raise ValueError("%s: tensors on %s and %s" % (who, cams.device, t.device))
+            if t.data_ptr() % 16 != 0:
+                raise ValueError("%s: %s is not 16-byte aligned" % (who, name))
+        if stream is None:
+            stream = torch.cuda.current_stream(cams.device)
+        if not isinstance(stream, int):
+            stream = stream.cuda_stream
+        self._chk(lib.pwn_trace_viewport_hits_device(self._ctx, layout._ptr, C.c_void_p(cams.data_ptr()),
+                                                     _lib.PWN_VIEWS_HAS_W if has_w else 0, C.c_void_p(label.data_ptr()),
+                                                     C.c_void_p(cell.data_ptr() if cell is not None else None),
+                                                     C.c_void_p(dist.data_ptr() if dist is not None else None), C.c_void_p(stream or 0)),
+                  "pwn_trace_viewport_hits_device")
+
     def set_call_strips(self, n):
         """PWN_OPT_CALL_STRIPS: -1 = by frame size (default), 0 = one launch per pass, 2..32 = that many row strips"""
         self._chk(lib.pwn_set_option(self._ctx, _lib.PWN_OPT_CALL_STRIPS, int(n)), "pwn_set_option(CALL_STRIPS)")

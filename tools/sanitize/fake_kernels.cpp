@@ -54,6 +54,33 @@ extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size
 		if(count && P->counters) P->counters[0] += (unsigned long long)P->nviews * P->plane;
 		return hipSuccess;
 	}
+	// first-hit planes of views of their own sizes (pwn_trace_viewport_hits; viewport_hits_driver.cpp): a word per pixel of every
+	// rectangle in every plane given, at (rec.y + y) * w + rec.x + x, that depends on the plane, the record's head and rectangle and
+	// the LOCAL pixel -- every word of every rectangle, and none beside them
+	if(P->vps != NULL && P->hits != NULL)
+	{
+		unsigned long long pixels = 0;
+		for(int v = 0; v < P->nvp; v++)
+		{
+			const pwn_viewport_rec &r = P->vps[v];
+			uint32_t rec = 0;
+			for(int i = 0; i < 16; i++) { uint32_t u; memcpy(&u, (const float *)&r + i, 4); rec = mix(rec, u); }
+			rec = mix(mix(rec, (uint32_t)r.w), (uint32_t)r.h);
+			for(int y = 0; y < r.h; y++)
+				for(int x = 0; x < r.w; x++)
+				{
+					const size_t o = (size_t)(r.y + y) * P->w + (size_t)(r.x + x);
+					const uint32_t k = mix(mix((uint32_t)x, (uint32_t)y), rec) | 1u;
+					((uint32_t *)P->hits)[o] = k;
+					if(P->sbuf != NULL) P->sbuf[o] = k ^ 0x11111110u;
+					if(P->zbuf != NULL) P->zbuf[o] = (float)(k >> 8) + 1.0f;
+				}
+			pixels += (unsigned long long)r.w * r.h;
+		}
+		if(P->tickets_next) for(unsigned q = 0; q < PWN_QUEUES; q++) P->tickets_next[q * PWN_QUEUE_STRIDE] = 0u;
+		if(count && P->counters) P->counters[0] += pixels;
+		return hipSuccess;
+	}
 	uint32_t tab = 0;
 	for(uint32_t i = 0; i < P->blob_bytes / 4; i += 7) tab = mix(tab, P->blob[i]);
 	uint32_t secbits, cambits = 0;
@@ -154,7 +181,8 @@ extern "C" hipError_t pwn_launch_viewport_setup(const pwn_viewport_rec *master, 
 			r.rdy[k] = ysrat * cam[4 + k];
 		}
 		memcpy(r.from, cam + 12, 16);
-		memcpy(&r.sec_current, secs + i, 4);
+		if(secs != NULL) memcpy(&r.sec_current, secs + i, 4);
+		else r.sec_current = 0.0f;
 		out[j] = r;
 	}
 	if(pwn_fake_viewport_setup_hook != NULL) pwn_fake_viewport_setup_hook(master, scal, perm, out, n);
