@@ -30,6 +30,7 @@ PWN_RAYS_HAS_W = 1
 PWN_VIEWS_HAS_W = 1
 PWN_RAYS_MAX = 1 << 28
 PWN_HIT_NONE, PWN_HIT_WALL, PWN_HIT_SPHERE = 0, 1, 2
+PWN_HIDE_NONE = -1
 PWN_PLAYERS_MAX = 1 << 20
 PWN_TICKS_MAX = 1024
 PWN_PIXELS_SHARED = 1
@@ -134,6 +135,7 @@ ABI = [
     ("pwn_call_strips_state", _i, [_vp, _vp]),
     ("pwn_trace_views", _i, [_vp, _i, _vp, _vp, _vp, _vp]),
     ("pwn_trace_views_device", _i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    ("pwn_trace_views_hide_device", _i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     ("pwn_viewports_plan", _i, [_i, _i, _i, _i, _vp, _vp]),
     ("pwn_trace_viewports", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     ("pwn_viewports_layout", _i, [_vp, _i, _i, _i, _vp, C.POINTER(_vp)]),
@@ -146,9 +148,11 @@ ABI = [
     ("pwn_trace_rays_device", _i, [_vp, _i, _vp, _vp, _f, _i, _vp, _vp, _vp]),
     ("pwn_trace_hits", _i, [_vp, _i, _vp, _vp]),
     ("pwn_trace_hits_device", _i, [_vp, _i, _vp, _i, _vp, _vp]),
+    ("pwn_trace_hits_hide_device", _i, [_vp, _i, _vp, _vp, _i, _vp, _vp]),
     ("pwn_get_object_ids", _i, [_vp, _vp, _i]),
     ("pwn_trace_view_hits", _i, [_vp, _i, _vp, _vp, _vp, _vp]),
     ("pwn_trace_view_hits_device", _i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    ("pwn_trace_view_hits_hide_device", _i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     ("pwn_trace_viewport_hits", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     ("pwn_trace_viewport_hits_device", _i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     ("pwn_players_step", _i, [_vp, _i, _vp, _f, _i, _vp, _vp, _vp]),

@@ -459,7 +459,7 @@ extern "C" int pwn_trace_views(pwn_ctx *c, int n, const float *cams, const float
 		pwn_view_rec &r = c->h_vrec[i];
 		frame_setup(c->w, c->h, cam, &r);
 		r.sec_current = secs[i];
-		r.pad_[0] = r.pad_[1] = r.pad_[2] = 0.0f;
+		r.hide = 0u; r.pad_[0] = r.pad_[1] = 0.0f;
 		if(camera_has_w(cam)) has_w = true;
 	}
 	HIPCHK(c, hipEventRecord(c->ev[0], s));
@@ -477,12 +477,23 @@ extern "C" int pwn_trace_views(pwn_ctx *c, int n, const float *cams, const float
 	return blocking_wait(c, true);
 }
 
+// d_hide of the *_hide_device calls (include/pwnhip.h): n int32 in device memory, 4-byte aligned, apart from every range the call
+// writes -- wr[k] .. + wr_bytes (NULL: not given)
+static bool hide_array_ok(const void *d_hide, size_t n, const void *const *wr, int nwr, size_t wr_bytes)
+{
+	if(d_hide == NULL || ((uintptr_t)d_hide & 3u) != 0) return false;
+	const uintptr_t h = (uintptr_t)d_hide, hb = (uintptr_t)n * 4;
+	for(int k = 0; k < nwr; k++)
+		if(wr[k] != NULL && h < (uintptr_t)wr[k] + wr_bytes && (uintptr_t)wr[k] < h + hb) return false;
+	return true;
+}
+
 // The device form: cameras and planes of the caller's in device memory, everything on the caller's stream, nothing waited for.
 // frame_setup runs on the device (view_setup.hip), into records of the library's.
-extern "C" int pwn_trace_views_device(pwn_ctx *c, int n, const void *d_cams, const void *d_secs, int flags,
+// hide: pwn_trace_views_hide_device -- d_hide goes into the records with the cameras, and the launch is one of the HIDE kernels.
+static int views_device(pwn_ctx *c, int n, const void *d_cams, const void *d_secs, bool hide, const void *d_hide, int flags,
 	void *d_work, void *d_sbuf, void *d_zbuf, void *stream)
 {
-	GRP_REFUSE(c, "pwn_trace_views_device");
 	if(c == NULL || d_cams == NULL || d_secs == NULL || d_sbuf == NULL || d_zbuf == NULL || n < 1 || n > PWN_VIEWS_MAX ||
 	   (flags & ~PWN_VIEWS_HAS_W) != 0) return PWN_EINVAL;
 	const size_t plane = (size_t)c->w * (size_t)c->h;
@@ -492,6 +503,8 @@ extern "C" int pwn_trace_views_device(pwn_ctx *c, int n, const void *d_cams, con
 		const uintptr_t bytes = (uintptr_t)n * plane * 4, p[3] = { (uintptr_t)d_sbuf, (uintptr_t)d_zbuf, (uintptr_t)d_work };
 		for(int i = 0; i < 3; i++) for(int k = i + 1; k < 3; k++)
 			if(p[i] != 0 && p[k] != 0 && p[i] < p[k] + bytes && p[k] < p[i] + bytes) return PWN_EINVAL;
+		const void *const wr[3] = { d_sbuf, d_zbuf, d_work };
+		if(hide && !hide_array_ok(d_hide, (size_t)n, wr, 3, bytes)) return PWN_EINVAL;
 	}
 	// (the rules above and the first two of pwn_i_batch_refuse all answer PWN_EINVAL: their order among themselves decides nothing)
 	int rc = pwn_i_batch_refuse(c, n);
@@ -507,14 +520,27 @@ extern "C" int pwn_trace_views_device(pwn_ctx *c, int n, const void *d_cams, con
 	const unsigned rot = (unsigned)c->launch_rot;
 	if(c->launch_event[rot - 1] != NULL && c->launch_stream[rot - 1] != s) HIPCHK(c, hipStreamWaitEvent(s, c->launch_event[rot - 1], 0));
 	pwn_view_rec *recs = c->d_vrec_dev + (size_t)(c->ticket_set % (2u * rot)) * PWN_VIEWS_MAX;
-	HIPCHK(c, pwn_launch_view_setup((const float *)d_cams, (const float *)d_secs, recs, n, c->w, c->h, s));
+	if(hide) HIPCHK(c, pwn_launch_view_setup_hide((const float *)d_cams, (const float *)d_secs, (const int32_t *)d_hide, recs, n, c->w, c->h, s));
+	else HIPCHK(c, pwn_launch_view_setup((const float *)d_cams, (const float *)d_secs, recs, n, c->w, c->h, s));
 	// the trace into the plane from which the last blur pass lands in d_sbuf
 	uint32_t *cur = (c->blur_passes & 1) ? (uint32_t *)d_work : (uint32_t *)d_sbuf;
 	uint32_t *other = (c->blur_passes & 1) ? (uint32_t *)d_sbuf : (uint32_t *)d_work;
-	pwn_trace_launch T = { .y0 = 0, .y1 = c->h, .views = { recs, n, (flags & PWN_VIEWS_HAS_W) != 0, plane }, .d_sbuf = cur, .d_zbuf = (float *)d_zbuf, .stream = s };
+	pwn_trace_launch T = { .y0 = 0, .y1 = c->h, .views = { recs, n, (flags & PWN_VIEWS_HAS_W) != 0, plane, NULL, hide }, .d_sbuf = cur, .d_zbuf = (float *)d_zbuf, .stream = s };
 	rc = pwn_i_launch_trace(c, &T);
 	if(rc != PWN_OK) return rc;
 	return pwn_i_blur_passes_run(c, { .y0 = 0, .y1 = c->h, .d_z = (const float *)d_zbuf, .stream = s, .views = n }, &cur, other);
+}
+extern "C" int pwn_trace_views_device(pwn_ctx *c, int n, const void *d_cams, const void *d_secs, int flags,
+	void *d_work, void *d_sbuf, void *d_zbuf, void *stream)
+{
+	GRP_REFUSE(c, "pwn_trace_views_device");
+	return views_device(c, n, d_cams, d_secs, false, NULL, flags, d_work, d_sbuf, d_zbuf, stream);
+}
+extern "C" int pwn_trace_views_hide_device(pwn_ctx *c, int n, const void *d_cams, const void *d_secs, const void *d_hide, int flags,
+	void *d_work, void *d_sbuf, void *d_zbuf, void *stream)
+{
+	GRP_REFUSE(c, "pwn_trace_views_hide_device");
+	return views_device(c, n, d_cams, d_secs, true, d_hide, flags, d_work, d_sbuf, d_zbuf, stream);
 }
 
 // ---- views of their own sizes in one frame (pwn_trace_viewports) ----------------
@@ -746,16 +772,27 @@ extern "C" int pwn_trace_hits(pwn_ctx *c, int n, const float *rays, pwn_hit *hit
 	return PWN_OK;
 }
 
-extern "C" int pwn_trace_hits_device(pwn_ctx *c, int n, const void *d_rays, int flags, void *d_hits, void *stream)
+// hide: pwn_trace_hits_hide_device -- the launch reads ray i's hidden sphere from d_hide beside its record and is one of the HIDE kernels
+static int hits_device(pwn_ctx *c, int n, const void *d_rays, bool hide, const void *d_hide, int flags, void *d_hits, void *stream)
 {
-	GRP_REFUSE(c, "pwn_trace_hits_device");
 	if(c == NULL || n < 0 || n > PWN_RAYS_MAX || (n > 0 && (d_rays == NULL || d_hits == NULL)) || (flags & ~PWN_RAYS_HAS_W) != 0) return PWN_EINVAL;
 	if(((uintptr_t)d_rays & 15u) != 0 || ((uintptr_t)d_hits & 15u) != 0) return PWN_EINVAL;
+	if(hide && n > 0 && !hide_array_ok(d_hide, (size_t)n, &d_hits, 1, (size_t)n * sizeof(pwn_hit))) return PWN_EINVAL;
 	const int rc = pwn_i_batch_refuse(c);
 	if(rc != PWN_OK || n == 0) return rc;
 	(void)hipSetDevice(c->device);
-	pwn_trace_launch T = { .rays = { (const float *)d_rays, NULL, (uint32_t)n, (flags & PWN_RAYS_HAS_W) != 0, d_hits }, .stream = (hipStream_t)stream };
+	pwn_trace_launch T = { .rays = { (const float *)d_rays, NULL, (uint32_t)n, (flags & PWN_RAYS_HAS_W) != 0, d_hits, hide ? (const int32_t *)d_hide : NULL }, .stream = (hipStream_t)stream };
 	return pwn_i_launch_trace(c, &T);
+}
+extern "C" int pwn_trace_hits_device(pwn_ctx *c, int n, const void *d_rays, int flags, void *d_hits, void *stream)
+{
+	GRP_REFUSE(c, "pwn_trace_hits_device");
+	return hits_device(c, n, d_rays, false, NULL, flags, d_hits, stream);
+}
+extern "C" int pwn_trace_hits_hide_device(pwn_ctx *c, int n, const void *d_rays, const void *d_hide, int flags, void *d_hits, void *stream)
+{
+	GRP_REFUSE(c, "pwn_trace_hits_hide_device");
+	return hits_device(c, n, d_rays, true, d_hide, flags, d_hits, stream);
 }
 
 // ---- first-hit planes of a batch of views (pwn_trace_view_hits) ------------------
@@ -786,7 +823,7 @@ extern "C" int pwn_trace_view_hits(pwn_ctx *c, int n, const float *cams, uint32_
 		pwn_view_rec &r = c->h_vrec[i];
 		frame_setup(c->w, c->h, cam, &r);
 		r.sec_current = 0.0f;
-		r.pad_[0] = r.pad_[1] = r.pad_[2] = 0.0f;
+		r.hide = 0u; r.pad_[0] = r.pad_[1] = 0.0f;
 		if(camera_has_w(cam)) has_w = true;
 	}
 	HIPCHK(c, hipEventRecord(c->ev[0], s));
@@ -812,9 +849,9 @@ extern "C" int pwn_trace_view_hits(pwn_ctx *c, int n, const float *cams, uint32_
 
 // The device form: cameras and planes of the caller's in device memory, the set-up kernel (no times) and the trace launch on the
 // caller's stream, nothing waited for -- pwn_trace_views_device without its blur
-extern "C" int pwn_trace_view_hits_device(pwn_ctx *c, int n, const void *d_cams, int flags, void *d_label, void *d_cell, void *d_dist, void *stream)
+// hide: pwn_trace_view_hits_hide_device, as views_device
+static int view_hits_device(pwn_ctx *c, int n, const void *d_cams, bool hide, const void *d_hide, int flags, void *d_label, void *d_cell, void *d_dist, void *stream)
 {
-	GRP_REFUSE(c, "pwn_trace_view_hits_device");
 	if(c == NULL || d_cams == NULL || d_label == NULL || n < 1 || n > PWN_VIEWS_MAX || (flags & ~PWN_VIEWS_HAS_W) != 0) return PWN_EINVAL;
 	if((((uintptr_t)d_cams | (uintptr_t)d_label | (uintptr_t)d_cell | (uintptr_t)d_dist) & 15u) != 0) return PWN_EINVAL;
 	const size_t plane = (size_t)c->w * (size_t)c->h;
@@ -822,6 +859,8 @@ extern "C" int pwn_trace_view_hits_device(pwn_ctx *c, int n, const void *d_cams,
 		const uintptr_t bytes = (uintptr_t)n * plane * 4, p[3] = { (uintptr_t)d_label, (uintptr_t)d_cell, (uintptr_t)d_dist };
 		for(int i = 0; i < 3; i++) for(int k = i + 1; k < 3; k++)
 			if(p[i] != 0 && p[k] != 0 && p[i] < p[k] + bytes && p[k] < p[i] + bytes) return PWN_EINVAL;
+		const void *const wr[3] = { d_label, d_cell, d_dist };
+		if(hide && !hide_array_ok(d_hide, (size_t)n, wr, 3, bytes)) return PWN_EINVAL;
 	}
 	int rc = pwn_i_batch_refuse(c, n, false);
 	if(rc != PWN_OK) return rc;
@@ -834,10 +873,21 @@ extern "C" int pwn_trace_view_hits_device(pwn_ctx *c, int n, const void *d_cams,
 	const unsigned rot = (unsigned)c->launch_rot;
 	if(c->launch_event[rot - 1] != NULL && c->launch_stream[rot - 1] != s) HIPCHK(c, hipStreamWaitEvent(s, c->launch_event[rot - 1], 0));
 	pwn_view_rec *recs = c->d_vrec_dev + (size_t)(c->ticket_set % (2u * rot)) * PWN_VIEWS_MAX;
-	HIPCHK(c, pwn_launch_view_setup((const float *)d_cams, NULL, recs, n, c->w, c->h, s));
-	pwn_trace_launch T = { .y0 = 0, .y1 = c->h, .views = { recs, n, (flags & PWN_VIEWS_HAS_W) != 0, plane, (uint32_t *)d_label },
+	if(hide) HIPCHK(c, pwn_launch_view_setup_hide((const float *)d_cams, NULL, (const int32_t *)d_hide, recs, n, c->w, c->h, s));
+	else HIPCHK(c, pwn_launch_view_setup((const float *)d_cams, NULL, recs, n, c->w, c->h, s));
+	pwn_trace_launch T = { .y0 = 0, .y1 = c->h, .views = { recs, n, (flags & PWN_VIEWS_HAS_W) != 0, plane, (uint32_t *)d_label, hide },
 		.d_sbuf = (uint32_t *)d_cell, .d_zbuf = (float *)d_dist, .stream = s };
 	return pwn_i_launch_trace(c, &T);
+}
+extern "C" int pwn_trace_view_hits_device(pwn_ctx *c, int n, const void *d_cams, int flags, void *d_label, void *d_cell, void *d_dist, void *stream)
+{
+	GRP_REFUSE(c, "pwn_trace_view_hits_device");
+	return view_hits_device(c, n, d_cams, false, NULL, flags, d_label, d_cell, d_dist, stream);
+}
+extern "C" int pwn_trace_view_hits_hide_device(pwn_ctx *c, int n, const void *d_cams, const void *d_hide, int flags, void *d_label, void *d_cell, void *d_dist, void *stream)
+{
+	GRP_REFUSE(c, "pwn_trace_view_hits_hide_device");
+	return view_hits_device(c, n, d_cams, true, d_hide, flags, d_label, d_cell, d_dist, stream);
 }
 
 // ---- first-hit planes of views of their own sizes (pwn_trace_viewport_hits) -------

@@ -26,6 +26,7 @@
 // d_label (pwn_trace_view_hits / pwn_trace_view_hits_device): not NULL = the launch writes the views' first-hit planes instead, from the
 // primary segments alone: the label plane there, the cell plane to the launch's d_sbuf and the distance plane to its d_zbuf (each
 // unless NULL); the records' times are then not read.
+// hide (pwn_trace_views_hide_device / pwn_trace_view_hits_hide_device): the records' `hide` words count -- the launch runs the HIDE kernels.
 struct pwn_views_launch
 {
 	const pwn_view_rec *d_recs;
@@ -33,6 +34,7 @@ struct pwn_views_launch
 	bool has_w;
 	unsigned long long plane;
 	uint32_t *d_label;
+	bool hide;
 };
 
 // Views of their own sizes in rectangles of one frame (pwn_trace_viewports) as what a launch traces or blurs: n records (tables.h
@@ -58,6 +60,7 @@ struct pwn_vps_launch
 // d_sbuf (colour) / d_zbuf (depth) of the launch; has_w: their w lanes count (PWN_RAYS_HAS_W).  n = 0: none.
 // d_hits (pwn_trace_hits / pwn_trace_hits_device): not NULL = the launch writes n first-hit records (pwn_hit) there instead,
 // from the primary segments alone; d_seeds, d_sbuf, d_zbuf and sec are then not read.
+// d_hide (pwn_trace_hits_hide_device; with d_hits only): not NULL = n int32, ray i's hidden sphere -- the launch runs the HIDE kernels.
 struct pwn_rays_launch
 {
 	const float *d_rays;
@@ -65,6 +68,7 @@ struct pwn_rays_launch
 	uint32_t n;
 	bool has_w;
 	void *d_hits;
+	const int32_t *d_hide;
 };
 
 // One trace launch (pwn_i_launch_trace).  All zero but what is traced and where to: a plain launch, nothing cleared or
@@ -101,6 +105,8 @@ struct pwn_blur_launch
 };
 
 extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream);
+// the units kernel's HIDE instantiations (trace_hide.hip): a launch of views with view_hide set, or of first-hit records with ray_hide
+extern "C" hipError_t pwn_launch_trace_hide(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream);
 extern "C" hipError_t pwn_launch_trace_refill(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream);
 extern "C" unsigned pwn_trace_refill_lds_extra(bool has_w);
 extern "C" int pwn_trace_refill_blocks_per_cu(size_t lds_bytes, bool count, bool has_w);
@@ -115,6 +121,8 @@ extern "C" hipError_t pwn_launch_upscale(const uint32_t *src, uint32_t *dst, int
 extern "C" hipError_t pwn_launch_upload(const void *h_pinned_src, void *d_dst, size_t bytes, hipStream_t stream);
 // the camera set-up of n views from device memory (view_setup.hip): d_cams n x 16 floats and d_out 16-byte aligned; d_secs NULL: every time 0
 extern "C" hipError_t pwn_launch_view_setup(const float *d_cams, const float *d_secs, pwn_view_rec *d_out, int n, int w, int h, hipStream_t stream);
+// ... with every view's hidden sphere: d_hide n int32 (or NULL: the call above), record i's `hide` word = d_hide[i] + 1 where that is 1 .. PWN_OBJ_MAX, else 0
+extern "C" hipError_t pwn_launch_view_setup_hide(const float *d_cams, const float *d_secs, const int32_t *d_hide, pwn_view_rec *d_out, int n, int w, int h, hipStream_t stream);
 // the records of pwn_trace_viewports_device (viewport_setup.hip): record j's geometry words from the layout's master copy d_master, its
 // head from camera d_perm[j] and time d_secs[d_perm[j]] with the view's own scalars d_scal[j] = (-yrat, xsrat, ysrat, 0); all but
 // d_secs and d_perm 16-byte aligned, every d_perm[j] < n; d_secs NULL: every time 0 (pwn_trace_viewport_hits_device)

@@ -260,6 +260,7 @@ int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L)
 	{
 		P.views = views->d_recs; P.nviews = views->n; P.plane = views->plane;
 		P.hits = views->d_label;        // (first-hit planes, pwn_trace_view_hits: the label plane; d_sbuf is then the cell plane, d_zbuf the distance plane)
+		P.view_hide = views->hide ? 1 : 0;
 	}
 	if(vps != NULL)
 	{
@@ -270,6 +271,7 @@ int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L)
 	{
 		P.rays = rays->d_rays; P.ray_seeds = rays->d_seeds; P.nrays = rays->n; P.ray_w = rays->has_w ? 1 : 0;
 		P.hits = rays->d_hits;
+		P.ray_hide = rays->d_hits != NULL ? rays->d_hide : NULL;
 	}
 	P.sbuf = L->d_sbuf; P.zbuf = L->d_zbuf;
 	P.counters = c->d_counters;
@@ -326,6 +328,8 @@ int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L)
 	rc = rotation_wait(c, stream);
 	if(rc != PWN_OK) return rc;
 	if(refill) HIPCHK(c, pwn_launch_trace_refill(&P, plan.grid, lds_bytes, c->counters_on != 0, stream));
+	// (one hidden sphere per view or ray: the HIDE instantiations, in a unit of their own)
+	else if(P.view_hide != 0 || P.ray_hide != NULL) HIPCHK(c, pwn_launch_trace_hide(&P, plan.grid, lds_bytes, c->counters_on != 0, stream));
 	else HIPCHK(c, pwn_launch_trace(&P, plan.grid, lds_bytes, c->counters_on != 0, stream));
 	return launch_went_out(c, cur, stream, L->tables_event);
 }

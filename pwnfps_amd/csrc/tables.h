@@ -238,6 +238,13 @@ struct pwn_trace_params
 	int tile_pairs;
 	uint32_t tx_magic; int tx_shift;
 	int pair_single_rows;
+	// One hidden sphere per ray or view (pwn_trace_hits_hide_device, pwn_trace_views_hide_device, pwn_trace_view_hits_hide_device; the
+	// kernel's HIDE parameter).  ray_hide: NULL, or nrays int32 beside `rays`: ray i does not see the sphere whose index in the live table
+	// (pwn_hit.object's numbering) is ray_hide[i]; any other value hides nothing.  view_hide != 0: a launch of `views` whose records'
+	// `hide` words count (pwn_view_rec).  Either one picks the HIDE instantiations (pwn_launch_trace_hide, trace_hide.hip); no other
+	// kernel reads them.  (Behind everything else, as the tile pairs were: no other field moves.)
+	const int32_t *ray_hide;
+	int view_hide;
 };
 #define PWN_HIT_REC_BYTES 48u
 
@@ -273,14 +280,20 @@ struct pwn_blur_params
 
 // what a launch of the trace kernel traces (its MODE parameter, trace_kernel.hip)
 enum { PWN_KM_FRAME = 0, PWN_KM_VIEWS = 1, PWN_KM_RAYS = 2, PWN_KM_HITS = 3, PWN_KM_VIEWPORTS = 4, PWN_KM_VIEW_HITS = 5, PWN_KM_VIEWPORT_HITS = 6 };
+// ... or'ed to PWN_KM_VIEWS, PWN_KM_VIEW_HITS or PWN_KM_HITS: its HIDE parameter -- every view or ray names one sphere it does not see
+enum { PWN_KM_HIDE = 8 };
 
 // One view of a batch: the camera set-up of screen.h:43-57 for that view's camera (pwn_internal.h frame_setup) and its
 // sec_current.  80 bytes; the kernel reads a view's record with scalar loads.
+// hide (word 17): 0 = the view sees every sphere; k + 1 = it does not see sphere k of the live table (pwn_trace_views_hide_device:
+// view_setup.hip writes k + 1 for 0 <= k < PWN_OBJ_MAX and 0 for anything else).  Only the HIDE instantiations read the word; every
+// other path that makes records writes 0 there (a float 0.0f before the word had a name: the same bits).
 struct pwn_view_rec
 {
 	float rayb[4], rdx[4], rdy[4], from[4];
 	float sec_current;
-	float pad_[3];
+	uint32_t hide;
+	float pad_[2];
 };
 #define PWN_VIEWS_REC_BYTES 80u
 

@@ -36,12 +36,19 @@
 #define EV_OUT_OF_STEPS 0
 #define WALK_EV_KEEP ev
 #define WALK_EV_OPEN(e) ((e) <= 0)
+// The hidden sphere (HIDE, at the kernel): hide1 = 0 for none, k + 1 for sphere k of the live table -- a view's from its record, one
+// value for the wave; a ray's from pwn_trace_params.ray_hide, one per lane.  The value is only ever compared with an object number that
+// comes out of the tables (trace_walk.inc PWN_ST_OBJECT): no bit pattern of it reaches an address or a loop bound.  Object numbers are
+// below PWN_OBJ_MAX, so 0, and whatever a value that is no index turns into, equal none of them.  With HIDE false the test is the
+// constant `false` and its argument is not evaluated: no instruction is made for it.
+#define WALK_HIDDEN(object) (HIDE && (object) + 1u == hide1)
 
 // One pixel = trace_ray(0, ...) of screen.h:22-24 with the recursion unrolled.
-template<bool COUNT, bool HAS_W, int LISTS>
+// HIDE: the sphere hide1 stands for (WALK_HIDDEN above) is not there for this ray, on any of its segments.
+template<bool COUNT, bool HAS_W, int LISTS, bool HIDE = false>
 __device__ __forceinline__ void trace_pixel(const Lds &L, float sec_current, uint32_t seed,
 	Vec<HAS_W> from, Vec<HAS_W> iray, float &out_x, float &out_y, float &out_z, float &out_w,
-	float *zpix, Counters &cnt)
+	float *zpix, Counters &cnt, [[maybe_unused]] uint32_t hide1 = 0u)
 {
 	typedef Vec<HAS_W> V;
 	// (trace_walk.inc: nothing is kept for hit records here; the two names it would write are never touched)
@@ -196,8 +203,8 @@ __device__ __forceinline__ void trace_pixel(const Lds &L, float sec_current, uin
 // trace_hit is the one body; what becomes of the words is its callers': hit_store_record (a batch of rays) writes all twelve,
 // hit_store_planes (a batch of views) packs the first four into one and keeps two more.
 struct HitWords { uint4 r0, r1, r2; };
-template<bool COUNT, bool HAS_W, int LISTS>
-__device__ __forceinline__ HitWords trace_hit(const Lds &L, Vec<HAS_W> from, Vec<HAS_W> iray, Counters &cnt)
+template<bool COUNT, bool HAS_W, int LISTS, bool HIDE = false>
+__device__ __forceinline__ HitWords trace_hit(const Lds &L, Vec<HAS_W> from, Vec<HAS_W> iray, Counters &cnt, [[maybe_unused]] uint32_t hide1 = 0u)
 {
 	typedef Vec<HAS_W> V;
 	constexpr bool HITREC = true;
@@ -327,10 +334,17 @@ template<bool HAS_W> __device__ __forceinline__ void chain_rounds(Vec<HAS_W> &v,
 // of the pitch-P.w frame, P.hits / sbuf / zbuf.  The last six are instantiated with ORDER = false only.
 // LISTS (tables.h PWN_LF_*): the form of the per-cell sphere lists -- indexed or inline records in LDS, or, for sphere sets whose
 // lists outgrow LDS, records in device memory (PWN_LF_GLOBAL: instantiated with ORDER = false only).
-template<bool COUNT, bool HAS_W, bool ORDER, int LISTS, int MODE>
+// HIDE (tables.h PWN_KM_HIDE, a bit of the MODE argument: the names of the kernels without it are as they were, and tests and
+// tools/issue_model.py find kernels by name): every view, or every ray, names one sphere of the table that it does not see
+// (pwn_trace_views_hide_device, pwn_trace_view_hits_hide_device, pwn_trace_hits_hide_device).  Instantiated for PWN_KM_VIEWS,
+// PWN_KM_VIEW_HITS and PWN_KM_HITS only, in a translation unit of its own (trace_hide.hip).
+template<bool COUNT, bool HAS_W, bool ORDER, int LISTS, int MODE_ARG>
 __global__ void __launch_bounds__(PWN_BLOCK, PWN_MIN_WAVES)
 pwn_trace_kernel(pwn_trace_params P)
 {
+	constexpr int MODE = MODE_ARG & ~PWN_KM_HIDE;
+	constexpr bool HIDE = (MODE_ARG & PWN_KM_HIDE) != 0;
+	static_assert(!HIDE || (!ORDER && (MODE == PWN_KM_VIEWS || MODE == PWN_KM_VIEW_HITS || MODE == PWN_KM_HITS)), "HIDE: views, their first hits, rays' first hits");
 	constexpr bool VHITS = MODE == PWN_KM_VIEW_HITS, VIEWS = MODE == PWN_KM_VIEWS || VHITS, HITS = MODE == PWN_KM_HITS, RAYS = MODE == PWN_KM_RAYS || HITS;
 	constexpr bool VPHITS = MODE == PWN_KM_VIEWPORT_HITS, VPS = MODE == PWN_KM_VIEWPORTS || VPHITS;
 	//@R k_prologue
@@ -532,8 +546,23 @@ pwn_trace_kernel(pwn_trace_params P)
 					// from the cell's liststart entry to the record with the end mark: inside the nrec records the host packed).
 					// Global: hits + 48 i for i < nrays <= 2^28 in 64-bit arithmetic lies in the
 					// caller's array of n records; a lane with i >= nrays stores nothing.  No seed, colour or depth is touched.
-					uint4 *const out = (uint4 *)((unsigned char *)P.hits + (size_t)i * PWN_HIT_REC_BYTES);
-					hit_store_record(trace_hit<COUNT, HAS_W, LISTS>(L, org, dir, cnt), out);
+					// HIDE: the ray's hidden sphere, ray_hide[i] for i < nrays in the caller's array of n int32 (pwn_calls.cpp checks it), as
+					// k + 1 (WALK_HIDDEN: only ever compared)
+					if constexpr(HIDE)
+					{
+						const uint32_t hide1 = (uint32_t)P.ray_hide[i] + 1u;
+						const HitWords hw = trace_hit<COUNT, HAS_W, LISTS, true>(L, org, dir, cnt, hide1);
+						// (the record's address is made behind the walk, from the ray's number: one register across the walk where the
+						// address is two, which is the register hide1 takes)
+						uint32_t il = i;
+						asm volatile("" : "+v"(il));
+						hit_store_record(hw, (uint4 *)((unsigned char *)P.hits + (size_t)il * PWN_HIT_REC_BYTES));
+					}
+					else
+					{
+						uint4 *const out = (uint4 *)((unsigned char *)P.hits + (size_t)i * PWN_HIT_REC_BYTES);
+						hit_store_record(trace_hit<COUNT, HAS_W, LISTS>(L, org, dir, cnt), out);
+					}
 				}
 				else
 				{
@@ -563,6 +592,7 @@ pwn_trace_kernel(pwn_trace_params P)
 		uint32_t *sbuf = P.sbuf;
 		float *zbuf = P.zbuf;
 		[[maybe_unused]] size_t vh_base = 0;              // (first-hit planes: where the view's planes begin, in words)
+		[[maybe_unused]] uint32_t hide1 = 0u;             // (HIDE: the view's hidden sphere, WALK_HIDDEN)
 		if constexpr(VIEWS)
 		{
 			fu = P.views_shift >= 0 ? __umulhi(unit, P.views_magic) >> P.views_shift : unit;
@@ -573,6 +603,8 @@ pwn_trace_kernel(pwn_trace_params P)
 			rdx.x = r[4]; rdx.y = r[5]; rdx.z = r[6]; rdx.w = HAS_W ? r[7] : 0.0f;
 			rdy.x = r[8]; rdy.y = r[9]; rdy.z = r[10]; rdy.w = HAS_W ? r[11] : 0.0f;
 			from.x = r[12]; from.y = r[13]; from.z = r[14]; from.w = HAS_W ? r[15] : 1.0f;
+			// (the record's `hide` word, with the rest of the record: one scalar load, one value for the wave)
+			if constexpr(HIDE) hide1 = ((const __attribute__((address_space(4))) uint32_t *)r)[17];
 			// (the view's planes: 64-bit offsets, a batch may hold 2^28 pixels per plane array)
 			if constexpr(VHITS) vh_base = (size_t)view * (size_t)P.plane;
 			else
@@ -730,7 +762,7 @@ pwn_trace_kernel(pwn_trace_params P)
 				{
 					const size_t o = vh_base + (size_t)y * (size_t)P.w + (size_t)x;
 					// (tables.h: the label plane is P.hits, the cell plane P.sbuf, the distance plane P.zbuf)
-					hit_store_planes(trace_hit<COUNT, HAS_W, LISTS>(L, from, rayl, cnt), (uint32_t *)P.hits + o, P.sbuf != NULL ? P.sbuf + o : NULL, P.zbuf != NULL ? P.zbuf + o : NULL);
+					hit_store_planes(trace_hit<COUNT, HAS_W, LISTS, HIDE>(L, from, rayl, cnt, hide1), (uint32_t *)P.hits + o, P.sbuf != NULL ? P.sbuf + o : NULL, P.zbuf != NULL ? P.zbuf + o : NULL);
 				}
 			}
 			else if constexpr(VPHITS)
@@ -754,7 +786,7 @@ pwn_trace_kernel(pwn_trace_params P)
 				const uint32_t seed = pixel_seed(x, y, fw);
 				float ox, oy, oz, ow;
 				const uint32_t o = __umul24((uint32_t)y, (uint32_t)P.w) + (uint32_t)x + org;      // w, h <= 32768 (pwn_init)
-				trace_pixel<COUNT, HAS_W, LISTS>(L, sec_current, seed, from, rayl, ox, oy, oz, ow, zbuf + o, cnt);
+				trace_pixel<COUNT, HAS_W, LISTS, HIDE>(L, sec_current, seed, from, rayl, ox, oy, oz, ow, zbuf + o, cnt, hide1);
 				sbuf[o] = col_pack4(ox, oy, oz, ow);
 			}
 			if(!(PAIRABLE && right_next)) break;
@@ -845,6 +877,25 @@ template<bool ORDER, int LISTS, int MODE>
 using Units = TraceKernels<pwn_trace_kernel<true, true, ORDER, LISTS, MODE>, pwn_trace_kernel<true, false, ORDER, LISTS, MODE>,
 	pwn_trace_kernel<false, true, ORDER, LISTS, MODE>, pwn_trace_kernel<false, false, ORDER, LISTS, MODE>>;
 
+#ifdef PWN_TRACE_HIDE_UNIT
+// trace_hide.hip: this file's text with the HIDE instantiations alone -- thirty-six kernels, three modes x three list forms x COUNT x
+// HAS_W -- and the one function that launches them.  (A unit of its own: in this file they would add a third to its build time.)
+template<int LISTS>
+static hipError_t launch_hide(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
+{
+	if(P->views != NULL && P->view_hide != 0)
+		return P->hits != NULL ? Units<false, LISTS, PWN_KM_VIEW_HITS | PWN_KM_HIDE>::launch(P, grid, lds_bytes, count, stream)
+		                       : Units<false, LISTS, PWN_KM_VIEWS | PWN_KM_HIDE>::launch(P, grid, lds_bytes, count, stream);
+	if(P->rays != NULL && P->hits != NULL && P->ray_hide != NULL) return Units<false, LISTS, PWN_KM_HITS | PWN_KM_HIDE>::launch(P, grid, lds_bytes, count, stream);
+	// (a missing kernel is an error: nothing else has a HIDE instantiation)
+	return hipErrorInvalidValue;
+}
+extern "C" hipError_t pwn_launch_trace_hide(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
+{
+	if(P->g_rec != NULL) return launch_hide<PWN_LF_GLOBAL>(P, grid, lds_bytes, count, stream);
+	return P->off_recsph != 0u ? launch_hide<PWN_LF_INLINE>(P, grid, lds_bytes, count, stream) : launch_hide<PWN_LF_INDEXED>(P, grid, lds_bytes, count, stream);
+}
+#else
 extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
 {
 	// (the blob says which form its per-cell lists have: pwn_i_pack_blob, pwn_tables.cpp)
@@ -893,3 +944,4 @@ extern "C" int pwn_trace_global_blocks_per_cu(size_t lds_bytes, bool count, bool
 {
 	return Units<false, PWN_LF_GLOBAL, PWN_KM_FRAME>::blocks_per_cu(lds_bytes, count, has_w);
 }
+#endif

@@ -1,5 +1,6 @@
 // One sphere against the ray at `pos` (trace.h:256-294); textually included by trace_walk.inc inside each list form's loop.
-// In scope: s0 = the record (x, y, z, r*r); PWN_ST_RAD2 = r*r as a float; PWN_ST_WHICH = what aux_idx remembers of the sphere.
+// In scope: s0 = the record (x, y, z, r*r); PWN_ST_RAD2 = r*r as a float; PWN_ST_WHICH = what aux_idx remembers of the sphere;
+// PWN_ST_OBJECT = the sphere's index in the live table (pwn_hit.object), evaluated only where WALK_HIDDEN asks for it (trace_walk.inc).
 // A file of its own (not a macro) so that every instruction keeps a source line: tools/issue_model.py's regions (//@R).
 //@R w_sphtest
 {
@@ -19,7 +20,10 @@
 			WAVE_PATH(7);
 			float sd2 = 1.0f - calc / rad2;
 			float sdist = sqrtf(d2) - sqrtf(sd2);
-			if(sdist + cdist < aux_dist)
+			// (the hidden sphere of this view or ray, pwn_trace_*_hide_device: a candidate that would win and is that sphere changes no
+			// state -- aux_dist, aux_pos, aux_diff and aux_idx stay, as if the table did not hold it.  Asked last, on the rare path:
+			// which sphere a record is of is a table look-up in two of the three list forms.  Without HIDE the test is `false`.)
+			if(sdist + cdist < aux_dist && !WALK_HIDDEN(PWN_ST_OBJECT))
 			{
 				//@R w_sphupd
 				RG(RG_SPHUPD);

@@ -10,12 +10,19 @@
 //   HITREC (compile-time; false in every kernel that shades): the walk also keeps what a first-hit record needs and the
 //   shading never asks for -- hit_cxz, the reference's cx, cz when the segment returns, and hit_portals, the portals
 //   this lane crossed.  With HITREC false the two names are not touched and no instruction is made for them.
+//   WALK_HIDDEN(object): optional.  True where the sphere with that index in the live table is one this lane's ray does not see
+//   (trace_kernel.hip's HIDE instantiations: a compare with a value of the lane's or the wave's).  An including file that does not
+//   define it -- the refill kernel -- gets the default, `false`, which does not evaluate its argument: no instruction is made.
 // One cell per iteration, one loop exit at the bottom.  The cell class is a bit test on the
 // LDS word (tables.h).  The room body - by far the most frequent - is written with selects;
 // lanes whose ray ended in it carry on through the (then meaningless) cell advance and leave
 // at the bottom.
 //@R w_head
 #define AUX_HIT() (cdist > aux_dist)
+#ifndef WALK_HIDDEN
+#define WALK_HIDDEN(object) false
+#define WALK_HIDDEN_DEFAULTED
+#endif
 if(COUNT)
 {
 	cnt.steps++;
@@ -102,9 +109,11 @@ if((int)cw < 0)
 			nx = L.g_rec[(size_t)ri + 1u];
 #define PWN_ST_RAD2 __uint_as_float(wb & 0x7fffffffu)
 #define PWN_ST_WHICH ri
+#define PWN_ST_OBJECT L.g_which[ri]
 #include "trace_sphere.inc"
 #undef PWN_ST_RAD2
 #undef PWN_ST_WHICH
+#undef PWN_ST_OBJECT
 			if((int)wb < 0) break;
 			ri++;
 		}
@@ -128,9 +137,11 @@ if((int)cw < 0)
 			nx = rp[1];
 #define PWN_ST_RAD2 __uint_as_float(wb & 0x7fffffffu)
 #define PWN_ST_WHICH ((uint32_t)(uintptr_t)rp)
+#define PWN_ST_OBJECT ((uint32_t)L.recsph[(PWN_ST_WHICH - PWN_T_BINIDX) >> 4] >> 5)
 #include "trace_sphere.inc"
 #undef PWN_ST_RAD2
 #undef PWN_ST_WHICH
+#undef PWN_ST_OBJECT
 			if((int)wb < 0) break;
 			rp++;
 		}
@@ -147,9 +158,11 @@ if((int)cw < 0)
 			const pwn_f4 s0 = *(const PWN_LDS pwn_f4 *)((const PWN_LDS unsigned char *)L.sph + si);         // x, y, z, r*r
 #define PWN_ST_RAD2 s0.w
 #define PWN_ST_WHICH si
+#define PWN_ST_OBJECT (si >> 5)
 #include "trace_sphere.inc"
 #undef PWN_ST_RAD2
 #undef PWN_ST_WHICH
+#undef PWN_ST_OBJECT
 		}
 	}
 }
@@ -416,3 +429,7 @@ else
 }
 // (trace.h:250,677, running out of steps, is the including loop's business)
 #undef AUX_HIT
+#ifdef WALK_HIDDEN_DEFAULTED
+#undef WALK_HIDDEN
+#undef WALK_HIDDEN_DEFAULTED
+#endif

@@ -298,13 +298,15 @@ class Renderer:
                                       zbuf.ctypes.data if want_z else None), "pwn_trace_views")
         return (sbuf, zbuf) if want_z else sbuf
 
-    def trace_views_device(self, cams, secs, sbuf, zbuf, work=None, has_w=False, stream=None):
+    def trace_views_device(self, cams, secs, sbuf, zbuf, work=None, has_w=False, stream=None, hide=None):
         """pwn_trace_views_device: the batch of trace_views from cameras on the GPU into planes on the GPU, stream-ordered, no
         synchronisation and no host copy.  All torch tensors on this context's GPU, contiguous: cams (n,16) or (n,4,4) float32,
         secs (n,) float32, sbuf (n,h,w) int32 or uint32 (the finished views), zbuf (n,h,w) float32 (in / out: a primary ray that
         runs out of steps keeps what it holds), work (n,h,w) int32 or uint32 scratch, needed with blur on.  has_w: honour the
         cameras' w lanes (PWN_VIEWS_HAS_W; else they are taken as 0, 0, 0, 1).  stream: a torch.cuda.Stream or a raw hipStream_t;
-        None = torch's current stream on the tensors' device."""
+        None = torch's current stream on the tensors' device.
+        hide: None, or an (n,) int32 tensor (pwn_trace_views_hide_device): view i does not see sphere hide[i] of the table in force,
+        on any segment of its rays; PWN_HIDE_NONE (-1) and every other value that is no sphere's index hide nothing."""
         import torch
         who = "trace_views_device"
         words = (torch.int32, getattr(torch, "uint32", torch.int32))
@@ -319,13 +321,21 @@ class Renderer:
             _tensor_check(torch, t, name, dtypes, 3, n, who=who)
             if tuple(t.shape) != (n, self.h, self.w):
                 raise ValueError("%s: %s must have shape (%d,%d,%d), not %s" % (who, name, n, self.h, self.w, tuple(t.shape)))
-        for name, t in [("secs", secs)] + [(name, t) for name, t, _ in planes]:
+        if hide is not None:
+            _tensor_check(torch, hide, "hide", (torch.int32,), 1, n, who=who)
+        for name, t in [("secs", secs)] + [(name, t) for name, t, _ in planes] + ([("hide", hide)] if hide is not None else []):
             if t.device != cams.device:
                 raise ValueError("%s: tensors on %s and %s" % (who, cams.device, t.device))
         if stream is None:
             stream = torch.cuda.current_stream(cams.device)
         if not isinstance(stream, int):
             stream = stream.cuda_stream
+        if hide is not None:
+            self._chk(lib.pwn_trace_views_hide_device(self._ctx, n, C.c_void_p(cams.data_ptr()), C.c_void_p(secs.data_ptr()),
+                                                      C.c_void_p(hide.data_ptr()), _lib.PWN_VIEWS_HAS_W if has_w else 0,
+                                                      C.c_void_p(work.data_ptr() if work is not None else None), C.c_void_p(sbuf.data_ptr()),
+                                                      C.c_void_p(zbuf.data_ptr()), C.c_void_p(stream or 0)), "pwn_trace_views_hide_device")
+            return
         self._chk(lib.pwn_trace_views_device(self._ctx, n, C.c_void_p(cams.data_ptr()), C.c_void_p(secs.data_ptr()),
                                              _lib.PWN_VIEWS_HAS_W if has_w else 0,
                                              C.c_void_p(work.data_ptr() if work is not None else None), C.c_void_p(sbuf.data_ptr()),
@@ -487,10 +497,12 @@ class Renderer:
         self._chk(lib.pwn_trace_hits(self._ctx, n, rays.ctypes.data if n else None, hits.ctypes.data if n else None), "pwn_trace_hits")
         return hits
 
-    def trace_hits_device(self, rays, hits, has_w=False, stream=None, n=None):
+    def trace_hits_device(self, rays, hits, has_w=False, stream=None, n=None, hide=None):
         """pwn_trace_hits_device: one trace launch, stream-ordered, no synchronisation.  rays (n,8) float32 and hits -- (n,12) int32
         or float32, or (n,48) uint8: n records of HIT_DTYPE -- are torch tensors on this context's GPU, both 16-byte aligned, or
-        raw device pointers with n given.  has_w and stream as trace_rays_device takes them."""
+        raw device pointers with n given.  has_w and stream as trace_rays_device takes them.
+        hide: None, or an (n,) int32 tensor on the same GPU (pwn_trace_hits_hide_device): ray i does not see sphere hide[i] of the
+        table in force; PWN_HIDE_NONE (-1) and every other value that is no sphere's index hide nothing."""
         tensors = [t for t in (rays, hits) if not isinstance(t, int)]
         if tensors:
             import torch
@@ -516,8 +528,20 @@ class Renderer:
             p_rays, p_hits = rays, hits
         if int(n) < 0 or int(n) > _lib.PWN_RAYS_MAX:
             raise ValueError("trace_hits_device: n = %d, 0 ... %d" % (n, _lib.PWN_RAYS_MAX))
+        if hide is not None:
+            import torch
+            _tensor_check(torch, hide, "hide", (torch.int32,), 1, int(n), who="trace_hits_device")
+            if tensors and hide.device != rays.device:
+                raise ValueError("trace_hits_device: tensors on %s and %s" % (rays.device, hide.device))
+            if stream is None:
+                stream = torch.cuda.current_stream(hide.device)
         if stream is not None and not isinstance(stream, int):
             stream = stream.cuda_stream
+        if hide is not None:
+            self._chk(lib.pwn_trace_hits_hide_device(self._ctx, int(n), C.c_void_p(p_rays), C.c_void_p(hide.data_ptr()),
+                                                     _lib.PWN_RAYS_HAS_W if has_w else 0, C.c_void_p(p_hits), C.c_void_p(stream or 0)),
+                      "pwn_trace_hits_hide_device")
+            return
         self._chk(lib.pwn_trace_hits_device(self._ctx, int(n), C.c_void_p(p_rays), _lib.PWN_RAYS_HAS_W if has_w else 0,
                                             C.c_void_p(p_hits), C.c_void_p(stream or 0)), "pwn_trace_hits_device")
 
@@ -551,11 +575,13 @@ class Renderer:
                                           dist.ctypes.data if want_dist else None), "pwn_trace_view_hits")
         return label, cell, dist
 
-    def trace_view_hits_device(self, cams, label, cell=None, dist=None, has_w=False, stream=None):
+    def trace_view_hits_device(self, cams, label, cell=None, dist=None, has_w=False, stream=None, hide=None):
         """pwn_trace_view_hits_device: the planes of trace_view_hits from cameras on the GPU into planes on the GPU, stream-ordered,
         no synchronisation and no host copy.  All torch tensors on this context's GPU, contiguous and 16-byte aligned: cams (n,16)
         or (n,4,4) float32, label (n,h,w) int32 or uint32, cell (n,h,w) int32 or uint32 -- or (n,h,w,2) int16 -- or None, dist
-        (n,h,w) float32 or None.  Every pixel of every plane given is written.  has_w and stream as trace_views_device takes them."""
+        (n,h,w) float32 or None.  Every pixel of every plane given is written.  has_w and stream as trace_views_device takes them.
+        hide: None, or an (n,) int32 tensor (pwn_trace_view_hits_hide_device): view i does not see sphere hide[i] of the table in
+        force (object numbers stay those of the whole table); values that are no sphere's index hide nothing."""
         import torch
         who = "trace_view_hits_device"
         words = (torch.int32, getattr(torch, "uint32", torch.int32))
@@ -580,10 +606,21 @@ class Renderer:
         for name, t in [("cams", cams)] + [(name, t) for name, t, _, _ in planes]:
             if t.data_ptr() % 16 != 0:
                 raise ValueError("%s: %s is not 16-byte aligned" % (who, name))
+        if hide is not None:
+            _tensor_check(torch, hide, "hide", (torch.int32,), 1, n, who=who)
+            if hide.device != cams.device:
+                raise ValueError("%s: tensors on %s and %s" % (who, cams.device, hide.device))
         if stream is None:
             stream = torch.cuda.current_stream(cams.device)
         if not isinstance(stream, int):
             stream = stream.cuda_stream
+        if hide is not None:
+            self._chk(lib.pwn_trace_view_hits_hide_device(self._ctx, n, C.c_void_p(cams.data_ptr()), C.c_void_p(hide.data_ptr()),
+                                                          _lib.PWN_VIEWS_HAS_W if has_w else 0, C.c_void_p(label.data_ptr()),
+                                                          C.c_void_p(cell.data_ptr() if cell is not None else None),
+                                                          C.c_void_p(dist.data_ptr() if dist is not None else None), C.c_void_p(stream or 0)),
+                      "pwn_trace_view_hits_hide_device")
+            return
         self._chk(lib.pwn_trace_view_hits_device(self._ctx, n, C.c_void_p(cams.data_ptr()), _lib.PWN_VIEWS_HAS_W if has_w else 0,
                                                  C.c_void_p(label.data_ptr()), C.c_void_p(cell.data_ptr() if cell is not None else None),
                                                  C.c_void_p(dist.data_ptr() if dist is not None else None), C.c_void_p(stream or 0)),

@@ -102,6 +102,8 @@ extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size
 	return hipSuccess;
 }
 extern "C" hipError_t pwn_launch_trace_refill(const pwn_trace_params *P, int g, size_t l, bool c, hipStream_t s) { return pwn_launch_trace(P, g, l, c, s); }
+// (the HIDE kernels, trace_hide.hip: the same stand-in -- what the hide words do to a pixel is the kernels' business)
+extern "C" hipError_t pwn_launch_trace_hide(const pwn_trace_params *P, int g, size_t l, bool c, hipStream_t s) { return pwn_launch_trace(P, g, l, c, s); }
 extern "C" unsigned pwn_trace_refill_lds_extra(bool) { return 16u; }
 extern "C" int pwn_trace_refill_blocks_per_cu(size_t, bool, bool) { return 4; }
 extern "C" int pwn_trace_blocks_per_cu(size_t, bool, bool) { return 5; }
@@ -140,9 +142,20 @@ extern "C" hipError_t pwn_launch_upscale(const uint32_t *src, uint32_t *dst, int
 }
 extern "C" hipError_t pwn_launch_upload(const void *src, void *dst, size_t bytes, hipStream_t) { small_launch("upload", src, dst, { bytes }); memcpy(dst, src, bytes); return hipSuccess; }
 // (the camera set-up of pwn_trace_views_device: view_setup.hip's arithmetic, on "device" memory that is host memory here)
+static hipError_t view_setup(const float *cams, const float *secs, const int32_t *hide, pwn_view_rec *out, int n, int w, int h);
 extern "C" hipError_t pwn_launch_view_setup(const float *cams, const float *secs, pwn_view_rec *out, int n, int w, int h, hipStream_t)
 {
 	small_launch("view_setup", cams, out, { (size_t)n, (size_t)w, (size_t)h });
+	return view_setup(cams, secs, NULL, out, n, w, h);
+}
+// (... with every view's hidden sphere, pwn_trace_views_hide_device: reads exactly n entries of hide)
+extern "C" hipError_t pwn_launch_view_setup_hide(const float *cams, const float *secs, const int32_t *hide, pwn_view_rec *out, int n, int w, int h, hipStream_t)
+{
+	small_launch("view_setup_hide", cams, out, { (size_t)n, (size_t)w, (size_t)h });
+	return view_setup(cams, secs, hide, out, n, w, h);
+}
+static hipError_t view_setup(const float *cams, const float *secs, const int32_t *hide, pwn_view_rec *out, int n, int w, int h)
+{
 	const pwn_setup_scalars S = pwn_frame_setup_scalars(w, h);
 	for(int v = 0; v < n; v++)
 	{
@@ -157,6 +170,7 @@ extern "C" hipError_t pwn_launch_view_setup(const float *cams, const float *secs
 			r.from[i] = cam[12 + i];
 		}
 		r.sec_current = secs != NULL ? secs[v] : 0.0f;
+		if(hide != NULL && hide[v] >= 0 && hide[v] < PWN_OBJ_MAX) r.hide = (uint32_t)hide[v] + 1u;
 		out[v] = r;
 	}
 	return hipSuccess;
