@@ -849,11 +849,13 @@ int pwn_trace_viewport_hits_device(pwn_ctx *ctx, const pwn_vp_layout *layout, co
 	void *d_label, void *d_cell, void *d_dist, void *stream);
 
 /*
- * One hidden sphere per view or ray: pwn_trace_views_device, pwn_trace_view_hits_device and pwn_trace_hits_device for viewers that do
+ * One hidden sphere per view or ray: pwn_trace_views_device, pwn_trace_view_hits_device and pwn_trace_hits_device -- and
+ * pwn_trace_viewports_device, pwn_trace_viewport_hits_device and pwn_trace_rays_device -- for viewers that do
  * not see one object of the table -- their own body (player i's sphere sits where camera i is, and a camera inside or next to a
  * sphere sees it in every ray that points at its centre, a crosshair ray reports it as its first hit), a carried item, the object a
  * preview camera is mounted on.  One sphere table and one launch for all agents, where the alternative is a table and a launch each.
- *   d_hide               n int32 in device memory, 4-byte aligned, required for n > 0.  Entry i is an index into the sphere table in
+ *   d_hide               n int32 in device memory, 4-byte aligned, required for n > 0; for the viewports pair n is the layout's count,
+ *                        and entry i belongs to rectangle i and camera i of the layout, in the caller's order.  Entry i is an index into the sphere table in
  *                        force in pwn_hit.object's numbering: the order of pwn_upload_spheres' array, of pwn_get_objects, of d_spheres
  *                        for tables built by pwn_upload_spheres_device.  View i (ray i) does not see that sphere.  Any value that is
  *                        not the index of a live sphere hides nothing: PWN_HIDE_NONE, any negative value, any value >= the live
@@ -865,18 +867,22 @@ int pwn_trace_viewport_hits_device(pwn_ctx *ctx, const pwn_vp_layout *layout, co
  *                        and every field of pwn_hit -- except that object numbers are still those of the FULL table (an object
  *                        j > d_hide[i] reports as j, not j - 1).  The sphere is hidden on EVERY segment of the ray: the primary one and
  *                        the bounces off walls, floors and other spheres -- it is not in that view's mirrors either; that is what
- *                        "taken out of the table" means.  With every entry PWN_HIDE_NONE the three calls are bit-identical to
- *                        pwn_trace_views_device / pwn_trace_view_hits_device / pwn_trace_hits_device, counters included.
+ *                        "taken out of the table" means.  With every entry PWN_HIDE_NONE each call is bit-identical to the call
+ *                        it shadows (pwn_trace_views_device / pwn_trace_view_hits_device / pwn_trace_hits_device /
+ *                        pwn_trace_viewports_device / pwn_trace_viewport_hits_device / pwn_trace_rays_device), counters included.
+ *                        For the viewports pair "view i" is rectangle i of the layout; nothing is written outside the rectangles.
  *   counters             with PWN_OPT_COUNTERS on: rays, steps, portals and exhausted are those of the table without the sphere,
  *                        summed as the calls without `_hide` sum them.  sphere_tests goes on counting the records of the lists walked,
  *                        the hidden sphere's included (it is tested and then passed over): not part of the exactness above.
- *   everything else      is the rule of the call each one shadows: launches (the camera set-up launch takes d_hide along; one trace
- *                        launch, of kernels of their own), ordering, the view records per counter set, d_zbuf in / out, blur and
+ *   everything else      is the rule of the call each one shadows: launches (the camera set-up launch -- the viewport set-up launch
+ *                        of the viewports pair -- takes d_hide along; one trace launch, of kernels of their own; pwn_trace_rays_hide_device
+ *                        is one trace launch), ordering, the layout-use event, the view records per counter set, d_zbuf in / out
+ *                        (the viewports': by destination pixel; the rays': d_depth in / out per ray), blur and
  *                        d_work, PWN_VIEWS_HAS_W / PWN_RAYS_HAS_W, the empty batch of rays (d_hide may then be NULL), "not followed",
  *                        "left alone", errors -- a pwn_init_multi handle and a row tiling refuse them like their siblings.
  *   errors, added        PWN_EINVAL for a NULL d_hide or one that is not 4-byte aligned with n > 0, and for the n x 4 bytes of d_hide
- *                        overlapping any range the call writes (d_work / d_sbuf / d_zbuf; d_label / d_cell / d_dist; d_hits).  A
- *                        refused call launches nothing.
+ *                        overlapping any range the call writes (d_work / d_sbuf / d_zbuf; d_label / d_cell / d_dist; d_hits;
+ *                        d_col / d_depth).  A refused call launches nothing and changes nothing.
  */
 #define PWN_HIDE_NONE (-1)
 int pwn_trace_views_hide_device(pwn_ctx *ctx, int n, const void *d_cams, const void *d_secs, const void *d_hide, int flags,
@@ -884,6 +890,12 @@ int pwn_trace_views_hide_device(pwn_ctx *ctx, int n, const void *d_cams, const v
 int pwn_trace_view_hits_hide_device(pwn_ctx *ctx, int n, const void *d_cams, const void *d_hide, int flags,
 	void *d_label, void *d_cell, void *d_dist, void *stream);
 int pwn_trace_hits_hide_device(pwn_ctx *ctx, int n, const void *d_rays, const void *d_hide, int flags, void *d_hits, void *stream);
+int pwn_trace_viewports_hide_device(pwn_ctx *ctx, const pwn_vp_layout *layout, const void *d_cams, const void *d_secs,
+	const void *d_hide, int flags, void *d_work, void *d_sbuf, void *d_zbuf, void *stream);
+int pwn_trace_viewport_hits_hide_device(pwn_ctx *ctx, const pwn_vp_layout *layout, const void *d_cams, const void *d_hide,
+	int flags, void *d_label, void *d_cell, void *d_dist, void *stream);
+int pwn_trace_rays_hide_device(pwn_ctx *ctx, int n, const void *d_rays, const void *d_seeds, const void *d_hide,
+	float sec_current, int flags, void *d_col, void *d_depth, void *stream);
 
 /*
  * The players' step: what produces the cameras of pwn_trace_views[_device].  The motion of the reference's loop (main.c:188-379:

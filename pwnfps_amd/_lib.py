@@ -142,6 +142,7 @@ ABI = [
     ("pwn_viewports_layout_free", _i, [_vp, _vp]),
     ("pwn_viewports_layout_info", _i, [_vp, _vp]),
     ("pwn_trace_viewports_device", _i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    ("pwn_trace_viewports_hide_device", _i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     ("pwn_pixel_rays", _i, [_i, _i, _vp, _i, _vp, _vp, _vp]),
     ("pwn_pixel_rays_device", _i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     ("pwn_trace_rays", _i, [_vp, _i, _vp, _vp, _f, _vp, _vp]),
@@ -149,12 +150,14 @@ ABI = [
     ("pwn_trace_hits", _i, [_vp, _i, _vp, _vp]),
     ("pwn_trace_hits_device", _i, [_vp, _i, _vp, _i, _vp, _vp]),
     ("pwn_trace_hits_hide_device", _i, [_vp, _i, _vp, _vp, _i, _vp, _vp]),
+    ("pwn_trace_rays_hide_device", _i, [_vp, _i, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp]),
     ("pwn_get_object_ids", _i, [_vp, _vp, _i]),
     ("pwn_trace_view_hits", _i, [_vp, _i, _vp, _vp, _vp, _vp]),
     ("pwn_trace_view_hits_device", _i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     ("pwn_trace_view_hits_hide_device", _i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     ("pwn_trace_viewport_hits", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     ("pwn_trace_viewport_hits_device", _i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    ("pwn_trace_viewport_hits_hide_device", _i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     ("pwn_players_step", _i, [_vp, _i, _vp, _f, _i, _vp, _vp, _vp]),
     ("pwn_players_step_device", _i, [_vp, _i, _vp, _f, _i, _vp, _vp, _vp, _vp]),
     ("pwn_frames_config", _i, [_vp, _i, _i, _i, _i]),

@@ -479,7 +479,7 @@ extern "C" int pwn_trace_views(pwn_ctx *c, int n, const float *cams, const float
 
 // d_hide of the *_hide_device calls (include/pwnhip.h): n int32 in device memory, 4-byte aligned, apart from every range the call
 // writes -- wr[k] .. + wr_bytes (NULL: not given)
-static bool hide_array_ok(const void *d_hide, size_t n, const void *const *wr, int nwr, size_t wr_bytes)
+bool pwn_i_hide_array_ok(const void *d_hide, size_t n, const void *const *wr, int nwr, size_t wr_bytes)
 {
 	if(d_hide == NULL || ((uintptr_t)d_hide & 3u) != 0) return false;
 	const uintptr_t h = (uintptr_t)d_hide, hb = (uintptr_t)n * 4;
@@ -504,7 +504,7 @@ static int views_device(pwn_ctx *c, int n, const void *d_cams, const void *d_sec
 		for(int i = 0; i < 3; i++) for(int k = i + 1; k < 3; k++)
 			if(p[i] != 0 && p[k] != 0 && p[i] < p[k] + bytes && p[k] < p[i] + bytes) return PWN_EINVAL;
 		const void *const wr[3] = { d_sbuf, d_zbuf, d_work };
-		if(hide && !hide_array_ok(d_hide, (size_t)n, wr, 3, bytes)) return PWN_EINVAL;
+		if(hide && !pwn_i_hide_array_ok(d_hide, (size_t)n, wr, 3, bytes)) return PWN_EINVAL;
 	}
 	// (the rules above and the first two of pwn_i_batch_refuse all answer PWN_EINVAL: their order among themselves decides nothing)
 	int rc = pwn_i_batch_refuse(c, n);
@@ -592,7 +592,7 @@ uint32_t pwn_i_viewport_recs_bake(int n, const pwn_viewport *vp, pwn_viewport_re
 		r.seg_first = first; r.seg_round = prev;
 		pwn_unit_div_magic((uint32_t)(n - j), &r.seg_magic, &sh); r.seg_shift = sh;
 		first += (uint32_t)(n - j) * (r.units - prev); prev = r.units;
-		r.pad_[0] = r.pad_[1] = 0u;
+		r.hide = 0u; r.pad_ = 0u;
 	}
 	return first;
 }
@@ -731,20 +731,37 @@ extern "C" int pwn_trace_rays(pwn_ctx *c, int n, const float *rays, const uint32
 	return PWN_OK;
 }
 
-extern "C" int pwn_trace_rays_device(pwn_ctx *c, int n, const void *d_rays, const void *d_seeds, float sec, int flags,
+// hide: pwn_trace_rays_hide_device -- the launch reads ray i's hidden sphere from d_hide beside its record and is one of the HIDE kernels
+static int rays_device(pwn_ctx *c, int n, const void *d_rays, const void *d_seeds, bool hide, const void *d_hide, float sec, int flags,
 	void *d_col, void *d_depth, void *stream)
 {
-	GRP_REFUSE(c, "pwn_trace_rays_device");
 	if(c == NULL || n < 0 || n > PWN_RAYS_MAX || (n > 0 && (d_rays == NULL || d_col == NULL || d_depth == NULL)) ||
 	   (flags & ~PWN_RAYS_HAS_W) != 0) return PWN_EINVAL;
 	if(((uintptr_t)d_rays & 15u) != 0 || ((uintptr_t)d_seeds & 3u) != 0 || ((uintptr_t)d_col & 3u) != 0 || ((uintptr_t)d_depth & 3u) != 0)
 		return PWN_EINVAL;
+	if(hide && n > 0)
+	{
+		const void *const wr[2] = { d_col, d_depth };
+		if(!pwn_i_hide_array_ok(d_hide, (size_t)n, wr, 2, (size_t)n * 4)) return PWN_EINVAL;
+	}
 	const int rc = pwn_i_batch_refuse(c);
 	if(rc != PWN_OK || n == 0) return rc;
 	(void)hipSetDevice(c->device);
-	pwn_trace_launch T = { .sec = sec, .rays = { (const float *)d_rays, (const uint32_t *)d_seeds, (uint32_t)n, (flags & PWN_RAYS_HAS_W) != 0 },
+	pwn_trace_launch T = { .sec = sec, .rays = { (const float *)d_rays, (const uint32_t *)d_seeds, (uint32_t)n, (flags & PWN_RAYS_HAS_W) != 0, NULL, hide ? (const int32_t *)d_hide : NULL },
 		.d_sbuf = (uint32_t *)d_col, .d_zbuf = (float *)d_depth, .stream = (hipStream_t)stream };
 	return pwn_i_launch_trace(c, &T);
+}
+extern "C" int pwn_trace_rays_device(pwn_ctx *c, int n, const void *d_rays, const void *d_seeds, float sec, int flags,
+	void *d_col, void *d_depth, void *stream)
+{
+	GRP_REFUSE(c, "pwn_trace_rays_device");
+	return rays_device(c, n, d_rays, d_seeds, false, NULL, sec, flags, d_col, d_depth, stream);
+}
+extern "C" int pwn_trace_rays_hide_device(pwn_ctx *c, int n, const void *d_rays, const void *d_seeds, const void *d_hide, float sec, int flags,
+	void *d_col, void *d_depth, void *stream)
+{
+	GRP_REFUSE(c, "pwn_trace_rays_hide_device");
+	return rays_device(c, n, d_rays, d_seeds, true, d_hide, sec, flags, d_col, d_depth, stream);
 }
 
 static_assert(sizeof(pwn_hit) == PWN_HIT_REC_BYTES, "the kernel writes a pwn_hit as three 16-byte words (trace_kernel.hip trace_hit)");
@@ -777,7 +794,7 @@ static int hits_device(pwn_ctx *c, int n, const void *d_rays, bool hide, const v
 {
 	if(c == NULL || n < 0 || n > PWN_RAYS_MAX || (n > 0 && (d_rays == NULL || d_hits == NULL)) || (flags & ~PWN_RAYS_HAS_W) != 0) return PWN_EINVAL;
 	if(((uintptr_t)d_rays & 15u) != 0 || ((uintptr_t)d_hits & 15u) != 0) return PWN_EINVAL;
-	if(hide && n > 0 && !hide_array_ok(d_hide, (size_t)n, &d_hits, 1, (size_t)n * sizeof(pwn_hit))) return PWN_EINVAL;
+	if(hide && n > 0 && !pwn_i_hide_array_ok(d_hide, (size_t)n, &d_hits, 1, (size_t)n * sizeof(pwn_hit))) return PWN_EINVAL;
 	const int rc = pwn_i_batch_refuse(c);
 	if(rc != PWN_OK || n == 0) return rc;
 	(void)hipSetDevice(c->device);
@@ -860,7 +877,7 @@ static int view_hits_device(pwn_ctx *c, int n, const void *d_cams, bool hide, co
 		for(int i = 0; i < 3; i++) for(int k = i + 1; k < 3; k++)
 			if(p[i] != 0 && p[k] != 0 && p[i] < p[k] + bytes && p[k] < p[i] + bytes) return PWN_EINVAL;
 		const void *const wr[3] = { d_label, d_cell, d_dist };
-		if(hide && !hide_array_ok(d_hide, (size_t)n, wr, 3, bytes)) return PWN_EINVAL;
+		if(hide && !pwn_i_hide_array_ok(d_hide, (size_t)n, wr, 3, bytes)) return PWN_EINVAL;
 	}
 	int rc = pwn_i_batch_refuse(c, n, false);
 	if(rc != PWN_OK) return rc;

@@ -45,6 +45,7 @@ struct pwn_views_launch
 // d_label (pwn_trace_viewport_hits / pwn_trace_viewport_hits_device): not NULL = the launch writes the views' first-hit planes instead,
 // from the primary segments alone: the label plane there, the cell plane to the launch's d_sbuf and the distance plane to its d_zbuf
 // (each unless NULL), one plane of fw x fh words each; the records' times are then not read.
+// hide (pwn_trace_viewports_hide_device / pwn_trace_viewport_hits_hide_device): the records' `hide` words count -- the launch runs the HIDE kernels.
 struct pwn_vps_launch
 {
 	const pwn_viewport_rec *d_recs, *h_recs;
@@ -54,13 +55,15 @@ struct pwn_vps_launch
 	int fw, fh;
 	const uint2 *d_skip;
 	uint32_t *d_label;
+	bool hide;
 };
 
 // A batch of caller-supplied rays (pwn_trace_rays / pwn_trace_rays_device; tables.h pwn_trace_params.rays): n rays into
 // d_sbuf (colour) / d_zbuf (depth) of the launch; has_w: their w lanes count (PWN_RAYS_HAS_W).  n = 0: none.
 // d_hits (pwn_trace_hits / pwn_trace_hits_device): not NULL = the launch writes n first-hit records (pwn_hit) there instead,
 // from the primary segments alone; d_seeds, d_sbuf, d_zbuf and sec are then not read.
-// d_hide (pwn_trace_hits_hide_device; with d_hits only): not NULL = n int32, ray i's hidden sphere -- the launch runs the HIDE kernels.
+// d_hide (pwn_trace_hits_hide_device with d_hits, pwn_trace_rays_hide_device without): not NULL = n int32, ray i's hidden sphere -- the
+// launch runs the HIDE kernels.
 struct pwn_rays_launch
 {
 	const float *d_rays;
@@ -107,6 +110,8 @@ struct pwn_blur_launch
 extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream);
 // the units kernel's HIDE instantiations (trace_hide.hip): a launch of views with view_hide set, or of first-hit records with ray_hide
 extern "C" hipError_t pwn_launch_trace_hide(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream);
+// ... those of the other three batch modes (trace_hide_vp.hip): a launch of vps with view_hide set, or of rays' colours with ray_hide
+extern "C" hipError_t pwn_launch_trace_hide2(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream);
 extern "C" hipError_t pwn_launch_trace_refill(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream);
 extern "C" unsigned pwn_trace_refill_lds_extra(bool has_w);
 extern "C" int pwn_trace_refill_blocks_per_cu(size_t lds_bytes, bool count, bool has_w);
@@ -128,6 +133,13 @@ extern "C" hipError_t pwn_launch_view_setup_hide(const float *d_cams, const floa
 // d_secs and d_perm 16-byte aligned, every d_perm[j] < n; d_secs NULL: every time 0 (pwn_trace_viewport_hits_device)
 extern "C" hipError_t pwn_launch_viewport_setup(const pwn_viewport_rec *d_master, const float *d_scal, const uint32_t *d_perm,
 	const float *d_cams, const float *d_secs, pwn_viewport_rec *d_out, int n, hipStream_t stream);
+// ... with every rectangle's hidden sphere: d_hide n int32 in the caller's order (or NULL: the call above), record j's `hide` word =
+// d_hide[d_perm[j]] + 1 where that is 1 .. PWN_OBJ_MAX, else 0
+extern "C" hipError_t pwn_launch_viewport_setup_hide(const pwn_viewport_rec *d_master, const float *d_scal, const uint32_t *d_perm,
+	const float *d_cams, const float *d_secs, const int32_t *d_hide, pwn_viewport_rec *d_out, int n, hipStream_t stream);
+// d_hide of the *_hide_device calls (include/pwnhip.h): n int32 in device memory, 4-byte aligned, apart from every range the call
+// writes -- wr[k] .. + wr_bytes (NULL: not given)
+bool pwn_i_hide_array_ok(const void *d_hide, size_t n, const void *const *wr, int nwr, size_t wr_bytes);
 // ticks of host/player.c's pwn_player_step for n players (player_step.hip): d_cams n x 16 floats and d_gravity n x 4 floats, 16-byte aligned,
 // d_traversals n int32 or NULL, d_keys n bytes; stage != 0: every workgroup copies the walk table into LDS first
 extern "C" hipError_t pwn_launch_players_step(float *d_cams, float *d_gravity, int32_t *d_traversals, const uint8_t *d_keys, int n,

@@ -266,12 +266,13 @@ int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L)
 	{
 		P.vps = vps->d_recs; P.nvp = vps->n;
 		P.hits = vps->d_label;          // (first-hit planes, pwn_trace_viewport_hits: the label plane; d_sbuf is then the cell plane, d_zbuf the distance plane)
+		P.view_hide = vps->hide ? 1 : 0;
 	}
 	if(rays != NULL)
 	{
 		P.rays = rays->d_rays; P.ray_seeds = rays->d_seeds; P.nrays = rays->n; P.ray_w = rays->has_w ? 1 : 0;
 		P.hits = rays->d_hits;
-		P.ray_hide = rays->d_hits != NULL ? rays->d_hide : NULL;
+		P.ray_hide = rays->d_hide;
 	}
 	P.sbuf = L->d_sbuf; P.zbuf = L->d_zbuf;
 	P.counters = c->d_counters;
@@ -329,6 +330,8 @@ int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L)
 	if(rc != PWN_OK) return rc;
 	if(refill) HIPCHK(c, pwn_launch_trace_refill(&P, plan.grid, lds_bytes, c->counters_on != 0, stream));
 	// (one hidden sphere per view or ray: the HIDE instantiations, in a unit of their own)
+	// (views of their own sizes and rays' colours: a third unit; a launch that neither matches is refused by the one it is sent to)
+	else if((P.vps != NULL && P.view_hide != 0) || (P.rays != NULL && P.hits == NULL && P.ray_hide != NULL)) HIPCHK(c, pwn_launch_trace_hide2(&P, plan.grid, lds_bytes, c->counters_on != 0, stream));
 	else if(P.view_hide != 0 || P.ray_hide != NULL) HIPCHK(c, pwn_launch_trace_hide(&P, plan.grid, lds_bytes, c->counters_on != 0, stream));
 	else HIPCHK(c, pwn_launch_trace(&P, plan.grid, lds_bytes, c->counters_on != 0, stream));
 	return launch_went_out(c, cur, stream, L->tables_event);

@@ -167,7 +167,9 @@ void pwn_i_viewports_device_release(pwn_ctx *c)
 // What the two device forms share once a call's own arguments are in order: the records of the ticket set the trace launch will count
 // in, made on the device (viewport_setup.hip) on the caller's stream, and the layout's entry for that stream.  d_secs NULL: every
 // time 0 (the first-hit planes read none).  *slot is the entry whose event vps_device_used records behind whatever the call launches.
-static int vps_device_records(pwn_ctx *c, pwn_vp_layout *lw, const void *d_cams, const void *d_secs, hipStream_t s, int *slot_out, pwn_viewport_rec **recs_out)
+// hide: the *_hide_device forms -- d_hide goes into the records with the cameras.  A call without it writes 0 into every record's
+// word (the master copy's), so a set that held a hide call's records before holds nothing of them.
+static int vps_device_records(pwn_ctx *c, pwn_vp_layout *lw, const void *d_cams, const void *d_secs, bool hide, const void *d_hide, hipStream_t s, int *slot_out, pwn_viewport_rec **recs_out)
 {
 	int rc;
 	// (tables that cannot be packed refuse the call before anything is launched)
@@ -188,7 +190,8 @@ static int vps_device_records(pwn_ctx *c, pwn_vp_layout *lw, const void *d_cams,
 	const unsigned rot = (unsigned)c->launch_rot;
 	if(c->launch_event[rot - 1] != NULL && c->launch_stream[rot - 1] != s) HIPCHK(c, hipStreamWaitEvent(s, c->launch_event[rot - 1], 0));
 	pwn_viewport_rec *recs = c->d_prec_dev + (size_t)(c->ticket_set % (2u * rot)) * PWN_VIEWS_MAX;
-	HIPCHK(c, pwn_launch_viewport_setup(lw->d_master, lw->d_scal, lw->d_perm, (const float *)d_cams, (const float *)d_secs, recs, lw->n, s));
+	if(hide) HIPCHK(c, pwn_launch_viewport_setup_hide(lw->d_master, lw->d_scal, lw->d_perm, (const float *)d_cams, (const float *)d_secs, (const int32_t *)d_hide, recs, lw->n, s));
+	else HIPCHK(c, pwn_launch_viewport_setup(lw->d_master, lw->d_scal, lw->d_perm, (const float *)d_cams, (const float *)d_secs, recs, lw->n, s));
 	lw->use[slot].stream = s; lw->use[slot].used = true; lw->use[slot].stamp = ++lw->stamp;
 	*slot_out = slot; *recs_out = recs;
 	return PWN_OK;
@@ -215,27 +218,32 @@ static bool planes_apart(uintptr_t bytes, const void *a, const void *b, const vo
 // The device form of pwn_trace_viewports: cameras and planes of the caller's in device memory, everything on the caller's stream,
 // nothing waited for.  The records are made on the device (viewport_setup.hip) into the library's, per ticket set as
 // pwn_trace_views_device's; the planes are of the LAYOUT's size, which the launchers are told (pwn_vps_launch.fw / fh).
-extern "C" int pwn_trace_viewports_device(pwn_ctx *c, const pwn_vp_layout *l, const void *d_cams, const void *d_secs, int flags,
-	void *d_work, void *d_sbuf, void *d_zbuf, void *stream)
+// hide: pwn_trace_viewports_hide_device -- d_hide, one entry per rectangle in the caller's order, goes into the records with the
+// cameras, and the trace launch is one of the HIDE kernels; `who` names the entry in messages.
+static int viewports_device(pwn_ctx *c, const pwn_vp_layout *l, const void *d_cams, const void *d_secs, bool hide, const void *d_hide, int flags,
+	void *d_work, void *d_sbuf, void *d_zbuf, void *stream, const char *who)
 {
-	GRP_REFUSE(c, "pwn_trace_viewports_device");
 	if(c == NULL || l == NULL || d_cams == NULL || d_secs == NULL || d_sbuf == NULL || d_zbuf == NULL || (flags & ~PWN_VIEWS_HAS_W) != 0) return PWN_EINVAL;
 	if(!layout_of(c, l)) return PWN_EINVAL;
 	if(c->blur_passes > 0 && (d_work == NULL || !l->blur_ok)) return PWN_EINVAL;
 	if((((uintptr_t)d_cams | (uintptr_t)d_secs | (uintptr_t)d_work | (uintptr_t)d_sbuf | (uintptr_t)d_zbuf) & 15u) != 0) return PWN_EINVAL;
 	if(!planes_apart((uintptr_t)l->W * (uintptr_t)l->H * 4, d_sbuf, d_zbuf, d_work)) return PWN_EINVAL;
+	{
+		const void *const wr[3] = { d_sbuf, d_zbuf, d_work };
+		if(hide && !pwn_i_hide_array_ok(d_hide, (size_t)l->n, wr, 3, (size_t)l->W * (size_t)l->H * 4)) return PWN_EINVAL;
+	}
 	int rc = pwn_i_batch_refuse(c);
 	if(rc != PWN_OK) return rc;
 	(void)hipSetDevice(c->device);
 	hipStream_t s = (hipStream_t)stream;
 	pwn_vp_layout *lw = const_cast<pwn_vp_layout *>(l);
 	int slot; pwn_viewport_rec *recs;
-	rc = vps_device_records(c, lw, d_cams, d_secs, s, &slot, &recs);
+	rc = vps_device_records(c, lw, d_cams, d_secs, hide, d_hide, s, &slot, &recs);
 	if(rc != PWN_OK) return rc;
 	// the trace into the plane from which the last blur pass lands in d_sbuf
 	uint32_t *cur = (c->blur_passes & 1) ? (uint32_t *)d_work : (uint32_t *)d_sbuf;
 	uint32_t *other = (c->blur_passes & 1) ? (uint32_t *)d_sbuf : (uint32_t *)d_work;
-	const pwn_vps_launch V = { recs, l->h_recs, l->n, (flags & PWN_VIEWS_HAS_W) != 0, l->units, l->W, l->H, l->d_skip, NULL };
+	const pwn_vps_launch V = { recs, l->h_recs, l->n, (flags & PWN_VIEWS_HAS_W) != 0, l->units, l->W, l->H, l->d_skip, NULL, hide };
 	pwn_trace_launch T = { .y0 = 0, .y1 = l->H, .vps = V, .d_sbuf = cur, .d_zbuf = (float *)d_zbuf, .stream = s };
 	rc = pwn_i_launch_trace(c, &T);
 	// The blur reads a record's rectangle alone, and reads it from the layout's master copy, which nothing ever writes: the trace launch
@@ -243,29 +251,57 @@ extern "C" int pwn_trace_viewports_device(pwn_ctx *c, const pwn_vp_layout *l, co
 	// while this call's blur passes are still to run.
 	const pwn_vps_launch VB = { l->d_master, l->h_recs, l->n, V.has_w, l->units, l->W, l->H, l->d_skip, NULL };
 	if(rc == PWN_OK) rc = pwn_i_blur_passes_run(c, { .y0 = 0, .y1 = l->H, .d_z = (const float *)d_zbuf, .stream = s, .vps = VB }, &cur, other);
-	return vps_device_used(c, lw, slot, s, rc, "pwn_trace_viewports_device");
+	return vps_device_used(c, lw, slot, s, rc, who);
+}
+extern "C" int pwn_trace_viewports_device(pwn_ctx *c, const pwn_vp_layout *l, const void *d_cams, const void *d_secs, int flags,
+	void *d_work, void *d_sbuf, void *d_zbuf, void *stream)
+{
+	GRP_REFUSE(c, "pwn_trace_viewports_device");
+	return viewports_device(c, l, d_cams, d_secs, false, NULL, flags, d_work, d_sbuf, d_zbuf, stream, "pwn_trace_viewports_device");
+}
+extern "C" int pwn_trace_viewports_hide_device(pwn_ctx *c, const pwn_vp_layout *l, const void *d_cams, const void *d_secs, const void *d_hide, int flags,
+	void *d_work, void *d_sbuf, void *d_zbuf, void *stream)
+{
+	GRP_REFUSE(c, "pwn_trace_viewports_hide_device");
+	return viewports_device(c, l, d_cams, d_secs, true, d_hide, flags, d_work, d_sbuf, d_zbuf, stream, "pwn_trace_viewports_hide_device");
 }
 
 // The device form of pwn_trace_viewport_hits: the call above with the first-hit planes in the place of colour and depth -- the same
 // records (their times 0), rotation and layout-use event, one set-up launch and one trace launch, no blur.  Every layout qualifies.
-extern "C" int pwn_trace_viewport_hits_device(pwn_ctx *c, const pwn_vp_layout *l, const void *d_cams, int flags,
-	void *d_label, void *d_cell, void *d_dist, void *stream)
+// hide: pwn_trace_viewport_hits_hide_device, as viewports_device
+static int viewport_hits_device(pwn_ctx *c, const pwn_vp_layout *l, const void *d_cams, bool hide, const void *d_hide, int flags,
+	void *d_label, void *d_cell, void *d_dist, void *stream, const char *who)
 {
-	GRP_REFUSE(c, "pwn_trace_viewport_hits_device");
 	if(c == NULL || l == NULL || d_cams == NULL || d_label == NULL || (flags & ~PWN_VIEWS_HAS_W) != 0) return PWN_EINVAL;
 	if(!layout_of(c, l)) return PWN_EINVAL;
 	if((((uintptr_t)d_cams | (uintptr_t)d_label | (uintptr_t)d_cell | (uintptr_t)d_dist) & 15u) != 0) return PWN_EINVAL;
 	if(!planes_apart((uintptr_t)l->W * (uintptr_t)l->H * 4, d_label, d_cell, d_dist)) return PWN_EINVAL;
+	{
+		const void *const wr[3] = { d_label, d_cell, d_dist };
+		if(hide && !pwn_i_hide_array_ok(d_hide, (size_t)l->n, wr, 3, (size_t)l->W * (size_t)l->H * 4)) return PWN_EINVAL;
+	}
 	int rc = pwn_i_batch_refuse(c, 0, false);
 	if(rc != PWN_OK) return rc;
 	(void)hipSetDevice(c->device);
 	hipStream_t s = (hipStream_t)stream;
 	pwn_vp_layout *lw = const_cast<pwn_vp_layout *>(l);
 	int slot; pwn_viewport_rec *recs;
-	rc = vps_device_records(c, lw, d_cams, NULL, s, &slot, &recs);
+	rc = vps_device_records(c, lw, d_cams, NULL, hide, d_hide, s, &slot, &recs);
 	if(rc != PWN_OK) return rc;
-	const pwn_vps_launch V = { recs, l->h_recs, l->n, (flags & PWN_VIEWS_HAS_W) != 0, l->units, l->W, l->H, NULL, (uint32_t *)d_label };
+	const pwn_vps_launch V = { recs, l->h_recs, l->n, (flags & PWN_VIEWS_HAS_W) != 0, l->units, l->W, l->H, NULL, (uint32_t *)d_label, hide };
 	pwn_trace_launch T = { .y0 = 0, .y1 = l->H, .vps = V, .d_sbuf = (uint32_t *)d_cell, .d_zbuf = (float *)d_dist, .stream = s };
 	rc = pwn_i_launch_trace(c, &T);
-	return vps_device_used(c, lw, slot, s, rc, "pwn_trace_viewport_hits_device");
+	return vps_device_used(c, lw, slot, s, rc, who);
+}
+extern "C" int pwn_trace_viewport_hits_device(pwn_ctx *c, const pwn_vp_layout *l, const void *d_cams, int flags,
+	void *d_label, void *d_cell, void *d_dist, void *stream)
+{
+	GRP_REFUSE(c, "pwn_trace_viewport_hits_device");
+	return viewport_hits_device(c, l, d_cams, false, NULL, flags, d_label, d_cell, d_dist, stream, "pwn_trace_viewport_hits_device");
+}
+extern "C" int pwn_trace_viewport_hits_hide_device(pwn_ctx *c, const pwn_vp_layout *l, const void *d_cams, const void *d_hide, int flags,
+	void *d_label, void *d_cell, void *d_dist, void *stream)
+{
+	GRP_REFUSE(c, "pwn_trace_viewport_hits_hide_device");
+	return viewport_hits_device(c, l, d_cams, true, d_hide, flags, d_label, d_cell, d_dist, stream, "pwn_trace_viewport_hits_hide_device");
 }

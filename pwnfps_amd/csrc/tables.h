@@ -240,9 +240,11 @@ struct pwn_trace_params
 	int pair_single_rows;
 	// One hidden sphere per ray or view (pwn_trace_hits_hide_device, pwn_trace_views_hide_device, pwn_trace_view_hits_hide_device; the
 	// kernel's HIDE parameter).  ray_hide: NULL, or nrays int32 beside `rays`: ray i does not see the sphere whose index in the live table
-	// (pwn_hit.object's numbering) is ray_hide[i]; any other value hides nothing.  view_hide != 0: a launch of `views` whose records'
-	// `hide` words count (pwn_view_rec).  Either one picks the HIDE instantiations (pwn_launch_trace_hide, trace_hide.hip); no other
-	// kernel reads them.  (Behind everything else, as the tile pairs were: no other field moves.)
+	// (pwn_hit.object's numbering) is ray_hide[i]; any other value hides nothing -- with `hits` the rays' first hits, without it their
+	// colours (pwn_trace_rays_hide_device).  view_hide != 0: a launch of `views` or of `vps` whose records' `hide` words count
+	// (pwn_view_rec, pwn_viewport_rec).  Either one picks the HIDE instantiations (pwn_launch_trace_hide, trace_hide.hip: views, their
+	// first hits, rays' first hits; pwn_launch_trace_hide2, trace_hide_vp.hip: views of their own sizes, their first hits, rays'
+	// colours); no other kernel reads them.  (Behind everything else, as the tile pairs were: no other field moves.)
 	const int32_t *ray_hide;
 	int view_hide;
 };
@@ -280,7 +282,8 @@ struct pwn_blur_params
 
 // what a launch of the trace kernel traces (its MODE parameter, trace_kernel.hip)
 enum { PWN_KM_FRAME = 0, PWN_KM_VIEWS = 1, PWN_KM_RAYS = 2, PWN_KM_HITS = 3, PWN_KM_VIEWPORTS = 4, PWN_KM_VIEW_HITS = 5, PWN_KM_VIEWPORT_HITS = 6 };
-// ... or'ed to PWN_KM_VIEWS, PWN_KM_VIEW_HITS or PWN_KM_HITS: its HIDE parameter -- every view or ray names one sphere it does not see
+// ... or'ed to PWN_KM_VIEWS, PWN_KM_VIEW_HITS or PWN_KM_HITS (trace_hide.hip), to PWN_KM_VIEWPORTS, PWN_KM_VIEWPORT_HITS or PWN_KM_RAYS
+// (trace_hide_vp.hip): its HIDE parameter -- every view or ray names one sphere it does not see
 enum { PWN_KM_HIDE = 8 };
 
 // One view of a batch: the camera set-up of screen.h:43-57 for that view's camera (pwn_internal.h frame_setup) and its
@@ -304,6 +307,9 @@ struct pwn_view_rec
 // Views s .. nvp-1 take part in rounds [units of record s-1, units of record s): "segment" s, whose fields sit in record s --
 // seg_first = the launch's first ticket of the segment (rising with s; equal for an empty segment), seg_round = its first round,
 // seg_magic / seg_shift = the division by its nvp - s participants (pwn_unit_div_magic; shift < 0: one participant).
+// hide (word 30, byte 120): pwn_view_rec's word of that name -- 0 = the view sees every sphere, k + 1 = it does not see sphere k of
+// the live table (pwn_trace_viewports_hide_device, pwn_trace_viewport_hits_hide_device: viewport_setup.hip writes it from the entry
+// of the record's RECTANGLE, d_hide[perm[j]]).  Only the HIDE instantiations read it; every other path that makes records leaves 0.
 struct pwn_viewport_rec
 {
 	float rayb[4], rdx[4], rdy[4], from[4];
@@ -313,7 +319,8 @@ struct pwn_viewport_rec
 	uint32_t rows_u;                          // ceil(h / 4)
 	uint32_t units;                           // units_x * rows_u
 	uint32_t seg_first, seg_round, seg_magic; int32_t seg_shift;
-	uint32_t pad_[2];
+	uint32_t hide;
+	uint32_t pad_;
 };
 #define PWN_VP_REC_BYTES 128u
 

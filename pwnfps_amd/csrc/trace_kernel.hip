@@ -337,14 +337,20 @@ template<bool HAS_W> __device__ __forceinline__ void chain_rounds(Vec<HAS_W> &v,
 // HIDE (tables.h PWN_KM_HIDE, a bit of the MODE argument: the names of the kernels without it are as they were, and tests and
 // tools/issue_model.py find kernels by name): every view, or every ray, names one sphere of the table that it does not see
 // (pwn_trace_views_hide_device, pwn_trace_view_hits_hide_device, pwn_trace_hits_hide_device).  Instantiated for PWN_KM_VIEWS,
-// PWN_KM_VIEW_HITS and PWN_KM_HITS only, in a translation unit of its own (trace_hide.hip).
+// PWN_KM_VIEW_HITS and PWN_KM_HITS in a translation unit of its own (trace_hide.hip), and for PWN_KM_VIEWPORTS, PWN_KM_VIEWPORT_HITS and
+// PWN_KM_RAYS (pwn_trace_viewports_hide_device, pwn_trace_viewport_hits_hide_device, pwn_trace_rays_hide_device) in a third
+// (trace_hide_vp.hip), where the kernel has a name of its own, PWN_TRACE_KERNEL_NAME: tests pin the set of pwn_trace_kernel's
+// instantiations with the HIDE bit to the first three modes, and a second name changes nothing of what the other two units compile.
+#ifndef PWN_TRACE_KERNEL_NAME
+#define PWN_TRACE_KERNEL_NAME pwn_trace_kernel
+#endif
 template<bool COUNT, bool HAS_W, bool ORDER, int LISTS, int MODE_ARG>
 __global__ void __launch_bounds__(PWN_BLOCK, PWN_MIN_WAVES)
-pwn_trace_kernel(pwn_trace_params P)
+PWN_TRACE_KERNEL_NAME(pwn_trace_params P)
 {
 	constexpr int MODE = MODE_ARG & ~PWN_KM_HIDE;
 	constexpr bool HIDE = (MODE_ARG & PWN_KM_HIDE) != 0;
-	static_assert(!HIDE || (!ORDER && (MODE == PWN_KM_VIEWS || MODE == PWN_KM_VIEW_HITS || MODE == PWN_KM_HITS)), "HIDE: views, their first hits, rays' first hits");
+	static_assert(!HIDE || (!ORDER && MODE != PWN_KM_FRAME), "HIDE: batches of views, of views of their own sizes and of rays");
 	constexpr bool VHITS = MODE == PWN_KM_VIEW_HITS, VIEWS = MODE == PWN_KM_VIEWS || VHITS, HITS = MODE == PWN_KM_HITS, RAYS = MODE == PWN_KM_RAYS || HITS;
 	constexpr bool VPHITS = MODE == PWN_KM_VIEWPORT_HITS, VPS = MODE == PWN_KM_VIEWPORTS || VPHITS;
 	//@R k_prologue
@@ -567,7 +573,10 @@ pwn_trace_kernel(pwn_trace_params P)
 				else
 				{
 					float ox, oy, oz, ow;
-					trace_pixel<COUNT, HAS_W, LISTS>(L, sec_current, seed, org, dir, ox, oy, oz, ow, P.zbuf + i, cnt);
+					// HIDE (pwn_trace_rays_hide_device): the ray's hidden sphere as the first-hit records' above -- ray_hide[i] for i < nrays,
+					// the RAY's index, in the caller's array of n int32, as k + 1 (WALK_HIDDEN: only ever compared)
+					if constexpr(HIDE) trace_pixel<COUNT, HAS_W, LISTS, true>(L, sec_current, seed, org, dir, ox, oy, oz, ow, P.zbuf + i, cnt, (uint32_t)P.ray_hide[i] + 1u);
+					else trace_pixel<COUNT, HAS_W, LISTS>(L, sec_current, seed, org, dir, ox, oy, oz, ow, P.zbuf + i, cnt);
 					P.sbuf[i] = col_pack4(ox, oy, oz, ow);
 				}
 			}
@@ -661,6 +670,8 @@ pwn_trace_kernel(pwn_trace_params P)
 			if constexpr(!VPHITS) sec_current = r[16];        // (first-hit planes read no time)
 			fw = (int)ri[19]; fh = (int)ri[20]; fy0 = 0; fy1 = fh;
 			fux = ri[21]; fmagic = ri[22]; fshift = (int)ri[23]; rows_u = ri[24];
+			// (the record's `hide` word, with the rest of the record: one scalar load, one value for the wave)
+			if constexpr(HIDE) hide1 = ri[30];
 			// (the rectangle lies inside the w x h <= 2^30 pixels of the planes: pwn_viewports_plan)
 			org = ri[18] * (uint32_t)P.w + ri[17];
 		}
@@ -778,7 +789,7 @@ pwn_trace_kernel(pwn_trace_params P)
 				{
 					const uint32_t o = __umul24((uint32_t)y, (uint32_t)P.w) + (uint32_t)x + org;      // w, h <= 32768
 					// (tables.h: the label plane is P.hits, the cell plane P.sbuf, the distance plane P.zbuf)
-					hit_store_planes(trace_hit<COUNT, HAS_W, LISTS>(L, from, rayl, cnt), (uint32_t *)P.hits + o, P.sbuf != NULL ? P.sbuf + o : NULL, P.zbuf != NULL ? P.zbuf + o : NULL);
+					hit_store_planes(trace_hit<COUNT, HAS_W, LISTS, HIDE>(L, from, rayl, cnt, hide1), (uint32_t *)P.hits + o, P.sbuf != NULL ? P.sbuf + o : NULL, P.zbuf != NULL ? P.zbuf + o : NULL);
 				}
 			}
 			else if(x < fw && y < fy1)
@@ -874,10 +885,28 @@ pwn_trace_kernel(pwn_trace_params P)
 
 // (ORDER, LISTS, MODE) -> the four kernels a launch's count and has_w pick from (trace_common.h)
 template<bool ORDER, int LISTS, int MODE>
-using Units = TraceKernels<pwn_trace_kernel<true, true, ORDER, LISTS, MODE>, pwn_trace_kernel<true, false, ORDER, LISTS, MODE>,
-	pwn_trace_kernel<false, true, ORDER, LISTS, MODE>, pwn_trace_kernel<false, false, ORDER, LISTS, MODE>>;
+using Units = TraceKernels<PWN_TRACE_KERNEL_NAME<true, true, ORDER, LISTS, MODE>, PWN_TRACE_KERNEL_NAME<true, false, ORDER, LISTS, MODE>,
+	PWN_TRACE_KERNEL_NAME<false, true, ORDER, LISTS, MODE>, PWN_TRACE_KERNEL_NAME<false, false, ORDER, LISTS, MODE>>;
 
-#ifdef PWN_TRACE_HIDE_UNIT
+#if defined(PWN_TRACE_HIDE_VP_UNIT)
+// trace_hide_vp.hip: this file's text with the HIDE instantiations of the viewport modes and of the rays' colours alone -- thirty-six
+// kernels, three modes x three list forms x COUNT x HAS_W, under the name that unit gives them -- and the one function that launches them.
+template<int LISTS>
+static hipError_t launch_hide2(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
+{
+	if(P->vps != NULL && P->view_hide != 0)
+		return P->hits != NULL ? Units<false, LISTS, PWN_KM_VIEWPORT_HITS | PWN_KM_HIDE>::launch(P, grid, lds_bytes, count, stream)
+		                       : Units<false, LISTS, PWN_KM_VIEWPORTS | PWN_KM_HIDE>::launch(P, grid, lds_bytes, count, stream);
+	if(P->rays != NULL && P->hits == NULL && P->ray_hide != NULL) return Units<false, LISTS, PWN_KM_RAYS | PWN_KM_HIDE>::launch(P, grid, lds_bytes, count, stream);
+	// (a missing kernel is an error: nothing else has a HIDE instantiation here)
+	return hipErrorInvalidValue;
+}
+extern "C" hipError_t pwn_launch_trace_hide2(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
+{
+	if(P->g_rec != NULL) return launch_hide2<PWN_LF_GLOBAL>(P, grid, lds_bytes, count, stream);
+	return P->off_recsph != 0u ? launch_hide2<PWN_LF_INLINE>(P, grid, lds_bytes, count, stream) : launch_hide2<PWN_LF_INDEXED>(P, grid, lds_bytes, count, stream);
+}
+#elif defined(PWN_TRACE_HIDE_UNIT)
 // trace_hide.hip: this file's text with the HIDE instantiations alone -- thirty-six kernels, three modes x three list forms x COUNT x
 // HAS_W -- and the one function that launches them.  (A unit of its own: in this file they would add a third to its build time.)
 template<int LISTS>

@@ -12,13 +12,14 @@
 
 static_assert(sizeof(pwn_viewport_rec) == PWN_VP_REC_BYTES, "a viewport record is eight 16-byte words");
 static_assert(offsetof(pwn_viewport_rec, sec_current) == 64 && offsetof(pwn_viewport_rec, x) == 68, "the head is four 16-byte words and the time");
+static_assert(offsetof(pwn_viewport_rec, hide) == 120, "the hide word is word 30: the third of the record's last 16-byte word");
 
 // Record j stands for rectangle perm[j] (the records are in order of rising units, the cameras in the caller's order).
 // scal[j] = (-yrat, xsrat, ysrat, 0) of the view's own w x h (pwn_frame_setup_scalars, computed on the host: the divisions stay there).
 // Every index is j, or a perm[j] that the library wrote and checked to be below n: no bit of a camera reaches an address.
 __global__ void __launch_bounds__(64)
 pwn_viewport_setup_kernel(const uint4 *__restrict__ master, const float4 *__restrict__ scal, const uint32_t *__restrict__ perm,
-	const float4 *__restrict__ cams, const uint32_t *__restrict__ secs, uint4 *__restrict__ out, int n)
+	const float4 *__restrict__ cams, const uint32_t *__restrict__ secs, const int32_t *__restrict__ hide, uint4 *__restrict__ out, int n)
 {
 	const int j = blockIdx.x * 64 + threadIdx.x;
 	if(j >= n) return;
@@ -41,15 +42,30 @@ pwn_viewport_setup_kernel(const uint4 *__restrict__ master, const float4 *__rest
 	r[1] = make_uint4(__float_as_uint(rdx.x), __float_as_uint(rdx.y), __float_as_uint(rdx.z), __float_as_uint(rdx.w));
 	r[2] = make_uint4(__float_as_uint(rdy.x), __float_as_uint(rdy.y), __float_as_uint(rdy.z), __float_as_uint(rdy.w));
 	r[3] = cw;
-	r[4] = g4; r[5] = m[5]; r[6] = m[6]; r[7] = m[7];        // h, units_x, ux_magic, ux_shift; rows_u, units, seg_first, seg_round; seg_magic, seg_shift, padding
+	// The record's `hide` word (tables.h pwn_viewport_rec, view_setup.hip's rule): k + 1 for a value k that can be a sphere's index, 0 for
+	// every other one and where the call has no array (the master's word is 0: pwn_i_viewport_recs_bake).  The entry is the RECTANGLE's,
+	// hide[perm[j]], as the camera is.  The value is compared and incremented, nothing else.
+	uint4 g7 = m[7];                 // seg_magic, seg_shift, hide, padding
+	if(hide != NULL)
+	{
+		const int32_t k = hide[i];
+		g7.z = k >= 0 && k < PWN_OBJ_MAX ? (uint32_t)k + 1u : 0u;
+	}
+	r[4] = g4; r[5] = m[5]; r[6] = m[6]; r[7] = g7;        // h, units_x, ux_magic, ux_shift; rows_u, units, seg_first, seg_round; seg_magic, seg_shift, hide, padding
 }
 
 // (d_master, d_scal, d_cams and d_out 16-byte aligned: the kernel moves whole 16-byte words)
-extern "C" hipError_t pwn_launch_viewport_setup(const pwn_viewport_rec *d_master, const float *d_scal, const uint32_t *d_perm,
-	const float *d_cams, const float *d_secs, pwn_viewport_rec *d_out, int n, hipStream_t stream)
+// (d_hide: NULL, or n int32 in the caller's order, each rectangle's hidden sphere -- pwn_trace_viewports_hide_device)
+extern "C" hipError_t pwn_launch_viewport_setup_hide(const pwn_viewport_rec *d_master, const float *d_scal, const uint32_t *d_perm,
+	const float *d_cams, const float *d_secs, const int32_t *d_hide, pwn_viewport_rec *d_out, int n, hipStream_t stream)
 {
 	if(n <= 0) return hipSuccess;
 	hipLaunchKernelGGL(pwn_viewport_setup_kernel, dim3((n + 63) / 64), dim3(64), 0, stream,
-		(const uint4 *)d_master, (const float4 *)d_scal, d_perm, (const float4 *)d_cams, (const uint32_t *)d_secs, (uint4 *)d_out, n);
+		(const uint4 *)d_master, (const float4 *)d_scal, d_perm, (const float4 *)d_cams, (const uint32_t *)d_secs, d_hide, (uint4 *)d_out, n);
 	return hipGetLastError();
+}
+extern "C" hipError_t pwn_launch_viewport_setup(const pwn_viewport_rec *d_master, const float *d_scal, const uint32_t *d_perm,
+	const float *d_cams, const float *d_secs, pwn_viewport_rec *d_out, int n, hipStream_t stream)
+{
+	return pwn_launch_viewport_setup_hide(d_master, d_scal, d_perm, d_cams, d_secs, NULL, d_out, n, stream);
 }

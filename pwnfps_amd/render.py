@@ -381,13 +381,15 @@ class Renderer:
         self._layouts.append(lay)
         return lay
 
-    def trace_viewports_device(self, layout, cams, secs, sbuf, zbuf, work=None, has_w=False, stream=None):
+    def trace_viewports_device(self, layout, cams, secs, sbuf, zbuf, work=None, has_w=False, stream=None, hide=None):
         """pwn_trace_viewports_device: the views of a viewports_layout from cameras on the GPU into ONE frame of the layout's W x H on
         the GPU, stream-ordered, no synchronisation and no host copy.  All torch tensors on this context's GPU, contiguous and
         16-byte aligned: cams (n,16) or (n,4,4) float32, camera i for rectangle i; secs (n,) float32; sbuf (H,W) int32 or uint32
         (rectangle i as trace_screen_centred renders it on a context of w_i x h_i; nothing outside the rectangles is written);
         zbuf (H,W) float32 (in / out: a primary ray that runs out of steps keeps what it holds); work (H,W) int32 or uint32 scratch,
-        needed with blur on.  has_w and stream as trace_views_device takes them."""
+        needed with blur on.  has_w and stream as trace_views_device takes them.
+        hide: None, or an (n,) int32 tensor on the same GPU (pwn_trace_viewports_hide_device): rectangle i does not see sphere hide[i]
+        of the table in force; PWN_HIDE_NONE (-1) and every other value that is no sphere's index hide nothing."""
         import torch
         who = "trace_viewports_device"
         if not isinstance(layout, ViewportsLayout) or layout._ptr is None or layout._renderer is not self:
@@ -409,10 +411,20 @@ class Renderer:
                 raise ValueError("%s: tensors on %s and %s" % (who, cams.device, t.device))
             if t.data_ptr() % 16 != 0:
                 raise ValueError("%s: %s is not 16-byte aligned" % (who, name))
+        if hide is not None:
+            _tensor_check(torch, hide, "hide", (torch.int32,), 1, n, who=who)
+            if hide.device != cams.device:
+                raise ValueError("%s: tensors on %s and %s" % (who, cams.device, hide.device))
         if stream is None:
             stream = torch.cuda.current_stream(cams.device)
         if not isinstance(stream, int):
             stream = stream.cuda_stream
+        if hide is not None:
+            self._chk(lib.pwn_trace_viewports_hide_device(self._ctx, layout._ptr, C.c_void_p(cams.data_ptr()), C.c_void_p(secs.data_ptr()),
+                                                          C.c_void_p(hide.data_ptr()), _lib.PWN_VIEWS_HAS_W if has_w else 0,
+                                                          C.c_void_p(work.data_ptr() if work is not None else None), C.c_void_p(sbuf.data_ptr()),
+                                                          C.c_void_p(zbuf.data_ptr()), C.c_void_p(stream or 0)), "pwn_trace_viewports_hide_device")
+            return
         self._chk(lib.pwn_trace_viewports_device(self._ctx, layout._ptr, C.c_void_p(cams.data_ptr()), C.c_void_p(secs.data_ptr()),
                                                  _lib.PWN_VIEWS_HAS_W if has_w else 0,
                                                  C.c_void_p(work.data_ptr() if work is not None else None), C.c_void_p(sbuf.data_ptr()),
@@ -446,12 +458,14 @@ class Renderer:
                                      float(sec_current), col.ctypes.data, z.ctypes.data), "pwn_trace_rays")
         return col, z
 
-    def trace_rays_device(self, rays, col, depth, seeds=None, sec_current=0.0, has_w=False, stream=None, n=None):
+    def trace_rays_device(self, rays, col, depth, seeds=None, sec_current=0.0, has_w=False, stream=None, n=None, hide=None):
         """pwn_trace_rays_device: one trace launch, stream-ordered, no synchronisation.  rays / col / depth / seeds are torch
         tensors on this context's GPU -- rays (n,8) float32 16-byte aligned, col (n,) int32 or uint32, depth (n,) float32 (in / out),
         seeds (n,) int32 or uint32 or None -- or raw device pointers, with n given.  has_w: honour the records' w lanes
         (PWN_RAYS_HAS_W; else they are taken as 1 and 0).  stream: a torch.cuda.Stream or a raw hipStream_t; None = torch's
-        current stream on this device for tensors, the default stream for pointers."""
+        current stream on this device for tensors, the default stream for pointers.
+        hide: None, or an (n,) int32 tensor on the same GPU (pwn_trace_rays_hide_device): ray i does not see sphere hide[i] of the
+        table in force, on any of its segments; PWN_HIDE_NONE (-1) and every other value that is no sphere's index hide nothing."""
         tensors = [t for t in (rays, col, depth, seeds) if t is not None and not isinstance(t, int)]
         if tensors:
             import torch
@@ -480,8 +494,20 @@ class Renderer:
             p_rays, p_col, p_depth, p_seeds = rays, col, depth, seeds
         if int(n) < 0 or int(n) > _lib.PWN_RAYS_MAX:
             raise ValueError("trace_rays_device: n = %d, 0 ... %d" % (n, _lib.PWN_RAYS_MAX))
+        if hide is not None:
+            import torch
+            _tensor_check(torch, hide, "hide", (torch.int32,), 1, int(n), who="trace_rays_device")
+            if tensors and hide.device != rays.device:
+                raise ValueError("trace_rays_device: tensors on %s and %s" % (rays.device, hide.device))
+            if stream is None:
+                stream = torch.cuda.current_stream(hide.device)
         if stream is not None and not isinstance(stream, int):
             stream = stream.cuda_stream
+        if hide is not None:
+            self._chk(lib.pwn_trace_rays_hide_device(self._ctx, int(n), C.c_void_p(p_rays), C.c_void_p(p_seeds), C.c_void_p(hide.data_ptr()),
+                                                     float(sec_current), _lib.PWN_RAYS_HAS_W if has_w else 0, C.c_void_p(p_col),
+                                                     C.c_void_p(p_depth), C.c_void_p(stream or 0)), "pwn_trace_rays_hide_device")
+            return
         self._chk(lib.pwn_trace_rays_device(self._ctx, int(n), C.c_void_p(p_rays), C.c_void_p(p_seeds), float(sec_current),
                                             _lib.PWN_RAYS_HAS_W if has_w else 0, C.c_void_p(p_col), C.c_void_p(p_depth),
                                             C.c_void_p(stream or 0)), "pwn_trace_rays_device")
@@ -797,12 +823,14 @@ class Renderer:
                   "pwn_trace_viewport_hits")
         return label, cell, dist
 
-    def trace_viewport_hits_device(self, layout, cams, label, cell=None, dist=None, has_w=False, stream=None):
+    def trace_viewport_hits_device(self, layout, cams, label, cell=None, dist=None, has_w=False, stream=None, hide=None):
         """pwn_trace_viewport_hits_device: the planes of trace_viewport_hits for the views of a viewports_layout, from cameras on the
         GPU into ONE frame of the layout's W x H on the GPU, stream-ordered, no synchronisation and no host copy.  All torch tensors
         on this context's GPU, contiguous and 16-byte aligned: cams (n,16) or (n,4,4) float32, camera i for rectangle i; label (H,W)
         int32 or uint32; cell (H,W) int32 or uint32 -- or (H,W,2) int16 -- or None; dist (H,W) float32 or None.  Every pixel of
-        every rectangle is written in every plane given, nothing outside them.  has_w and stream as trace_views_device takes them."""
+        every rectangle is written in every plane given, nothing outside them.  has_w and stream as trace_views_device takes them.
+        hide as trace_viewports_device takes it (pwn_trace_viewport_hits_hide_device); object numbers in the labels stay those of the
+        full table."""
         import torch
         who = "trace_viewport_hits_device"
         if not isinstance(layout, ViewportsLayout) or layout._ptr is None or layout._renderer is not self:
@@ -829,10 +857,21 @@ class Renderer:
                 raise ValueError("%s: tensors on %s and %s" % (who, cams.device, t.device))
             if t.data_ptr() % 16 != 0:
                 raise ValueError("%s: %s is not 16-byte aligned" % (who, name))
+        if hide is not None:
+            _tensor_check(torch, hide, "hide", (torch.int32,), 1, layout.n, who=who)
+            if hide.device != cams.device:
+                raise ValueError("%s: tensors on %s and %s" % (who, cams.device, hide.device))
         if stream is None:
             stream = torch.cuda.current_stream(cams.device)
         if not isinstance(stream, int):
             stream = stream.cuda_stream
+        if hide is not None:
+            self._chk(lib.pwn_trace_viewport_hits_hide_device(self._ctx, layout._ptr, C.c_void_p(cams.data_ptr()), C.c_void_p(hide.data_ptr()),
+                                                              _lib.PWN_VIEWS_HAS_W if has_w else 0, C.c_void_p(label.data_ptr()),
+                                                              C.c_void_p(cell.data_ptr() if cell is not None else None),
+                                                              C.c_void_p(dist.data_ptr() if dist is not None else None), C.c_void_p(stream or 0)),
+                      "pwn_trace_viewport_hits_hide_device")
+            return
         self._chk(lib.pwn_trace_viewport_hits_device(self._ctx, layout._ptr, C.c_void_p(cams.data_ptr()),
                                                      _lib.PWN_VIEWS_HAS_W if has_w else 0, C.c_void_p(label.data_ptr()),
                                                      C.c_void_p(cell.data_ptr() if cell is not None else None),

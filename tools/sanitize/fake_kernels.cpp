@@ -103,7 +103,16 @@ extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size
 }
 extern "C" hipError_t pwn_launch_trace_refill(const pwn_trace_params *P, int g, size_t l, bool c, hipStream_t s) { return pwn_launch_trace(P, g, l, c, s); }
 // (the HIDE kernels, trace_hide.hip: the same stand-in -- what the hide words do to a pixel is the kernels' business)
-extern "C" hipError_t pwn_launch_trace_hide(const pwn_trace_params *P, int g, size_t l, bool c, hipStream_t s) { return pwn_launch_trace(P, g, l, c, s); }
+// (... counted, each: hide_viewports_driver.cpp looks at which launcher a call's trace launch went to)
+extern "C" { int pwn_fake_hide_launches = 0, pwn_fake_hide2_launches = 0; }
+extern "C" hipError_t pwn_launch_trace_hide(const pwn_trace_params *P, int g, size_t l, bool c, hipStream_t s) { pwn_fake_hide_launches++; return pwn_launch_trace(P, g, l, c, s); }
+// (trace_hide_vp.hip's: views of their own sizes with the records' hide words, or rays' colours with ray_hide -- anything else it refuses)
+extern "C" hipError_t pwn_launch_trace_hide2(const pwn_trace_params *P, int g, size_t l, bool c, hipStream_t s)
+{
+	if(!((P->vps != NULL && P->view_hide != 0) || (P->rays != NULL && P->hits == NULL && P->ray_hide != NULL))) return hipErrorInvalidValue;
+	pwn_fake_hide2_launches++;
+	return pwn_launch_trace(P, g, l, c, s);
+}
 extern "C" unsigned pwn_trace_refill_lds_extra(bool) { return 16u; }
 extern "C" int pwn_trace_refill_blocks_per_cu(size_t, bool, bool) { return 4; }
 extern "C" int pwn_trace_blocks_per_cu(size_t, bool, bool) { return 5; }
@@ -178,10 +187,28 @@ static hipError_t view_setup(const float *cams, const float *secs, const int32_t
 // (the records of pwn_trace_viewports_device; viewports_device_driver.cpp: viewport_setup.hip's algorithm, one record after the other --
 // the geometry words from the master copy, the head from camera perm[j] with the view's own scalars, every product and sum rounded
 // by itself.  Reads exactly n master records, n scalar words, n perm entries, n cameras and n times, writes n records.)
+static hipError_t viewport_setup(const pwn_viewport_rec *master, const float *scal, const uint32_t *perm, const float *cams, const float *secs,
+	const int32_t *hide, pwn_viewport_rec *out, int n);
 extern "C" hipError_t pwn_launch_viewport_setup(const pwn_viewport_rec *master, const float *scal, const uint32_t *perm,
 	const float *cams, const float *secs, pwn_viewport_rec *out, int n, hipStream_t)
 {
 	small_launch("viewport_setup", cams, out, { (size_t)n });
+	return viewport_setup(master, scal, perm, cams, secs, NULL, out, n);
+}
+// (... with every rectangle's hidden sphere, pwn_trace_viewports_hide_device: reads exactly n entries of hide, entry perm[j] for record j.
+// The same launch name: the drivers count set-up launches by it; pwn_fake_viewport_hide_hook says which array one was handed)
+extern "C" void (*pwn_fake_viewport_hide_hook)(const int32_t *hide, int n);
+void (*pwn_fake_viewport_hide_hook)(const int32_t *hide, int n) = NULL;
+extern "C" hipError_t pwn_launch_viewport_setup_hide(const pwn_viewport_rec *master, const float *scal, const uint32_t *perm,
+	const float *cams, const float *secs, const int32_t *hide, pwn_viewport_rec *out, int n, hipStream_t)
+{
+	small_launch("viewport_setup", cams, out, { (size_t)n });
+	if(pwn_fake_viewport_hide_hook != NULL) pwn_fake_viewport_hide_hook(hide, n);
+	return viewport_setup(master, scal, perm, cams, secs, hide, out, n);
+}
+static hipError_t viewport_setup(const pwn_viewport_rec *master, const float *scal, const uint32_t *perm, const float *cams, const float *secs,
+	const int32_t *hide, pwn_viewport_rec *out, int n)
+{
 	for(int j = 0; j < n; j++)
 	{
 		const uint32_t i = perm[j];
@@ -197,6 +224,7 @@ extern "C" hipError_t pwn_launch_viewport_setup(const pwn_viewport_rec *master, 
 		memcpy(r.from, cam + 12, 16);
 		if(secs != NULL) memcpy(&r.sec_current, secs + i, 4);
 		else r.sec_current = 0.0f;
+		if(hide != NULL) r.hide = hide[i] >= 0 && hide[i] < PWN_OBJ_MAX ? (uint32_t)hide[i] + 1u : 0u;
 		out[j] = r;
 	}
 	if(pwn_fake_viewport_setup_hook != NULL) pwn_fake_viewport_setup_hook(master, scal, perm, out, n);
