@@ -203,6 +203,12 @@ __device__ __forceinline__ uint32_t col_pack(v4 c) { return col_pack4(c.x, c.y, 
 #define PWN_HPI_INV 0x1.45F306DC9C883p+23
 #define PWN_HPI     0x1.921FB54442D18p0
 #define PWN_PI63    0x1.921FB54442D18p-62
+// A double constant that takes a register pair.  A kernel that holds more than one copy of the code below may define PWN_F64_HERE
+// so that the pair is made where it is used (trace_kernel.hip); left alone, the compiler makes a constant that several copies share
+// once, at the top of the kernel, and keeps the pair alive from there.
+#ifndef PWN_F64_HERE
+#define PWN_F64_HERE(c) (c)
+#endif
 
 __device__ __forceinline__ uint32_t abstop12(float x) { return (__float_as_uint(x) >> 20) & 0x7ffu; }
 
@@ -212,7 +218,7 @@ __device__ __forceinline__ float sincos_poly(double x, double x2, double csign, 
 	if((n & 1) == 0)
 	{
 		double x3 = x * x2;
-		double s1 = fma(x2, -0x1.994eb3774cf24p-13, 0x1.1107605230bc4p-7);
+		double s1 = fma(x2, -0x1.994eb3774cf24p-13, PWN_F64_HERE(0x1.1107605230bc4p-7));
 		double x7 = x3 * x2;
 		double s = fma(x3, -0x1.555545995a603p-3, x);
 		return (float)fma(x7, s1, s);
@@ -220,7 +226,7 @@ __device__ __forceinline__ float sincos_poly(double x, double x2, double csign, 
 	else
 	{
 		double x4 = x2 * x2;
-		double c2 = fma(x2, csign * 0x1.99343027bf8c3p-16, csign * -0x1.6c087e89a359dp-10);
+		double c2 = fma(x2, csign * 0x1.99343027bf8c3p-16, csign * PWN_F64_HERE(-0x1.6c087e89a359dp-10));
 		double c1 = fma(x2, csign * -0x1.ffffffd0c621cp-2, csign * 0x1p0);
 		double x6 = x4 * x2;
 		double c = fma(x4, csign * 0x1.55553e1068f19p-5, c1);
@@ -246,7 +252,7 @@ __device__ __forceinline__ uint32_t inv_pio4_word(int i)
 __device__ __forceinline__ float sin_poly_pos(double x, double x2)
 {
 	double x3 = x * x2;
-	double s1 = fma(x2, -0x1.994eb3774cf24p-13, 0x1.1107605230bc4p-7);
+	double s1 = fma(x2, -0x1.994eb3774cf24p-13, PWN_F64_HERE(0x1.1107605230bc4p-7));
 	double x7 = x3 * x2;
 	double s = fma(x3, -0x1.555545995a603p-3, x);
 	return (float)fma(x7, s1, s);
@@ -254,7 +260,7 @@ __device__ __forceinline__ float sin_poly_pos(double x, double x2)
 __device__ __forceinline__ float cos_poly_pos(double x2)
 {
 	double x4 = x2 * x2;
-	double c2 = fma(x2, 0x1.99343027bf8c3p-16, -0x1.6c087e89a359dp-10);
+	double c2 = fma(x2, 0x1.99343027bf8c3p-16, PWN_F64_HERE(-0x1.6c087e89a359dp-10));
 	double c1 = fma(x2, -0x1.ffffffd0c621cp-2, 0x1p0);
 	double x6 = x4 * x2;
 	double c = fma(x4, 0x1.55553e1068f19p-5, c1);

@@ -205,7 +205,7 @@ static inline bool camera_has_w(const float cam[16]) { return !(cam[3] == 0.0f &
                           // of frame f+1's tables had to wait for the end of frame f-1 and so ran right where trace f starts;
                           // with three or four it runs at once, somewhere beside the trace grid: 0.3823 -> 0.3790 ms per 4K frame
 #endif
-#define PWN_NCOUNTERS 48     // device counters of the counting kernel variants: 16 (pwn_stats) + 27 regions + waves + spare
+#define PWN_NCOUNTERS 48     // device counters of the counting kernel variants: 16 (pwn_stats) + 31 regions + waves
 #define PWN_TILED_STREAMS_DEFAULT 2
 #define PWN_TICKET_SETS 6u  // launch n counts in set n mod 2R and clears set (n + R) mod 2R, R = pwn_ctx.launch_rot streams in rotation, 2 or 3 (pwn_i_launch_trace)
 #define PWN_NSTAGE 4      // pinned staging buffers for those uploads

@@ -193,7 +193,16 @@ enum { RG_SEG = 0, RG_SETUP_SLOW, RG_EXHAUSTED, RG_WALL, RG_SPHERE, RG_FLOOR, RG
 	RG_UNIT_HALF, RG_HC_R2, RG_HC_OUT, RG_PORTAL_WALL, RG_PORTAL_GO, RG_PORTAL_ODD, RG_PORTAL_ROT2,
 	RG_SPHBOUND, RG_SPHSKIP,       // a list's ball is tested by the wave (trace_walk.inc, sphere_bound.h); ... and the list skipped
 	RG_UNIT_RIGHT,                 // tile pairs: a tile's right half is rebuilt from what its left half put aside (trace_kernel.hip)
+	// The units kernel holds the segment's text once per bounce depth (trace_segment.inc): RG_SEG counts the entries of all copies,
+	// these the entries of copy 1 and of copy 2 alone (copy 0's are the rest), and the walk iterations of copy 1 and of copy 2 (of
+	// pwn_stats.wave_steps, which counts all).  A wave enters copy d + 1 exactly when it ran copy d's jitter: RG_SEG1 and RG_SEG2 are
+	// also the per-copy split of RG_JITTER.
+	// RG_COMP1 / RG_COMP1_FOG there: the composite with entry A, the first surface (lanes of depth >= 1); RG_COMP2 / RG_COMP2_FOG:
+	// with entry B, the second surface (lanes of depth 2), which runs first.  The entry counts are those of the shifted stack's two
+	// levels; the FOG counts are per ENTRY now, where they were per stack level (top, below) before.
+	RG_SEG1, RG_SEG2, RG_WSTEPS1, RG_WSTEPS2,
 	RG_N };
+static_assert(RG_N + 1 <= 32, "pwn_stats.regions: the regions, then the waves of the launch");
 struct Counters { uint32_t rays, steps, portals, tests, exhausted, wsteps, wp[8], apasses, apass_lanes, rg[RG_N]; };
 // one count per wave64 that enters a code path with at least one lane (pwn_stats.wave_paths)
 #define WAVE_PATH(k) do { if(COUNT && (__ffsll((long long)__ballot(1)) - 1) == (int)(threadIdx.x & 63)) cnt.wp[k]++; } while(0)

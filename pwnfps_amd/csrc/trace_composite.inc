@@ -3,6 +3,9 @@
 // Names it uses from the including scope:
 //   L (Lds), COUNT, cnt;  depth (the number of surfaces the ray bounced off);  the composite stack, top entry first:
 //   st_refl0, st_fog0, sc0x, sc0y, sc0z;  st_refl1, st_fog1, sc1x, sc1y, sc1z.
+//   (The refill kernel keeps a two-entry shifted stack and includes this once.  The units kernel keeps its entries under names of their
+//   own and includes it once per ENTRY, each time as a stack one entry deep -- `depth` 0 or 1, the second level's names aliased to the
+//   first's and dead: trace_kernel.hip, ray_done.)
 // Names it writes:
 //   vx, vy, vz, vw (in: the last segment's colour; out: the pixel's, without w_acc).
 //@R p_comp

@@ -26,6 +26,15 @@
 //     is arithmetically identical to the 4-lane SSE code (see HAS_W below),
 //   - no device function calls (dev_math.h) and no SLP packing (Makefile).
 #include <hip/hip_runtime.h>
+// (dev_math.h: the segment's text stands here once per bounce depth, and with it the floor's sine and cosine -- their constants are
+// made where they are used, not once in front of the unit loop, where they would be two register pairs more across every walk)
+template<unsigned long long BITS> static __device__ __forceinline__ double pwn_f64_here()
+{
+	unsigned lo, hi;
+	asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %3" : "=v"(lo), "=v"(hi) : "i"((unsigned)BITS), "i"((unsigned)(BITS >> 32)));
+	return __builtin_bit_cast(double, (unsigned long long)lo | ((unsigned long long)hi << 32));
+}
+#define PWN_F64_HERE(c) pwn_f64_here<__builtin_bit_cast(unsigned long long, (double)(c))>()
 #include "trace_common.h"
 #include "pwnhip.h"      // PWN_OBJ_MAX (hit_store_planes)
 
@@ -59,25 +68,17 @@ __device__ __forceinline__ void trace_pixel(const Lds &L, float sec_current, uin
 	// x * 0.0f (COL_* have a = 0, defs.h:17-19; spheres get b,g,r only, script.h:30-32):
 	// +-0 for any finite input, and the sign of a zero never reaches a pixel, so the
 	// w lanes of icol and of the composite stack are not kept.
-	// The composite stack (reflectivity, fog, colour of the surfaces the ray bounced off), two entries, as a
-	// shift register: a bounce moves the top entry down and writes the new one on top (plain moves; indexing by
-	// the segment number made ten selects of it).  The top entry's colour IS the next segment's icol
-	// (trace.h:90), so it starts as 1,1,1 and icol needs no registers of its own.
-	// (an entry is written when its surface is met and read only by a lane that bounced that often: the entries start as whatever
-	// their registers hold -- an asm statement without instructions, volatile so that two of them are not taken for one value)
-	float st_refl0, st_refl1, st_fog0, st_fog1;
-	float sc0x = 1.0f, sc0y = 1.0f, sc0z = 1.0f;
-	float sc1x, sc1y, sc1z;
-	asm volatile("" : "=v"(st_refl0)); asm volatile("" : "=v"(st_refl1)); asm volatile("" : "=v"(st_fog0)); asm volatile("" : "=v"(st_fog1));
-	asm volatile("" : "=v"(sc1x)); asm volatile("" : "=v"(sc1y)); asm volatile("" : "=v"(sc1z));
-#define icx sc0x
-#define icy sc0y
-#define icz sc0z
-	// Every lane still in the segment loop is on the same segment, so the segment number `seg` is one scalar
-	// for the wave (tests on it are scalar branches); `depth`, the number of surfaces a pixel's ray bounced off,
-	// is per lane and set where the lane leaves the loop.
-	int depth, seg = 0;
-	asm volatile("" : "=v"(depth));
+	// The composite stack (reflectivity, fog, colour of the surfaces the ray bounced off): two entries under names of their
+	// own, A for the first surface and B for the second.  The segment's text stands below once per bounce depth
+	// (trace_segment.inc), so which entry a copy writes, and which one's colour it is lit with -- the entry of the surface
+	// it came off IS the segment's icol (trace.h:90); the primary segment's is 1,1,1 -- is settled where the copy is
+	// included: nothing is shifted, copied at a join or tested.
+	// (an entry is written when its surface is met and read only by a lane that bounced that often; it has no value before,
+	// and so takes no register in the copies in front of the one that writes it)
+	float stA_refl, stA_fog, scAx, scAy, scAz;
+	float stB_refl, stB_fog, scBx, scBy, scBz;
+	// `depth`, the number of surfaces a pixel's ray bounced off, is per lane and set where the lane leaves its copy.
+	int depth;
 	float vx, vy, vz, vw;
 	asm volatile("" : "=v"(vx)); asm volatile("" : "=v"(vy)); asm volatile("" : "=v"(vz));
 	// The colour's w lane is not carried: every surface colour has w = 0 (defs.h:16-18, spheres'
@@ -96,100 +97,73 @@ __device__ __forceinline__ void trace_pixel(const Lds &L, float sec_current, uin
 	V aux_pos, aux_norm;
 	aux_pos.x = aux_pos.y = aux_pos.z = aux_pos.w = 0.0f;
 	aux_norm = aux_pos;
-#pragma unroll 1
-	for(;;)
+	// The reference's recursion, one copy of the segment's text per depth (the last one cannot bounce).  One text with the depth in a
+	// scalar register was this kernel's form before: its joins, the stack's shift and its tests on the depth were a tenth of a
+	// frame's vector moves and more scalar than vector work behind every walk.
+	static_assert(REFLECT_MAX == 2, "trace_segment.inc is included once per bounce depth");
+#define PWN_SEG 0
+#include "trace_segment.inc"
+#undef PWN_SEG
+#define PWN_SEG 1
+#include "trace_segment.inc"
+#undef PWN_SEG
+#define PWN_SEG 2
+#include "trace_segment.inc"
+#undef PWN_SEG
+
+ray_done:
+	// trace.h:91-101, innermost first: the composite's text (trace_composite.inc) takes the stack's top entry first, and which
+	// entry that is depends on the lane -- B for a ray that bounced twice, A for one that bounced once.  So the text is included
+	// once per entry, each time as a stack of that one entry: B for the lanes with depth 2, then A for those with depth >= 1 --
+	// the same operations in the same order per lane as one pass over a shifted stack.  (The text's second level is dead in both:
+	// the stack it sees is one entry deep.  The first inclusion's counters are that level's: RG_COMP2 and RG_COMP2_FOG count entry B's
+	// pass, RG_COMP1 and RG_COMP1_FOG entry A's -- the entry counts of the shifted stack's two levels, the fog counts per entry where
+	// they were per level: trace_common.h.)
 	{
-		//@R p_setup
-		RG(RG_SEG);
-		seg = __builtin_amdgcn_readfirstlane(seg);
-		// ------------------------------------------------ trace.h:186-248 (trace_setup.inc)
-		// the segment's ray and what the walk keeps of it.  Declared here, without values, because the set-up's text is shared
-		// with the refill kernel, where they outlive the segment.  The ORDER of these declarations is that of the set-up's
-		// first writes and is not a matter of style: in another order the compiler numbers registers differently and this
-		// kernel's assembly is no longer the one that was measured (profiles/shared_segment/asm.txt).
-		float cdist, fog, aux_dist;
-		bool gyp;
-		uint32_t cxz, sx, sz, cw;
-		float wx, wy, wz;
-		int ldy, ldx, ldz;
-		V ray;
-		float iax, iaz, iay, iay_dn;
-		uint32_t iay_up_bits;
-		int ldir, ev, base;
-#include "trace_setup.inc"
-
-		// ------------------------------------------------ trace.h:250-675 (trace_walk.inc)
-		//@R p_walk_ctl
-		// How the walk loop ends: ev is the step count and the event in one register.  It starts a segment at -WALK_STEPS, is counted up
-		// at the top of every iteration, and a step without an event leaves it as it is (trace_walk.inc WALK_EV_KEEP: the room body's two
-		// selects -- sphere hit / floor-ceiling / neither); the loop runs while ev < 0, one compare.  A lane that leaves with ev == 0 has made
-		// WALK_STEPS steps without an event: out of steps (trace.h:250,677); an event in the last step still wins.  The limit in a counter
-		// of its own, folded into ev at the bottom, was three more VALU and one more scalar instruction per step
-		// (profiles/walk_exit/ab.txt, with both latches as compiled).
-		// Two other forms were built and measured in round 3 (profiles/r3_walk_exit.txt; the code is in commit 2b36426):
-		// the step limit as a scalar count with a branch of its own (-3 VALU, +2 scalar per step: +3.9 % time at 4K), and a
-		// lane mask `done` = hit || ymin with WHICH of the two read off cdist against aux_dist after the walk (-4 VALU,
-		// +10 scalar mask instructions per step as compiled: +5.3 %).  Scalar instructions are not free here.
-		ev = -WALK_STEPS;
-#pragma unroll 1
-		do
+		const int depth_lane = depth;
+#define st_refl1 st_refl0
+#define st_fog1 st_fog0
+#define sc1x sc0x
+#define sc1y sc0y
+#define sc1z sc0z
 		{
-			ev++;
-#include "trace_walk.inc"
-		} while(ev < 0);
-		// what the ray ended on is read back from the register: without this the compiler keeps
-		// "ev == EV_OUT_OF_STEPS" as a lane mask that it updates in every iteration of the walk
-		// (5 of ~85 instructions per step)
-		asm volatile("" : "+v"(ev));
-
-		//@R p_post
-		if(ev == EV_OUT_OF_STEPS)
-		{
-			//@R p_exhausted
-			RG(RG_EXHAUSTED);
-			// trace.h:677-678: out of steps -- the walked ray is the colour
-			if(COUNT) cnt.exhausted++;
-			vx = ray.x; vy = ray.y; vz = ray.z; vw = HAS_W ? ray.w : 0.0f;
-			depth = seg;
-			break;
-		}
-		//@R p_post
-		if(ev == EV_WALL && base == BASE_ROOM_Y) { ldir = ldy; base = (gyp ? BASE_CEIL : BASE_FLOOR); }
-		// zbuf = the PRIMARY ray's hit distance (trace.h:102-105); a primary ray that ran out of steps
-		// leaves the old depth in place (trace.h:677)
-		if(seg == 0) *zpix = (ev == EV_SPHERE ? aux_dist : cdist);
-
-		// (the segment's colour is computed into the pixel's own registers: a segment that ends the ray has nothing to copy)
-		float refl;
-#define colx vx
-#define coly vy
-#define colz vz
-		// trace.h:108-154 / 283-291: the wall's or the sphere's colour, the ray mirrored at a wall
-#include "trace_shade.inc"
-
-		//@R p_post
-		// trace.h:3-7
-		if(seg >= REFLECT_MAX || refl == 0.0f) { vw = 0.0f; depth = seg; break; }
-
-		// trace.h:9-84: off the rippled floor or a sphere, then the jitter (straight into the next segment's direction)
-#include "trace_bounce.inc"
-#include "trace_jitter.inc"
-
-		//@R p_jitter
-		// (the entry below the top is moved down only once there is one)
-		if(seg != 0) { st_refl1 = st_refl0; st_fog1 = st_fog0; sc1x = sc0x; sc1y = sc0y; sc1z = sc0z; }
-		st_refl0 = refl; st_fog0 = fog; sc0x = colx; sc0y = coly; sc0z = colz;
-#undef colx
-#undef coly
-#undef colz
-		seg++;
-	}
-
-	// trace.h:91-101
+			const int depth = depth_lane >= 2 ? 1 : 0;
+#define st_refl0 stB_refl
+#define st_fog0 stB_fog
+#define sc0x scBx
+#define sc0y scBy
+#define sc0z scBz
+#define RG_COMP1 RG_COMP2
+#define RG_COMP1_FOG RG_COMP2_FOG
 #include "trace_composite.inc"
-#undef icx
-#undef icy
-#undef icz
+#undef RG_COMP1
+#undef RG_COMP1_FOG
+#undef st_refl0
+#undef st_fog0
+#undef sc0x
+#undef sc0y
+#undef sc0z
+		}
+		{
+			const int depth = depth_lane >= 1 ? 1 : 0;
+#define st_refl0 stA_refl
+#define st_fog0 stA_fog
+#define sc0x scAx
+#define sc0y scAy
+#define sc0z scAz
+#include "trace_composite.inc"
+#undef st_refl0
+#undef st_fog0
+#undef sc0x
+#undef sc0y
+#undef sc0z
+		}
+#undef st_refl1
+#undef st_fog1
+#undef sc1x
+#undef sc1y
+#undef sc1z
+	}
 	//@R p_comp
 	out_x = vx; out_y = vy; out_z = vz; out_w = vw + w_acc;
 }

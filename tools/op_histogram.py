@@ -25,13 +25,11 @@ def main():
           if (s["level"], s["w"], s["h"]) == ("pwnfps_level", 3840, 2160)][0]
     cnt = sc["counts"]
 
+    # (a region of the segment's text has a copy per bounce depth, region@d, each with its own entries: issue_model.copy_entries)
+    ent = im.copy_entries({reg.split("~")[0] for _, reg, _, _ in ins}, dict(cnt, waves=5120, units=129600))
+
     def entries(region):
-        key = im.COUNT_OF.get(region)
-        if key == "waves":
-            return 5120
-        if key == "units":
-            return 129600
-        return cnt.get(key, 0) if key else 0
+        return ent.get(region, 0)
     w = collections.Counter()
     by = collections.defaultdict(collections.Counter)
     movs, valu = collections.Counter(), collections.Counter()
