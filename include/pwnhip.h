@@ -898,6 +898,66 @@ int pwn_trace_rays_hide_device(pwn_ctx *ctx, int n, const void *d_rays, const vo
 	float sec_current, int flags, void *d_col, void *d_depth, void *stream);
 
 /*
+ * Rays that stop after a given distance: pwn_trace_hits with a reach per ray -- for whatever flies (a projectile moves `reach` a
+ * tick and is the next tick's ray from where it got to) and for weapons with a range (the walk ends where the answer is decided,
+ * not at the far wall).  The point a distance along a ray cannot be computed outside the walk once a portal, a two-high room or a
+ * ramp lies in between: position and direction are re-expressed at every crossing, and a portal cell is crossed without adding to
+ * the distance (trace.h:186 the set-up, trace.h:250 the walk's loop).
+ * Ray records, PWN_RAYS_HAS_W, the 3-lane / 4-lane rule, PWN_RAYS_MAX and the empty batch are pwn_trace_hits' / pwn_trace_hits_device's /
+ * pwn_trace_hits_hide_device's; so are the ordering of the forms, "not followed", "left alone", the buffers the host form keeps, the
+ * timings it sets and every refusal (a pwn_init_multi handle, a row tiling, no level, alignment, overlaps).
+ *   reach                n floats (device forms: in device memory), 4-byte aligned, required for n > 0; d_reach must not overlap d_hits.
+ *   unit                 reach is measured as pwn_hit.dist is: in the walk's own distance, after the set-up's approximate normalise.
+ *   the definition       a process, not geometry.  Ray i runs the primary walk of pwn_trace_hits.  Step k begins, at the top of the
+ *                        walk's loop (trace.h:250), with pos_k, ray_k, cdist_k, the cell c_k and p_k portals crossed so far; cdist_{k+1}
+ *                        is cdist when the step is over.  The walk stops behind the first step that leaves cdist > reach, or where the
+ *                        unlimited walk returns, whichever comes first.  D is what the record's dist would be at that moment: aux_dist
+ *                        for a sphere, cdist for a wall.
+ *                          - the walk returned and D <= reach: pwn_trace_hits' record for that ray, bit for bit.
+ *                          - the walk ran out of steps first: PWN_HIT_NONE, as there.
+ *                          - otherwise PWN_HIT_FREE, read off the step the walk stopped behind, the reach step k with
+ *                            cdist_k <= reach < cdist_{k+1}:
+ *                              face = object = -1, portals = p_k, dist = reach, cell_x,z = c_k;
+ *                              dx,dy,dz = ray_k: normalised, clamped, turned by the portals crossed, and WITHOUT a ramp's skew, so that
+ *                              a caller can fly on along it tick after tick without drifting;
+ *                              x,y,z = pos_k + (reach - cdist_k) * a, per lane one subtraction, one multiply and one add, never fused, in
+ *                              the walk's float mode (denormals flushed); a is the ray with which step k itself advances pos: ray_k in
+ *                              a room cell, ray_k with the ramp's skew applied in a ramp cell (trace.h:443-505).
+ *                        A portal step adds nothing to cdist and is therefore never the reach step: the point is always in the
+ *                        coordinates of the far side of the portals crossed, as pwn_hit.x,y,z are.  A wall met at cdist > reach and a
+ *                        sphere with aux_dist > reach are both FREE.  A step that leaves cdist > reach and is the walk's last of
+ *                        WALK_STEPS is FREE too (the stop is asked first).
+ *   hostile values       reach is only ever compared, subtracted from and multiplied.  No bit pattern of it reaches an address or a loop
+ *                        bound.  +inf gives pwn_trace_hits bit for bit, counters included.  NaN is never exceeded and behaves as +inf.
+ *                        A negative reach is exceeded by the first step whatever that step does (a ray that starts in a portal's cell
+ *                        included: the record is then read off that step's top, p_0 = 0, in front of the crossing) and gives FREE with
+ *                        the point behind the origin -- unless that step returns a sphere whose aux_dist is below the reach too.
+ *                        reach = 0 gives FREE at the set-up's pos_0, or what the first step returns at distance 0.
+ *   hide                 d_hide has pwn_trace_hits_hide_device's meaning, safety and exactness: the table with that sphere taken out,
+ *                        objects numbered by the full table -- a projectile a tick old is still inside its shooter's body and must not
+ *                        hit it.  With every entry PWN_HIDE_NONE the call is bit-identical to pwn_trace_reach_device.  d_hide must
+ *                        not overlap d_hits (d_reach may be anywhere else).
+ *   counters             with PWN_OPT_COUNTERS on: rays = n; steps, portals, sphere_tests and exhausted count the steps actually taken,
+ *                        up to and including the reach step.
+ *   launches             the device forms: ONE trace launch on `stream`, of kernels of their own, under the rule for trace launches at
+ *                        the top of this file.  pwn_trace_reach stages 84 B a ray (32 record, 4 reach, 48 out) through pwn_trace_hits'
+ *                        buffers: the larger need counts.
+ *   errors, added        PWN_EINVAL for a NULL reach / d_reach with n > 0, for a d_reach that is not 4-byte aligned and for its n x 4
+ *                        bytes overlapping the n x 48 bytes of d_hits.  A refused call launches nothing and changes nothing.
+ *   cost                 2^20 crosshair-like rays, MI355X, device time against pwn_trace_hits_device on the same rays
+ *                        (profiles/reach/bench.txt): hall of mirrors 0.296 ms without a reach; reach +inf 0.331 (+12 %), 20: 0.058, 2: 0.051,
+ *                        0.35: 0.050.  level.txt 0.056 ms without a reach (3.7 steps a ray, the launch's floor); +inf 0.062 (+9 %), 2: 0.064,
+ *                        0.35: 0.056.  The copies of the top-of-step state cost a tenth per step; a caller without a reach calls pwn_trace_hits.
+ */
+#define PWN_HIT_FREE   3   /* the ray travelled `reach` and met nothing */
+/* Blocking, host memory. */
+int pwn_trace_reach(pwn_ctx *ctx, int n, const float *rays, const float *reach, pwn_hit *hits);
+/* Device pointers, ONE trace launch, stream-ordered on `stream` (NULL = default stream): d_rays and d_hits 16-byte aligned, d_reach n floats. */
+int pwn_trace_reach_device(pwn_ctx *ctx, int n, const void *d_rays, const void *d_reach, int flags, void *d_hits, void *stream);
+int pwn_trace_reach_hide_device(pwn_ctx *ctx, int n, const void *d_rays, const void *d_reach, const void *d_hide, int flags,
+	void *d_hits, void *stream);
+
+/*
  * The players' step: what produces the cameras of pwn_trace_views[_device].  The motion of the reference's loop (main.c:188-379:
  * turning, walking with push-back out of solid cells, gravity, the step between the floors of a two-high room, walking through a
  * portal with its turn) for a batch of n players at once, on the device, on the level in force -- so that step -> observe -> step

@@ -29,7 +29,7 @@ PWN_VIEWS_MAX = 1024
 PWN_RAYS_HAS_W = 1
 PWN_VIEWS_HAS_W = 1
 PWN_RAYS_MAX = 1 << 28
-PWN_HIT_NONE, PWN_HIT_WALL, PWN_HIT_SPHERE = 0, 1, 2
+PWN_HIT_NONE, PWN_HIT_WALL, PWN_HIT_SPHERE, PWN_HIT_FREE = 0, 1, 2, 3
 PWN_HIDE_NONE = -1
 PWN_PLAYERS_MAX = 1 << 20
 PWN_TICKS_MAX = 1024
@@ -151,6 +151,9 @@ ABI = [
     ("pwn_trace_hits_device", _i, [_vp, _i, _vp, _i, _vp, _vp]),
     ("pwn_trace_hits_hide_device", _i, [_vp, _i, _vp, _vp, _i, _vp, _vp]),
     ("pwn_trace_rays_hide_device", _i, [_vp, _i, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp]),
+    ("pwn_trace_reach", _i, [_vp, _i, _vp, _vp, _vp]),
+    ("pwn_trace_reach_device", _i, [_vp, _i, _vp, _vp, _i, _vp, _vp]),
+    ("pwn_trace_reach_hide_device", _i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     ("pwn_get_object_ids", _i, [_vp, _vp, _i]),
     ("pwn_trace_view_hits", _i, [_vp, _i, _vp, _vp, _vp, _vp]),
     ("pwn_trace_view_hits_device", _i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),

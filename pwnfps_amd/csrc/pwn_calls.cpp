@@ -682,10 +682,10 @@ int pwn_i_staging_reserve(pwn_ctx *c, size_t n, size_t per_ray, const char *who,
 	return PWN_OK;
 }
 
-// What the two blocking ray calls do between filling their staging and reading it: N records into the staging's head, whether any
+// What the blocking ray calls (the two here and pwn_reach.cpp's) do between filling their staging and reading it: N records into the staging's head, whether any
 // has the w lanes of anything but an ordinary camera's rays (camera_has_w's rule for rays: origin.w 1, direction.w 0), the first
 // `up` bytes of the staging to the device, the launch T of them, bytes [lo, hi) back, the wait and the times.
-static int rays_stage_and_launch(pwn_ctx *c, hipStream_t s, const float *rays, size_t N, unsigned char *h, unsigned char *d, size_t up,
+int pwn_i_rays_stage_and_launch(pwn_ctx *c, hipStream_t s, const float *rays, size_t N, unsigned char *h, unsigned char *d, size_t up,
 	pwn_trace_launch *T, size_t lo, size_t hi)
 {
 	memcpy(h, rays, 32 * N);
@@ -724,7 +724,7 @@ extern "C" int pwn_trace_rays(pwn_ctx *c, int n, const float *rays, const uint32
 	if(depth != NULL) memcpy(h + 36 * N, depth, 4 * N); else memset(h + 36 * N, 0, 4 * N);
 	pwn_trace_launch T = { .sec = sec, .rays = { (const float *)d, (const uint32_t *)(d + 32 * N), (uint32_t)n },
 		.d_sbuf = (uint32_t *)(d + 40 * N), .d_zbuf = (float *)(d + 36 * N), .stream = s };
-	rc = rays_stage_and_launch(c, s, rays, N, h, d, 40 * N, &T, depth != NULL ? 36 * N : 40 * N, col != NULL ? 44 * N : 40 * N);
+	rc = pwn_i_rays_stage_and_launch(c, s, rays, N, h, d, 40 * N, &T, depth != NULL ? 36 * N : 40 * N, col != NULL ? 44 * N : 40 * N);
 	if(rc != PWN_OK) return rc;
 	if(depth != NULL) memcpy(depth, h + 36 * N, 4 * N);
 	if(col != NULL) memcpy(col, h + 40 * N, 4 * N);
@@ -783,7 +783,7 @@ extern "C" int pwn_trace_hits(pwn_ctx *c, int n, const float *rays, pwn_hit *hit
 	const size_t N = (size_t)n;
 	unsigned char *h = c->h_hits, *d = c->d_hits;
 	pwn_trace_launch T = { .rays = { (const float *)d, NULL, (uint32_t)n, false, d + 32 * N }, .stream = s };
-	rc = rays_stage_and_launch(c, s, rays, N, h, d, 32 * N, &T, 32 * N, (32 + sizeof(pwn_hit)) * N);
+	rc = pwn_i_rays_stage_and_launch(c, s, rays, N, h, d, 32 * N, &T, 32 * N, (32 + sizeof(pwn_hit)) * N);
 	if(rc != PWN_OK) return rc;
 	memcpy(hits, h + 32 * N, sizeof(pwn_hit) * N);
 	return PWN_OK;

@@ -5,6 +5,7 @@
 //   pwn_launch.cpp  the trace and blur launchers (the launch geometry itself: launch_plan.h), the unit order, the *_rows_device calls
 //   pwn_calls.cpp   the blocking call and its strips, host registration, the batches of views, viewports, rays and hits
 //   pwn_players.cpp the players' step: a batch of cameras walked through the level (host and device form)
+//   pwn_reach.cpp   rays that stop after a given distance (pwn_trace_reach and its device forms)
 //   pwn_pixel_rays.cpp  pixel rays from cameras on the device (pwn_pixel_rays_device)
 //   pwn_spheres_device.cpp  the sphere tables built on the device (pwn_upload_spheres_device)
 //   pwn_viewports_device.cpp  views of their own sizes from device cameras (pwn_viewports_layout, pwn_trace_viewports_device)
@@ -64,6 +65,8 @@ struct pwn_vps_launch
 // from the primary segments alone; d_seeds, d_sbuf, d_zbuf and sec are then not read.
 // d_hide (pwn_trace_hits_hide_device with d_hits, pwn_trace_rays_hide_device without): not NULL = n int32, ray i's hidden sphere -- the
 // launch runs the HIDE kernels.
+// d_reach (pwn_trace_reach / pwn_trace_reach_device / pwn_trace_reach_hide_device, with d_hits): not NULL = n floats, ray i's reach -- the
+// launch runs the REACH kernels, with d_hide those that hide as well.
 struct pwn_rays_launch
 {
 	const float *d_rays;
@@ -72,6 +75,7 @@ struct pwn_rays_launch
 	bool has_w;
 	void *d_hits;
 	const int32_t *d_hide;
+	const float *d_reach;
 };
 
 // One trace launch (pwn_i_launch_trace).  All zero but what is traced and where to: a plain launch, nothing cleared or
@@ -112,6 +116,8 @@ extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size
 extern "C" hipError_t pwn_launch_trace_hide(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream);
 // ... those of the other three batch modes (trace_hide_vp.hip): a launch of vps with view_hide set, or of rays' colours with ray_hide
 extern "C" hipError_t pwn_launch_trace_hide2(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream);
+// the REACH instantiations (trace_reach.hip): a launch of first-hit records with ray_reach, with or without ray_hide
+extern "C" hipError_t pwn_launch_trace_reach(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream);
 extern "C" hipError_t pwn_launch_trace_refill(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream);
 extern "C" unsigned pwn_trace_refill_lds_extra(bool has_w);
 extern "C" int pwn_trace_refill_blocks_per_cu(size_t lds_bytes, bool count, bool has_w);
@@ -458,6 +464,10 @@ int pwn_i_tables_uploaded(pwn_ctx *c, int cur, hipStream_t stream);      // a la
 int pwn_i_batch_refuse(const pwn_ctx *c, int views = 0, bool blurs = true);
 int pwn_i_wait_frames_in_flight(pwn_ctx *c, hipStream_t s);
 int pwn_i_staging_reserve(pwn_ctx *c, size_t n, size_t per_ray, const char *who, unsigned char **h, unsigned char **d, size_t *cap_io, size_t cap_max = PWN_RAYS_MAX, const char *unit = "rays");
+// what the blocking ray calls do between filling their staging and reading it (pwn_calls.cpp): N records into the staging's head, the 3-lane /
+// 4-lane rule over them, the first `up` bytes to the device, the launch T, bytes [lo, hi) back, the wait and the times
+int pwn_i_rays_stage_and_launch(pwn_ctx *c, hipStream_t s, const float *rays, size_t N, unsigned char *h, unsigned char *d, size_t up,
+	pwn_trace_launch *T, size_t lo, size_t hi);
 void pwn_launch_history_clear(pwn_ctx *c);      // the launch-order events are about to be destroyed (streams idle)
 int pwn_i_set_launch_rotation(pwn_ctx *c, int rot);
 int pwn_i_launch_order(pwn_ctx *c, hipStream_t stream);      // behind a frame's last kernel on `stream`: sort that stream's unit costs (no-op when there are none)

@@ -273,6 +273,7 @@ int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L)
 		P.rays = rays->d_rays; P.ray_seeds = rays->d_seeds; P.nrays = rays->n; P.ray_w = rays->has_w ? 1 : 0;
 		P.hits = rays->d_hits;
 		P.ray_hide = rays->d_hide;
+		P.ray_reach = rays->d_reach;
 	}
 	P.sbuf = L->d_sbuf; P.zbuf = L->d_zbuf;
 	P.counters = c->d_counters;
@@ -329,6 +330,8 @@ int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L)
 	rc = rotation_wait(c, stream);
 	if(rc != PWN_OK) return rc;
 	if(refill) HIPCHK(c, pwn_launch_trace_refill(&P, plan.grid, lds_bytes, c->counters_on != 0, stream));
+	// (rays that stop after a given distance, with or without a hidden sphere: the REACH instantiations, in a unit of their own)
+	else if(P.ray_reach != NULL) HIPCHK(c, pwn_launch_trace_reach(&P, plan.grid, lds_bytes, c->counters_on != 0, stream));
 	// (one hidden sphere per view or ray: the HIDE instantiations, in a unit of their own)
 	// (views of their own sizes and rays' colours: a third unit; a launch that neither matches is refused by the one it is sent to)
 	else if((P.vps != NULL && P.view_hide != 0) || (P.rays != NULL && P.hits == NULL && P.ray_hide != NULL)) HIPCHK(c, pwn_launch_trace_hide2(&P, plan.grid, lds_bytes, c->counters_on != 0, stream));

@@ -247,6 +247,12 @@ struct pwn_trace_params
 	// colours); no other kernel reads them.  (Behind everything else, as the tile pairs were: no other field moves.)
 	const int32_t *ray_hide;
 	int view_hide;
+	// Rays that stop after a given distance (pwn_trace_reach, pwn_trace_reach_device, pwn_trace_reach_hide_device; the kernel's REACH
+	// parameter).  NULL, or nrays floats beside `rays` in a launch of `hits`: ray i's walk stops behind the first step that leaves its
+	// distance above ray_reach[i], and a ray that stops so gets a PWN_HIT_FREE record (pwnhip.h).  The value is only ever compared and
+	// multiplied.  Not NULL picks the REACH instantiations (pwn_launch_trace_reach, trace_reach.hip), with or without ray_hide; no other
+	// kernel reads it.  (Behind everything else, as ray_hide was: no other field moves.)
+	const float *ray_reach;
 };
 #define PWN_HIT_REC_BYTES 48u
 
@@ -285,6 +291,9 @@ enum { PWN_KM_FRAME = 0, PWN_KM_VIEWS = 1, PWN_KM_RAYS = 2, PWN_KM_HITS = 3, PWN
 // ... or'ed to PWN_KM_VIEWS, PWN_KM_VIEW_HITS or PWN_KM_HITS (trace_hide.hip), to PWN_KM_VIEWPORTS, PWN_KM_VIEWPORT_HITS or PWN_KM_RAYS
 // (trace_hide_vp.hip): its HIDE parameter -- every view or ray names one sphere it does not see
 enum { PWN_KM_HIDE = 8 };
+// ... or'ed to PWN_KM_HITS alone, with or without PWN_KM_HIDE (trace_reach.hip): its REACH parameter -- every ray names a distance behind
+// which it stops (pwn_trace_params.ray_reach)
+enum { PWN_KM_REACH = 16 };
 
 // One view of a batch: the camera set-up of screen.h:43-57 for that view's camera (pwn_internal.h frame_setup) and its
 // sec_current.  80 bytes; the kernel reads a view's record with scalar loads.

@@ -177,8 +177,18 @@ ray_done:
 // trace_hit is the one body; what becomes of the words is its callers': hit_store_record (a batch of rays) writes all twelve,
 // hit_store_planes (a batch of views) packs the first four into one and keeps two more.
 struct HitWords { uint4 r0, r1, r2; };
-template<bool COUNT, bool HAS_W, int LISTS, bool HIDE = false>
-__device__ __forceinline__ HitWords trace_hit(const Lds &L, Vec<HAS_W> from, Vec<HAS_W> iray, Counters &cnt, [[maybe_unused]] uint32_t hide1 = 0u)
+// REACH (pwn_trace_reach: tables.h PWN_KM_REACH, the kernel): the walk stops behind the first step that leaves cdist above `reach`, or
+// where it returns anyway, and a ray that D -- the distance its record would carry, aux_dist of a sphere, cdist of a wall -- shows
+// beyond `reach` gets a PWN_HIT_FREE record read off the step it stopped in: that step's cell, portal count and ray as they were at the
+// top of the loop, and the point pos + (reach - cdist) * a of that moment, a = the ray the step advances pos with (in a ramp cell the
+// skewed one: WALK_REACH_ADV, trace_walk.inc).  So the loop keeps the top-of-step pos, ray, cdist, cell and portal count, ten registers
+// that only these instantiations have; with REACH false none of the names is touched and no instruction is made for them (HITREC's
+// rule).  `reach` is only ever compared, subtracted from and multiplied: no bit pattern of it reaches an address or a loop bound.  A NaN
+// is never exceeded and +inf neither: the walk, the record and the counters are then pwn_trace_hits'.
+#define WALK_REACH_ADV(y) do { if constexpr(REACH) reach_adv_y = (y); } while(0)
+template<bool COUNT, bool HAS_W, int LISTS, bool HIDE = false, bool REACH = false>
+__device__ __forceinline__ HitWords trace_hit(const Lds &L, Vec<HAS_W> from, Vec<HAS_W> iray, Counters &cnt, [[maybe_unused]] uint32_t hide1 = 0u,
+	[[maybe_unused]] float reach = 0.0f)
 {
 	typedef Vec<HAS_W> V;
 	constexpr bool HITREC = true;
@@ -200,6 +210,10 @@ __device__ __forceinline__ HitWords trace_hit(const Lds &L, Vec<HAS_W> from, Vec
 	float iax, iaz, iay, iay_dn;
 	uint32_t iay_up_bits;
 	int ldir, ev, base;
+	// (REACH: the step's state at the top of the loop)
+	[[maybe_unused]] float reach_px, reach_py, reach_pz, reach_rx, reach_ry, reach_rz, reach_cdist, reach_adv_y;
+	[[maybe_unused]] uint32_t reach_cxz;
+	[[maybe_unused]] int reach_portals;
 #include "trace_setup.inc"
 	//@R p_walk_ctl
 	// (the step limit is carried in ev: trace_pixel)
@@ -208,14 +222,37 @@ __device__ __forceinline__ HitWords trace_hit(const Lds &L, Vec<HAS_W> from, Vec
 	do
 	{
 		ev++;
+		if constexpr(REACH)
+		{
+			reach_px = pos.x; reach_py = pos.y; reach_pz = pos.z;
+			reach_rx = ray.x; reach_ry = ray.y; reach_rz = ray.z;
+			reach_cdist = cdist; reach_cxz = cxz; reach_portals = hit_portals;
+			reach_adv_y = ray.y;
+		}
 #include "trace_walk.inc"
+		// (behind the step: a portal step adds nothing to cdist, so it ends the walk only for a reach below the set-up's 0)
+		if constexpr(REACH) { if(cdist > reach) break; }
 	} while(ev < 0);
 	asm volatile("" : "+v"(ev));
 
 	//@R p_post
 	static_assert(EV_WALL == 1 && EV_SPHERE == 2, "pwnhip.h PWN_HIT_WALL, PWN_HIT_SPHERE");
+	static_assert(PWN_HIT_FREE == 3, "the record's kind below");
 	uint4 r0, r1, r2;
-	if(ev == EV_OUT_OF_STEPS)
+	// REACH: what the record's dist would be lies beyond the reach -- a walk the stop ended (ev still counts, or is this file's "out of
+	// steps" where the last step was the one), a wall met further out in the step that passed the reach, a sphere candidate further out
+	bool is_free = false;
+	if constexpr(REACH) is_free = (ev == EV_SPHERE ? aux_dist : cdist) > reach;
+	if(REACH && is_free)
+	{
+		// (per lane one subtraction, one product and one sum, each rounded by itself: the Makefile's -ffp-contract=off)
+		const float rem = reach - reach_cdist;
+		const float fx = reach_px + rem * reach_rx, fy = reach_py + rem * reach_adv_y, fz = reach_pz + rem * reach_rz;
+		r0 = make_uint4((uint32_t)PWN_HIT_FREE, 0xffffffffu, 0xffffffffu, (uint32_t)reach_portals);
+		r1 = make_uint4(__float_as_uint(reach), __float_as_uint(fx), __float_as_uint(fy), __float_as_uint(fz));
+		r2 = make_uint4(__float_as_uint(reach_rx), __float_as_uint(reach_ry), __float_as_uint(reach_rz), reach_cxz);
+	}
+	else if(ev == EV_OUT_OF_STEPS)
 	{
 		// trace.h:677: nothing was hit.  face = object = -1, every other field 0
 		if(COUNT) cnt.exhausted++;
@@ -247,6 +284,7 @@ __device__ __forceinline__ HitWords trace_hit(const Lds &L, Vec<HAS_W> from, Vec
 	}
 	return HitWords{ r0, r1, r2 };
 }
+#undef WALK_REACH_ADV
 
 // pwn_trace_hits: the record as it is -- three 16-byte stores (the record is 16-byte aligned: pwn_calls.cpp checks the array)
 __device__ __forceinline__ void hit_store_record(const HitWords &h, uint4 *out)
@@ -315,6 +353,9 @@ template<bool HAS_W> __device__ __forceinline__ void chain_rounds(Vec<HAS_W> &v,
 // PWN_KM_RAYS (pwn_trace_viewports_hide_device, pwn_trace_viewport_hits_hide_device, pwn_trace_rays_hide_device) in a third
 // (trace_hide_vp.hip), where the kernel has a name of its own, PWN_TRACE_KERNEL_NAME: tests pin the set of pwn_trace_kernel's
 // instantiations with the HIDE bit to the first three modes, and a second name changes nothing of what the other two units compile.
+// REACH (tables.h PWN_KM_REACH, a second bit of the MODE argument, valid with PWN_KM_HITS alone): every ray names a distance behind which
+// its walk stops (pwn_trace_reach, pwn_trace_reach_device, pwn_trace_reach_hide_device).  Instantiated with and without the HIDE bit in a
+// fourth unit (trace_reach.hip), under a name of its own as well.
 #ifndef PWN_TRACE_KERNEL_NAME
 #define PWN_TRACE_KERNEL_NAME pwn_trace_kernel
 #endif
@@ -322,8 +363,10 @@ template<bool COUNT, bool HAS_W, bool ORDER, int LISTS, int MODE_ARG>
 __global__ void __launch_bounds__(PWN_BLOCK, PWN_MIN_WAVES)
 PWN_TRACE_KERNEL_NAME(pwn_trace_params P)
 {
-	constexpr int MODE = MODE_ARG & ~PWN_KM_HIDE;
+	constexpr int MODE = MODE_ARG & ~(PWN_KM_HIDE | PWN_KM_REACH);
 	constexpr bool HIDE = (MODE_ARG & PWN_KM_HIDE) != 0;
+	constexpr bool REACH = (MODE_ARG & PWN_KM_REACH) != 0;
+	static_assert(!REACH || MODE == PWN_KM_HITS, "REACH: first-hit records of a batch of rays");
 	static_assert(!HIDE || (!ORDER && MODE != PWN_KM_FRAME), "HIDE: batches of views, of views of their own sizes and of rays");
 	constexpr bool VHITS = MODE == PWN_KM_VIEW_HITS, VIEWS = MODE == PWN_KM_VIEWS || VHITS, HITS = MODE == PWN_KM_HITS, RAYS = MODE == PWN_KM_RAYS || HITS;
 	constexpr bool VPHITS = MODE == PWN_KM_VIEWPORT_HITS, VPS = MODE == PWN_KM_VIEWPORTS || VPHITS;
@@ -528,7 +571,19 @@ PWN_TRACE_KERNEL_NAME(pwn_trace_params P)
 					// caller's array of n records; a lane with i >= nrays stores nothing.  No seed, colour or depth is touched.
 					// HIDE: the ray's hidden sphere, ray_hide[i] for i < nrays in the caller's array of n int32 (pwn_calls.cpp checks it), as
 					// k + 1 (WALK_HIDDEN: only ever compared)
-					if constexpr(HIDE)
+					// REACH (pwn_trace_reach): the ray's reach, ray_reach[i] for i < nrays in the caller's array of n floats (pwn_reach.cpp checks
+					// it): only ever compared and multiplied (trace_hit)
+					if constexpr(REACH)
+					{
+						uint32_t hide1 = 0u;
+						if constexpr(HIDE) hide1 = (uint32_t)P.ray_hide[i] + 1u;
+						const HitWords hw = trace_hit<COUNT, HAS_W, LISTS, HIDE, true>(L, org, dir, cnt, hide1, P.ray_reach[i]);
+						// (the record's address is made behind the walk, as the HIDE kernels' below)
+						uint32_t il = i;
+						asm volatile("" : "+v"(il));
+						hit_store_record(hw, (uint4 *)((unsigned char *)P.hits + (size_t)il * PWN_HIT_REC_BYTES));
+					}
+					else if constexpr(HIDE)
 					{
 						const uint32_t hide1 = (uint32_t)P.ray_hide[i] + 1u;
 						const HitWords hw = trace_hit<COUNT, HAS_W, LISTS, true>(L, org, dir, cnt, hide1);
@@ -862,7 +917,23 @@ template<bool ORDER, int LISTS, int MODE>
 using Units = TraceKernels<PWN_TRACE_KERNEL_NAME<true, true, ORDER, LISTS, MODE>, PWN_TRACE_KERNEL_NAME<true, false, ORDER, LISTS, MODE>,
 	PWN_TRACE_KERNEL_NAME<false, true, ORDER, LISTS, MODE>, PWN_TRACE_KERNEL_NAME<false, false, ORDER, LISTS, MODE>>;
 
-#if defined(PWN_TRACE_HIDE_VP_UNIT)
+#if defined(PWN_TRACE_REACH_UNIT)
+// trace_reach.hip: this file's text with the REACH instantiations alone -- twenty-four kernels, PWN_KM_HITS with and without HIDE x three
+// list forms x COUNT x HAS_W, under the name that unit gives them -- and the one function that launches them.
+template<int LISTS>
+static hipError_t launch_reach(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
+{
+	// (a missing kernel is an error: only a batch of rays' first hits has a REACH instantiation)
+	if(P->rays == NULL || P->hits == NULL || P->ray_reach == NULL || P->views != NULL || P->vps != NULL) return hipErrorInvalidValue;
+	return P->ray_hide != NULL ? Units<false, LISTS, PWN_KM_HITS | PWN_KM_HIDE | PWN_KM_REACH>::launch(P, grid, lds_bytes, count, stream)
+	                           : Units<false, LISTS, PWN_KM_HITS | PWN_KM_REACH>::launch(P, grid, lds_bytes, count, stream);
+}
+extern "C" hipError_t pwn_launch_trace_reach(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
+{
+	if(P->g_rec != NULL) return launch_reach<PWN_LF_GLOBAL>(P, grid, lds_bytes, count, stream);
+	return P->off_recsph != 0u ? launch_reach<PWN_LF_INLINE>(P, grid, lds_bytes, count, stream) : launch_reach<PWN_LF_INDEXED>(P, grid, lds_bytes, count, stream);
+}
+#elif defined(PWN_TRACE_HIDE_VP_UNIT)
 // trace_hide_vp.hip: this file's text with the HIDE instantiations of the viewport modes and of the rays' colours alone -- thirty-six
 // kernels, three modes x three list forms x COUNT x HAS_W, under the name that unit gives them -- and the one function that launches them.
 template<int LISTS>

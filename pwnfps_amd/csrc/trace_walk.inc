@@ -13,6 +13,9 @@
 //   WALK_HIDDEN(object): optional.  True where the sphere with that index in the live table is one this lane's ray does not see
 //   (trace_kernel.hip's HIDE instantiations: a compare with a value of the lane's or the wave's).  An including file that does not
 //   define it -- the refill kernel -- gets the default, `false`, which does not evaluate its argument: no instruction is made.
+//   WALK_REACH_ADV(y): optional.  Where a ramp step has skewed the ray it advances pos with, it hands that ray's y to an including loop that
+//   has to know it (trace_kernel.hip's REACH instantiations: the point a given distance along the step).  An including file that does
+//   not define it gets the default, which does not evaluate its argument: no instruction is made.
 // One cell per iteration, one loop exit at the bottom.  The cell class is a bit test on the
 // LDS word (tables.h).  The room body - by far the most frequent - is written with selects;
 // lanes whose ray ended in it carry on through the (then meaningless) cell advance and leave
@@ -22,6 +25,10 @@
 #ifndef WALK_HIDDEN
 #define WALK_HIDDEN(object) false
 #define WALK_HIDDEN_DEFAULTED
+#endif
+#ifndef WALK_REACH_ADV
+#define WALK_REACH_ADV(y) ((void)0)
+#define WALK_REACH_ADV_DEFAULTED
 #endif
 if(COUNT)
 {
@@ -294,6 +301,7 @@ else
 		const bool minus = (cw & PWN_C_RAMPM) != 0u;
 		float tilt = alongx ? ray.x : ray.z;
 		if(minus) ray.y -= ramp * tilt; else ray.y += ramp * tilt;
+		WALK_REACH_ADV(ray.y);
 		wy = pos.y;
 		if(ray.y >= 0.0f) wy = 1.0f - wy;
 		wy *= 1.0f / (ray.y < 0.0f ? -ray.y : ray.y);
@@ -432,4 +440,8 @@ else
 #ifdef WALK_HIDDEN_DEFAULTED
 #undef WALK_HIDDEN
 #undef WALK_HIDDEN_DEFAULTED
+#endif
+#ifdef WALK_REACH_ADV_DEFAULTED
+#undef WALK_REACH_ADV
+#undef WALK_REACH_ADV_DEFAULTED
 #endif

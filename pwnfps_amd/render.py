@@ -571,6 +571,57 @@ class Renderer:
         self._chk(lib.pwn_trace_hits_device(self._ctx, int(n), C.c_void_p(p_rays), _lib.PWN_RAYS_HAS_W if has_w else 0,
                                             C.c_void_p(p_hits), C.c_void_p(stream or 0)), "pwn_trace_hits_device")
 
+    # -- rays that stop after a given distance (pwn_trace_reach) ---------------
+    def trace_reach(self, rays, reach):
+        """pwn_trace_reach: trace_hits with a reach per ray -- (n,) float32, in the unit of the records' dist.  A ray that travels
+        its reach and meets nothing gets kind PWN_HIT_FREE (3): face = object = -1, dist = reach, x y z the point it got to, dx dy dz
+        the direction to fly on along (without a ramp's skew), portals and cell those of the step it stopped in.  +inf and NaN
+        give trace_hits.  Returns (n,) HIT_DTYPE records."""
+        rays = _ray_records(rays, "trace_reach")
+        n = rays.shape[0]
+        reach = np.ascontiguousarray(reach, np.float32)
+        if reach.shape != (n,):
+            raise ValueError("trace_reach: reach must be (%d,), not %s" % (n, reach.shape))
+        hits = np.zeros(n, HIT_DTYPE)
+        self._chk(lib.pwn_trace_reach(self._ctx, n, rays.ctypes.data if n else None, reach.ctypes.data if n else None,
+                                      hits.ctypes.data if n else None), "pwn_trace_reach")
+        return hits
+
+    def trace_reach_device(self, rays, reach, hits, hide=None, has_w=False, stream=None):
+        """pwn_trace_reach_device: one trace launch, stream-ordered, no synchronisation.  rays (n,8) float32, reach (n,) float32 and
+        hits -- (n,12) int32 or float32, or (n,48) uint8: n records of HIT_DTYPE -- are torch tensors on this context's GPU, rays and
+        hits 16-byte aligned.  has_w and stream as trace_hits_device takes them.
+        hide: None, or an (n,) int32 tensor on the same GPU (pwn_trace_reach_hide_device): ray i does not see sphere hide[i] of the
+        table in force; PWN_HIDE_NONE (-1) and every other value that is no sphere's index hide nothing."""
+        import torch
+        who = "trace_reach_device"
+        n = _tensor_check(torch, rays, "rays", (torch.float32,), 2, who=who)
+        if rays.shape[1] != 8 or rays.data_ptr() % 16 != 0:
+            raise ValueError("trace_reach_device: rays must be (n,8) and 16-byte aligned")
+        _tensor_check(torch, reach, "reach", (torch.float32,), 1, n, who=who)
+        _tensor_check(torch, hits, "hits", (torch.int32, torch.float32, torch.uint8), 2, n, who=who)
+        if hits.shape[1] * hits.element_size() != HIT_DTYPE.itemsize or hits.data_ptr() % 16 != 0:
+            raise ValueError("trace_reach_device: hits must hold %d bytes a row and be 16-byte aligned" % HIT_DTYPE.itemsize)
+        if hide is not None:
+            _tensor_check(torch, hide, "hide", (torch.int32,), 1, n, who=who)
+        for t in (reach, hits, hide):
+            if t is not None and t.device != rays.device:
+                raise ValueError("trace_reach_device: tensors on %s and %s" % (rays.device, t.device))
+        if n > _lib.PWN_RAYS_MAX:
+            raise ValueError("trace_reach_device: n = %d, 0 ... %d" % (n, _lib.PWN_RAYS_MAX))
+        if stream is None:
+            stream = torch.cuda.current_stream(rays.device)
+        if not isinstance(stream, int):
+            stream = stream.cuda_stream
+        flags = _lib.PWN_RAYS_HAS_W if has_w else 0
+        if hide is not None:
+            self._chk(lib.pwn_trace_reach_hide_device(self._ctx, n, C.c_void_p(rays.data_ptr()), C.c_void_p(reach.data_ptr()),
+                                                      C.c_void_p(hide.data_ptr()), flags, C.c_void_p(hits.data_ptr()), C.c_void_p(stream or 0)),
+                      "pwn_trace_reach_hide_device")
+            return
+        self._chk(lib.pwn_trace_reach_device(self._ctx, n, C.c_void_p(rays.data_ptr()), C.c_void_p(reach.data_ptr()), flags,
+                                             C.c_void_p(hits.data_ptr()), C.c_void_p(stream or 0)), "pwn_trace_reach_device")
+
     def object_ids(self):
         """pwn_get_object_ids: per live sphere, in get_objects()' order (what a hit's `object` indexes), the obj_new handle"""
         n = self._chk(lib.pwn_get_object_ids(self._ctx, None, 0), "pwn_get_object_ids")

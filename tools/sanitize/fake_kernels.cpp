@@ -113,6 +113,28 @@ extern "C" hipError_t pwn_launch_trace_hide2(const pwn_trace_params *P, int g, s
 	pwn_fake_hide2_launches++;
 	return pwn_launch_trace(P, g, l, c, s);
 }
+// (trace_reach.hip's: first-hit records of rays with ray_reach, with or without ray_hide -- anything else it refuses.  reach_driver.cpp: a
+// record per ray made of the ray's number, its eight floats, its reach and its hide word -- exactly n entries of each array are read,
+// exactly n records written)
+extern "C" { int pwn_fake_reach_launches = 0; }
+extern "C" hipError_t pwn_launch_trace_reach(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t)
+{
+	if(P->rays == NULL || P->hits == NULL || P->ray_reach == NULL || P->views != NULL || P->vps != NULL) return hipErrorInvalidValue;
+	pwn_fake_reach_launches++;
+	if(pwn_fake_trace_hook != NULL) pwn_fake_trace_hook(P, grid, lds_bytes);
+	for(uint32_t i = 0; i < P->nrays; i++)
+	{
+		uint32_t k = mix(i, P->ray_hide != NULL ? (uint32_t)P->ray_hide[i] : 0x5555u), u;
+		for(int q = 0; q < 8; q++) { memcpy(&u, P->rays + 8 * (size_t)i + q, 4); k = mix(k, (P->ray_w || (q & 3) != 3) ? u : 0u); }
+		memcpy(&u, P->ray_reach + i, 4);
+		k = mix(k, u);
+		uint32_t *o = (uint32_t *)((unsigned char *)P->hits + (size_t)i * PWN_HIT_REC_BYTES);
+		for(uint32_t q = 0; q < PWN_HIT_REC_BYTES / 4u; q++) o[q] = mix(k, q);
+	}
+	if(P->tickets_next) for(unsigned q = 0; q < PWN_QUEUES; q++) P->tickets_next[q * PWN_QUEUE_STRIDE] = 0u;
+	if(count && P->counters) P->counters[0] += P->nrays;
+	return hipSuccess;
+}
 extern "C" unsigned pwn_trace_refill_lds_extra(bool) { return 16u; }
 extern "C" int pwn_trace_refill_blocks_per_cu(size_t, bool, bool) { return 4; }
 extern "C" int pwn_trace_blocks_per_cu(size_t, bool, bool) { return 5; }
