@@ -5,6 +5,7 @@
 // arithmetic).  Host code only: no HIP, no pwn_ctx, and not for the .hip files.
 #pragma once
 #include <stdint.h>
+#include "trace_variants.h"      // PWN_KM_*
 
 // The trace kernel turns a unit number into (row of units, unit in the row): a division by the units per row, which
 // is the same number for every unit of a launch.  For d >= 2 and s the largest shift with 2^s < d, M = ceil(2^(32+s) / d)
@@ -29,6 +30,26 @@ static inline void pwn_unit_div_magic(uint32_t d, uint32_t *magic, int *shift)
 static inline uint32_t pwn_lds_fit(uint32_t bytes) { return 155648u / ((bytes + 2047u) & ~2047u); }
 
 enum { PWN_LAUNCH_FRAME = 0, PWN_LAUNCH_VIEWS, PWN_LAUNCH_RAYS, PWN_LAUNCH_VIEWPORTS };
+
+// What a launch is (pwn_internal.h pwn_trace_launch), as far as the choice of the kernel goes: PWN_LAUNCH_* -- the frame, or the batch
+// whose n is not 0 -- and, of that batch: label = its d_label / d_hits is given (first hits in the place of colours), hide = its
+// `hide` is set / its d_hide is given, reach = its d_reach is given (rays alone have one).
+struct pwn_launch_what { int kind; bool label, hide, reach; };
+// ... as the trace kernel's MODE argument (PWN_KM_*).  The mode is only NAMED here: whether a kernel of that mode exists is for
+// trace_variants.h to say, and for pwn_launch_trace to refuse (a reach without first hits or a hidden sphere in a frame has none).
+// -1: no mode at all -- a frame has no planes of labels.
+static inline int pwn_launch_mode(const pwn_launch_what &W)
+{
+	int mode;
+	switch(W.kind)
+	{
+		case PWN_LAUNCH_RAYS: mode = W.label ? PWN_KM_HITS : PWN_KM_RAYS; break;
+		case PWN_LAUNCH_VIEWS: mode = W.label ? PWN_KM_VIEW_HITS : PWN_KM_VIEWS; break;
+		case PWN_LAUNCH_VIEWPORTS: mode = W.label ? PWN_KM_VIEWPORT_HITS : PWN_KM_VIEWPORTS; break;
+		default: if(W.label) return -1; mode = PWN_KM_FRAME;
+	}
+	return mode | (W.hide ? PWN_KM_HIDE : 0) | (W.reach ? PWN_KM_REACH : 0);
+}
 
 struct pwn_launch_shape
 {

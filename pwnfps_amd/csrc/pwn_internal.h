@@ -111,13 +111,9 @@ struct pwn_blur_launch
 	pwn_vps_launch vps;                          // views of their own sizes in one frame (pwn_trace_viewports): each rectangle a frame of its own (rows not read)
 };
 
-extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream);
-// the units kernel's HIDE instantiations (trace_hide.hip): a launch of views with view_hide set, or of first-hit records with ray_hide
-extern "C" hipError_t pwn_launch_trace_hide(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream);
-// ... those of the other three batch modes (trace_hide_vp.hip): a launch of vps with view_hide set, or of rays' colours with ray_hide
-extern "C" hipError_t pwn_launch_trace_hide2(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream);
-// the REACH instantiations (trace_reach.hip): a launch of first-hit records with ray_reach, with or without ray_hide
-extern "C" hipError_t pwn_launch_trace_reach(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream);
+// the units kernel: mode (PWN_KM_*, with its HIDE and REACH bits; launch_plan.h pwn_launch_mode), lists (PWN_LF_*) and order pick the
+// variant, whichever unit compiles it; hipErrorInvalidValue where trace_variants.h has none
+extern "C" hipError_t pwn_launch_trace(int mode, int lists, bool order, const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream);
 extern "C" hipError_t pwn_launch_trace_refill(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream);
 extern "C" unsigned pwn_trace_refill_lds_extra(bool has_w);
 extern "C" int pwn_trace_refill_blocks_per_cu(size_t lds_bytes, bool count, bool has_w);

@@ -240,6 +240,13 @@ int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L)
 	const pwn_rays_launch *rays = L->rays.n > 0 ? &L->rays : NULL;
 	const pwn_vps_launch *vps = L->vps.n > 0 ? &L->vps : NULL;
 	const bool batch = views != NULL || rays != NULL || vps != NULL;
+	// what is traced, once: the plan's kind and the kernel's mode (launch_plan.h)
+	// (a launch is one of the three batches at the most)
+	pwn_launch_what what = { PWN_LAUNCH_FRAME, false, false, false };
+	if(views != NULL) what = { PWN_LAUNCH_VIEWS, views->d_label != NULL, views->hide, false };
+	if(vps != NULL) what = { PWN_LAUNCH_VIEWPORTS, vps->d_label != NULL, vps->hide, false };
+	if(rays != NULL) what = { PWN_LAUNCH_RAYS, rays->d_hits != NULL, rays->d_hide != NULL, rays->d_reach != NULL };
+	const int mode = pwn_launch_mode(what);
 	const int y0 = L->y0, y1 = L->y1;
 	const hipStream_t stream = L->stream;
 	L->cost_mul = L->cost_div = 1u;
@@ -303,9 +310,10 @@ int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L)
 
 	// the geometry (launch_plan.h): the units, how they are handed out, the grid
 	pwn_launch_shape S = { .w = fw, .y0 = y0, .y1 = y1, .tile_w = pwn_trace_tile_w(), .tile_h = pwn_trace_tile_h() };
-	if(views != NULL) { S.kind = PWN_LAUNCH_VIEWS; S.n = (uint32_t)views->n; }
-	if(vps != NULL) { S.kind = PWN_LAUNCH_VIEWPORTS; S.n = (uint32_t)vps->n; S.vp_units = vps->units; }
-	if(rays != NULL) { S.kind = PWN_LAUNCH_RAYS; S.n = rays->n; }
+	S.kind = what.kind;
+	if(views != NULL) S.n = (uint32_t)views->n;
+	if(vps != NULL) { S.n = (uint32_t)vps->n; S.vp_units = vps->units; }
+	if(rays != NULL) S.n = rays->n;
 	S.resident = c->num_cus * resident_per_cu(c, glb, refill, P.has_w != 0, lds_bytes);
 	const int room = c->room.mode >= 0 ? c->room.mode : L->room;        // (a host that set a number gets it for every launch)
 	S.reserve = c->grid_reserve > room ? c->grid_reserve : room;
@@ -330,13 +338,14 @@ int pwn_i_launch_trace(pwn_ctx *c, pwn_trace_launch *L)
 	rc = rotation_wait(c, stream);
 	if(rc != PWN_OK) return rc;
 	if(refill) HIPCHK(c, pwn_launch_trace_refill(&P, plan.grid, lds_bytes, c->counters_on != 0, stream));
-	// (rays that stop after a given distance, with or without a hidden sphere: the REACH instantiations, in a unit of their own)
-	else if(P.ray_reach != NULL) HIPCHK(c, pwn_launch_trace_reach(&P, plan.grid, lds_bytes, c->counters_on != 0, stream));
-	// (one hidden sphere per view or ray: the HIDE instantiations, in a unit of their own)
-	// (views of their own sizes and rays' colours: a third unit; a launch that neither matches is refused by the one it is sent to)
-	else if((P.vps != NULL && P.view_hide != 0) || (P.rays != NULL && P.hits == NULL && P.ray_hide != NULL)) HIPCHK(c, pwn_launch_trace_hide2(&P, plan.grid, lds_bytes, c->counters_on != 0, stream));
-	else if(P.view_hide != 0 || P.ray_hide != NULL) HIPCHK(c, pwn_launch_trace_hide(&P, plan.grid, lds_bytes, c->counters_on != 0, stream));
-	else HIPCHK(c, pwn_launch_trace(&P, plan.grid, lds_bytes, c->counters_on != 0, stream));
+	else
+	{
+		// the units kernel's variant (trace_variants.h): the mode, the form of the tables' per-cell lists (pwn_i_pack_blob says which the
+		// blob has), and whether the launch reads an order or writes its units' costs.  A combination without a kernel is refused there.
+		const int lists = glb ? PWN_LF_GLOBAL : P.off_recsph != 0u ? PWN_LF_INLINE : PWN_LF_INDEXED;
+		const bool order = P.perm != NULL || P.unit_cost != NULL;
+		HIPCHK(c, pwn_launch_trace(mode, lists, order, &P, plan.grid, lds_bytes, c->counters_on != 0, stream));
+	}
 	return launch_went_out(c, cur, stream, L->tables_event);
 }
 

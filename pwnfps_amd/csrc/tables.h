@@ -242,16 +242,15 @@ struct pwn_trace_params
 	// kernel's HIDE parameter).  ray_hide: NULL, or nrays int32 beside `rays`: ray i does not see the sphere whose index in the live table
 	// (pwn_hit.object's numbering) is ray_hide[i]; any other value hides nothing -- with `hits` the rays' first hits, without it their
 	// colours (pwn_trace_rays_hide_device).  view_hide != 0: a launch of `views` or of `vps` whose records' `hide` words count
-	// (pwn_view_rec, pwn_viewport_rec).  Either one picks the HIDE instantiations (pwn_launch_trace_hide, trace_hide.hip: views, their
-	// first hits, rays' first hits; pwn_launch_trace_hide2, trace_hide_vp.hip: views of their own sizes, their first hits, rays'
-	// colours); no other kernel reads them.  (Behind everything else, as the tile pairs were: no other field moves.)
+	// (pwn_view_rec, pwn_viewport_rec).  Only kernels with the HIDE bit in their mode read ray_hide; NO kernel reads view_hide -- the
+	// launch's mode says it (pwn_launch_trace) -- and the word is still set and stays where it is: without it ray_reach would move in
+	// every kernel's arguments.  (Behind everything else, as the tile pairs were: no other field moves.)
 	const int32_t *ray_hide;
 	int view_hide;
 	// Rays that stop after a given distance (pwn_trace_reach, pwn_trace_reach_device, pwn_trace_reach_hide_device; the kernel's REACH
 	// parameter).  NULL, or nrays floats beside `rays` in a launch of `hits`: ray i's walk stops behind the first step that leaves its
 	// distance above ray_reach[i], and a ray that stops so gets a PWN_HIT_FREE record (pwnhip.h).  The value is only ever compared and
-	// multiplied.  Not NULL picks the REACH instantiations (pwn_launch_trace_reach, trace_reach.hip), with or without ray_hide; no other
-	// kernel reads it.  (Behind everything else, as ray_hide was: no other field moves.)
+	// multiplied.  Only kernels with the REACH bit in their mode read it.  (Behind everything else, as ray_hide was: no other field moves.)
 	const float *ray_reach;
 };
 #define PWN_HIT_REC_BYTES 48u
@@ -286,13 +285,11 @@ struct pwn_blur_params
 	int nvp, vp_tiles;
 };
 
-// what a launch of the trace kernel traces (its MODE parameter, trace_kernel.hip)
+// what a launch of the trace kernel traces (its MODE parameter, trace_kernel.hip; which modes have kernels, and where: trace_variants.h)
 enum { PWN_KM_FRAME = 0, PWN_KM_VIEWS = 1, PWN_KM_RAYS = 2, PWN_KM_HITS = 3, PWN_KM_VIEWPORTS = 4, PWN_KM_VIEW_HITS = 5, PWN_KM_VIEWPORT_HITS = 6 };
-// ... or'ed to PWN_KM_VIEWS, PWN_KM_VIEW_HITS or PWN_KM_HITS (trace_hide.hip), to PWN_KM_VIEWPORTS, PWN_KM_VIEWPORT_HITS or PWN_KM_RAYS
-// (trace_hide_vp.hip): its HIDE parameter -- every view or ray names one sphere it does not see
+// ... or'ed to it: its HIDE parameter -- every view or ray names one sphere it does not see
 enum { PWN_KM_HIDE = 8 };
-// ... or'ed to PWN_KM_HITS alone, with or without PWN_KM_HIDE (trace_reach.hip): its REACH parameter -- every ray names a distance behind
-// which it stops (pwn_trace_params.ray_reach)
+// ... its REACH parameter -- every ray names a distance behind which it stops (pwn_trace_params.ray_reach)
 enum { PWN_KM_REACH = 16 };
 
 // One view of a batch: the camera set-up of screen.h:43-57 for that view's camera (pwn_internal.h frame_setup) and its

@@ -343,19 +343,15 @@ template<bool HAS_W> __device__ __forceinline__ void chain_rounds(Vec<HAS_W> &v,
 // primary segment only (trace_hit) and writes packed first-hit words to the planes P.hits / sbuf / zbuf (label, cell, distance) instead
 // of a colour and a depth.  PWN_KM_VIEWPORT_HITS: views of their own sizes handed out and placed as PWN_KM_VIEWPORTS'
 // (pwn_trace_viewport_hits), of which every lane traces the primary segment only and writes the same packed words into ONE plane each
-// of the pitch-P.w frame, P.hits / sbuf / zbuf.  The last six are instantiated with ORDER = false only.
+// of the pitch-P.w frame, P.hits / sbuf / zbuf.
 // LISTS (tables.h PWN_LF_*): the form of the per-cell sphere lists -- indexed or inline records in LDS, or, for sphere sets whose
-// lists outgrow LDS, records in device memory (PWN_LF_GLOBAL: instantiated with ORDER = false only).
+// lists outgrow LDS, records in device memory (PWN_LF_GLOBAL).
 // HIDE (tables.h PWN_KM_HIDE, a bit of the MODE argument: the names of the kernels without it are as they were, and tests and
-// tools/issue_model.py find kernels by name): every view, or every ray, names one sphere of the table that it does not see
-// (pwn_trace_views_hide_device, pwn_trace_view_hits_hide_device, pwn_trace_hits_hide_device).  Instantiated for PWN_KM_VIEWS,
-// PWN_KM_VIEW_HITS and PWN_KM_HITS in a translation unit of its own (trace_hide.hip), and for PWN_KM_VIEWPORTS, PWN_KM_VIEWPORT_HITS and
-// PWN_KM_RAYS (pwn_trace_viewports_hide_device, pwn_trace_viewport_hits_hide_device, pwn_trace_rays_hide_device) in a third
-// (trace_hide_vp.hip), where the kernel has a name of its own, PWN_TRACE_KERNEL_NAME: tests pin the set of pwn_trace_kernel's
-// instantiations with the HIDE bit to the first three modes, and a second name changes nothing of what the other two units compile.
+// tools/issue_model.py find kernels by name): every view, or every ray, names one sphere of the table that it does not see.
 // REACH (tables.h PWN_KM_REACH, a second bit of the MODE argument, valid with PWN_KM_HITS alone): every ray names a distance behind which
-// its walk stops (pwn_trace_reach, pwn_trace_reach_device, pwn_trace_reach_hide_device).  Instantiated with and without the HIDE bit in a
-// fourth unit (trace_reach.hip), under a name of its own as well.
+// its walk stops.
+// Which combinations are instantiated, in which translation unit and under which name (PWN_TRACE_KERNEL_NAME, set by the unit file):
+// trace_variants.h, the one table; the host part at the bottom of this file expands it.
 #ifndef PWN_TRACE_KERNEL_NAME
 #define PWN_TRACE_KERNEL_NAME pwn_trace_kernel
 #endif
@@ -917,87 +913,52 @@ template<bool ORDER, int LISTS, int MODE>
 using Units = TraceKernels<PWN_TRACE_KERNEL_NAME<true, true, ORDER, LISTS, MODE>, PWN_TRACE_KERNEL_NAME<true, false, ORDER, LISTS, MODE>,
 	PWN_TRACE_KERNEL_NAME<false, true, ORDER, LISTS, MODE>, PWN_TRACE_KERNEL_NAME<false, false, ORDER, LISTS, MODE>>;
 
-#if defined(PWN_TRACE_REACH_UNIT)
-// trace_reach.hip: this file's text with the REACH instantiations alone -- twenty-four kernels, PWN_KM_HITS with and without HIDE x three
-// list forms x COUNT x HAS_W, under the name that unit gives them -- and the one function that launches them.
-template<int LISTS>
-static hipError_t launch_reach(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
+// The host part.  The unit file that includes this text says which unit of trace_variants.h it is (PWN_TRACE_UNIT; this file by
+// itself is MAIN) and compiles that unit's rows of the table: one function that launches them, whose uses of Units<> are what
+// instantiates the unit's kernels -- templates are instantiated where they are used, so no unit compiles another's.
+#include "trace_variants.h"
+#ifndef PWN_TRACE_UNIT
+#define PWN_TRACE_UNIT MAIN
+#define PWN_TRACE_MAIN_UNIT
+#endif
+
+// One row: its kernels over the (ORDER, LISTS) the table gives every row, and those it gives the rows with ORDER variants.  Anything
+// else is no kernel, and a missing kernel is an error.
+template<int MODE, bool HAS_ORDER>
+static hipError_t launch_row(int lists, bool order, const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
 {
-	// (a missing kernel is an error: only a batch of rays' first hits has a REACH instantiation)
-	if(P->rays == NULL || P->hits == NULL || P->ray_reach == NULL || P->views != NULL || P->vps != NULL) return hipErrorInvalidValue;
-	return P->ray_hide != NULL ? Units<false, LISTS, PWN_KM_HITS | PWN_KM_HIDE | PWN_KM_REACH>::launch(P, grid, lds_bytes, count, stream)
-	                           : Units<false, LISTS, PWN_KM_HITS | PWN_KM_REACH>::launch(P, grid, lds_bytes, count, stream);
-}
-extern "C" hipError_t pwn_launch_trace_reach(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
-{
-	if(P->g_rec != NULL) return launch_reach<PWN_LF_GLOBAL>(P, grid, lds_bytes, count, stream);
-	return P->off_recsph != 0u ? launch_reach<PWN_LF_INLINE>(P, grid, lds_bytes, count, stream) : launch_reach<PWN_LF_INDEXED>(P, grid, lds_bytes, count, stream);
-}
-#elif defined(PWN_TRACE_HIDE_VP_UNIT)
-// trace_hide_vp.hip: this file's text with the HIDE instantiations of the viewport modes and of the rays' colours alone -- thirty-six
-// kernels, three modes x three list forms x COUNT x HAS_W, under the name that unit gives them -- and the one function that launches them.
-template<int LISTS>
-static hipError_t launch_hide2(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
-{
-	if(P->vps != NULL && P->view_hide != 0)
-		return P->hits != NULL ? Units<false, LISTS, PWN_KM_VIEWPORT_HITS | PWN_KM_HIDE>::launch(P, grid, lds_bytes, count, stream)
-		                       : Units<false, LISTS, PWN_KM_VIEWPORTS | PWN_KM_HIDE>::launch(P, grid, lds_bytes, count, stream);
-	if(P->rays != NULL && P->hits == NULL && P->ray_hide != NULL) return Units<false, LISTS, PWN_KM_RAYS | PWN_KM_HIDE>::launch(P, grid, lds_bytes, count, stream);
-	// (a missing kernel is an error: nothing else has a HIDE instantiation here)
+#define PWN_FORM(ORDER, LISTS) if(order == ORDER && lists == LISTS) return Units<ORDER, LISTS, MODE>::launch(P, grid, lds_bytes, count, stream);
+#define PWN_FORM_ORDER(ORDER, LISTS) if constexpr(HAS_ORDER) PWN_FORM(ORDER, LISTS)
+	PWN_TRACE_ROW_FORMS(PWN_FORM, PWN_FORM_ORDER)
+#undef PWN_FORM
+#undef PWN_FORM_ORDER
 	return hipErrorInvalidValue;
 }
-extern "C" hipError_t pwn_launch_trace_hide2(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
+extern "C" hipError_t PWN_TRACE_UNIT_LAUNCH(PWN_TRACE_UNIT)(int mode, int lists, bool order, const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
 {
-	if(P->g_rec != NULL) return launch_hide2<PWN_LF_GLOBAL>(P, grid, lds_bytes, count, stream);
-	return P->off_recsph != 0u ? launch_hide2<PWN_LF_INLINE>(P, grid, lds_bytes, count, stream) : launch_hide2<PWN_LF_INDEXED>(P, grid, lds_bytes, count, stream);
-}
-#elif defined(PWN_TRACE_HIDE_UNIT)
-// trace_hide.hip: this file's text with the HIDE instantiations alone -- thirty-six kernels, three modes x three list forms x COUNT x
-// HAS_W -- and the one function that launches them.  (A unit of its own: in this file they would add a third to its build time.)
-template<int LISTS>
-static hipError_t launch_hide(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
-{
-	if(P->views != NULL && P->view_hide != 0)
-		return P->hits != NULL ? Units<false, LISTS, PWN_KM_VIEW_HITS | PWN_KM_HIDE>::launch(P, grid, lds_bytes, count, stream)
-		                       : Units<false, LISTS, PWN_KM_VIEWS | PWN_KM_HIDE>::launch(P, grid, lds_bytes, count, stream);
-	if(P->rays != NULL && P->hits != NULL && P->ray_hide != NULL) return Units<false, LISTS, PWN_KM_HITS | PWN_KM_HIDE>::launch(P, grid, lds_bytes, count, stream);
-	// (a missing kernel is an error: nothing else has a HIDE instantiation)
-	return hipErrorInvalidValue;
-}
-extern "C" hipError_t pwn_launch_trace_hide(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
-{
-	if(P->g_rec != NULL) return launch_hide<PWN_LF_GLOBAL>(P, grid, lds_bytes, count, stream);
-	return P->off_recsph != 0u ? launch_hide<PWN_LF_INLINE>(P, grid, lds_bytes, count, stream) : launch_hide<PWN_LF_INDEXED>(P, grid, lds_bytes, count, stream);
-}
-#else
-extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
-{
-	// (the blob says which form its per-cell lists have: pwn_i_pack_blob, pwn_tables.cpp)
-	// The global form: twenty-eight variants, MODE x COUNT x HAS_W, never ordered (pwn_i_launch_trace hands such a launch neither an
-	// order nor a cost array).
-	if(P->g_rec != NULL)
+	switch(mode)
 	{
-		if(P->vps != NULL && P->hits != NULL) return Units<false, PWN_LF_GLOBAL, PWN_KM_VIEWPORT_HITS>::launch(P, grid, lds_bytes, count, stream);
-		if(P->views != NULL && P->hits != NULL) return Units<false, PWN_LF_GLOBAL, PWN_KM_VIEW_HITS>::launch(P, grid, lds_bytes, count, stream);
-		if(P->hits != NULL) return Units<false, PWN_LF_GLOBAL, PWN_KM_HITS>::launch(P, grid, lds_bytes, count, stream);
-		if(P->rays != NULL) return Units<false, PWN_LF_GLOBAL, PWN_KM_RAYS>::launch(P, grid, lds_bytes, count, stream);
-		if(P->views != NULL) return Units<false, PWN_LF_GLOBAL, PWN_KM_VIEWS>::launch(P, grid, lds_bytes, count, stream);
-		if(P->vps != NULL) return Units<false, PWN_LF_GLOBAL, PWN_KM_VIEWPORTS>::launch(P, grid, lds_bytes, count, stream);
-		if(P->perm != NULL || P->unit_cost != NULL) return hipErrorInvalidValue;
-		return Units<false, PWN_LF_GLOBAL, PWN_KM_FRAME>::launch(P, grid, lds_bytes, count, stream);
+#define PWN_ROW(UNIT, NAME, MODE, HAS_ORDER) case (MODE): return launch_row<(MODE), HAS_ORDER>(lists, order, P, grid, lds_bytes, count, stream);
+	PWN_TRACE_UNIT_VARIANTS(PWN_TRACE_UNIT)(PWN_ROW)
+#undef PWN_ROW
 	}
-	const bool inl = P->off_recsph != 0u;
-	// a batch of rays (pwn_trace_rays), of their first hits (pwn_trace_hits), of views (pwn_trace_views) or of views of their own sizes
-	// (pwn_trace_viewports), of views' first-hit planes (pwn_trace_view_hits, pwn_trace_viewport_hits): eight variants each, never ordered
-	if(P->vps != NULL && P->hits != NULL) return inl ? Units<false, PWN_LF_INLINE, PWN_KM_VIEWPORT_HITS>::launch(P, grid, lds_bytes, count, stream) : Units<false, PWN_LF_INDEXED, PWN_KM_VIEWPORT_HITS>::launch(P, grid, lds_bytes, count, stream);
-	if(P->views != NULL && P->hits != NULL) return inl ? Units<false, PWN_LF_INLINE, PWN_KM_VIEW_HITS>::launch(P, grid, lds_bytes, count, stream) : Units<false, PWN_LF_INDEXED, PWN_KM_VIEW_HITS>::launch(P, grid, lds_bytes, count, stream);
-	if(P->hits != NULL) return inl ? Units<false, PWN_LF_INLINE, PWN_KM_HITS>::launch(P, grid, lds_bytes, count, stream) : Units<false, PWN_LF_INDEXED, PWN_KM_HITS>::launch(P, grid, lds_bytes, count, stream);
-	if(P->rays != NULL) return inl ? Units<false, PWN_LF_INLINE, PWN_KM_RAYS>::launch(P, grid, lds_bytes, count, stream) : Units<false, PWN_LF_INDEXED, PWN_KM_RAYS>::launch(P, grid, lds_bytes, count, stream);
-	if(P->views != NULL) return inl ? Units<false, PWN_LF_INLINE, PWN_KM_VIEWS>::launch(P, grid, lds_bytes, count, stream) : Units<false, PWN_LF_INDEXED, PWN_KM_VIEWS>::launch(P, grid, lds_bytes, count, stream);
-	if(P->vps != NULL) return inl ? Units<false, PWN_LF_INLINE, PWN_KM_VIEWPORTS>::launch(P, grid, lds_bytes, count, stream) : Units<false, PWN_LF_INDEXED, PWN_KM_VIEWPORTS>::launch(P, grid, lds_bytes, count, stream);
-	const bool order = P->perm != NULL || P->unit_cost != NULL;
-	if(inl) return order ? Units<true, PWN_LF_INLINE, PWN_KM_FRAME>::launch(P, grid, lds_bytes, count, stream) : Units<false, PWN_LF_INLINE, PWN_KM_FRAME>::launch(P, grid, lds_bytes, count, stream);
-	return order ? Units<true, PWN_LF_INDEXED, PWN_KM_FRAME>::launch(P, grid, lds_bytes, count, stream) : Units<false, PWN_LF_INDEXED, PWN_KM_FRAME>::launch(P, grid, lds_bytes, count, stream);
+	return hipErrorInvalidValue;
+}
+
+#ifdef PWN_TRACE_MAIN_UNIT
+// The launcher: the unit that holds the mode's row launches it.  A mode without a row is no kernel.
+#define PWN_ROW(UNIT, NAME, MODE, HAS_ORDER) extern "C" hipError_t PWN_TRACE_UNIT_LAUNCH(UNIT)(int, int, bool, const pwn_trace_params *, int, size_t, bool, hipStream_t);
+PWN_TRACE_VARIANTS(PWN_ROW)
+#undef PWN_ROW
+extern "C" hipError_t pwn_launch_trace(int mode, int lists, bool order, const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t stream)
+{
+	switch(mode)
+	{
+#define PWN_ROW(UNIT, NAME, MODE, HAS_ORDER) case (MODE): return PWN_TRACE_UNIT_LAUNCH(UNIT)(mode, lists, order, P, grid, lds_bytes, count, stream);
+	PWN_TRACE_VARIANTS(PWN_ROW)
+#undef PWN_ROW
+	}
+	return hipErrorInvalidValue;
 }
 
 extern "C" int pwn_trace_tile_h(void) { return TILE_H; }

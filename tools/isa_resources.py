@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Kernel resources and instruction counts of two builds, side by side: for every kernel symbol in the assembly files of directory A
 (the parent commit's) and B (this tree's) -- hipcc --cuda-device-only -S of the trace units and post_kernels.hip with the Makefile's
-flags -- VGPRs, SGPRs, scratch bytes and the number of instruction lines, and whether the instruction streams differ.
+flags -- VGPRs, SGPRs, scratch bytes and the number of instruction lines, and whether the instruction streams differ (a branch
+counts by the instruction it goes to, not by the name of its label: the names number the file's functions in the order they come out).
 
     tools/isa_resources.py DIR_A DIR_B        prints the table (profiles/reach/isa_resources.txt is one)
 """
@@ -10,6 +11,9 @@ import os
 import re
 import subprocess
 import sys
+
+
+LABEL = re.compile(r"\.LBB\d+_\d+")
 
 
 def kernels(path):
@@ -23,8 +27,16 @@ def kernels(path):
             return int(re.search(r"\.amdhsa_%s\s+(\d+)" % name, desc).group(1))
         start = text.index("\n" + sym + ":")
         body = text[start:text.index("s_endpgm", start)]
-        ins = [ln.split(";")[0].strip() for ln in body.splitlines()[2:]]
-        ins = [ln for ln in ins if ln and not ln.startswith((".", ";")) and not ln.endswith(":")]
+        ins, at = [], {}
+        for ln in body.splitlines()[2:]:
+            ln = ln.split(";")[0].strip()
+            if ln.endswith(":"):
+                at[ln[:-1]] = len(ins)
+            elif ln and not ln.startswith((".", ";")):
+                ins.append(ln)
+        # A block label (.LBB<n>_<k>) carries the number n of its function within the file, which moves when the file's kernels come
+        # out in another order: a branch is compared by the instruction it goes to, "@<index in this kernel>", not by the label's name
+        ins = [LABEL.sub(lambda m: "@%d" % at[m.group(0)] if m.group(0) in at else m.group(0), ln) for ln in ins]
         out[sym] = (field("next_free_vgpr"), field("next_free_sgpr"), field("private_segment_fixed_size"), ins)
     return out
 

@@ -11,6 +11,7 @@
 #include <string.h>
 #include <initializer_list>
 #include "pwn_internal.h"
+#include "trace_variants.h"
 
 static uint32_t mix(uint32_t a, uint32_t b) { a ^= b + 0x9e3779b9u + (a << 6) + (a >> 2); return a * 2654435761u; }
 
@@ -29,12 +30,28 @@ static void small_launch(const char *name, const void *src, const void *dst, std
 {
 	if(pwn_fake_launch_hook != NULL) pwn_fake_launch_hook(name, src, dst, (int)sizes.size(), sizes.begin());
 }
-extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t)
+// (the mode of the calling thread's last trace launch, set before the hook runs: the drivers require the exact mode per call; -1: none
+// yet.  Per thread: a group's members launch from threads of their own)
+extern "C" { thread_local int pwn_fake_trace_mode = -1; }
+static hipError_t reach_records(const pwn_trace_params *P, bool count);
+extern "C" hipError_t pwn_launch_trace(int mode, int, bool, const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t)
 {
+	// (a mode without a row of the table is no kernel, as in trace_kernel.hip; the refill kernel's launches come with PWN_KM_FRAME)
+	switch(mode)
+	{
+#define PWN_ROW(UNIT, NAME, MODE, HAS_ORDER) case (MODE):
+	PWN_TRACE_VARIANTS(PWN_ROW)
+#undef PWN_ROW
+		break;
+		default: return hipErrorInvalidValue;
+	}
+	pwn_fake_trace_mode = mode;
 	if(pwn_fake_trace_hook != NULL) pwn_fake_trace_hook(P, grid, lds_bytes);
+	if((mode & PWN_KM_REACH) != 0) return reach_records(P, count);
 	// first-hit planes of views (pwn_trace_view_hits; view_hits_driver.cpp): a word per pixel of every plane given that depends on the
 	// plane, the view's record and the pixel -- every word of n x h x w, and none beside them
-	if(P->views != NULL && P->hits != NULL)
+	const int what = mode & ~(PWN_KM_HIDE | PWN_KM_REACH);
+	if(what == PWN_KM_VIEW_HITS)
 	{
 		for(int v = 0; v < P->nviews; v++)
 		{
@@ -57,7 +74,7 @@ extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size
 	// first-hit planes of views of their own sizes (pwn_trace_viewport_hits; viewport_hits_driver.cpp): a word per pixel of every
 	// rectangle in every plane given, at (rec.y + y) * w + rec.x + x, that depends on the plane, the record's head and rectangle and
 	// the LOCAL pixel -- every word of every rectangle, and none beside them
-	if(P->vps != NULL && P->hits != NULL)
+	if(what == PWN_KM_VIEWPORT_HITS)
 	{
 		unsigned long long pixels = 0;
 		for(int v = 0; v < P->nvp; v++)
@@ -101,27 +118,12 @@ extern "C" hipError_t pwn_launch_trace(const pwn_trace_params *P, int grid, size
 	if(count && P->counters) { P->counters[0] += (unsigned long long)(P->y1 - P->y0) * P->w * 3ull; P->counters[1] += (unsigned long long)(P->y1 - P->y0) * P->w * 12ull; }
 	return hipSuccess;
 }
-extern "C" hipError_t pwn_launch_trace_refill(const pwn_trace_params *P, int g, size_t l, bool c, hipStream_t s) { return pwn_launch_trace(P, g, l, c, s); }
-// (the HIDE kernels, trace_hide.hip: the same stand-in -- what the hide words do to a pixel is the kernels' business)
-// (... counted, each: hide_viewports_driver.cpp looks at which launcher a call's trace launch went to)
-extern "C" { int pwn_fake_hide_launches = 0, pwn_fake_hide2_launches = 0; }
-extern "C" hipError_t pwn_launch_trace_hide(const pwn_trace_params *P, int g, size_t l, bool c, hipStream_t s) { pwn_fake_hide_launches++; return pwn_launch_trace(P, g, l, c, s); }
-// (trace_hide_vp.hip's: views of their own sizes with the records' hide words, or rays' colours with ray_hide -- anything else it refuses)
-extern "C" hipError_t pwn_launch_trace_hide2(const pwn_trace_params *P, int g, size_t l, bool c, hipStream_t s)
+extern "C" hipError_t pwn_launch_trace_refill(const pwn_trace_params *P, int g, size_t l, bool c, hipStream_t s) { return pwn_launch_trace(PWN_KM_FRAME, PWN_LF_INDEXED, false, P, g, l, c, s); }
+// (the HIDE bit of a mode changes nothing here: what the hide words do to a pixel is the kernels' business)
+// (the REACH bit; reach_driver.cpp: a record per ray made of the ray's number, its eight floats, its reach and its hide word -- exactly n
+// entries of each array are read, exactly n records written)
+static hipError_t reach_records(const pwn_trace_params *P, bool count)
 {
-	if(!((P->vps != NULL && P->view_hide != 0) || (P->rays != NULL && P->hits == NULL && P->ray_hide != NULL))) return hipErrorInvalidValue;
-	pwn_fake_hide2_launches++;
-	return pwn_launch_trace(P, g, l, c, s);
-}
-// (trace_reach.hip's: first-hit records of rays with ray_reach, with or without ray_hide -- anything else it refuses.  reach_driver.cpp: a
-// record per ray made of the ray's number, its eight floats, its reach and its hide word -- exactly n entries of each array are read,
-// exactly n records written)
-extern "C" { int pwn_fake_reach_launches = 0; }
-extern "C" hipError_t pwn_launch_trace_reach(const pwn_trace_params *P, int grid, size_t lds_bytes, bool count, hipStream_t)
-{
-	if(P->rays == NULL || P->hits == NULL || P->ray_reach == NULL || P->views != NULL || P->vps != NULL) return hipErrorInvalidValue;
-	pwn_fake_reach_launches++;
-	if(pwn_fake_trace_hook != NULL) pwn_fake_trace_hook(P, grid, lds_bytes);
 	for(uint32_t i = 0; i < P->nrays; i++)
 	{
 		uint32_t k = mix(i, P->ray_hide != NULL ? (uint32_t)P->ray_hide[i] : 0x5555u), u;

@@ -3,8 +3,8 @@
 // against the stand-in runtime and the stand-in launches (fake_kernels.cpp), as viewport_hits_driver.cpp runs the calls they shadow.
 // "Device" memory is malloc'ed to the byte.  What is looked at: d_hide reaches the set-up launcher and the records carry
 // hide[perm[j]] + 1 (0 for a value that is no index); a plain call hands the set-up launcher no array and its records' words are 0,
-// also in a record set that held a hide call's before; the trace launch of a hide call goes to the HIDE launcher of its unit and a
-// plain one does not; every refusal -- NULL, misaligned, overlapping each written range -- with nothing launched and nothing written;
+// also in a record set that held a hide call's before; the trace launch of every call has exactly the call's mode, the HIDE bit for a
+// hide call and none for a plain one; every refusal -- NULL, misaligned, overlapping each written range -- with nothing launched and nothing written;
 // the ticket sets over mixed plain and hide calls on one and on two streams; no allocation, synchronisation or host wait after the
 // first device call; the layout-use event of a hide call, which pwn_viewports_layout_free waits for; the rays' call: the array in the
 // launch's parameters, the empty batch, refusals; a group's handle; no leak behind pwn_destroy.
@@ -22,7 +22,7 @@ extern "C" void (*pwn_fake_trace_hook)(const pwn_trace_params *P, int grid, size
 extern "C" void (*pwn_fake_blur_hook)(const pwn_blur_params *B);
 extern "C" void (*pwn_fake_viewport_hide_hook)(const int32_t *hide, int n);
 extern "C" void (*fakehip_call_hook)(const char *name, const void *a, const void *b, size_t bytes);
-extern "C" int pwn_fake_hide_launches, pwn_fake_hide2_launches;
+extern "C" thread_local int pwn_fake_trace_mode;
 
 #define REQ(x) do { if(!(x)) { fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #x); exit(1); } } while(0)
 
@@ -31,6 +31,7 @@ static std::vector<std::string> g_log;
 static int g_setups, g_traces, g_blurs, g_small_other, g_allocs, g_syncs, g_waits, g_event_syncs;
 static std::vector<pwn_viewport_rec> g_recs;      // the records the last trace launch was handed
 static pwn_trace_params g_P;
+static int g_mode = -1;                           // the mode of the last trace launch
 static const int32_t *g_hide_seen;                // the array the last set-up launch was handed (NULL: none)
 static int g_hide_n, g_hide_calls;
 
@@ -42,7 +43,7 @@ static void on_small(const char *name, const void *, const void *, int, const si
 static void on_hide(const int32_t *hide, int n) { g_hide_seen = hide; g_hide_n = n; g_hide_calls++; }
 static void on_trace(const pwn_trace_params *P, int, size_t)
 {
-	g_traces++; g_log.push_back("trace"); g_P = *P;
+	g_traces++; g_log.push_back("trace"); g_P = *P; g_mode = pwn_fake_trace_mode;
 	g_recs.clear();
 	if(P->vps != NULL) g_recs.assign(P->vps, P->vps + P->nvp);
 }
@@ -107,7 +108,7 @@ static void one_call(pwn_ctx *c, pwn_vp_layout *l, int kind, const int32_t *hide
 {
 	std::vector<float> cams, secs;
 	make_cams(cams, secs, NV, salt);
-	const int su = g_setups, tr = g_traces, bl = g_blurs, hc = g_hide_calls, h1 = pwn_fake_hide_launches, h2 = pwn_fake_hide2_launches;
+	const int su = g_setups, tr = g_traces, bl = g_blurs, hc = g_hide_calls;
 	const unsigned set = c->ticket_set % (2u * (unsigned)c->launch_rot);
 	const size_t log0 = g_log.size();
 	int rc = PWN_EINVAL;
@@ -129,8 +130,8 @@ static void one_call(pwn_ctx *c, pwn_vp_layout *l, int kind, const int32_t *hide
 	REQ(g_hide_calls == hc + (hid ? 1 : 0));
 	REQ(g_hide_seen == (hid ? hide : NULL) && g_hide_n == (hid ? NV : 0));
 	check_words(hid ? hide : NULL);
-	// the trace launch: the HIDE launcher of the viewports' unit for a hide call, the plain one otherwise; the set's records and tickets
-	REQ(pwn_fake_hide2_launches == h2 + (hid ? 1 : 0) && pwn_fake_hide_launches == h1);
+	// the trace launch: the call's mode, with the HIDE bit for a hide call and without it otherwise; the set's records and tickets
+	REQ(g_mode == ((col ? PWN_KM_VIEWPORTS : PWN_KM_VIEWPORT_HITS) | (hid ? PWN_KM_HIDE : 0)));
 	REQ(g_P.view_hide == (hid ? 1 : 0) && g_P.ray_hide == NULL && g_P.vps != NULL && g_P.views == NULL && g_P.rays == NULL);
 	REQ((g_P.hits != NULL) == !col);
 	REQ(g_P.vps == c->d_prec_dev + (size_t)set * PWN_VIEWS_MAX);
@@ -287,28 +288,26 @@ int main(int argc, char **argv)
 		REQ(g_setups == su && pl.a.poisoned());
 	}
 
-	// ---- the rays' call: the array travels in the launch's parameters, to the HIDE launcher of the same unit
+	// ---- the rays' call: the array travels in the launch's parameters, and the launch has the HIDE bit
 	{
 		const int n = 65;
 		dev rays(8 * (size_t)n + 4), seeds(n), col((size_t)n + 4), depth(n), rh((size_t)n + 2);
 		const int tr = g_traces, su = g_setups;
-		int h1n = pwn_fake_hide_launches, h2n = pwn_fake_hide2_launches;
 		unsigned set = c->ticket_set % (2u * (unsigned)c->launch_rot);
 		REQ(pwn_trace_rays_hide_device(c, n, rays.p(), seeds.p(), rh.p(), 1.25f, 0, col.p(), depth.p(), c->stream) == PWN_OK);
-		REQ(g_traces == tr + 1 && g_setups == su && pwn_fake_hide2_launches == h2n + 1 && pwn_fake_hide_launches == h1n);
+		REQ(g_traces == tr + 1 && g_setups == su && g_mode == (PWN_KM_RAYS | PWN_KM_HIDE));
 		REQ(g_P.ray_hide == (const int32_t *)rh.q && g_P.view_hide == 0 && g_P.hits == NULL && g_P.rays == (const float *)rays.q && g_P.nrays == (uint32_t)n);
 		REQ(g_P.ray_seeds == seeds.q && g_P.sbuf == col.q && g_P.zbuf == (float *)depth.q && g_P.sec_current == 1.25f && g_P.ray_w == 0);
 		REQ(g_P.tickets == c->d_tickets + set * PWN_QUEUES * PWN_QUEUE_STRIDE);
 		REQ(pwn_trace_rays_hide_device(c, n, rays.p(), NULL, rh.q + 1, 0.0f, PWN_RAYS_HAS_W, col.p(), depth.p(), s2) == PWN_OK);
-		REQ(g_P.ray_hide == (const int32_t *)rh.q + 1 && g_P.ray_w == 1 && g_P.ray_seeds == NULL);
-		// a plain call passes none, and goes to the plain launcher; the first hits' hide call to the other unit's
-		h2n = pwn_fake_hide2_launches;
+		REQ(g_P.ray_hide == (const int32_t *)rh.q + 1 && g_P.ray_w == 1 && g_P.ray_seeds == NULL && g_traces == tr + 2 && g_mode == (PWN_KM_RAYS | PWN_KM_HIDE));
+		// a plain call passes none, and its mode has no HIDE bit; the first hits' hide call has its own mode
 		REQ(pwn_trace_rays_device(c, n, rays.p(), seeds.p(), 1.25f, 0, col.p(), depth.p(), c->stream) == PWN_OK);
-		REQ(g_P.ray_hide == NULL && pwn_fake_hide2_launches == h2n && pwn_fake_hide_launches == h1n);
+		REQ(g_P.ray_hide == NULL && g_traces == tr + 3 && g_mode == PWN_KM_RAYS);
 		{
 			dev hits(12 * (size_t)n);
 			REQ(pwn_trace_hits_hide_device(c, n, rays.p(), rh.p(), 0, hits.p(), c->stream) == PWN_OK);
-			REQ(g_P.ray_hide == (const int32_t *)rh.q && g_P.hits == hits.q && pwn_fake_hide2_launches == h2n && pwn_fake_hide_launches == h1n + 1);
+			REQ(g_P.ray_hide == (const int32_t *)rh.q && g_P.hits == hits.q && g_traces == tr + 4 && g_mode == (PWN_KM_HITS | PWN_KM_HIDE));
 		}
 		// the empty batch: nothing launched, d_hide may be NULL
 		const int tr1 = g_traces;

@@ -1,9 +1,9 @@
 // reach_driver.cpp -- the host side of pwn_trace_reach / pwn_trace_reach_device / pwn_trace_reach_hide_device on the CPU, under
-// AddressSanitizer + UBSan: pwn_reach.cpp against the stand-in runtime and a stand-in launcher (fake_kernels.cpp pwn_launch_trace_reach),
-// which writes every ray a record made of the ray's number, its eight floats, its reach and its hide word ("device" memory is
+// AddressSanitizer + UBSan: pwn_reach.cpp against the stand-in runtime and the stand-in launcher (fake_kernels.cpp pwn_launch_trace),
+// which for a mode with the REACH bit writes every ray a record made of the ray's number, its eight floats, its reach and its hide word ("device" memory is
 // malloc'ed to the byte: a staging that is too small, an array read past its n entries or a pointer that is off is a report).  What is
 // looked at: the host form's arrays there and back as its staging grows -- pwn_trace_hits' buffers, the larger need counts --, where in
-// the staging the launch finds records, reaches and hits, which launcher a call goes to, the 3-lane / 4-lane rule, the empty batch,
+// the staging the launch finds records, reaches and hits, the exact mode of every call's launch, the 3-lane / 4-lane rule, the empty batch,
 // every refusal -- a group's handle among them -- and the overlap rules with nothing launched and nothing written, no leak behind
 // pwn_destroy.
 //     reach_asan LEVEL.txt        prints "ok"
@@ -15,12 +15,12 @@
 #include "pwn_internal.h"
 
 extern "C" void (*pwn_fake_trace_hook)(const pwn_trace_params *P, int grid, size_t lds_bytes);
-extern "C" int pwn_fake_reach_launches, pwn_fake_hide_launches, pwn_fake_hide2_launches;
+extern "C" thread_local int pwn_fake_trace_mode;
 
 #define REQ(x) do { if(!(x)) { fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #x); exit(1); } } while(0)
 static pwn_trace_params g_P;
-static int g_launches;
-static void on_trace(const pwn_trace_params *P, int, size_t) { g_P = *P; g_launches++; }
+static int g_launches, g_mode = -1, g_reach_launches;      // trace launches; the mode of the last one; those with the REACH bit
+static void on_trace(const pwn_trace_params *P, int, size_t) { g_P = *P; g_launches++; g_mode = pwn_fake_trace_mode; if(g_mode & PWN_KM_REACH) g_reach_launches++; }
 
 // (fake_kernels.cpp's record)
 static uint32_t mix(uint32_t a, uint32_t b) { a ^= b + 0x9e3779b9u + (a << 6) + (a >> 2); return a * 2654435761u; }
@@ -60,16 +60,16 @@ int main(int argc, char **argv)
 	// same 4096 rays of pwn_trace_reach need 84 B each and have to make them grow
 	fill(false);
 	REQ(pwn_trace_hits(c, 4096, rays.data(), hits.data()) == PWN_OK);
-	REQ(c->hits_cap == 4096 && pwn_fake_reach_launches == 0);
+	REQ(c->hits_cap == 4096 && g_reach_launches == 0 && g_mode == PWN_KM_HITS);
 	const int ns[6] = { 3, 4096, 65, NMAX, 7, 1 };
 	for(int k = 0; k < 6; k++)
 		for(int w = 0; w < 2; w++)
 		{
 			fill(w != 0);
-			const int n = ns[k], before = pwn_fake_reach_launches;
+			const int n = ns[k], before = g_reach_launches, gl = g_launches;
 			const size_t cap0 = c->hits_cap;
 			REQ(pwn_trace_reach(c, n, rays.data(), reach.data(), hits.data()) == PWN_OK);
-			REQ(pwn_fake_reach_launches == before + 1 && pwn_fake_hide_launches == 0 && pwn_fake_hide2_launches == 0);
+			REQ(g_reach_launches == before + 1 && g_launches == gl + 1 && g_mode == (PWN_KM_HITS | PWN_KM_REACH));
 			const size_t N = (size_t)n, hoff = (36 * N + 15) & ~(size_t)15;
 			REQ(c->hits_cap * 80 + 16 >= hoff + 48 * N && c->hits_cap >= cap0);
 			if(n == 4096 && w == 0) REQ(c->hits_cap > 4096);
@@ -87,7 +87,7 @@ int main(int argc, char **argv)
 			}
 		}
 	// (pwn_trace_hits goes on in the grown buffers)
-	REQ(pwn_trace_hits(c, NMAX, rays.data(), hits.data()) == PWN_OK);
+	REQ(pwn_trace_hits(c, NMAX, rays.data(), hits.data()) == PWN_OK && g_mode == PWN_KM_HITS);
 
 	// ---- the device forms: arrays of exactly n entries
 	for(int hide = 0; hide < 2; hide++)
@@ -100,10 +100,10 @@ int main(int argc, char **argv)
 			REQ(hipMalloc((void **)&d_hide, 4 * (size_t)n) == hipSuccess && hipMalloc((void **)&d_hits, 48 * (size_t)n) == hipSuccess);
 			memcpy(d_rays, rays.data(), 32 * (size_t)n); memcpy(d_reach, reach.data(), 4 * (size_t)n);
 			for(int i = 0; i < n; i++) d_hide[i] = i % 3 == 0 ? PWN_HIDE_NONE : i;
-			const int before = pwn_fake_reach_launches, gl = g_launches;
+			const int before = g_reach_launches, gl = g_launches;
 			if(hide) REQ(pwn_trace_reach_hide_device(c, n, d_rays, d_reach, d_hide, flags ? PWN_RAYS_HAS_W : 0, d_hits, c->stream2) == PWN_OK);
 			else REQ(pwn_trace_reach_device(c, n, d_rays, d_reach, flags ? PWN_RAYS_HAS_W : 0, d_hits, c->stream2) == PWN_OK);
-			REQ(pwn_fake_reach_launches == before + 1 && g_launches == gl + 1 && pwn_fake_hide_launches == 0 && pwn_fake_hide2_launches == 0);
+			REQ(g_reach_launches == before + 1 && g_launches == gl + 1 && g_mode == (PWN_KM_HITS | PWN_KM_REACH | (hide ? PWN_KM_HIDE : 0)));
 			REQ(g_P.rays == d_rays && g_P.ray_reach == d_reach && g_P.hits == (void *)d_hits && g_P.ray_hide == (hide ? d_hide : NULL));
 			REQ(g_P.ray_w == flags && g_P.has_w == flags && g_P.nrays == (uint32_t)n);
 			for(int i = 0; i < n; i++)
@@ -120,7 +120,7 @@ int main(int argc, char **argv)
 	const int n = 70;
 	std::vector<int32_t> hide(NMAX, PWN_HIDE_NONE);
 	const std::vector<pwn_hit> h0(hits);
-	const int before = pwn_fake_reach_launches, gl = g_launches;
+	const int before = g_reach_launches, gl = g_launches;
 	const float *pr = rays.data(), *pq = reach.data(); pwn_hit *ph = hits.data(); const int32_t *pi = hide.data();
 	REQ(((uintptr_t)pr & 15u) == 0 && ((uintptr_t)ph & 15u) == 0);
 #define ALL3(code, N, R, Q, H) do { REQ(pwn_trace_reach(ctx, N, R, Q, H) == code); REQ(pwn_trace_reach_device(ctx, N, R, Q, 0, H, NULL) == code); \
@@ -167,14 +167,14 @@ int main(int argc, char **argv)
 		// arrays that touch without overlapping are taken: reach right behind the records written, hide right in front of them
 		std::vector<unsigned char> blk(4 * n + 48 * n + 4 * n + 16);
 		unsigned char *b = (unsigned char *)(((uintptr_t)blk.data() + 15) & ~(uintptr_t)15);
-		const int l0 = pwn_fake_reach_launches;
+		const int l0 = g_reach_launches;
 		int32_t *hd = (int32_t *)(b + 16 * ((4 * n + 15) / 16) - 4 * n);
 		for(int i = 0; i < n; i++) hd[i] = PWN_HIDE_NONE;
 		unsigned char *hh = b + 16 * ((4 * n + 15) / 16);
 		memcpy(hh + 48 * n, pq, 4 * n);
 		REQ(pwn_trace_reach_hide_device(ctx, n, pr, hh + 48 * n, hd, 0, hh, NULL) == PWN_OK);
-		REQ(pwn_fake_reach_launches == l0 + 1);
-		pwn_fake_reach_launches = l0; g_launches--;
+		REQ(g_reach_launches == l0 + 1 && g_mode == (PWN_KM_HITS | PWN_KM_HIDE | PWN_KM_REACH));
+		g_reach_launches = l0; g_launches--;
 	}
 	// ---- a group's handle (pwn_init_multi): PWN_ENOTSUP from all three, whatever else is right or wrong with the call
 	{
@@ -187,7 +187,7 @@ int main(int argc, char **argv)
 		ALL3(PWN_ENOTSUP, -1, pr, pq, ph);
 		pwn_destroy(ctx);
 	}
-	REQ(pwn_fake_reach_launches == before && g_launches == gl);
+	REQ(g_reach_launches == before && g_launches == gl);
 	REQ(memcmp(hits.data(), h0.data(), sizeof(pwn_hit) * (size_t)NMAX) == 0);
 
 	pwn_destroy(bare);
