@@ -237,25 +237,12 @@ class Renderer:
         tensor (n,8) on this context's GPU, 16-byte aligned, rows r, refl, x, y, z, cb, cg, cr (SPHERE_DTYPE's order); max_pairs: the
         most (cell, sphere) pairs the tables may hold -- spheres that make more put tables without any sphere into force
         (spheres_device_state says so).  The tensor may be overwritten, in stream order, once the call has returned."""
-        import torch
         who = "upload_spheres_device"
-        n = _tensor_check(torch, spheres, "spheres", (torch.float32,), 2, who=who)
-        if spheres.shape[1] != 8:
-            raise ValueError("%s: spheres must have shape (n,8), not %s" % (who, tuple(spheres.shape)))
-        if n > _lib.PWN_OBJ_MAX:
-            raise ValueError("%s: %d spheres are more than PWN_OBJ_MAX (%d)" % (who, n, _lib.PWN_OBJ_MAX))
-        if spheres.device.index != self.device:
-            raise ValueError("%s: spheres are on %s, the context is on GPU %d" % (who, spheres.device, self.device))
-        if n and spheres.data_ptr() % 16 != 0:
-            raise ValueError("%s: spheres is not 16-byte aligned" % who)
+        n, dev = _check(who, [("spheres", spheres, _F32, (None, 8), 16)], device=self.device)
+        _count(who, "spheres", n, 0, _lib.PWN_OBJ_MAX)
         if isinstance(max_pairs, bool) or not isinstance(max_pairs, (int, np.integer)) or not 0 <= int(max_pairs) < 2 ** 31:
             raise ValueError("%s: max_pairs must be an integer 0 .. 2^31 - 1, not %r" % (who, max_pairs))
-        if stream is None:
-            stream = torch.cuda.current_stream(spheres.device)
-        if not isinstance(stream, int):
-            stream = stream.cuda_stream
-        self._chk(lib.pwn_upload_spheres_device(self._ctx, n, C.c_void_p(spheres.data_ptr() if n else None), int(max_pairs), C.c_void_p(stream or 0)),
-                  "pwn_upload_spheres_device")
+        _device_call(self, lib.pwn_upload_spheres_device, stream, dev, (n, _ptr(spheres), int(max_pairs)))
 
     def spheres_device_state(self):
         """pwn_spheres_device_state (blocks: waits for the last build): dict(in_force, n, max_pairs, pairs, cells, longest, reason,
@@ -279,18 +266,11 @@ class Renderer:
     def trace_views(self, cams, secs, want_z=True):
         """pwn_trace_views: n views of this context's size in one call.  cams (n,4,4) or (n,16), secs (n,).  Returns (n,h,w)
         uint32 colour and, with want_z, (n,h,w) float32 depth; view i as trace_screen_centred(cams[i], secs[i]) renders it."""
-        cams = np.asarray(cams)
-        if cams.ndim == 3 and cams.shape[1:] == (4, 4):
-            cams = cams.reshape(cams.shape[0], 16)
-        if cams.ndim != 2 or cams.shape[1] != 16 or cams.shape[0] < 1:
-            raise ValueError("trace_views: cams must have shape (n,4,4) or (n,16) with n >= 1, not %s" % (cams.shape,))
-        n = cams.shape[0]
-        if n > _lib.PWN_VIEWS_MAX:
-            raise ValueError("trace_views: %d views, at most %d" % (n, _lib.PWN_VIEWS_MAX))
+        cams = _cam_records(cams, "trace_views")
+        n = _count("trace_views", "views (cams' rows)", cams.shape[0], 1, _lib.PWN_VIEWS_MAX)
         secs = np.asarray(secs)
         if secs.shape != (n,):
             raise ValueError("trace_views: secs must have shape (%d,), not %s" % (n, secs.shape))
-        cams = np.ascontiguousarray(cams, np.float32)
         secs = np.ascontiguousarray(secs, np.float32)
         sbuf = np.empty((n, self.h, self.w), np.uint32)
         zbuf = np.empty((n, self.h, self.w), np.float32) if want_z else None
@@ -307,39 +287,14 @@ class Renderer:
         None = torch's current stream on the tensors' device.
         hide: None, or an (n,) int32 tensor (pwn_trace_views_hide_device): view i does not see sphere hide[i] of the table in force,
         on any segment of its rays; PWN_HIDE_NONE (-1) and every other value that is no sphere's index hide nothing."""
-        import torch
         who = "trace_views_device"
-        words = (torch.int32, getattr(torch, "uint32", torch.int32))
-        if isinstance(cams, torch.Tensor) and cams.dim() == 3 and tuple(cams.shape[1:]) == (4, 4) and cams.is_contiguous():
-            cams = cams.view(cams.shape[0], 16)
-        n = _tensor_check(torch, cams, "cams", (torch.float32,), 2, who=who)
-        if cams.shape[1] != 16 or n < 1 or n > _lib.PWN_VIEWS_MAX:
-            raise ValueError("%s: cams must have shape (n,4,4) or (n,16) with 1 <= n <= %d, not %s" % (who, _lib.PWN_VIEWS_MAX, tuple(cams.shape)))
-        _tensor_check(torch, secs, "secs", (torch.float32,), 1, n, who=who)
-        planes = [("sbuf", sbuf, words), ("zbuf", zbuf, (torch.float32,))] + ([("work", work, words)] if work is not None else [])
-        for name, t, dtypes in planes:
-            _tensor_check(torch, t, name, dtypes, 3, n, who=who)
-            if tuple(t.shape) != (n, self.h, self.w):
-                raise ValueError("%s: %s must have shape (%d,%d,%d), not %s" % (who, name, n, self.h, self.w, tuple(t.shape)))
-        if hide is not None:
-            _tensor_check(torch, hide, "hide", (torch.int32,), 1, n, who=who)
-        for name, t in [("secs", secs)] + [(name, t) for name, t, _ in planes] + ([("hide", hide)] if hide is not None else []):
-            if t.device != cams.device:
-                raise ValueError("%s: tensors on %s and %s" % (who, cams.device, t.device))
-        if stream is None:
-            stream = torch.cuda.current_stream(cams.device)
-        if not isinstance(stream, int):
-            stream = stream.cuda_stream
-        if hide is not None:
-            self._chk(lib.pwn_trace_views_hide_device(self._ctx, n, C.c_void_p(cams.data_ptr()), C.c_void_p(secs.data_ptr()),
-                                                      C.c_void_p(hide.data_ptr()), _lib.PWN_VIEWS_HAS_W if has_w else 0,
-                                                      C.c_void_p(work.data_ptr() if work is not None else None), C.c_void_p(sbuf.data_ptr()),
-                                                      C.c_void_p(zbuf.data_ptr()), C.c_void_p(stream or 0)), "pwn_trace_views_hide_device")
-            return
-        self._chk(lib.pwn_trace_views_device(self._ctx, n, C.c_void_p(cams.data_ptr()), C.c_void_p(secs.data_ptr()),
-                                             _lib.PWN_VIEWS_HAS_W if has_w else 0,
-                                             C.c_void_p(work.data_ptr() if work is not None else None), C.c_void_p(sbuf.data_ptr()),
-                                             C.c_void_p(zbuf.data_ptr()), C.c_void_p(stream or 0)), "pwn_trace_views_device")
+        cams, plane = _cams16(cams), (None, self.h, self.w)
+        n, dev = _check(who, [("cams", cams, _F32, (None, 16), 4), ("secs", secs, _F32, (None,), 4),
+                              ("sbuf", sbuf, _WORDS, plane, 4), ("zbuf", zbuf, _F32, plane, 4)],
+                        [("work", work, _WORDS, plane, 4), ("hide", hide, _I32, (None,), 4)])
+        _count(who, "views (cams' rows)", n, 1, _lib.PWN_VIEWS_MAX)
+        _device_call(self, lib.pwn_trace_views_hide_device if hide is not None else lib.pwn_trace_views_device, stream, dev,
+                     (n, _ptr(cams), _ptr(secs), _lib.PWN_VIEWS_HAS_W if has_w else 0, _ptr(work), _ptr(sbuf), _ptr(zbuf)), hide, 3)
 
     def trace_viewports(self, rects, cams, secs, want_z=True, sbuf=None, zbuf=None):
         """pwn_trace_viewports: n views of their own sizes composited into ONE frame of this context's size in one call.  rects
@@ -348,15 +303,10 @@ class Renderer:
         sbuf / zbuf: the caller's own frame buffers (host_register makes their copies plain DMA)."""
         rects = _rect_records(rects, "trace_viewports")
         n = rects.shape[0]
-        cams = np.asarray(cams)
-        if cams.ndim == 3 and cams.shape[1:] == (4, 4):
-            cams = cams.reshape(cams.shape[0], 16)
-        if cams.shape != (n, 16):
-            raise ValueError("trace_viewports: cams must have shape (%d,4,4) or (%d,16), not %s" % (n, n, cams.shape))
+        cams = _cam_records(cams, "trace_viewports", n)
         secs = np.asarray(secs)
         if secs.shape != (n,):
             raise ValueError("trace_viewports: secs must have shape (%d,), not %s" % (n, secs.shape))
-        cams = np.ascontiguousarray(cams, np.float32)
         secs = np.ascontiguousarray(secs, np.float32)
         if sbuf is None:
             sbuf = np.empty((self.h, self.w), np.uint32)
@@ -390,45 +340,14 @@ class Renderer:
         needed with blur on.  has_w and stream as trace_views_device takes them.
         hide: None, or an (n,) int32 tensor on the same GPU (pwn_trace_viewports_hide_device): rectangle i does not see sphere hide[i]
         of the table in force; PWN_HIDE_NONE (-1) and every other value that is no sphere's index hide nothing."""
-        import torch
         who = "trace_viewports_device"
-        if not isinstance(layout, ViewportsLayout) or layout._ptr is None or layout._renderer is not self:
-            raise ValueError("%s: layout must be a live ViewportsLayout of this renderer" % who)
-        words = (torch.int32, getattr(torch, "uint32", torch.int32))
-        if isinstance(cams, torch.Tensor) and cams.dim() == 3 and tuple(cams.shape[1:]) == (4, 4) and cams.is_contiguous():
-            cams = cams.view(cams.shape[0], 16)
-        n = _tensor_check(torch, cams, "cams", (torch.float32,), 2, layout.n, who=who)
-        if cams.shape[1] != 16:
-            raise ValueError("%s: cams must have shape (%d,4,4) or (%d,16), not %s" % (who, layout.n, layout.n, tuple(cams.shape)))
-        _tensor_check(torch, secs, "secs", (torch.float32,), 1, n, who=who)
-        planes = [("sbuf", sbuf, words), ("zbuf", zbuf, (torch.float32,))] + ([("work", work, words)] if work is not None else [])
-        for name, t, dtypes in planes:
-            _tensor_check(torch, t, name, dtypes, 2, who=who)
-            if tuple(t.shape) != (layout.H, layout.W):
-                raise ValueError("%s: %s must have shape (%d,%d), not %s" % (who, name, layout.H, layout.W, tuple(t.shape)))
-        for name, t in [("cams", cams), ("secs", secs)] + [(name, t) for name, t, _ in planes]:
-            if t.device != cams.device:
-                raise ValueError("%s: tensors on %s and %s" % (who, cams.device, t.device))
-            if t.data_ptr() % 16 != 0:
-                raise ValueError("%s: %s is not 16-byte aligned" % (who, name))
-        if hide is not None:
-            _tensor_check(torch, hide, "hide", (torch.int32,), 1, n, who=who)
-            if hide.device != cams.device:
-                raise ValueError("%s: tensors on %s and %s" % (who, cams.device, hide.device))
-        if stream is None:
-            stream = torch.cuda.current_stream(cams.device)
-        if not isinstance(stream, int):
-            stream = stream.cuda_stream
-        if hide is not None:
-            self._chk(lib.pwn_trace_viewports_hide_device(self._ctx, layout._ptr, C.c_void_p(cams.data_ptr()), C.c_void_p(secs.data_ptr()),
-                                                          C.c_void_p(hide.data_ptr()), _lib.PWN_VIEWS_HAS_W if has_w else 0,
-                                                          C.c_void_p(work.data_ptr() if work is not None else None), C.c_void_p(sbuf.data_ptr()),
-                                                          C.c_void_p(zbuf.data_ptr()), C.c_void_p(stream or 0)), "pwn_trace_viewports_hide_device")
-            return
-        self._chk(lib.pwn_trace_viewports_device(self._ctx, layout._ptr, C.c_void_p(cams.data_ptr()), C.c_void_p(secs.data_ptr()),
-                                                 _lib.PWN_VIEWS_HAS_W if has_w else 0,
-                                                 C.c_void_p(work.data_ptr() if work is not None else None), C.c_void_p(sbuf.data_ptr()),
-                                                 C.c_void_p(zbuf.data_ptr()), C.c_void_p(stream or 0)), "pwn_trace_viewports_device")
+        _live_layout(who, self, layout)
+        cams, plane = _cams16(cams), (layout.H, layout.W)
+        _, dev = _check(who, [("cams", cams, _F32, (None, 16), 16), ("secs", secs, _F32, (None,), 16),
+                              ("sbuf", sbuf, _WORDS, plane, 16), ("zbuf", zbuf, _F32, plane, 16)],
+                        [("work", work, _WORDS, plane, 16), ("hide", hide, _I32, (None,), 4)], n=layout.n)
+        _device_call(self, lib.pwn_trace_viewports_hide_device if hide is not None else lib.pwn_trace_viewports_device, stream, dev,
+                     (layout._ptr, _ptr(cams), _ptr(secs), _lib.PWN_VIEWS_HAS_W if has_w else 0, _ptr(work), _ptr(sbuf), _ptr(zbuf)), hide, 3)
 
     # -- caller-supplied rays (pwn_trace_rays) --------------------------------
     def pixel_rays(self, cam, xy=None, order="rows"):
@@ -466,51 +385,16 @@ class Renderer:
         current stream on this device for tensors, the default stream for pointers.
         hide: None, or an (n,) int32 tensor on the same GPU (pwn_trace_rays_hide_device): ray i does not see sphere hide[i] of the
         table in force, on any of its segments; PWN_HIDE_NONE (-1) and every other value that is no sphere's index hide nothing."""
-        tensors = [t for t in (rays, col, depth, seeds) if t is not None and not isinstance(t, int)]
-        if tensors:
-            import torch
-            if len(tensors) != sum(t is not None for t in (rays, col, depth, seeds)):
-                raise ValueError("trace_rays_device: give all tensors or all device pointers")
-            rays_n = _tensor_check(torch, rays, "rays", (torch.float32,), 2)
-            if n is not None and int(n) != rays_n:
-                raise ValueError("trace_rays_device: n = %d, but rays has %d rows" % (n, rays_n))
-            n = rays_n
-            if rays.shape[1] != 8 or rays.data_ptr() % 16 != 0:
-                raise ValueError("trace_rays_device: rays must be (n,8) and 16-byte aligned")
-            _tensor_check(torch, col, "col", (torch.int32, getattr(torch, "uint32", torch.int32)), 1, n)
-            _tensor_check(torch, depth, "depth", (torch.float32,), 1, n)
-            if seeds is not None:
-                _tensor_check(torch, seeds, "seeds", (torch.int32, getattr(torch, "uint32", torch.int32)), 1, n)
-            for t in tensors:
-                if t.device != rays.device:
-                    raise ValueError("trace_rays_device: tensors on %s and %s" % (rays.device, t.device))
-            if stream is None:
-                stream = torch.cuda.current_stream(rays.device)
-            p_rays, p_col, p_depth = rays.data_ptr(), col.data_ptr(), depth.data_ptr()
-            p_seeds = seeds.data_ptr() if seeds is not None else None
+        who, hidden = "trace_rays_device", ("hide", hide, _I32, (None,), 4)
+        if _tensors_given(who, [a for a in (rays, col, depth, seeds) if a is not None]):
+            n, dev = _check(who, [("rays", rays, _F32, (None, 8), 16), ("col", col, _WORDS, (None,), 4), ("depth", depth, _F32, (None,), 4)],
+                            [("seeds", seeds, _WORDS, (None,), 4), hidden], None if n is None else int(n))
+            rays, col, depth, seeds = _ptr(rays), _ptr(col), _ptr(depth), _ptr(seeds)
         else:
-            if n is None:
-                raise ValueError("trace_rays_device: n is needed with device pointers")
-            p_rays, p_col, p_depth, p_seeds = rays, col, depth, seeds
-        if int(n) < 0 or int(n) > _lib.PWN_RAYS_MAX:
-            raise ValueError("trace_rays_device: n = %d, 0 ... %d" % (n, _lib.PWN_RAYS_MAX))
-        if hide is not None:
-            import torch
-            _tensor_check(torch, hide, "hide", (torch.int32,), 1, int(n), who="trace_rays_device")
-            if tensors and hide.device != rays.device:
-                raise ValueError("trace_rays_device: tensors on %s and %s" % (rays.device, hide.device))
-            if stream is None:
-                stream = torch.cuda.current_stream(hide.device)
-        if stream is not None and not isinstance(stream, int):
-            stream = stream.cuda_stream
-        if hide is not None:
-            self._chk(lib.pwn_trace_rays_hide_device(self._ctx, int(n), C.c_void_p(p_rays), C.c_void_p(p_seeds), C.c_void_p(hide.data_ptr()),
-                                                     float(sec_current), _lib.PWN_RAYS_HAS_W if has_w else 0, C.c_void_p(p_col),
-                                                     C.c_void_p(p_depth), C.c_void_p(stream or 0)), "pwn_trace_rays_hide_device")
-            return
-        self._chk(lib.pwn_trace_rays_device(self._ctx, int(n), C.c_void_p(p_rays), C.c_void_p(p_seeds), float(sec_current),
-                                            _lib.PWN_RAYS_HAS_W if has_w else 0, C.c_void_p(p_col), C.c_void_p(p_depth),
-                                            C.c_void_p(stream or 0)), "pwn_trace_rays_device")
+            n, dev = _check(who, (), [hidden], _rays_n(who, n))
+        _rays_n(who, n)
+        _device_call(self, lib.pwn_trace_rays_hide_device if hide is not None else lib.pwn_trace_rays_device, stream, dev,
+                     (n, rays, seeds, float(sec_current), _lib.PWN_RAYS_HAS_W if has_w else 0, col, depth), hide, 3)
 
     # -- first hits of caller-supplied rays (pwn_trace_hits) -------------------
     def trace_hits(self, rays):
@@ -529,47 +413,15 @@ class Renderer:
         raw device pointers with n given.  has_w and stream as trace_rays_device takes them.
         hide: None, or an (n,) int32 tensor on the same GPU (pwn_trace_hits_hide_device): ray i does not see sphere hide[i] of the
         table in force; PWN_HIDE_NONE (-1) and every other value that is no sphere's index hide nothing."""
-        tensors = [t for t in (rays, hits) if not isinstance(t, int)]
-        if tensors:
-            import torch
-            if len(tensors) != 2:
-                raise ValueError("trace_hits_device: give both tensors or both device pointers")
-            rays_n = _tensor_check(torch, rays, "rays", (torch.float32,), 2)
-            if n is not None and int(n) != rays_n:
-                raise ValueError("trace_hits_device: n = %d, but rays has %d rows" % (n, rays_n))
-            n = rays_n
-            if rays.shape[1] != 8 or rays.data_ptr() % 16 != 0:
-                raise ValueError("trace_hits_device: rays must be (n,8) and 16-byte aligned")
-            _tensor_check(torch, hits, "hits", (torch.int32, torch.float32, torch.uint8), 2, n)
-            if hits.shape[1] * hits.element_size() != HIT_DTYPE.itemsize or hits.data_ptr() % 16 != 0:
-                raise ValueError("trace_hits_device: hits must hold %d bytes a row and be 16-byte aligned" % HIT_DTYPE.itemsize)
-            if hits.device != rays.device:
-                raise ValueError("trace_hits_device: tensors on %s and %s" % (rays.device, hits.device))
-            if stream is None:
-                stream = torch.cuda.current_stream(rays.device)
-            p_rays, p_hits = rays.data_ptr(), hits.data_ptr()
+        who, hidden = "trace_hits_device", ("hide", hide, _I32, (None,), 4)
+        if _tensors_given(who, (rays, hits)):
+            n, dev = _check(who, [("rays", rays, _F32, (None, 8), 16), _hits_spec(hits)], [hidden], None if n is None else int(n))
+            rays, hits = _ptr(rays), _ptr(hits)
         else:
-            if n is None:
-                raise ValueError("trace_hits_device: n is needed with device pointers")
-            p_rays, p_hits = rays, hits
-        if int(n) < 0 or int(n) > _lib.PWN_RAYS_MAX:
-            raise ValueError("trace_hits_device: n = %d, 0 ... %d" % (n, _lib.PWN_RAYS_MAX))
-        if hide is not None:
-            import torch
-            _tensor_check(torch, hide, "hide", (torch.int32,), 1, int(n), who="trace_hits_device")
-            if tensors and hide.device != rays.device:
-                raise ValueError("trace_hits_device: tensors on %s and %s" % (rays.device, hide.device))
-            if stream is None:
-                stream = torch.cuda.current_stream(hide.device)
-        if stream is not None and not isinstance(stream, int):
-            stream = stream.cuda_stream
-        if hide is not None:
-            self._chk(lib.pwn_trace_hits_hide_device(self._ctx, int(n), C.c_void_p(p_rays), C.c_void_p(hide.data_ptr()),
-                                                     _lib.PWN_RAYS_HAS_W if has_w else 0, C.c_void_p(p_hits), C.c_void_p(stream or 0)),
-                      "pwn_trace_hits_hide_device")
-            return
-        self._chk(lib.pwn_trace_hits_device(self._ctx, int(n), C.c_void_p(p_rays), _lib.PWN_RAYS_HAS_W if has_w else 0,
-                                            C.c_void_p(p_hits), C.c_void_p(stream or 0)), "pwn_trace_hits_device")
+            n, dev = _check(who, (), [hidden], _rays_n(who, n))
+        _rays_n(who, n)
+        _device_call(self, lib.pwn_trace_hits_hide_device if hide is not None else lib.pwn_trace_hits_device, stream, dev,
+                     (n, rays, _lib.PWN_RAYS_HAS_W if has_w else 0, hits), hide, 2)
 
     # -- rays that stop after a given distance (pwn_trace_reach) ---------------
     def trace_reach(self, rays, reach):
@@ -593,34 +445,12 @@ class Renderer:
         hits 16-byte aligned.  has_w and stream as trace_hits_device takes them.
         hide: None, or an (n,) int32 tensor on the same GPU (pwn_trace_reach_hide_device): ray i does not see sphere hide[i] of the
         table in force; PWN_HIDE_NONE (-1) and every other value that is no sphere's index hide nothing."""
-        import torch
         who = "trace_reach_device"
-        n = _tensor_check(torch, rays, "rays", (torch.float32,), 2, who=who)
-        if rays.shape[1] != 8 or rays.data_ptr() % 16 != 0:
-            raise ValueError("trace_reach_device: rays must be (n,8) and 16-byte aligned")
-        _tensor_check(torch, reach, "reach", (torch.float32,), 1, n, who=who)
-        _tensor_check(torch, hits, "hits", (torch.int32, torch.float32, torch.uint8), 2, n, who=who)
-        if hits.shape[1] * hits.element_size() != HIT_DTYPE.itemsize or hits.data_ptr() % 16 != 0:
-            raise ValueError("trace_reach_device: hits must hold %d bytes a row and be 16-byte aligned" % HIT_DTYPE.itemsize)
-        if hide is not None:
-            _tensor_check(torch, hide, "hide", (torch.int32,), 1, n, who=who)
-        for t in (reach, hits, hide):
-            if t is not None and t.device != rays.device:
-                raise ValueError("trace_reach_device: tensors on %s and %s" % (rays.device, t.device))
-        if n > _lib.PWN_RAYS_MAX:
-            raise ValueError("trace_reach_device: n = %d, 0 ... %d" % (n, _lib.PWN_RAYS_MAX))
-        if stream is None:
-            stream = torch.cuda.current_stream(rays.device)
-        if not isinstance(stream, int):
-            stream = stream.cuda_stream
-        flags = _lib.PWN_RAYS_HAS_W if has_w else 0
-        if hide is not None:
-            self._chk(lib.pwn_trace_reach_hide_device(self._ctx, n, C.c_void_p(rays.data_ptr()), C.c_void_p(reach.data_ptr()),
-                                                      C.c_void_p(hide.data_ptr()), flags, C.c_void_p(hits.data_ptr()), C.c_void_p(stream or 0)),
-                      "pwn_trace_reach_hide_device")
-            return
-        self._chk(lib.pwn_trace_reach_device(self._ctx, n, C.c_void_p(rays.data_ptr()), C.c_void_p(reach.data_ptr()), flags,
-                                             C.c_void_p(hits.data_ptr()), C.c_void_p(stream or 0)), "pwn_trace_reach_device")
+        n, dev = _check(who, [("rays", rays, _F32, (None, 8), 16), ("reach", reach, _F32, (None,), 4), _hits_spec(hits)],
+                        [("hide", hide, _I32, (None,), 4)])
+        _rays_n(who, n)
+        _device_call(self, lib.pwn_trace_reach_hide_device if hide is not None else lib.pwn_trace_reach_device, stream, dev,
+                     (n, _ptr(rays), _ptr(reach), _lib.PWN_RAYS_HAS_W if has_w else 0, _ptr(hits)), hide, 3)
 
     def object_ids(self):
         """pwn_get_object_ids: per live sphere, in get_objects()' order (what a hit's `object` indexes), the obj_new handle"""
@@ -636,15 +466,8 @@ class Renderer:
         (label, cell, dist): label (n,h,w) uint32 packed words (unpack_labels takes them apart), cell (n,h,w,2) int16 cell x, z
         and dist (n,h,w) float32 -- cell / dist None where not wanted.  Pixel (x, y) of view i is the record trace_hits returns
         for pixel_rays(cams[i])'s ray of that pixel; a primary segment that ran out of steps gives 0 in all three."""
-        cams = np.asarray(cams)
-        if cams.ndim == 3 and cams.shape[1:] == (4, 4):
-            cams = cams.reshape(cams.shape[0], 16)
-        if cams.ndim != 2 or cams.shape[1] != 16 or cams.shape[0] < 1:
-            raise ValueError("trace_view_hits: cams must have shape (n,4,4) or (n,16) with n >= 1, not %s" % (cams.shape,))
-        n = cams.shape[0]
-        if n > _lib.PWN_VIEWS_MAX:
-            raise ValueError("trace_view_hits: %d views, at most %d" % (n, _lib.PWN_VIEWS_MAX))
-        cams = np.ascontiguousarray(cams, np.float32)
+        cams = _cam_records(cams, "trace_view_hits")
+        n = _count("trace_view_hits", "views (cams' rows)", cams.shape[0], 1, _lib.PWN_VIEWS_MAX)
         label = np.empty((n, self.h, self.w), np.uint32)
         cell = np.empty((n, self.h, self.w, 2), np.int16) if want_cell else None
         dist = np.empty((n, self.h, self.w), np.float32) if want_dist else None
@@ -659,49 +482,13 @@ class Renderer:
         (n,h,w) float32 or None.  Every pixel of every plane given is written.  has_w and stream as trace_views_device takes them.
         hide: None, or an (n,) int32 tensor (pwn_trace_view_hits_hide_device): view i does not see sphere hide[i] of the table in
         force (object numbers stay those of the whole table); values that are no sphere's index hide nothing."""
-        import torch
         who = "trace_view_hits_device"
-        words = (torch.int32, getattr(torch, "uint32", torch.int32))
-        if isinstance(cams, torch.Tensor) and cams.dim() == 3 and tuple(cams.shape[1:]) == (4, 4) and cams.is_contiguous():
-            cams = cams.view(cams.shape[0], 16)
-        n = _tensor_check(torch, cams, "cams", (torch.float32,), 2, who=who)
-        if cams.shape[1] != 16 or n < 1 or n > _lib.PWN_VIEWS_MAX:
-            raise ValueError("%s: cams must have shape (n,4,4) or (n,16) with 1 <= n <= %d, not %s" % (who, _lib.PWN_VIEWS_MAX, tuple(cams.shape)))
-        planes = [("label", label, words, 3)]
-        if cell is not None:
-            pairs = isinstance(cell, torch.Tensor) and cell.dtype == torch.int16
-            planes.append(("cell", cell, (torch.int16,), 4) if pairs else ("cell", cell, words, 3))
-        if dist is not None:
-            planes.append(("dist", dist, (torch.float32,), 3))
-        for name, t, dtypes, ndim in planes:
-            _tensor_check(torch, t, name, dtypes, ndim, n, who=who)
-            want = (n, self.h, self.w) + ((2,) if ndim == 4 else ())
-            if tuple(t.shape) != want:
-                raise ValueError("%s: %s must have shape %s, not %s" % (who, name, want, tuple(t.shape)))
-            if t.device != cams.device:
-                raise ValueError("%s: tensors on %s and %s" % (who, cams.device, t.device))
-        for name, t in [("cams", cams)] + [(name, t) for name, t, _, _ in planes]:
-            if t.data_ptr() % 16 != 0:
-                raise ValueError("%s: %s is not 16-byte aligned" % (who, name))
-        if hide is not None:
-            _tensor_check(torch, hide, "hide", (torch.int32,), 1, n, who=who)
-            if hide.device != cams.device:
-                raise ValueError("%s: tensors on %s and %s" % (who, cams.device, hide.device))
-        if stream is None:
-            stream = torch.cuda.current_stream(cams.device)
-        if not isinstance(stream, int):
-            stream = stream.cuda_stream
-        if hide is not None:
-            self._chk(lib.pwn_trace_view_hits_hide_device(self._ctx, n, C.c_void_p(cams.data_ptr()), C.c_void_p(hide.data_ptr()),
-                                                          _lib.PWN_VIEWS_HAS_W if has_w else 0, C.c_void_p(label.data_ptr()),
-                                                          C.c_void_p(cell.data_ptr() if cell is not None else None),
-                                                          C.c_void_p(dist.data_ptr() if dist is not None else None), C.c_void_p(stream or 0)),
-                      "pwn_trace_view_hits_hide_device")
-            return
-        self._chk(lib.pwn_trace_view_hits_device(self._ctx, n, C.c_void_p(cams.data_ptr()), _lib.PWN_VIEWS_HAS_W if has_w else 0,
-                                                 C.c_void_p(label.data_ptr()), C.c_void_p(cell.data_ptr() if cell is not None else None),
-                                                 C.c_void_p(dist.data_ptr() if dist is not None else None), C.c_void_p(stream or 0)),
-                  "pwn_trace_view_hits_device")
+        cams, plane = _cams16(cams), (None, self.h, self.w)
+        n, dev = _check(who, [("cams", cams, _F32, (None, 16), 16), ("label", label, _WORDS, plane, 16)],
+                        [_cell_spec(cell, plane), ("dist", dist, _F32, plane, 16), ("hide", hide, _I32, (None,), 4)])
+        _count(who, "views (cams' rows)", n, 1, _lib.PWN_VIEWS_MAX)
+        _device_call(self, lib.pwn_trace_view_hits_hide_device if hide is not None else lib.pwn_trace_view_hits_device, stream, dev,
+                     (n, _ptr(cams), _lib.PWN_VIEWS_HAS_W if has_w else 0, _ptr(label), _ptr(cell), _ptr(dist)), hide, 2)
 
     # -- the players' step (pwn_players_step) ---------------------------------
     def players_step(self, keys, cams, gravity, traversals=None, tdiff=1 / 60, ticks=1):
@@ -710,12 +497,8 @@ class Renderer:
         None.  Returns new arrays (cams, gravity, traversals) -- traversals None where none was given; the arguments are not changed."""
         who = "players_step"
         keys = np.asarray(keys)
-        cams_in = np.asarray(cams)
-        shape = cams_in.shape
-        if cams_in.ndim == 3 and shape[1:] == (4, 4):
-            cams_in = cams_in.reshape(shape[0], 16)
-        if cams_in.ndim != 2 or cams_in.shape[1] != 16:
-            raise ValueError("%s: cams must have shape (n,4,4) or (n,16), not %s" % (who, shape))
+        shape = np.shape(cams)
+        cams_in = _cam_records(cams, who)
         n = cams_in.shape[0]
         gravity = np.asarray(gravity)
         if keys.shape != (n,) or keys.dtype != np.uint8:
@@ -738,35 +521,13 @@ class Renderer:
         torch's current stream), no synchronisation.  Torch tensors on this context's GPU, contiguous: keys (n,) uint8, cams (n,16) or
         (n,4,4) float32 and gravity (n,4) float32, both 16-byte aligned, traversals (n,) int32 or None.  cams is the tensor
         trace_views_device takes: step, then observe, on one stream."""
-        import torch
         who = "players_step_device"
-        if isinstance(cams, torch.Tensor) and cams.dim() == 3 and tuple(cams.shape[1:]) == (4, 4) and cams.is_contiguous():
-            cams = cams.view(cams.shape[0], 16)
-        n = _tensor_check(torch, cams, "cams", (torch.float32,), 2, who=who)
-        if cams.shape[1] != 16:
-            raise ValueError("%s: cams must have shape (n,4,4) or (n,16), not %s" % (who, tuple(cams.shape)))
+        cams = _cams16(cams)
+        n, dev = _check(who, [("cams", cams, _F32, (None, 16), 16), ("keys", keys, _U8, (None,), 1), ("gravity", gravity, _F32, (None, 4), 16)],
+                        [("traversals", traversals, _I32, (None,), 4)])
         _players_numbers(who, n, tdiff, ticks)
-        if not isinstance(keys, torch.Tensor) or keys.device.type != "cuda" or keys.dtype != torch.uint8 or keys.dim() != 1 or keys.shape[0] != n or not keys.is_contiguous():
-            raise ValueError("%s: keys must be a contiguous uint8 GPU tensor of shape (%d,)" % (who, n))
-        _tensor_check(torch, gravity, "gravity", (torch.float32,), 2, n, who=who)
-        if gravity.shape[1] != 4:
-            raise ValueError("%s: gravity must have shape (%d,4), not %s" % (who, n, tuple(gravity.shape)))
-        if traversals is not None:
-            _tensor_check(torch, traversals, "traversals", (torch.int32,), 1, n, who=who)
-        for name, t in (("keys", keys), ("gravity", gravity), ("traversals", traversals)):
-            if t is not None and t.device != cams.device:
-                raise ValueError("%s: tensors on %s and %s" % (who, cams.device, t.device))
-        for name, t in (("cams", cams), ("gravity", gravity)):
-            if t.data_ptr() % 16 != 0:
-                raise ValueError("%s: %s is not 16-byte aligned" % (who, name))
-        if stream is None:
-            stream = torch.cuda.current_stream(cams.device)
-        if not isinstance(stream, int):
-            stream = stream.cuda_stream
-        self._chk(lib.pwn_players_step_device(self._ctx, n, C.c_void_p(keys.data_ptr() if n else None), float(tdiff), int(ticks),
-                                              C.c_void_p(cams.data_ptr() if n else None), C.c_void_p(gravity.data_ptr() if n else None),
-                                              C.c_void_p(traversals.data_ptr() if traversals is not None and n else None), C.c_void_p(stream or 0)),
-                  "pwn_players_step_device")
+        _device_call(self, lib.pwn_players_step_device, stream, dev,
+                     (n, _ptr(keys), float(tdiff), int(ticks), _ptr(cams), _ptr(gravity), _ptr(traversals)))
 
     # -- pixel rays from cameras on the GPU (pwn_pixel_rays_device) ------------
     def pixel_rays_device(self, cams, xy=None, *, width=None, height=None, shared=None, rays=None, seeds=None, work=None, stream=None):
@@ -780,12 +541,9 @@ class Renderer:
         trace_rays_device / trace_hits_device take them as they are (has_w for cameras with w components)."""
         import torch
         who = "pixel_rays_device"
-        words = (torch.int32, getattr(torch, "uint32", torch.int32))
-        if isinstance(cams, torch.Tensor) and cams.dim() == 3 and tuple(cams.shape[1:]) == (4, 4) and cams.is_contiguous():
-            cams = cams.view(cams.shape[0], 16)
-        n = _tensor_check(torch, cams, "cams", (torch.float32,), 2, who=who)
-        if cams.shape[1] != 16 or n > _lib.PWN_PLAYERS_MAX:
-            raise ValueError("%s: cams must have shape (n,4,4) or (n,16) with n <= %d, not %s" % (who, _lib.PWN_PLAYERS_MAX, tuple(cams.shape)))
+        cams = _cams16(cams)
+        n, dev = _check(who, [("cams", cams, _F32, (None, 16), 16)])
+        _count(who, "cameras (cams' rows)", n, 0, _lib.PWN_PLAYERS_MAX)
         width, height = self.w if width is None else width, self.h if height is None else height
         for name, v in (("width", width), ("height", height)):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1 or v > 32768:
@@ -798,57 +556,27 @@ class Renderer:
                 raise ValueError("%s: the whole frame (xy=None) is shared by every camera" % who)
             shared, m = True, width * height
         else:
-            if not isinstance(xy, torch.Tensor) or xy.dim() not in (2, 3):
+            if getattr(xy, "ndim", 0) not in (2, 3):
                 raise ValueError("%s: xy must be a GPU tensor of shape (m,2) or (n,m,2), or None" % who)
-            _tensor_check(torch, xy, "xy", (torch.int32,), xy.dim(), n if xy.dim() == 3 else None, who=who)
-            if xy.shape[-1] != 2:
-                raise ValueError("%s: xy must have shape (m,2) or (n,m,2), not %s" % (who, tuple(xy.shape)))
-            if shared is not None and bool(shared) != (xy.dim() == 2):
+            m = int(xy.shape[-2])
+            _check(who, [("xy", xy, _I32, (m, 2) if xy.ndim == 2 else (n, m, 2), 8)], device=dev)
+            if shared is not None and bool(shared) != (xy.ndim == 2):
                 raise ValueError("%s: shared=%s does not go with xy of shape %s" % (who, bool(shared), tuple(xy.shape)))
-            shared, m = xy.dim() == 2, int(xy.shape[-2])
-            if xy.data_ptr() % 8 != 0:
-                raise ValueError("%s: xy is not 8-byte aligned" % who)
-        total = n * m
-        if total > _lib.PWN_RAYS_MAX:
-            raise ValueError("%s: %d x %d rays, at most %d" % (who, n, m, _lib.PWN_RAYS_MAX))
-        dev = cams.device
+            shared = xy.ndim == 2
+        total = _count(who, "cameras x pixels", n * m, 0, _lib.PWN_RAYS_MAX)
+        _check(who, (), [("rays", rays, _F32, (n, m, 8) if getattr(rays, "ndim", 2) == 3 else (total, 8), 16),
+                         ("seeds", None if seeds is False else seeds, _WORDS, (n, m) if getattr(seeds, "ndim", 1) == 2 else (total,), 4),
+                         ("work", work, _F32, (n, _lib.PWN_PIXEL_WORK_BYTES // 4), 16)], device=dev)
         if rays is None:
-            rays = torch.empty((total, 8), dtype=torch.float32, device=dev)
-        else:
-            _tensor_check(torch, rays, "rays", (torch.float32,), rays.dim() if isinstance(rays, torch.Tensor) and rays.dim() in (2, 3) else 2, who=who)
-            if tuple(rays.shape) not in ((total, 8), (n, m, 8)):
-                raise ValueError("%s: rays must have shape (%d,8) or (%d,%d,8), not %s" % (who, total, n, m, tuple(rays.shape)))
+            rays = torch.empty((total, 8), dtype=torch.float32, device=cams.device)
         if seeds is None:
-            seeds = torch.empty(total, dtype=torch.int32, device=dev)
+            seeds = torch.empty(total, dtype=torch.int32, device=cams.device)
         elif seeds is False:
             seeds = None
-        else:
-            _tensor_check(torch, seeds, "seeds", words, seeds.dim() if isinstance(seeds, torch.Tensor) and seeds.dim() in (1, 2) else 1, who=who)
-            if tuple(seeds.shape) not in ((total,), (n, m)):
-                raise ValueError("%s: seeds must have shape (%d,) or (%d,%d), not %s" % (who, total, n, m, tuple(seeds.shape)))
         if work is None:
-            work = torch.empty((n, _lib.PWN_PIXEL_WORK_BYTES // 4), dtype=torch.float32, device=dev)
-        else:
-            _tensor_check(torch, work, "work", (torch.float32,), 2, n, who=who)
-            if work.shape[1] != _lib.PWN_PIXEL_WORK_BYTES // 4:
-                raise ValueError("%s: work must have shape (%d,%d), not %s" % (who, n, _lib.PWN_PIXEL_WORK_BYTES // 4, tuple(work.shape)))
-        for name, t in (("xy", xy), ("rays", rays), ("seeds", seeds), ("work", work)):
-            if t is not None and t.device != dev:
-                raise ValueError("%s: tensors on %s and %s" % (who, dev, t.device))
-        for name, t in (("cams", cams), ("rays", rays), ("work", work)):
-            if t.data_ptr() % 16 != 0:
-                raise ValueError("%s: %s is not 16-byte aligned" % (who, name))
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        if not isinstance(stream, int):
-            stream = stream.cuda_stream
-        live = total > 0
-        self._chk(lib.pwn_pixel_rays_device(self._ctx, width, height, n, C.c_void_p(cams.data_ptr() if n else None), m,
-                                            C.c_void_p(xy.data_ptr() if xy is not None and xy.numel() else None),
-                                            _lib.PWN_PIXELS_SHARED if shared else 0, C.c_void_p(work.data_ptr() if n else None),
-                                            C.c_void_p(rays.data_ptr() if live else None),
-                                            C.c_void_p(seeds.data_ptr() if seeds is not None and live else None), C.c_void_p(stream or 0)),
-                  "pwn_pixel_rays_device")
+            work = torch.empty((n, _lib.PWN_PIXEL_WORK_BYTES // 4), dtype=torch.float32, device=cams.device)
+        _device_call(self, lib.pwn_pixel_rays_device, stream, dev, (width, height, n, _ptr(cams), m, _ptr(xy), _lib.PWN_PIXELS_SHARED if shared else 0,
+                                                                    _ptr(work), _ptr(rays), _ptr(seeds)))
         return rays, seeds
 
     # -- first-hit planes of views of their own sizes (pwn_trace_viewport_hits) --
@@ -860,12 +588,7 @@ class Renderer:
         all three where the primary segment ran out of steps, and outside the rectangles."""
         rects = _rect_records(rects, "trace_viewport_hits")
         n = rects.shape[0]
-        cams = np.asarray(cams)
-        if cams.ndim == 3 and cams.shape[1:] == (4, 4):
-            cams = cams.reshape(cams.shape[0], 16)
-        if cams.shape != (n, 16):
-            raise ValueError("trace_viewport_hits: cams must have shape (%d,4,4) or (%d,16), not %s" % (n, n, cams.shape))
-        cams = np.ascontiguousarray(cams, np.float32)
+        cams = _cam_records(cams, "trace_viewport_hits", n)
         label = np.empty((self.h, self.w), np.uint32)
         cell = np.empty((self.h, self.w, 2), np.int16) if want_cell else None
         dist = np.empty((self.h, self.w), np.float32) if want_dist else None
@@ -882,52 +605,13 @@ class Renderer:
         every rectangle is written in every plane given, nothing outside them.  has_w and stream as trace_views_device takes them.
         hide as trace_viewports_device takes it (pwn_trace_viewport_hits_hide_device); object numbers in the labels stay those of the
         full table."""
-        import torch
         who = "trace_viewport_hits_device"
-        if not isinstance(layout, ViewportsLayout) or layout._ptr is None or layout._renderer is not self:
-            raise ValueError("%s: layout must be a live ViewportsLayout of this renderer" % who)
-        words = (torch.int32, getattr(torch, "uint32", torch.int32))
-        if isinstance(cams, torch.Tensor) and cams.dim() == 3 and tuple(cams.shape[1:]) == (4, 4) and cams.is_contiguous():
-            cams = cams.view(cams.shape[0], 16)
-        _tensor_check(torch, cams, "cams", (torch.float32,), 2, layout.n, who=who)
-        if cams.shape[1] != 16:
-            raise ValueError("%s: cams must have shape (%d,4,4) or (%d,16), not %s" % (who, layout.n, layout.n, tuple(cams.shape)))
-        planes = [("label", label, words, 2)]
-        if cell is not None:
-            pairs = isinstance(cell, torch.Tensor) and cell.dtype == torch.int16
-            planes.append(("cell", cell, (torch.int16,), 3) if pairs else ("cell", cell, words, 2))
-        if dist is not None:
-            planes.append(("dist", dist, (torch.float32,), 2))
-        for name, t, dtypes, ndim in planes:
-            _tensor_check(torch, t, name, dtypes, ndim, who=who)
-            want = (layout.H, layout.W) + ((2,) if ndim == 3 else ())
-            if tuple(t.shape) != want:
-                raise ValueError("%s: %s must have shape %s, not %s" % (who, name, want, tuple(t.shape)))
-        for name, t in [("cams", cams)] + [(name, t) for name, t, _, _ in planes]:
-            if t.device != cams.device:
-                raise ValueError("%s: tensors on %s and %s" % (who, cams.device, t.device))
-            if t.data_ptr() % 16 != 0:
-                raise ValueError("%s: %s is not 16-byte aligned" % (who, name))
-        if hide is not None:
-            _tensor_check(torch, hide, "hide", (torch.int32,), 1, layout.n, who=who)
-            if hide.device != cams.device:
-                raise ValueError("%s: tensors on %s and %s" % (who, cams.device, hide.device))
-        if stream is None:
-            stream = torch.cuda.current_stream(cams.device)
-        if not isinstance(stream, int):
-            stream = stream.cuda_stream
-        if hide is not None:
-            self._chk(lib.pwn_trace_viewport_hits_hide_device(self._ctx, layout._ptr, C.c_void_p(cams.data_ptr()), C.c_void_p(hide.data_ptr()),
-                                                              _lib.PWN_VIEWS_HAS_W if has_w else 0, C.c_void_p(label.data_ptr()),
-                                                              C.c_void_p(cell.data_ptr() if cell is not None else None),
-                                                              C.c_void_p(dist.data_ptr() if dist is not None else None), C.c_void_p(stream or 0)),
-                      "pwn_trace_viewport_hits_hide_device")
-            return
-        self._chk(lib.pwn_trace_viewport_hits_device(self._ctx, layout._ptr, C.c_void_p(cams.data_ptr()),
-                                                     _lib.PWN_VIEWS_HAS_W if has_w else 0, C.c_void_p(label.data_ptr()),
-                                                     C.c_void_p(cell.data_ptr() if cell is not None else None),
-                                                     C.c_void_p(dist.data_ptr() if dist is not None else None), C.c_void_p(stream or 0)),
-                  "pwn_trace_viewport_hits_device")
+        _live_layout(who, self, layout)
+        cams, plane = _cams16(cams), (layout.H, layout.W)
+        _, dev = _check(who, [("cams", cams, _F32, (None, 16), 16), ("label", label, _WORDS, plane, 16)],
+                        [_cell_spec(cell, plane), ("dist", dist, _F32, plane, 16), ("hide", hide, _I32, (None,), 4)], n=layout.n)
+        _device_call(self, lib.pwn_trace_viewport_hits_hide_device if hide is not None else lib.pwn_trace_viewport_hits_device, stream, dev,
+                     (layout._ptr, _ptr(cams), _lib.PWN_VIEWS_HAS_W if has_w else 0, _ptr(label), _ptr(cell), _ptr(dist)), hide, 2)
 
     def set_call_strips(self, n):
         """PWN_OPT_CALL_STRIPS: -1 = by frame size (default), 0 = one launch per pass, 2..32 = that many row strips"""
@@ -1201,6 +885,16 @@ def _rect_records(rects, who):
     return np.ascontiguousarray(rects, np.int32)
 
 
+def _cam_records(cams, who, n=None):
+    """(n,16) float32 cameras from an (n,4,4) or (n,16) array; n given: exactly so many"""
+    cams = np.asarray(cams)
+    if cams.ndim == 3 and cams.shape[1:] == (4, 4):
+        cams = cams.reshape(cams.shape[0], 16)
+    if cams.ndim != 2 or cams.shape[1] != 16 or (n is not None and cams.shape[0] != n):
+        raise ValueError("%s: cams must have shape (n,4,4) or (n,16)%s, not %s" % (who, "" if n is None else " with n = %d" % n, cams.shape))
+    return np.ascontiguousarray(cams, np.float32)
+
+
 def viewports_plan(W, H, rects, blur):
     """pwn_viewports_plan: what pwn_trace_viewports would make of these rectangles (n,4: x, y, w, h) in a W x H frame under `blur`
     passes.  No context, no device.  Returns a dict: ok (the call would accept them), units (16 x 4 units of the launch), pixels
@@ -1272,15 +966,108 @@ def players_spawn(spawn, n):
     return cams, np.zeros((int(n), 4), np.float32), np.zeros(int(n), np.int32)
 
 
-def _tensor_check(torch, t, name, dtypes, ndim, n=None, who="trace_rays_device"):
-    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-        raise ValueError("%s: %s must be a GPU tensor" % (who, name))
-    if t.dtype not in dtypes or t.dim() != ndim or (n is not None and t.shape[0] != n) or not t.is_contiguous():
-        raise ValueError("%s: %s must be a contiguous %s tensor of %d dimension(s)%s, not %s %s" % (
-            who, name, "/".join(str(d) for d in dtypes), ndim, "" if n is None else " and %d rows" % n, t.dtype, tuple(t.shape)))
-    if t.data_ptr() % 4 != 0:
-        raise ValueError("%s: %s is not 4-byte aligned" % (who, name))
-    return t.shape[0]
+# -- the device forms' argument checks and calls: a method is its specs, _check, _device_call ----------------
+_F32, _I32, _I16, _U8, _WORDS = ("float32",), ("int32",), ("int16",), ("uint8",), ("int32", "uint32")
+
+
+def _cams16(cams):
+    """a contiguous (n,4,4) camera tensor seen as (n,16), what the library reads; anything else as it is, for _check to judge"""
+    import torch
+    if isinstance(cams, torch.Tensor) and cams.dim() == 3 and tuple(cams.shape[1:]) == (4, 4) and cams.is_contiguous():
+        cams = cams.view(cams.shape[0], 16)
+    return cams
+
+
+_DTYPE_NAMES = {}         # torch.dtype -> "float32" ..., filled as dtypes are met (str(dtype) costs more than the rest of a check)
+
+
+def _check(who, required, optional=(), n=None, device=None):
+    """The argument check of a device form.  A spec is (name, tensor, dtype names, shape, alignment in bytes); a shape that begins
+    with None has n rows, and the first such tensor sets n where none is given.  ValueError unless every tensor -- of `optional`,
+    those that are not None -- is a contiguous GPU tensor of one of its dtypes and exactly its shape, starts at a multiple of its
+    alignment and is on GPU `device` (none given: the first tensor's).  Refuses nothing else; returns (n, device)."""
+    import torch
+    for specs, needed in ((required, True), (optional, False)):
+        for name, t, dtypes, shape, align in specs:
+            if t is None and not needed:
+                continue
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise ValueError("%s: %s must be a GPU tensor" % (who, name))
+            if shape[0] is None:
+                if n is None and t.dim():
+                    n = t.shape[0]
+                shape = (n,) + shape[1:]
+            dtype = _DTYPE_NAMES.get(t.dtype) or _DTYPE_NAMES.setdefault(t.dtype, str(t.dtype)[6:])
+            if dtype not in dtypes or t.shape != shape or not t.is_contiguous():
+                raise ValueError("%s: %s must be a contiguous %s tensor of shape %s, not %s %s" % (
+                    who, name, "/".join(dtypes), shape, dtype, tuple(t.shape)))
+            if t.data_ptr() % align != 0:
+                raise ValueError("%s: %s is not %d-byte aligned" % (who, name, align))
+            if device is None:
+                device = t.get_device()
+            elif t.get_device() != device:
+                raise ValueError("%s: %s is on GPU %d, not on GPU %d" % (who, name, t.get_device(), device))
+    return n, device
+
+
+def _count(who, what, n, lo, hi):
+    if not lo <= n <= hi:
+        raise ValueError("%s: %s = %d, %d ... %d" % (who, what, n, lo, hi))
+    return n
+
+
+def _rays_n(who, n):
+    """the ray count of a form that also takes raw pointers: given -- by the caller or by rays' rows -- and 0 ... PWN_RAYS_MAX"""
+    if n is None:
+        raise ValueError("%s: n is needed with device pointers" % who)
+    return _count(who, "n", int(n), 0, _lib.PWN_RAYS_MAX)
+
+
+def _cell_spec(cell, shape):
+    """a cell plane: a word per pixel, or -- elements of two bytes -- a pair of int16 per pixel"""
+    if getattr(cell, "itemsize", 4) == 2:
+        return ("cell", cell, _I16, shape + (2,), 16)
+    return ("cell", cell, _WORDS, shape, 16)
+
+
+def _hits_spec(hits):
+    """n records of HIT_DTYPE: (n,12) int32 or float32, or (n,48) uint8"""
+    return ("hits", hits, ("int32", "float32", "uint8"), (None, HIT_DTYPE.itemsize // (getattr(hits, "itemsize", 4) or 4)), 16)
+
+
+def _live_layout(who, r, layout):
+    if not isinstance(layout, ViewportsLayout) or layout._ptr is None or layout._renderer is not r:
+        raise ValueError("%s: layout must be a live ViewportsLayout of this renderer" % who)
+
+
+def _tensors_given(who, args):
+    """device arrays come as tensors or as raw device pointers (ints): True for tensors, False for pointers, ValueError for both"""
+    raw = len([a for a in args if isinstance(a, int)])
+    if 0 < raw < len(args):
+        raise ValueError("%s: give all tensors or all device pointers" % who)
+    return raw < len(args)
+
+
+def _ptr(t):
+    """the pointer of a tensor as the library takes it: None for no tensor and for an empty one"""
+    return None if t is None else t.data_ptr() or None
+
+
+def _stream_handle(stream, device):
+    """a raw hipStream_t of a torch stream, of a raw handle, or of None: torch's current stream on GPU `device` (no device: stream 0)"""
+    if stream is None:
+        if device is None:
+            return 0
+        import torch
+        stream = torch.cuda.current_stream(device)
+    return stream if isinstance(stream, int) else stream.cuda_stream
+
+
+def _device_call(r, fn, stream, device, args, hide=None, at=None):
+    """fn(ctx, *args, stream) on the renderer r, checked; with hide, fn is the _hide_device form: hide's pointer goes in at args[at]"""
+    if hide is not None:
+        args = args[:at] + (_ptr(hide),) + args[at:]
+    r._chk(fn(r._ctx, *args, _stream_handle(stream, device)), fn.__name__)
 
 
 def unit_order_xy(width, height):
