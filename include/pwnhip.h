@@ -378,6 +378,71 @@ int pwn_upload_spheres_device(pwn_ctx *ctx, int n, const void *d_spheres, int ma
 int pwn_spheres_device_state(pwn_ctx *ctx, unsigned long long out[8]);
 
 /*
+ * The level's tables baked on the device: pwn_upload_level for a grid that is already in device memory, on the caller's stream, with
+ * no host round trip -- an arena generated at every episode reset, a door a policy opens, a wall a projectile removes.  (The
+ * reference's script interface names the operation and leaves it a stub: level_set, script.h:65-69.)
+ *   what                 d_data holds 4096 cell bytes, z * 64 + x, the layout of pwn_upload_level's data; d_pmap 26 records of
+ *                        pwn_portal (7 int32 each) or NULL.  Both in device memory, 16-byte aligned, read by the call's own launches
+ *                        only: in stream order the caller may overwrite them afterwards.  No byte of the grid is special: '*', CR,
+ *                        LF and lower-case letters are cells like any other (their text meaning belongs to the parser).
+ *   d_pmap given         the level in force becomes bit for bit what pwn_upload_level(data, pmap) followed by pwn_upload_spheres(NULL, 0)
+ *                        puts into force, for every call family of this header and pwn_players_step[_device]: results, records,
+ *                        depth, the five counters.  c1 / c2 are taken by their low byte and rot12 by & 3, as the host does.
+ *   d_pmap NULL          the portal table is derived on the device from the cells as stored, the way pwn_level_load derives it: the
+ *                        first two cells holding a letter, in scan order (z major, then x), are its endpoints 1 and 2, a third sighting
+ *                        is ignored; for a letter with both, rot12 = (d2 - d1 + 2) & 3 with the directions' order +x, +z, -x, -z and
+ *                        the fall-back to +x, and c1 / c2 are the cell in that direction, read through the FLAT 4096-byte array (x = 64
+ *                        aliases the next row, a read outside the array is '.'); a letter with fewer than two sightings keeps
+ *                        coordinates -1, rot12 0, c1 = c2 = ';' for what it lacks.  For a grid holding none of CR, LF, '*',
+ *                        'a'..'y' the result is bit for bit what pwn_level_load_mem(those 4096 bytes, 4096) puts into force, and
+ *                        pwn_get_level_device returns the same 26 x 7 int32 as pwn_get_level (full rows need no line end).
+ *   the device cannot refuse   a given table that pwn_upload_level would refuse -- a coordinate outside -1 .. 63, or a cell outside
+ *                        the grid at coordinate -1 that would stand on an endpoint and see or do something there -- leaves the LEVEL
+ *                        that was in force in force, and pwn_level_device_state says why.  The checks run first, on the 26 x 4
+ *                        coordinates as integers and on the 130 cells outside the grid; no bit pattern of d_pmap or d_data reaches
+ *                        an address, a loop bound or a shift count before it has passed them.  Endpoints are compared with cell
+ *                        coordinates, never used as indices; a derived table's coordinates are the kernel's own and always pass.
+ *   spheres              either way the call puts tables WITHOUT any sphere into force, exactly what
+ *                        pwn_upload_spheres_device(n = 0, max_pairs = 0) makes.  Follow it with pwn_upload_spheres_device on the same
+ *                        stream.
+ *   ordering             FIVE launches on `stream` (a hipStream_t, NULL = the default stream): one that derives, checks, bakes and
+ *                        commits, and the four of a sphere-less build; in a context's first device build one more, which brings the
+ *                        static head of the tables into the device-resident base copy.  No host wait, no synchronisation and, after
+ *                        that first build, no copy from host memory.  The bake waits ON `stream` for the device builds that still
+ *                        read the base copy, for the launches and steps that still read the copy of the tables it takes, and for
+ *                        the upload stream as it stands (its walk table goes into a buffer no other copy refers to, whose readers
+ *                        the upload stream is behind).  Trace launches and players' steps made after the call returns read the new
+ *                        level, on any stream; launches made before it keep the copy they were given; later host uploads stay
+ *                        ordered behind the call.  No work-queue counters are used and the launch rotation is not entered.
+ *   in force until       the next call that builds tables from the host's level or object table: pwn_level_load, pwn_level_load_mem,
+ *                        pwn_upload_level, pwn_upload_spheres, pwn_prepare_render, which behave exactly as they always did and put
+ *                        the HOST's level back.  pwn_upload_spheres_device keeps the device level.  pwn_get_level, pwn_level_get,
+ *                        the spawn, pwn_get_objects and pwn_get_bins go on describing the host's state.  pwn_set_option never
+ *                        repacks while device tables are in force.
+ *   left alone           everything pwn_upload_spheres_device leaves alone.
+ *   memory               the builder's buffers of pwn_upload_spheres_device, and 32 bytes of status words.
+ *   cost                 measured on an MI355X (profiles/level_device/bench.txt): the call 52 us alone and 54 to 56 us
+ *                        back to back on the three shipped levels, given or derived table alike, against 67 to 71 us for copying
+ *                        the grid and the table down, pwn_upload_level and the wait for its upload.
+ *   errors               PWN_EINVAL for a NULL ctx, a NULL or misaligned d_data, a misaligned d_pmap; PWN_ENOLEVEL before a first
+ *                        level (a context gets its static tables with its first host level); PWN_ENOTSUP on a pwn_init_multi
+ *                        handle; PWN_EBUSY under a row tiling; PWN_ENOMEM.  A refused call launches nothing and changes nothing.
+ *   pwn_level_device_state   BLOCKS until the last device level build is done.  All eight words are 0 before any such build.
+ *                        out[0]  1 if a device-built level is in force
+ *                        out[1]  device level uploads so far
+ *                        out[2]  the last build's verdict: 0 taken, 1 a coordinate outside -1 .. 63, 2 the rule for cells outside the grid
+ *                        out[3]  the lowest letter that offends against that rule, 0 .. 25, else 26
+ *                        out[4]  endpoint records baked           out[5]  letters with both endpoints
+ *                        out[6]  1 if the table was derived       out[7]  0
+ *                        PWN_EINVAL for a NULL ctx or out, PWN_ENOTSUP on a pwn_init_multi handle, PWN_EBUSY under a row tiling.
+ *   pwn_get_level_device   BLOCKS.  The cells and the portal table (as given, or as derived) of the device-built level in force,
+ *                        read from its walk table; either pointer may be NULL.  PWN_EINVAL when none is in force.
+ */
+int pwn_upload_level_device(pwn_ctx *ctx, const void *d_data, const void *d_pmap, void *stream);
+int pwn_level_device_state(pwn_ctx *ctx, unsigned long long out[8]);
+int pwn_get_level_device(pwn_ctx *ctx, uint8_t data[4096], pwn_portal pmap[26]);
+
+/*
  * The object table behind those lists, driven the way game.lua drives the
  * reference (script.h:1-64): lv->objs[OBJ_MAX] (defs.h:4,98-99).
  *   pwn_obj_new        level_obj_new (level.h:41-62): first freed slot, else

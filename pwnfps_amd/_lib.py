@@ -123,6 +123,9 @@ ABI = [
     ("pwn_sphere_tables_state", _i, [_vp, _vp]),
     ("pwn_upload_spheres_device", _i, [_vp, _i, _vp, _i, _vp]),
     ("pwn_spheres_device_state", _i, [_vp, _vp]),
+    ("pwn_upload_level_device", _i, [_vp, _vp, _vp, _vp]),
+    ("pwn_level_device_state", _i, [_vp, _vp]),
+    ("pwn_get_level_device", _i, [_vp, _vp, _vp]),
     ("pwn_obj_new", _i, [_vp]),
     ("pwn_obj_set_sphere", _i, [_vp, _i, _d, _d, _d, _d, _d, _d, _d, _d]),
     ("pwn_obj_free", _i, [_vp, _i]),

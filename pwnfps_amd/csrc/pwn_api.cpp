@@ -93,6 +93,7 @@ extern "C" int pwn_init(pwn_ctx **out, int device, int width, int height)
 	for(int i = 0; i < PWN_NSTAGE; i++) c->h_walk[i] = NULL;
 	c->walk_dirty = false;
 	memset(&c->sd, 0, sizeof(c->sd));
+	memset(&c->ld, 0, sizeof(c->ld));
 	memset(&c->room, 0, sizeof(c->room)); c->room.mode = -1;
 	if(const char *e = getenv("PWN_TRACE_ROOM")) if(*e) c->room.mode = atoi(e) < 0 ? -1 : atoi(e);      // (the option's default for every context of a process)
 	c->d_scratch = NULL; c->scratch_cap = 0;
@@ -234,6 +235,7 @@ extern "C" void pwn_destroy(pwn_ctx *c)
 		(void)hipFree(c->d_big[i]);
 	}
 	pwn_i_spheres_device_release(c);
+	pwn_i_level_device_release(c);
 	pwn_i_viewports_device_release(c);
 	for(int i = 0; i < PWN_NSTAGE; i++)
 	{

@@ -8,6 +8,7 @@
 //   pwn_reach.cpp   rays that stop after a given distance (pwn_trace_reach and its device forms)
 //   pwn_pixel_rays.cpp  pixel rays from cameras on the device (pwn_pixel_rays_device)
 //   pwn_spheres_device.cpp  the sphere tables built on the device (pwn_upload_spheres_device)
+//   pwn_level_device.cpp  the level's tables baked on the device (pwn_upload_level_device)
 //   pwn_viewports_device.cpp  views of their own sizes from device cameras (pwn_viewports_layout, pwn_trace_viewports_device)
 //   pwn_frames.cpp  frames in flight
 //   pwn_tiled.cpp   row tiling over RCCL
@@ -161,6 +162,15 @@ extern "C" hipError_t pwn_launch_sphere_bins(const void *d_spheres, uint32_t n, 
 #define PWN_SD_STATUS_WORD (PWN_SD_BOX_WORDS + 8192u)
 #define PWN_SD_SCRATCH_BYTES ((PWN_SD_STATUS_WORD + 8u) * 4u)
 enum { PWN_SD_ST_PAIRS = 0, PWN_SD_ST_NCELL = 1, PWN_SD_ST_LONGEST = 2, PWN_SD_ST_REASON = 3, PWN_SD_ST_N = 4, PWN_SD_ST_MAX_PAIRS = 5 };
+// the level's part of the tables from a grid (and a portal table, or NULL: derived) in device memory (level_bake.hip): one launch on
+// `stream`.  On verdict 0 the cell words and endpoint records of d_base and the walk table d_walk are written; else d_base is left
+// alone and d_walk_prev (another buffer) is copied into d_walk.  d_status: PWN_LD_STATUS_WORDS words -- verdict, offending letter,
+// records, paired letters, derived, 0, 0, and word 7: a device-built level is in force, carried over from the build before where
+// prev_dev != 0 (else that word is not read).
+extern "C" hipError_t pwn_launch_level_bake(const void *d_data, const void *d_pmap, void *d_base, pwn_walk_table *d_walk,
+	const pwn_walk_table *d_walk_prev, uint32_t *d_status, int prev_dev, hipStream_t stream);
+#define PWN_LD_STATUS_WORDS 8u
+enum { PWN_LD_ST_VERDICT = 0, PWN_LD_ST_LETTER = 1, PWN_LD_ST_RECS = 2, PWN_LD_ST_PAIRED = 3, PWN_LD_ST_DERIVED = 4, PWN_LD_ST_DEV = 7 };
 extern "C" hipError_t pwn_launch_words(const uint32_t *d_all, const uint32_t *d_own, uint32_t *h_pinned_dst, int world, hipStream_t stream);
 extern "C" hipError_t pwn_launch_probe(int op, const uint32_t *in, uint32_t *out, int n, const uint16_t *tabs, hipStream_t stream);
 
@@ -341,6 +351,19 @@ struct pwn_ctx
 		uint8_t *d_base, *h_base, *d_scratch;
 		hipEvent_t ev_base, ev_build; hipStream_t build_stream;
 	} sd;
+	// pwn_upload_level_device (pwn_level_device.cpp): the level's part of the tables baked on the device, into sd.d_base, and a walk
+	// table with it; then sphere-less tables built from that base copy as pwn_upload_spheres_device builds them.  in_force: such a
+	// call has been made since the host's level last went up, so the base copy and the walk table of the tables in force MAY hold a
+	// device-built level (whether they do is the builds' verdicts, which only the device knows: d_status word PWN_LD_ST_DEV).
+	// pwn_i_pack_blob clears it, and with it sd.base_ok: the base copy is no longer the host's level.  ev_order: recorded on the
+	// upload stream and waited for on the call's stream, which puts the bake behind everything the upload stream is behind.
+	struct level_device_state
+	{
+		bool in_force, built;
+		unsigned long long uploads;
+		uint32_t *d_status;
+		hipEvent_t ev_order;
+	} ld;
 
 	uint32_t *d_pre, *d_out;         // pre-blur ("tsbuf") and final ("sbuf") frames
 	float *d_z;
@@ -475,6 +498,12 @@ void pwn_i_frames_release(pwn_ctx *c);
 void pwn_i_expand_tables(uint16_t *rcp, uint16_t *rsq);
 int pwn_i_pack_blob(pwn_ctx *c);
 void pwn_i_spheres_device_release(pwn_ctx *c);      // pwn_spheres_device.cpp: the device builder's buffers and events gone (pwn_destroy)
+// ... shared with pwn_level_device.cpp: the builder's own buffers, once; room for `need` bytes of the device-memory part in copy nb; the
+// base copy of the level in force made on stream s unless it is there
+int pwn_i_sd_buffers(pwn_ctx *c);
+int pwn_i_sd_big_reserve(pwn_ctx *c, int nb, size_t need);
+int pwn_i_sd_base(pwn_ctx *c, hipStream_t s);
+void pwn_i_level_device_release(pwn_ctx *c);        // pwn_level_device.cpp: its status words and event gone (pwn_destroy)
 void pwn_i_viewports_device_release(pwn_ctx *c);    // pwn_viewports_device.cpp: every layout and the records gone (pwn_destroy, streams idle)
 // pwn_calls.cpp, shared with pwn_viewports_device.cpp: the records of n rectangles in order of rising units, ties in the given order --
 // recs[j] stands for rectangle ord[j]; its geometry words (rectangle, units, division constants, segment) are filled in, its head

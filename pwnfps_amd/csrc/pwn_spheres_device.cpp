@@ -9,7 +9,7 @@
 static inline uint32_t lds_cells(int max_pairs) { return max_pairs < 4096 ? (uint32_t)max_pairs : 4096u; }
 
 // The builder's own buffers, once: the scratch of a build, the base copy and its pinned slot, two events
-static int sd_buffers(pwn_ctx *c)
+int pwn_i_sd_buffers(pwn_ctx *c)
 {
 	pwn_ctx::spheres_device_state &d = c->sd;
 	if(d.d_scratch != NULL) return PWN_OK;
@@ -42,7 +42,7 @@ void pwn_i_spheres_device_release(pwn_ctx *c)
 
 // Room for `need` bytes of the device-memory part in copy nb (pwn_tables.cpp big_reserve without the staging): grown to the largest
 // part so far, the device synchronised before a buffer that a launch may still read is freed
-static int sd_big_reserve(pwn_ctx *c, int nb, size_t need)
+int pwn_i_sd_big_reserve(pwn_ctx *c, int nb, size_t need)
 {
 	if(need > c->big_high) c->big_high = (need + 65535u) & ~(size_t)65535u;
 	if(need <= c->d_big_cap[nb]) return PWN_OK;
@@ -55,7 +55,7 @@ static int sd_big_reserve(pwn_ctx *c, int nb, size_t need)
 }
 
 // The base copy of the level in force, behind every build that read the one before it
-static int sd_base(pwn_ctx *c, hipStream_t s)
+int pwn_i_sd_base(pwn_ctx *c, hipStream_t s)
 {
 	pwn_ctx::spheres_device_state &d = c->sd;
 	if(d.base_ok) return PWN_OK;
@@ -87,15 +87,15 @@ extern "C" int pwn_upload_spheres_device(pwn_ctx *c, int n, const void *d_sphere
 	pwn_ctx::spheres_device_state &d = c->sd;
 	// (a level whose tables never went up -- a failed upload -- is sent first: the walk table and the baked cell words come with it)
 	if(c->blob_dirty && !d.in_force) { rc = pwn_i_pack_blob(c); if(rc != PWN_OK) return rc; }
-	rc = sd_buffers(c);
+	rc = pwn_i_sd_buffers(c);
 	if(rc != PWN_OK) return rc;
 	const int nb = (c->blob_cur + 1) % PWN_NBLOB;
-	rc = sd_big_reserve(c, nb, (size_t)big_bytes);
+	rc = pwn_i_sd_big_reserve(c, nb, (size_t)big_bytes);
 	if(rc != PWN_OK) return rc;
 
 	// from here on the runtime is talked to.  The build before this one shares the scratch and the base copy ...
 	if(d.built && d.build_stream != s) HIPCHK(c, hipStreamWaitEvent(s, d.ev_build, 0));
-	rc = sd_base(c, s);
+	rc = pwn_i_sd_base(c, s);
 	if(rc != PWN_OK) return rc;
 	// ... copy nb may still be on its way up, or be read by launches and players' steps: the build waits for them on ITS stream
 	if(c->upload_pending[nb]) HIPCHK(c, hipStreamWaitEvent(s, c->ev_upload[nb], 0));

@@ -280,6 +280,9 @@ int pwn_i_pack_blob(pwn_ctx *c)
 	c->blob_cur = nb;
 	c->blob_dirty = false;
 	c->sd.in_force = false;          // the tables in force are the host's again (pwn_upload_spheres_device)
+	// ... and so is the level (pwn_upload_level_device), whose bake has overwritten the device builder's base copy.  The walk table went
+	// up with this very upload: such a call leaves walk_dirty set.
+	if(c->ld.in_force) { c->ld.in_force = false; c->sd.base_ok = false; }
 	return PWN_OK;
 }
 

@@ -251,6 +251,33 @@ class Renderer:
         self._chk(lib.pwn_spheres_device_state(self._ctx, out), "pwn_spheres_device_state")
         return dict(zip(("in_force", "n", "max_pairs", "pairs", "cells", "longest", "reason", "uploads"), (int(v) for v in out)))
 
+    # -- the level's tables baked on the GPU (pwn_upload_level_device) ---------
+    def upload_level_device(self, data, pmap=None, stream=None):
+        """pwn_upload_level_device: upload_level for a grid that is on the GPU already, five launches on `stream` (a torch stream or a
+        raw hipStream_t; None = torch's current stream), no synchronisation.  data: a contiguous uint8 GPU tensor (64, 64), data[z][x];
+        pmap: a contiguous int32 GPU tensor (26, 7), rows x1 z1 x2 z2 rot12 c1 c2, or None -- the table is then derived from the cells
+        as the level loader derives it.  Both on this context's GPU and 16-byte aligned; they may be overwritten, in stream order, once
+        the call has returned.  A table that upload_level would refuse leaves the level in force in force (level_device_state says
+        why).  Either way the tables in force hold no sphere: follow the call with upload_spheres_device."""
+        who = "upload_level_device"
+        _, dev = _check(who, [("data", data, _U8, (64, 64), 16)], [("pmap", pmap, _I32, (26, 7), 16)], device=self.device)
+        _device_call(self, lib.pwn_upload_level_device, stream, dev, (_ptr(data), _ptr(pmap)))
+
+    def level_device_state(self):
+        """pwn_level_device_state (blocks: waits for the last device level build): dict(in_force, uploads, verdict, letter, records,
+        paired, derived); verdict 0 = taken, 1 = a coordinate outside -1 .. 63, 2 = the rule for cells outside the grid; letter =
+        the lowest offending letter 0 .. 25, else 26"""
+        out = (C.c_uint64 * 8)()
+        self._chk(lib.pwn_level_device_state(self._ctx, out), "pwn_level_device_state")
+        return dict(zip(("in_force", "uploads", "verdict", "letter", "records", "paired", "derived"), (int(v) for v in out)))
+
+    def get_level_device(self):
+        """pwn_get_level_device (blocks): (data (64,64) uint8, pmap (26,7) int32) of the device-built level in force, as numpy arrays"""
+        data = np.zeros((64, 64), np.uint8)
+        pmap = np.zeros((26, 7), np.int32)
+        self._chk(lib.pwn_get_level_device(self._ctx, data.ctypes.data, pmap.ctypes.data), "pwn_get_level_device")
+        return data, pmap
+
     # -- frame (screen.h:31-124) ---------------------------------------------
     def trace_screen_centred(self, cam, sec_current=0.0, want_z=True, sbuf=None, zbuf=None):
         cam = np.ascontiguousarray(cam, np.float32).reshape(16)

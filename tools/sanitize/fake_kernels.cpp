@@ -355,3 +355,68 @@ extern "C" hipError_t pwn_launch_words(const uint32_t *all, const uint32_t *own,
 	return hipSuccess;
 }
 extern "C" hipError_t pwn_launch_probe(int, const uint32_t *in, uint32_t *out, int n, const uint16_t *, hipStream_t) { for(int i = 0; i < n; i++) out[i] = in[i]; return hipSuccess; }
+// (the level of pwn_upload_level_device; level_device_driver.cpp: level_bake.hip's algorithm, sequentially, over level_bake.h -- the rules the
+// kernel shares with the host.  Reads exactly the 4096 cell bytes and, where given, the 182 words of the table; writes the cell words
+// and the records of the base copy and the walk table, or on another verdict the walk table alone, from the previous one; and the
+// status words.  Here too the stand-in IS the model: the driver holds what it leaves against pwn_bake_cells.)
+#include "level_bake.h"
+extern "C" { void (*pwn_fake_level_bake_hook)(const void *d_data, const void *d_pmap, const void *d_base, const void *d_walk, const void *d_walk_prev, const void *d_status) = NULL; }
+extern "C" hipError_t pwn_launch_level_bake(const void *d_data, const void *d_pmap, void *d_base, pwn_walk_table *d_walk,
+	const pwn_walk_table *d_walk_prev, uint32_t *status, int prev_dev, hipStream_t)
+{
+	small_launch("level_bake", d_data, d_walk, { (size_t)(d_pmap != NULL), (size_t)(prev_dev != 0) });
+	if(pwn_fake_level_bake_hook != NULL) pwn_fake_level_bake_hook(d_data, d_pmap, d_base, d_walk, d_walk_prev, status);
+	uint8_t cells[4096];
+	int32_t pmap[26 * PWN_LB_PM_WORDS];
+	memcpy(cells, d_data, 4096);
+	const bool derived = d_pmap == NULL;
+	if(!derived) memcpy(pmap, d_pmap, sizeof(pmap));
+	else
+	{
+		uint32_t first[26], second[26];
+		for(int i = 0; i < 26; i++) first[i] = second[i] = 0xffffffffu;
+		for(uint32_t cell = 0; cell < 4096u; cell++)
+		{
+			const int c = cells[cell];
+			if(c < 'A' || c > 'Z') continue;
+			if(first[c - 'A'] == 0xffffffffu) first[c - 'A'] = cell;
+			else if(second[c - 'A'] == 0xffffffffu) second[c - 'A'] = cell;
+		}
+		for(int i = 0; i < 26; i++) pwn_lb_derive_letter(cells, first[i], second[i], pmap + PWN_LB_PM_WORDS * i);
+	}
+	uint32_t bad1 = 26u, bad2 = 26u;
+	for(int i = 25; i >= 0; i--) if(pwn_lb_coords_bad(pmap + PWN_LB_PM_WORDS * i)) bad1 = (uint32_t)i;
+	for(int t = 0; t < 130; t++) { const int l = pwn_lb_outside_letter_nth(cells, pmap, t); if(l >= 0 && (uint32_t)l < bad2) bad2 = (uint32_t)l; }
+	const uint32_t verdict = bad1 < 26u ? (uint32_t)PWN_LB_BAD_COORD : (bad2 < 26u ? (uint32_t)PWN_LB_BAD_OUTSIDE : (uint32_t)PWN_LB_TAKEN);
+	if(verdict != PWN_LB_TAKEN)
+	{
+		const uint32_t dev = prev_dev ? status[PWN_LD_ST_DEV] : 0u;
+		memcpy(d_walk, d_walk_prev, sizeof(pwn_walk_table));
+		memset(status, 0, PWN_LD_STATUS_WORDS * 4u);
+		status[PWN_LD_ST_VERDICT] = verdict; status[PWN_LD_ST_LETTER] = verdict == PWN_LB_BAD_COORD ? bad1 : bad2;
+		status[PWN_LD_ST_DERIVED] = derived; status[PWN_LD_ST_DEV] = dev;
+		return hipSuccess;
+	}
+	uint32_t *words = (uint32_t *)((uint8_t *)d_base + PWN_T_CELLINFO), *recs = (uint32_t *)((uint8_t *)d_base + PWN_T_EPREC), nrec = 0;
+	memset(recs, 0, PWN_EP_MAX * 4u);
+	for(int z = 0; z < 64; z++) for(int x = 0; x < 64; x++)
+	{
+		const int c = cells[z * 64 + x];
+		uint32_t inside, outside, rec = 0;
+		const int has = pwn_lb_cell_bits(c, x, z, pmap, nrec, &inside, &outside, &rec);
+		if(has && nrec < PWN_EP_MAX) recs[nrec++] = rec;
+		const uint32_t cls = pwn_cell_class((uint32_t)c);
+		words[z * PWN_GRID_PITCH + x] = cls | inside;
+		if(x == 0) words[z * PWN_GRID_PITCH + 64] = cls | outside;
+		if(z == 0) words[64 * PWN_GRID_PITCH + x] = cls | outside;
+		if(x == 0 && z == 0) words[64 * PWN_GRID_PITCH + 64] = cls | outside;
+	}
+	memset(d_walk, 0, sizeof(pwn_walk_table));
+	memcpy(d_walk->cells, cells, 4096);
+	memcpy(d_walk->pmap, pmap, sizeof(pmap));
+	uint32_t paired = 0;
+	for(int i = 0; i < 26; i++) paired += pmap[PWN_LB_PM_WORDS * i + PWN_LB_X1] != -1 && pmap[PWN_LB_PM_WORDS * i + PWN_LB_X2] != -1;
+	memset(status, 0, PWN_LD_STATUS_WORDS * 4u);
+	status[PWN_LD_ST_LETTER] = 26u; status[PWN_LD_ST_RECS] = nrec; status[PWN_LD_ST_PAIRED] = paired; status[PWN_LD_ST_DERIVED] = derived; status[PWN_LD_ST_DEV] = 1u;
+	return hipSuccess;
+}
